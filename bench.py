@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - headline benchmark of the SVD minibatch training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N>1: under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment) this process is one rank; without
 them it starts its own N ranks as child processes BEFORE anything touches the GPU (no torch import, no library load in
@@ -44,6 +44,8 @@ if ROOT not in sys.path:
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8 TB/s spec peak
 PROFILE_ROUND = "r03"       # profiles/<round>_pmc_<workload>.csv: the committed counter summaries `traffic` is read from
 STREAM_CEILING_GBS = 6290.0 # same guide: 6.29 TB/s measured for a float4 streaming copy (79 % of spec)
+DUMP_LIMIT = 64 << 20       # --dump-outputs: tables up to this many bytes are written whole, larger ones as a row sample
+DUMP_ROWS = 32768           # rows drawn per side for that sample (fewer after removing repeats; ~33 MB at dim 128)
 
 WORKLOADS = {
     # BASELINE.json configs[0]: the reference's own CPU-runnable case (plumbing)
@@ -452,6 +454,36 @@ def self_launch(n, argv):
     return max(abs(q.returncode or 0) for q in procs)
 
 
+def dump_outputs(m, out_dir, device):
+    """--dump-outputs: what a caller of the timed path holds after its last step, the model's tables, as float32
+    out_dir/{mu,bu,bi,P,Q}.npy.  Tables over DUMP_LIMIT bytes: the same seeded sample of user and item rows in every run,
+    gathered on the device; out_dir/{user,item}_rows.npy (float64) name the rows."""
+    import torch
+    import tfrecomm_amd as T
+    L = T._lib
+    U, I, D = m.user_num, m.item_num, m.dim
+    os.makedirs(out_dir, exist_ok=True)
+    if 4 * (1 + (U + I) * (D + 1)) <= DUMP_LIMIT:
+        t = m.tables()
+        out = dict(mu=t[L.MU], bu=t[L.BU], bi=t[L.BI], P=t[L.P], Q=t[L.Q])
+    else:
+        rs = np.random.RandomState(0)
+        rows = dict(user=np.unique(rs.randint(0, U, DUMP_ROWS)), item=np.unique(rs.randint(0, I, DUMP_ROWS)))
+        ptrs = {w: m.table_devptr(w) for w in (L.BU, L.BI, L.P, L.Q)}    # brings back rows a fused big-table step parked
+        m.sync()
+
+        def take(which, side, width):
+            ptr, n = ptrs[which]
+            iface = {"shape": (n // width, width), "typestr": "<f4", "data": (ptr, False), "version": 3}
+            view = torch.as_tensor(type("_T", (), {"__cuda_array_interface__": iface})(), device=torch.device("cuda", device))
+            got = view.index_select(0, torch.from_numpy(rows[side]).to(view.device)).cpu().numpy()
+            return got.reshape(-1) if width == 1 else got
+        out = dict(mu=m.get_table(L.MU), bu=take(L.BU, "user", 1), bi=take(L.BI, "item", 1), P=take(L.P, "user", D),
+                   Q=take(L.Q, "item", D), user_rows=rows["user"].astype(np.float64), item_rows=rows["item"].astype(np.float64))
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a))
+
+
 def device_store(U, I, N, dev, seed=13575):
     """uniform synthetic (user, item, rating) triples drawn on the device (int32, int32, float32 tensors)"""
     import torch
@@ -463,10 +495,11 @@ def device_store(U, I, N, dev, seed=13575):
     return su, si, sr
 
 
-def svd_single_gpu(key, wl, K, W, device, *, zipf=0.0, feeds=True, cpu=True, convergence=True, cpu_steps=None):
+def svd_single_gpu(key, wl, K, W, device, *, zipf=0.0, feeds=True, cpu=True, convergence=True, cpu_steps=None, dump_dir=None):
     """One SVD workload on one GPU: the timed region of the bench contract (W warm-up + exactly K steps of the whole
     loop body, device-drawn ids), the other feeds, per-kernel HIP-event timing with the roofline of every kernel, and the
-    CPU baseline.  Returns the JSON object (the line itself for the headline workload, a nested object for the others)."""
+    CPU baseline.  Returns the JSON object (the line itself for the headline workload, a nested object for the others).
+    dump_dir: the tables right after the timed steps are written there (dump_outputs)."""
     import torch
     import tfrecomm_amd as T
     U, I, D, B = wl["U"], wl["I"], wl["D"], wl["B"]
@@ -513,6 +546,8 @@ def svd_single_gpu(key, wl, K, W, device, *, zipf=0.0, feeds=True, cpu=True, con
     elapsed = time.perf_counter() - t0
     ms_per_step = elapsed / K * 1e3
     value = K * B / elapsed
+    if dump_dir:                                                 # outside the clock, before the legs below train on
+        dump_outputs(m, dump_dir, device)
     sse, _, nval = m.eval_resident()
     val_rmse_timed = math.sqrt(sse / nval)
 
@@ -725,7 +760,13 @@ def main():
     ap.add_argument("--ns-dim", type=int, default=128)
     ap.add_argument("--ns-sequential", action="store_true")
     ap.add_argument("--ns-zipf", type=float, default=0.0, help="item ids ~ Zipf(a) instead of uniform (SURVEY 8d)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the tables after the last timed step as DIR/<name>.npy (single-GPU SVD training workloads)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.gpus > 1 or os.environ.get("TFR_FORCE_DP") or args.workload in ("c5", "als") or args.only_north_star):
+        ap.error("--dump-outputs: only the single-GPU SVD training step (workloads c1-c4) is dumped")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         os.environ["TFR_BENCH_LAUNCHER"] = "bench.py's own ranks (subprocess per GPU)"
@@ -797,7 +838,7 @@ def main():
         wl["name"] = wl["name"] + " [dim overridden to %d]" % args.dim
     t_start = time.perf_counter()
     out = svd_single_gpu(args.workload, wl, args.steps, args.warmup, local_rank, zipf=args.zipf, cpu=not args.no_cpu_baseline,
-                         convergence=not args.no_convergence)
+                         convergence=not args.no_convergence, dump_dir=args.dump_outputs)
     if not args.no_north_star:
         out["north_star_forward"] = north_star_forward(local_rank)                      # uniform ids: worst case for caches
         out["north_star_forward_zipf"] = north_star_forward(local_rank, zipf=1.05)      # reported separately

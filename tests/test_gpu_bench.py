@@ -44,6 +44,26 @@ def test_one_gpu_line_has_the_contract_fields():
     assert set(d["feeds"]) == {"device_drawn_ids", "host_drawn_ids", "prestaged_ids"}
 
 
+def test_dump_outputs_are_the_tables_after_the_timed_steps(tmp_path):
+    """--dump-outputs DIR: the headline tables after the last timed step, float32, the same in two runs with the same
+    arguments, and different after one more timed step."""
+    import numpy as np
+    quick = ["--warmup", "2", "--no-north-star", "--no-configs", "--no-convergence", "--no-cpu-baseline"]
+    dumps = []
+    for k, name in ((6, "a"), (6, "b"), (7, "c")):
+        d, _ = _run(["--steps", str(k)] + quick + ["--dump-outputs", str(tmp_path / name)])
+        assert d["steps"] == k and d["ms_per_step"] > 0
+        dumps.append({n: np.load(str(tmp_path / name / (n + ".npy"))) for n in ("mu", "bu", "bi", "P", "Q")})
+    U, I, D = d["config"]["users"], d["config"]["items"], d["config"]["dim"]
+    a, b, c = dumps
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["P.npy", "Q.npy", "bi.npy", "bu.npy", "mu.npy"]
+    assert [a[n].shape for n in ("mu", "bu", "bi", "P", "Q")] == [(), (U,), (I,), (U, D), (I, D)]
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    assert all(np.array_equal(a[n], b[n]) for n in a)
+    assert not np.array_equal(a["P"], c["P"]) and not np.array_equal(a["Q"], c["Q"])
+
+
 def test_two_rank_line_rehearsed_on_one_gpu():
     """`python bench.py --gpus 2` with no launcher: the parent starts the ranks; the line is the data-parallel headline with
     cpu_baseline, the single-GPU reference and BASELINE config 4 row-sharded over the two ranks (tables scaled down for the
