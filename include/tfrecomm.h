@@ -367,6 +367,33 @@ int tfr_fm_topk(tfr_fm* m, const int32_t* user_features, int64_t n_users, int64_
 int tfr_topk_plan(int32_t dim, int32_t k, int64_t n_users, int64_t item_num,
                   int64_t* lds_bytes, int32_t* users_per_block, int32_t* item_slices, int64_t* user_chunk);
 
+/* ---- batched per-user fine-tuning: every user of adaptive_test.py:87-116 / non_adaptive_test.py:56-87 in one launch -----------
+ *      A schedule: for user u = users[x] (each at most once), training rows items / rates [row_ptr[x], row_ptr[x+1]) and rounds
+ *      [round_ptr[x], round_ptr[x+1]).  Round k first predicts ask_items[k] with the parameters of the moment (its logit, the
+ *      forward's ((dot + mu) + bu) + bi, goes to ask_logits_out[k]), then runs nsteps training steps on the first prefix_len[k]
+ *      rows of its user (1 <= prefix_len[k] <= the user's rows): what tfr_forward + tfr_train_steps_repeat do per round.
+ *      round_seq[k] = the step, counted from this call's start, at which the sequential drivers would start round k (NULL =
+ *      k * nsteps, user-major order); with Adam each step uses the beta powers of that sequential position (the model's float32
+ *      recurrence replayed on the host), so lr_t is the sequential one.  Outputs: round_loss_out[k] = data loss of round k's
+ *      last step; final_logits_out[row] = pre-update logits of each user's last step over its last round's prefix (other rows
+ *      untouched).  Both may be NULL.
+ *      Needs bias_global, item_bias and item_features frozen and SGD or lazy Adam (TFR_ERR_ARG otherwise: tf1 Adam couples the
+ *      users).  Ids are checked on the host (TFR_ERR_OOB), the schedule's shape too (TFR_ERR_ARG), before any device work; on an
+ *      error nothing changes.  On success the users' user_features / user_bias rows and their slots are written back, the step
+ *      counter advances by n_rounds * nsteps and the beta powers end where the sequential drivers leave them; every other row
+ *      and table is untouched.  No atomics and fixed summation orders: a user's results are bit-identical whichever users share
+ *      the call.  Runs on the model's stream and synchronises.  Matches the sequential path to float32 rounding (the sums run in
+ *      a different order), not bit for bit. */
+int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, const int64_t* row_ptr /* [n_users+1] */,
+                       const int32_t* items, const float* rates, const int64_t* round_ptr /* [n_users+1] */,
+                       const int32_t* ask_items, const int32_t* prefix_len, const int64_t* round_seq /* or NULL */,
+                       int32_t nsteps, float* ask_logits_out /* [n_rounds] */, float* round_loss_out /* [n_rounds] or NULL */,
+                       float* final_logits_out /* [n_rows] or NULL */);
+/* host-only, no device: what the launcher does for a call whose largest user has max_rows rows - LDS bytes per workgroup (a CU
+ * has 160 KiB), users whose rows are staged in LDS (at most this many rows; larger users read their item rows from global
+ * memory), waves (users) per workgroup */
+int tfr_finetune_plan(int32_t dim, int64_t max_rows, int64_t* lds_bytes, int32_t* rows_staged, int32_t* waves_per_block);
+
 /* ---- per-kernel timing with HIP events on the model's stream (bench.py roofline) -------- */
 enum {
     TFR_K_FORWARD = 0,        /* gather-dot forward (+ fused loss/grad when training)       */

@@ -13,9 +13,11 @@
 #include <new>
 #include <chrono>
 #include <vector>
+#include <algorithm>
 #include "tfrecomm.h"
 #include "svd_kernels.h"
 #include "topk.h"
+#include "finetune.h"
 
 using namespace tfr;
 
@@ -155,6 +157,8 @@ struct tfr_model {
     int32_t* tk_items = nullptr; int64_t tk_out_cap = 0;
     float* tk_scores = nullptr; int64_t tk_scores_cap = 0;
     int32_t* tk_bad = nullptr;
+    // batched fine-tuning (tfr_finetune_users): one device buffer for a call's schedule and outputs
+    char* ft_buf = nullptr; int64_t ft_cap = 0;
     // profiling
     bool prof = false;
     std::vector<ProfEvent> events;
@@ -458,6 +462,7 @@ int tfr_destroy(tfr_model* m) {
     }
     dfree(m->tk_part); dfree(m->tk_users); dfree(m->tk_indptr); dfree(m->tk_excl); dfree(m->tk_items); dfree(m->tk_scores);
     dfree(m->tk_bad);
+    dfree(m->ft_buf);
     if (m->spec_ev) (void)hipEventDestroy(m->spec_ev);
     if (m->h_ring) (void)hipHostFree(m->h_ring);
     for (int z = 0; z < tfr_model::HRING; ++z) if (m->ring_ev[z]) (void)hipEventDestroy(m->ring_ev[z]);
@@ -3442,6 +3447,191 @@ int tfr_fm_topk(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_
     const TopkTables t = {m->w[TFR_P], m->w[TFR_BU], m->w[TFR_P] + item_lo * m->D, m->w[TFR_BU] + item_lo, m->w[TFR_MU],
                           m->U, item_hi - item_lo, 0};
     return topk_host(m, t, user_features, n_users, k, excl_indptr, excl_items, items_out, scores_out);
+}
+
+}  // extern "C"
+
+// ---- batched per-user fine-tuning (finetune.hip) ----------------------------------------------------------------------------
+// beta powers of the sequential drivers: the model's float32 recurrence (one multiply per step after the applies) replayed from
+// its current values.  out[2k], out[2k+1] = the powers at step seq[k] of the call; end = after n_total steps.  The walk stops
+// early once both powers reach a fixed point (they underflow to zero after ~10^5 steps with the default betas).
+static void ft_replay_powers(float b1p, float b2p, float b1, float b2, const int64_t* seq, int64_t n, int64_t n_total,
+                             std::vector<float>& out, float* end1, float* end2) {
+    std::vector<int64_t> idx((size_t)n);
+    for (int64_t k = 0; k < n; ++k) idx[(size_t)k] = k;
+    std::sort(idx.begin(), idx.end(), [&](int64_t x, int64_t y) { return seq[x] < seq[y]; });
+    out.resize((size_t)n * 2);
+    int64_t t = 0;
+    size_t q = 0;
+    bool fixed = false;
+    while (true) {
+        while (q < idx.size() && seq[idx[q]] == t) {
+            out[(size_t)idx[q] * 2] = b1p; out[(size_t)idx[q] * 2 + 1] = b2p;
+            ++q;
+        }
+        if (t == n_total || fixed) break;
+        const float n1 = b1p * b1, n2 = b2p * b2;
+        fixed = n1 == b1p && n2 == b2p;
+        b1p = n1; b2p = n2;
+        ++t;
+    }
+    for (; q < idx.size(); ++q) { out[(size_t)idx[q] * 2] = b1p; out[(size_t)idx[q] * 2 + 1] = b2p; }
+    *end1 = b1p; *end2 = b2p;
+}
+
+static size_t ft_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+extern "C" {
+
+int tfr_finetune_plan(int32_t dim, int64_t max_rows, int64_t* lds_bytes, int32_t* rows_staged, int32_t* waves_per_block) {
+    int G, VEC;
+    if (!geometry(dim, &G, &VEC)) return fail(TFR_ERR_ARG, "unsupported dim %d", dim);
+    if (max_rows < 0) return fail(TFR_ERR_ARG, "fine-tune plan: negative max_rows");
+    const FtPlan p = ft_plan(dim, max_rows);
+    if (lds_bytes) *lds_bytes = (int64_t)p.lds_bytes;
+    if (rows_staged) *rows_staged = p.rows_staged;
+    if (waves_per_block) *waves_per_block = FT_WAVES;
+    return TFR_OK;
+}
+
+int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, const int64_t* row_ptr, const int32_t* items,
+                       const float* rates, const int64_t* round_ptr, const int32_t* ask_items, const int32_t* prefix_len,
+                       const int64_t* round_seq, int32_t nsteps, float* ask_logits_out, float* round_loss_out,
+                       float* final_logits_out) {
+    MODEL_ENTER(m);
+    const tfr_opts& o = m->o;
+    const bool adam = o.optimizer == TFR_OPT_ADAM;
+    // --- every check before any device work: on an error nothing changes
+    if (n_users < 0) return fail(TFR_ERR_ARG, "fine-tune: negative n_users");
+    if (nsteps < 1) return fail(TFR_ERR_ARG, "fine-tune: nsteps must be at least 1 (got %d)", nsteps);
+    if (adam && o.adam_mode == TFR_ADAM_TF1)
+        return fail(TFR_ERR_ARG, "fine-tune: tf1-mode Adam moves every user row at every step, so the users are not independent "
+                                 "(use lazy Adam or SGD, or the sequential drivers)");
+    const uint32_t need = (1u << TFR_MU) | (1u << TFR_BI) | (1u << TFR_Q);
+    if ((m->frozen & need) != need)
+        return fail(TFR_ERR_ARG, "fine-tune: bias_global, item_bias and item_features must be frozen (frozen mask 0x%x)", m->frozen);
+    if (n_users == 0) return TFR_OK;
+    if (!users || !row_ptr || !round_ptr || !ask_logits_out) return fail(TFR_ERR_ARG, "fine-tune: null users / offsets / output");
+    if (row_ptr[0] != 0 || round_ptr[0] != 0) return fail(TFR_ERR_ARG, "fine-tune: row_ptr and round_ptr must start at 0");
+    for (int64_t u = 0; u < n_users; ++u) {
+        if (row_ptr[u + 1] < row_ptr[u]) return fail(TFR_ERR_ARG, "fine-tune: row_ptr decreases at user %lld", (long long)u);
+        if (round_ptr[u + 1] < round_ptr[u]) return fail(TFR_ERR_ARG, "fine-tune: round_ptr decreases at user %lld", (long long)u);
+    }
+    const int64_t n_rows = row_ptr[n_users], n_rounds = round_ptr[n_users];
+    if (n_rows > 0 && (!items || !rates)) return fail(TFR_ERR_ARG, "fine-tune: null items / rates");
+    if (n_rounds > 0 && (!ask_items || !prefix_len)) return fail(TFR_ERR_ARG, "fine-tune: null ask_items / prefix_len");
+    if (n_rounds > INT64_MAX / nsteps) return fail(TFR_ERR_ARG, "fine-tune: n_rounds x nsteps overflows");
+    if (n_users > INT32_MAX) return fail(TFR_ERR_ARG, "fine-tune: too many users");
+    for (int64_t u = 0; u < n_users; ++u)
+        if (users[u] < 0 || (int64_t)users[u] >= m->U)
+            return fail(TFR_ERR_OOB, "fine-tune: user id %d outside [0, %lld)", users[u], (long long)m->U);
+    for (int64_t r = 0; r < n_rows; ++r)
+        if (items[r] < 0 || (int64_t)items[r] >= m->I)
+            return fail(TFR_ERR_OOB, "fine-tune: item id %d outside [0, %lld)", items[r], (long long)m->I);
+    for (int64_t k = 0; k < n_rounds; ++k)
+        if (ask_items[k] < 0 || (int64_t)ask_items[k] >= m->I)
+            return fail(TFR_ERR_OOB, "fine-tune: asked item id %d outside [0, %lld)", ask_items[k], (long long)m->I);
+    {
+        // two waves on one user row would race: every user at most once
+        std::vector<int32_t> sorted(users, users + n_users);
+        std::sort(sorted.begin(), sorted.end());
+        for (int64_t u = 1; u < n_users; ++u)
+            if (sorted[(size_t)u] == sorted[(size_t)u - 1])
+                return fail(TFR_ERR_ARG, "fine-tune: user %d appears more than once", sorted[(size_t)u]);
+    }
+    const int64_t n_total = n_rounds * nsteps;
+    int64_t max_rows = 0;
+    std::vector<int64_t> work((size_t)n_users, 0);
+    for (int64_t u = 0; u < n_users; ++u) {
+        const int64_t n = row_ptr[u + 1] - row_ptr[u];
+        if (n > max_rows && round_ptr[u + 1] > round_ptr[u]) max_rows = n;
+        for (int64_t k = round_ptr[u]; k < round_ptr[u + 1]; ++k) {
+            if (prefix_len[k] < 1 || prefix_len[k] > n)
+                return fail(TFR_ERR_ARG, "fine-tune: round %lld trains on %d rows, its user has %lld", (long long)k, prefix_len[k],
+                            (long long)n);
+            work[(size_t)u] += prefix_len[k];
+        }
+    }
+    if (round_seq)
+        for (int64_t k = 0; k < n_rounds; ++k)
+            if (round_seq[k] < 0 || round_seq[k] > n_total - nsteps)
+                return fail(TFR_ERR_ARG, "fine-tune: round %lld starts at step %lld, outside [0, %lld]", (long long)k,
+                            (long long)round_seq[k], (long long)(n_total - nsteps));
+    int G, VEC;
+    if (!geometry(m->D, &G, &VEC)) return fail(TFR_ERR_ARG, "fine-tune: unsupported dim %d", m->D);
+    // --- host-side schedule: beta powers at each round's first step, users by descending work
+    std::vector<float> bpow;
+    float end1 = m->b1p, end2 = m->b2p;
+    if (adam) {
+        std::vector<int64_t> seq;
+        if (!round_seq) {
+            seq.resize((size_t)n_rounds);
+            for (int64_t k = 0; k < n_rounds; ++k) seq[(size_t)k] = k * nsteps;
+        }
+        ft_replay_powers(m->b1p, m->b2p, o.beta1, o.beta2, round_seq ? round_seq : seq.data(), n_rounds, n_total, bpow, &end1,
+                         &end2);
+    }
+    std::vector<int32_t> order((size_t)n_users);
+    for (int64_t u = 0; u < n_users; ++u) order[(size_t)u] = (int32_t)u;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return work[(size_t)x] > work[(size_t)y]; });
+    const FtPlan plan = ft_plan(m->D, max_rows);
+    // --- one device buffer: inputs, then outputs
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t at = off; off = ft_align(off + bytes); return at; };
+    const size_t o_users = take((size_t)n_users * 4), o_rowp = take((size_t)(n_users + 1) * 8), o_items = take((size_t)n_rows * 4),
+                 o_rates = take((size_t)n_rows * 4), o_rndp = take((size_t)(n_users + 1) * 8), o_ask = take((size_t)n_rounds * 4),
+                 o_pre = take((size_t)n_rounds * 4), o_bpow = take(bpow.size() * 4), o_order = take((size_t)n_users * 4),
+                 o_askout = take((size_t)n_rounds * 4), o_loss = take(round_loss_out ? (size_t)n_rounds * 4 : 0),
+                 o_final = take(final_logits_out ? (size_t)n_rows * 4 : 0);
+    if ((int64_t)off > m->ft_cap) {
+        HIPCHK(hipStreamSynchronize(m->stream));
+        dfree(m->ft_buf);
+        m->ft_buf = nullptr;
+        m->ft_cap = 0;
+        int rc = dmalloc(&m->ft_buf, off);
+        if (rc) return rc;
+        m->ft_cap = (int64_t)off;
+    }
+    int rc = settle_q(m);                                // item rows the fused big-table step left in q_alt come back first
+    if (rc) return rc;
+    char* b = m->ft_buf;
+    hipStream_t s = m->stream;
+    auto up = [&](size_t at, const void* src, size_t bytes) -> int {
+        if (bytes) HIPCHK(hipMemcpyAsync(b + at, src, bytes, hipMemcpyHostToDevice, s));
+        return TFR_OK;
+    };
+    if ((rc = up(o_users, users, (size_t)n_users * 4)) || (rc = up(o_rowp, row_ptr, (size_t)(n_users + 1) * 8)) ||
+        (rc = up(o_items, items, (size_t)n_rows * 4)) || (rc = up(o_rates, rates, (size_t)n_rows * 4)) ||
+        (rc = up(o_rndp, round_ptr, (size_t)(n_users + 1) * 8)) || (rc = up(o_ask, ask_items, (size_t)n_rounds * 4)) ||
+        (rc = up(o_pre, prefix_len, (size_t)n_rounds * 4)) || (rc = up(o_bpow, bpow.data(), bpow.size() * 4)) ||
+        (rc = up(o_order, order.data(), (size_t)n_users * 4)) ||
+        (final_logits_out && (rc = up(o_final, final_logits_out, (size_t)n_rows * 4))))   // rows the call does not write stay
+        return rc;
+    FtArgs a;
+    memset(&a, 0, sizeof(a));
+    a.P = m->w[TFR_P]; a.bu = m->w[TFR_BU];
+    a.Pm = m->m[TFR_P]; a.Pv = m->v[TFR_P]; a.bum = m->m[TFR_BU]; a.buv = m->v[TFR_BU];
+    a.Q = m->w[TFR_Q]; a.bi = m->w[TFR_BI]; a.mu = m->w[TFR_MU];
+    a.users = (const int32_t*)(b + o_users); a.row_ptr = (const int64_t*)(b + o_rowp);
+    a.items = (const int32_t*)(b + o_items); a.rates = (const float*)(b + o_rates);
+    a.round_ptr = (const int64_t*)(b + o_rndp); a.ask = (const int32_t*)(b + o_ask); a.prefix = (const int32_t*)(b + o_pre);
+    a.bpow = adam ? (const float*)(b + o_bpow) : nullptr; a.order = (const int32_t*)(b + o_order);
+    a.ask_out = (float*)(b + o_askout);
+    a.loss_out = round_loss_out ? (float*)(b + o_loss) : nullptr;
+    a.final_out = final_logits_out ? (float*)(b + o_final) : nullptr;
+    a.n_users = n_users; a.wave_floats = plan.wave_floats;
+    a.D = m->D; a.nsteps = nsteps; a.loss = o.loss; a.item_abs = o.item_abs; a.reg_bias = o.reg_bias; a.adam = adam ? 1 : 0;
+    a.frozen_rows = (m->frozen >> TFR_P) & 1; a.frozen_bias = (m->frozen >> TFR_BU) & 1; a.rows_staged = plan.rows_staged;
+    a.lam = o.reg; a.lr = o.lr; a.b1 = o.beta1; a.b2 = o.beta2; a.eps = o.eps;
+    launch_finetune(a, plan, s);
+    HIPCHK(hipGetLastError());
+    if (n_rounds) HIPCHK(hipMemcpyAsync(ask_logits_out, a.ask_out, (size_t)n_rounds * 4, hipMemcpyDeviceToHost, s));
+    if (round_loss_out && n_rounds) HIPCHK(hipMemcpyAsync(round_loss_out, a.loss_out, (size_t)n_rounds * 4, hipMemcpyDeviceToHost, s));
+    if (final_logits_out && n_rows) HIPCHK(hipMemcpyAsync(final_logits_out, a.final_out, (size_t)n_rows * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    m->step += n_total;
+    if (adam) { m->b1p = end1; m->b2p = end2; }
+    return TFR_OK;
 }
 
 }  // extern "C"

@@ -51,6 +51,13 @@ __device__ __forceinline__ void warm_args(const T& args) {
 }
 
 
+// LDS written by some lanes of a wave and read by others of the same wave
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 struct RedArgs {
     const int32_t* ks; const int32_t* ps; const int32_t* other; const float* g;
     const float* own; const float* partner; const float* own_bias;

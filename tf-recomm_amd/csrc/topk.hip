@@ -27,13 +27,6 @@ __device__ __forceinline__ float topk_key_score(uint64_t key) {
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
-// LDS written by some lanes of a wave and read by others of the same wave
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // descending bitonic sort of q[0..CAP) by one wave
 template <int CAP>
 __device__ __forceinline__ void wave_sort_desc(uint64_t* q, int lane) {

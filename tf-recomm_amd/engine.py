@@ -229,6 +229,46 @@ class SvdModel:
                                                  L.ptr_f32(loss) if want_loss else None))
         return logits, loss
 
+    # -- batched per-user fine-tuning (include/tfrecomm.h tfr_finetune_users) --------------------------
+    def finetune_users(self, users, row_ptr, items, rates, round_ptr, ask_items, prefix_len, nsteps, round_seq=None,
+                       want_loss=True, want_final=True):
+        """Every user's rounds of a fine-tuning schedule in one launch (``finetune.adaptive_schedule`` /
+        ``finetune.non_adaptive_schedule`` build one).
+        User ``users[x]`` trains on rows ``[row_ptr[x], row_ptr[x+1])`` of ``items`` / ``rates``; its rounds are
+        ``[round_ptr[x], round_ptr[x+1])``: round ``k`` predicts ``ask_items[k]``, then runs ``nsteps`` steps on the user's
+        first ``prefix_len[k]`` rows.  ``round_seq[k]``: the step (from this call's start) at which the sequential drivers
+        would start round ``k`` (None = ``k * nsteps``).  Needs mu and the item tables frozen and SGD or lazy Adam.
+        Returns (ask logits [n_rounds], data loss of each round's last step [n_rounds] or None, pre-update logits of
+        each user's last step over its last round's prefix [n_rows] or None; NaN at rows past that prefix)."""
+        u = L.as_i32(users, "user ids").reshape(-1)
+        rp = np.ascontiguousarray(np.asarray(row_ptr, np.int64)).reshape(-1)
+        it = L.as_i32(items, "item ids").reshape(-1)
+        r = L.as_f32(rates).reshape(-1)
+        kp = np.ascontiguousarray(np.asarray(round_ptr, np.int64)).reshape(-1)
+        ask = L.as_i32(ask_items, "asked item ids").reshape(-1)
+        pre = L.as_i32(prefix_len, "prefix lengths").reshape(-1)
+        if rp.size != u.size + 1 or kp.size != u.size + 1:
+            raise ValueError("row_ptr and round_ptr must hold n_users + 1 offsets")
+        n_rows, n_rounds = int(rp[-1]), int(kp[-1])
+        if it.size != n_rows or r.size != n_rows:
+            raise ValueError("items and rates must hold row_ptr[-1] = %d entries" % n_rows)
+        if ask.size != n_rounds or pre.size != n_rounds:
+            raise ValueError("ask_items and prefix_len must hold round_ptr[-1] = %d entries" % n_rounds)
+        seq = None
+        if round_seq is not None:
+            seq = np.ascontiguousarray(np.asarray(round_seq, np.int64)).reshape(-1)
+            if seq.size != n_rounds:
+                raise ValueError("round_seq must hold one position per round")
+        ask_out = np.empty(n_rounds, np.float32)
+        loss = np.empty(n_rounds, np.float32) if want_loss else None
+        final = np.full(n_rows, np.nan, np.float32) if want_final else None
+        L.check(self._lib.tfr_finetune_users(self._h, u.size, L.ptr_i32(u), L.ptr_i64(rp), L.ptr_i32(it), L.ptr_f32(r),
+                                             L.ptr_i64(kp), L.ptr_i32(ask), L.ptr_i32(pre),
+                                             None if seq is None else L.ptr_i64(seq), int(nsteps), L.ptr_f32(ask_out),
+                                             None if loss is None else L.ptr_f32(loss),
+                                             None if final is None else L.ptr_f32(final)))
+        return ask_out, loss, final
+
     # -- top-K recommendation (forward.py:47-61 get_ranking; include/tfrecomm.h tfr_topk) ---------------
     def recommend(self, users, k=10, exclude=None, return_scores=True):
         """The ``k`` best items for each of ``users`` by score ``((P[u].Q'[i] + mu) + bu[u]) + bi[i]`` (the logit under the
