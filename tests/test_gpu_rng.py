@@ -318,3 +318,31 @@ def test_records_beside_the_drawn_ids_are_invisible():
         assert p.returncode == 0, p.stderr.decode()[-2000:]
         out.append([l for l in p.stdout.decode().splitlines() if l.startswith("HASH")][0])
     assert out[0] == out[1]
+
+
+def test_a_device_draw_into_the_staged_ids_drops_their_records():
+    """tfr_draw_ids_dev into the buffer tfr_staged_ids_devptr hands out rewrites ids that a drawn call left store records
+    beside: the small-table step must read the new ids, not those records.  The same ids staged from the host (a host draw
+    from the same generator) give the same losses and tables, bit for bit."""
+    U, I, D, B, N = 3000, 2000, 64, 10000, 200000
+    rs = np.random.RandomState(11)
+    su, si, sr = rs.randint(0, U, N).astype(np.int32), rs.randint(0, I, N).astype(np.int32), rs.randint(1, 6, N).astype(np.float32)
+    out = []
+    for device_draw in (True, False):
+        with T.SvdModel(U, I, D, device=0) as m:
+            m.init_tables(seed=7)
+            m.upload_triples(su, si, sr)
+            m.rng_seed(21)
+            for _ in range(2):                     # the second call starts on the ids (and records) the first drew ahead
+                m.train_steps_drawn(B, 5)
+            if device_draw:
+                p, n = m.staged_ids_devptr()
+                assert p and n == 5 * B
+                m.draw_ids_dev(N, 5 * B, p)
+                m.join_draws()
+            else:
+                m.stage_ids(m.draw_ids(N, 5 * B))
+            loss = m.train_steps_staged(0, B, 5, want_loss=True)
+            out.append((loss.tobytes(), [np.ascontiguousarray(m.get_table(t)).tobytes() for t in (L.MU, L.BU, L.BI, L.P, L.Q)]))
+    assert out[0][0] == out[1][0]
+    assert out[0][1] == out[1][1]

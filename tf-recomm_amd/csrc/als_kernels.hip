@@ -18,6 +18,9 @@
 #include <vector>
 #include <algorithm>
 #include "tfrecomm.h"
+#include "devbuf.h"
+
+using tfr::DevBuf;
 
 namespace {
 
@@ -206,8 +209,6 @@ int als_fail(int code, const char* fmt, ...) {
                                               "%s: %s", #expr, hipGetErrorString(e_));                \
     } while (0)
 
-void als_free(void* p) { if (p) (void)hipFree(p); }
-
 }  // namespace
 
 struct tfr_als {
@@ -216,15 +217,15 @@ struct tfr_als {
     double lambda = 0.1, bias = 0.0;
     int device = 0;
     hipStream_t stream = nullptr;
-    double *U = nullptr, *V = nullptr, *Wu = nullptr, *Ww = nullptr;
-    int64_t *ptr_u = nullptr, *ptr_w = nullptr;
-    int32_t *ids_u = nullptr, *ids_w = nullptr, *users = nullptr, *works = nullptr;
-    double *val_u = nullptr, *val_w = nullptr;
+    DevBuf<double> U, V, Wu, Ww;
+    DevBuf<int64_t> ptr_u, ptr_w;
+    DevBuf<int32_t> ids_u, ids_w, users, works;
+    DevBuf<double> val_u, val_w;
     // chunk tables for long rating lists, per side (0 = users, 1 = works)
-    int32_t *cfirst[2] = {nullptr, nullptr}, *ccount[2] = {nullptr, nullptr}, *chunk_ent[2] = {nullptr, nullptr};
-    int64_t *chunk_lo[2] = {nullptr, nullptr}, *chunk_hi[2] = {nullptr, nullptr};
+    DevBuf<int32_t> cfirst[2], ccount[2], chunk_ent[2];
+    DevBuf<int64_t> chunk_lo[2], chunk_hi[2];
     int64_t n_chunks[2] = {0, 0};
-    double* partial = nullptr;
+    DevBuf<double> partial;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -234,12 +235,8 @@ const char* tfr_als_last_error(void) { return g_als_err; }
 
 int tfr_als_destroy(tfr_als* m) {
     if (!m) return TFR_OK;
-    (void)hipSetDevice(m->device);
+    (void)hipSetDevice(m->device);                       // the buffers are freed with the model's device current
     if (m->stream) (void)hipStreamSynchronize(m->stream);
-    void* ps[] = {m->U, m->V, m->Wu, m->Ww, m->ptr_u, m->ptr_w, m->ids_u, m->ids_w, m->users, m->works, m->val_u, m->val_w};
-    for (void* p : ps) als_free(p);
-    for (int z = 0; z < 2; ++z) { als_free(m->cfirst[z]); als_free(m->ccount[z]); als_free(m->chunk_ent[z]); als_free(m->chunk_lo[z]); als_free(m->chunk_hi[z]); }
-    als_free(m->partial);
     if (m->ev0) (void)hipEventDestroy(m->ev0);
     if (m->ev1) (void)hipEventDestroy(m->ev1);
     if (m->stream) (void)hipStreamDestroy(m->stream);
@@ -261,10 +258,10 @@ int tfr_als_create(tfr_als** out, int64_t nb_users, int64_t nb_works, int32_t nb
     if (!m) return als_fail(TFR_ERR_NOMEM, "host allocation failed");
     m->nu = nb_users; m->nw = nb_works; m->d = nb_components; m->lambda = lambda_; m->device = device;
     hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->U, (size_t)nb_users * m->d * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->V, (size_t)nb_works * m->d * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->Wu, (size_t)nb_users * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&m->Ww, (size_t)nb_works * 8);
+    if (e == hipSuccess) e = m->U.reserve(nb_users * m->d, m->stream);
+    if (e == hipSuccess) e = m->V.reserve(nb_works * m->d, m->stream);
+    if (e == hipSuccess) e = m->Wu.reserve(nb_users, m->stream);
+    if (e == hipSuccess) e = m->Ww.reserve(nb_works, m->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->U, 0, (size_t)nb_users * m->d * 8, m->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->V, 0, (size_t)nb_works * m->d * 8, m->stream);
     if (e == hipSuccess) e = hipMemsetAsync(m->Wu, 0, (size_t)nb_users * 8, m->stream);
@@ -345,17 +342,15 @@ int tfr_als_load(tfr_als* m, const int64_t* user_ids, const int64_t* work_ids, c
     build(user_ids, work_ids, m->nu, pu, iu, vu, lu);
     build(work_ids, user_ids, m->nw, pw, iw, vw, lw);
     ALSCHK(hipStreamSynchronize(m->stream));
-    void* old[] = {m->ptr_u, m->ptr_w, m->ids_u, m->ids_w, m->users, m->works, m->val_u, m->val_w};
-    for (void* p : old) als_free(p);
-    m->ptr_u = m->ptr_w = nullptr; m->ids_u = m->ids_w = m->users = m->works = nullptr; m->val_u = m->val_w = nullptr;
-    ALSCHK(hipMalloc((void**)&m->ptr_u, pu.size() * 8));
-    ALSCHK(hipMalloc((void**)&m->ptr_w, pw.size() * 8));
-    ALSCHK(hipMalloc((void**)&m->ids_u, (size_t)n * 4));
-    ALSCHK(hipMalloc((void**)&m->ids_w, (size_t)n * 4));
-    ALSCHK(hipMalloc((void**)&m->val_u, (size_t)n * 8));
-    ALSCHK(hipMalloc((void**)&m->val_w, (size_t)n * 8));
-    ALSCHK(hipMalloc((void**)&m->users, std::max<size_t>(1, lu.size()) * 4));
-    ALSCHK(hipMalloc((void**)&m->works, std::max<size_t>(1, lw.size()) * 4));
+    m->n = 0;
+    ALSCHK(m->ptr_u.reserve((int64_t)pu.size(), m->stream));
+    ALSCHK(m->ptr_w.reserve((int64_t)pw.size(), m->stream));
+    ALSCHK(m->ids_u.reserve(n, m->stream));
+    ALSCHK(m->ids_w.reserve(n, m->stream));
+    ALSCHK(m->val_u.reserve(n, m->stream));
+    ALSCHK(m->val_w.reserve(n, m->stream));
+    ALSCHK(m->users.reserve(std::max<int64_t>(1, (int64_t)lu.size()), m->stream));
+    ALSCHK(m->works.reserve(std::max<int64_t>(1, (int64_t)lw.size()), m->stream));
     ALSCHK(hipMemcpy(m->ptr_u, pu.data(), pu.size() * 8, hipMemcpyHostToDevice));
     ALSCHK(hipMemcpy(m->ptr_w, pw.data(), pw.size() * 8, hipMemcpyHostToDevice));
     ALSCHK(hipMemcpy(m->ids_u, iu.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -384,26 +379,22 @@ int tfr_als_load(tfr_als* m, const int64_t* user_ids, const int64_t* work_ids, c
                 cc[(size_t)r]++;
             }
         }
-        als_free(m->cfirst[z]); als_free(m->ccount[z]); als_free(m->chunk_ent[z]); als_free(m->chunk_lo[z]); als_free(m->chunk_hi[z]);
-        m->cfirst[z] = m->ccount[z] = m->chunk_ent[z] = nullptr; m->chunk_lo[z] = m->chunk_hi[z] = nullptr;
         m->n_chunks[z] = (int64_t)ce.size();
-        ALSCHK(hipMalloc((void**)&m->cfirst[z], (size_t)rows * 4));
-        ALSCHK(hipMalloc((void**)&m->ccount[z], (size_t)rows * 4));
+        ALSCHK(m->cfirst[z].reserve(rows, m->stream));
+        ALSCHK(m->ccount[z].reserve(rows, m->stream));
         ALSCHK(hipMemcpy(m->cfirst[z], cf.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
         ALSCHK(hipMemcpy(m->ccount[z], cc.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
         if (!ce.empty()) {
-            ALSCHK(hipMalloc((void**)&m->chunk_ent[z], ce.size() * 4));
-            ALSCHK(hipMalloc((void**)&m->chunk_lo[z], ce.size() * 8));
-            ALSCHK(hipMalloc((void**)&m->chunk_hi[z], ce.size() * 8));
+            ALSCHK(m->chunk_ent[z].reserve((int64_t)ce.size(), m->stream));
+            ALSCHK(m->chunk_lo[z].reserve((int64_t)ce.size(), m->stream));
+            ALSCHK(m->chunk_hi[z].reserve((int64_t)ce.size(), m->stream));
             ALSCHK(hipMemcpy(m->chunk_ent[z], ce.data(), ce.size() * 4, hipMemcpyHostToDevice));
             ALSCHK(hipMemcpy(m->chunk_lo[z], cl.data(), ce.size() * 8, hipMemcpyHostToDevice));
             ALSCHK(hipMemcpy(m->chunk_hi[z], chh.data(), ce.size() * 8, hipMemcpyHostToDevice));
         }
         max_chunks = std::max(max_chunks, ce.size());
     }
-    als_free(m->partial);
-    m->partial = nullptr;
-    if (max_chunks) ALSCHK(hipMalloc((void**)&m->partial, max_chunks * (size_t)(m->d * m->d + m->d) * 8));
+    ALSCHK(m->partial.reserve((int64_t)max_chunks * (m->d * m->d + m->d), m->stream));
     return TFR_OK;
 }
 
@@ -457,11 +448,11 @@ int tfr_als_predict(tfr_als* m, const int64_t* user_ids, const int64_t* work_ids
         u[(size_t)k] = (int32_t)user_ids[k];
         w[(size_t)k] = (int32_t)work_ids[k];
     }
-    int32_t *du = nullptr, *dw = nullptr;
-    double* dout = nullptr;
-    hipError_t e = hipMalloc((void**)&du, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&dw, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&dout, (size_t)n * 8);
+    DevBuf<int32_t> du, dw;
+    DevBuf<double> dout;
+    hipError_t e = du.reserve(n, m->stream);
+    if (e == hipSuccess) e = dw.reserve(n, m->stream);
+    if (e == hipSuccess) e = dout.reserve(n, m->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(du, u.data(), (size_t)n * 4, hipMemcpyHostToDevice, m->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dw, w.data(), (size_t)n * 4, hipMemcpyHostToDevice, m->stream);
     if (e == hipSuccess) {
@@ -473,7 +464,6 @@ int tfr_als_predict(tfr_als* m, const int64_t* user_ids, const int64_t* work_ids
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n * 8, hipMemcpyDeviceToHost, m->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
-    als_free(du); als_free(dw); als_free(dout);
     if (e != hipSuccess) return als_fail(TFR_ERR_HIP, "als_predict: %s", hipGetErrorString(e));
     return TFR_OK;
 }

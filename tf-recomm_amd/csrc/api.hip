@@ -18,6 +18,7 @@
 #include "svd_kernels.h"
 #include "topk.h"
 #include "finetune.h"
+#include "devbuf.h"
 
 using namespace tfr;
 
@@ -41,6 +42,15 @@ static int fail(int code, const char* fmt, ...) {
 
 struct ProfEvent { hipEvent_t a, b; int kid; };
 
+// an id buffer of the resident-store steps, with the store records of its leading n_recs ids beside it: left there by the
+// stream that filled the ids (in stream order before their chunk's event), so that the small-table step's sorts read one
+// record per id instead of ids -> store.  Reallocating or rewriting the ids clears n_recs.
+struct IdBuf {
+    DevBuf<int64_t> ids;
+    DevBuf<int4> recs;
+    int64_t n_recs = 0;
+};
+
 struct tfr_model {
     int64_t U = 0, I = 0;
     int32_t D = 0, G = 0, VEC = 0;
@@ -49,76 +59,69 @@ struct tfr_model {
     int device = 0;
     hipStream_t own_stream = nullptr, stream = nullptr;
     // tables: index TFR_MU..TFR_Q; slots m, v
-    float* w[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    float* m[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    float* v[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf<float> w[5], m[5], v[5];
     int64_t n[5] = {0, 0, 0, 0, 0};
     uint32_t frozen = 0;
     int64_t step = 0;
     float b1p = 0.f, b2p = 0.f;
     // batch workspace
     int64_t cap = 0;
-    int32_t *d_u = nullptr, *d_i = nullptr;
-    float *d_r = nullptr, *d_logits = nullptr, *d_g = nullptr;
-    int32_t *ks_u = nullptr, *ps_u = nullptr, *ks_i = nullptr, *ps_i = nullptr;
-    int32_t *ks2_u = nullptr, *ps2_u = nullptr, *ks2_i = nullptr, *ps2_i = nullptr;   // rsort ping-pong
-    int32_t *lrank_u = nullptr, *lrank_i = nullptr, *hist_u = nullptr, *hist_i = nullptr;   // csort
-    int32_t *offs_u = nullptr, *offs_i = nullptr, *binbase_u = nullptr, *binbase_i = nullptr;
-    int32_t *blocktot_u = nullptr, *blocktot_i = nullptr;
+    DevBuf<int32_t> d_u, d_i;
+    DevBuf<float> d_r, d_logits, d_g;
+    DevBuf<int32_t> ks_u, ps_u, ks_i, ps_i;
+    DevBuf<int32_t> ks2_u, ps2_u, ks2_i, ps2_i;   // rsort ping-pong
+    DevBuf<int32_t> lrank_u, lrank_i, hist_u, hist_i;   // csort
+    DevBuf<int32_t> offs_u, offs_i, binbase_u, binbase_i;
+    DevBuf<int32_t> blocktot_u, blocktot_i;
     // two-table form of the fused big-table step (RedArgs::sel): the alternate item table, the per-row "which table" word,
     // the per-entry {partner row | old table} words of the current batch; q_dirty = some row may live in q_alt
-    float* q_alt = nullptr; int32_t* q_sel = nullptr; int32_t* osel = nullptr; bool q_dirty = false;
+    DevBuf<float> q_alt; DevBuf<int32_t> q_sel, osel; bool q_dirty = false;
     bool csort_ok = false;
-    float *gq = nullptr, *gp = nullptr, *gbq = nullptr, *gbp = nullptr;
-    int32_t *map_u = nullptr, *map_i = nullptr;
-    float *dg_p = nullptr, *dg_q = nullptr, *dg_bu = nullptr, *dg_bi = nullptr;   // tf1: dense per-row gradients
-    float* partials = nullptr;
-    float* scalars = nullptr;         // {loss, reg, sum_g, -}
-    float* step_out = nullptr;        // per-step {loss, reg, sum_g} ring for multi-step calls
-    int64_t step_out_cap = 0;
-    int32_t* d_err = nullptr;
-    unsigned long long* d_auc = nullptr;   // {2 x rank sum of the positives, number of positives}
+    DevBuf<float> gq, gp, gbq, gbp;
+    DevBuf<int32_t> map_u, map_i;
+    DevBuf<float> dg_p, dg_q, dg_bu, dg_bi;   // tf1: dense per-row gradients
+    DevBuf<float> partials;
+    DevBuf<float> scalars;            // {loss, reg, sum_g, -}
+    DevBuf<float> step_out;           // per-step {loss, reg, sum_g} ring for multi-step calls
+    DevBuf<int32_t> d_err;
+    DevBuf<unsigned long long> d_auc;   // {2 x rank sum of the positives, number of positives}
     const float* last_r = nullptr; int64_t last_B = 0;     // rates of the last host-fed training batch whose logits were kept
     // host-fed calls (tfr_train_step / tfr_forward): one pinned staging buffer each way, so a step is one
     // H2D copy, the kernels and one D2H copy instead of five pageable transfers
-    int32_t* d_in = nullptr; int32_t* h_in = nullptr; float* h_out = nullptr; int64_t stage_cap = 0;
-    int32_t* h_err = nullptr;                                // pinned landing place of the device error flag
+    DevBuf<int32_t> d_in; HostBuf<int32_t> h_in; HostBuf<float> h_out;
+    HostBuf<int32_t> h_err;                                  // pinned landing place of the device error flag
     // look-ahead of the small-table step: the next batch's tile sort, published by the previous launch
-    int4* srt[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};   // [parity][side] sorted records {u, i, r, pos}
+    DevBuf<int4> srt[2][2];                                      // [parity][side] sorted records {u, i, r, pos}
     const int64_t* pf_ids = nullptr; int64_t pf_B = 0; int pf_par = 0; bool pf_valid = false;
     const int64_t* dp_next_ids = nullptr;                        // tfr_dp_hint_next: batch of the next tfr_dp_local_grads
+    DevBuf<unsigned long long> tile_dbg;                         // TFR_TILE_DEBUG=1: per-block stamps of k_tile_step
     // big-table look-ahead: the next batch is gathered and sorted on a second stream into the alternate
     // set of batch buffers while this step's bandwidth-bound kernels run
-    struct SortSet { int32_t *d_u = nullptr, *d_i = nullptr; float* d_r = nullptr;
-                     int32_t *ks_u = nullptr, *ps_u = nullptr, *ks_i = nullptr, *ps_i = nullptr; } alt;
-    int64_t alt_cap = 0;
+    struct SortSet { DevBuf<int32_t> d_u, d_i; DevBuf<float> d_r; DevBuf<int32_t> ks_u, ps_u, ks_i, ps_i; } alt;
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_sorted[2] = {nullptr, nullptr}, ev_free[2] = {nullptr, nullptr}, ev_first = nullptr;
     // tfr_draw_ids_dev / tfr_join_draws / tfr_join_draw: one event per issued draw (ring; draws complete in issue order)
     static const int DRAW_RING = 8;
     hipEvent_t draw_evs[DRAW_RING] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     int64_t draw_count = 0, draw_joined = 0;
-    MtScratch rng_ws = {nullptr, nullptr, nullptr, 0};     // wide form of the id draw (rng.hip), allocated with the generator state
+    // wide form of the id draw (rng.hip), allocated with the generator state; rng_ws points into the three buffers
+    DevBuf<uint32_t> rng_raw; DevBuf<int32_t> rng_counts, rng_hdr;
+    MtScratch rng_ws = {nullptr, nullptr, nullptr, 0};
     hipEvent_t ev_mid = nullptr; bool ev_mid_on = false;   // recorded between the item-side and the user-side kernel of a big-table step
     // resident store
-    int4* store = nullptr;            // {user, item, rate bits, -} per rating
+    DevBuf<int4> store;               // {user, item, rate bits, -} per rating
     int64_t N = 0;
-    int64_t* d_ids = nullptr;
+    IdBuf ids;                        // staged / drawn ids of the resident-store steps
     int64_t n_ids = 0;
-    int64_t d_ids_cap = 0;
     // device id draw (rng.hip): NumPy's MT19937 state {key[624], pos}; draws run on their own stream, ahead
     // of the steps that consume them; one event per drawn chunk
-    uint32_t* d_rng = nullptr;
+    DevBuf<uint32_t> d_rng;
     bool rng_set = false;
     // run-ahead between calls: after a drawn call the generator goes on into the alternate id buffer, so the next
     // call with the same batch size starts on ids that are already there; anything else that looks at the generator
     // first puts it back to the snapshot taken where the consumed ids end
-    int64_t* d_ids_alt = nullptr; int64_t d_ids_alt_cap = 0;
-    // store records of drawn / staged ids, left beside an id buffer by the stream that filled it (one round trip instead of
-    // ids -> store for the small-table step's sorts).  Keyed by the id buffer's address, so the buffers' swaps need no care;
-    // `n` = how many leading ids of that buffer have (or will have, in stream order before their chunk's event) their records.
-    struct RecBuf { const int64_t* ids_base = nullptr; int4* recs = nullptr; int64_t cap = 0; int64_t n = 0; } rb[2];
-    uint32_t* d_rng_snap = nullptr;
+    IdBuf ids_alt;
+    DevBuf<uint32_t> d_rng_snap;
     bool spec_valid = false; int64_t spec_B = 0, spec_N = 0, spec_steps = 0;
     hipEvent_t spec_ev = nullptr;
     hipStream_t stream3 = nullptr;
@@ -126,39 +129,39 @@ struct tfr_model {
     hipEvent_t ev_ids_free = nullptr;
     // host-drawn ids, one step at a time, without a host sync: pinned ring + device ring
     static const int HRING = 4;
-    int64_t* h_ring = nullptr; int64_t* d_ring = nullptr; int64_t ring_cap = 0; int ring_pos = 0;
+    HostBuf<int64_t> h_ring; DevBuf<int64_t> d_ring; int64_t ring_cap = 0; int ring_pos = 0;
     hipEvent_t ring_ev[HRING] = {nullptr, nullptr, nullptr, nullptr};
     // row-sharded step: the routed local batch (tfr_shard_route)
     // Two sets, so that a caller can route (and pre-sort) batch s+1 on a side stream while step s still reads its own:
     // tfr_shard_select picks the set the shard calls fill and consume.
     struct RouteSet {
-        int32_t *mine = nullptr, *u = nullptr, *it = nullptr, *slot = nullptr, *counts = nullptr;
-        float* r = nullptr;
-        int64_t cap = 0, B = 0, slots = 0;
-        int32_t cap_world = 0, world = 0;
+        DevBuf<int32_t> mine, u, it, slot, counts;
+        DevBuf<float> r;
+        int64_t B = 0, slots = 0;
+        int32_t world = 0;
         // sorted orders: of the routed samples by local user row / by request slot (forward + reduce), made by tfr_shard_presort
         // ahead of time or by the step itself; of the requests received as an owner (apply_items)
-        int32_t *ks_u = nullptr, *ps_u = nullptr, *ks_i = nullptr, *ps_i = nullptr;
-        int32_t *akeys = nullptr, *aks = nullptr, *aps = nullptr; int64_t acap = 0;
+        DevBuf<int32_t> ks_u, ps_u, ks_i, ps_i;
+        DevBuf<int32_t> akeys, aks, aps;
         bool sorted_fwd = false; const int32_t* sorted_req = nullptr; int64_t sorted_req_n = 0;
         const int32_t *fks_u = nullptr, *fps_u = nullptr, *fks_i = nullptr, *fps_i = nullptr;   // where the forward's sorted columns are
     } rt[2];
     int rt_sel = 0;
     // resident validation set (svd_train_val.py:33-38: the whole set is one batch)
-    int32_t *ev_u = nullptr, *ev_i = nullptr;
-    float* ev_r = nullptr;
+    DevBuf<int32_t> ev_u, ev_i;
+    DevBuf<float> ev_r;
     int64_t ev_n = 0;
     // top-K (tfr_topk*): the (row, item slice) key lists of one user chunk, the host entries' staged chunk inputs / outputs,
     // and the device entry's exclusion-check word
-    uint64_t* tk_part = nullptr; int64_t tk_part_cap = 0;
-    int32_t* tk_users = nullptr; int64_t tk_users_cap = 0;
-    int64_t* tk_indptr = nullptr; int64_t tk_indptr_cap = 0;
-    int32_t* tk_excl = nullptr; int64_t tk_excl_cap = 0;
-    int32_t* tk_items = nullptr; int64_t tk_out_cap = 0;
-    float* tk_scores = nullptr; int64_t tk_scores_cap = 0;
-    int32_t* tk_bad = nullptr;
+    DevBuf<uint64_t> tk_part;
+    DevBuf<int32_t> tk_users;
+    DevBuf<int64_t> tk_indptr;
+    DevBuf<int32_t> tk_excl;
+    DevBuf<int32_t> tk_items;
+    DevBuf<float> tk_scores;
+    DevBuf<int32_t> tk_bad;
     // batched fine-tuning (tfr_finetune_users): one device buffer for a call's schedule and outputs
-    char* ft_buf = nullptr; int64_t ft_cap = 0;
+    DevBuf<char> ft_buf;
     // profiling
     bool prof = false;
     std::vector<ProfEvent> events;
@@ -174,16 +177,19 @@ static int bits_for(int64_t rows) {
     return b;
 }
 
-template <typename T>
-static int dmalloc(T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    HIPCHK(hipMalloc((void**)p, count * sizeof(T)));
-    return TFR_OK;
+// reserve n elements in each buffer of a group (stops at the first failure)
+template <typename... Bufs>
+static hipError_t reserve_each(int64_t n, hipStream_t s, Bufs&... b) {
+    hipError_t e = hipSuccess;
+    (void)((e = b.reserve(n, s), e == hipSuccess) && ...);
+    return e;
 }
 
-static void dfree(void* p) {
-    if (p) (void)hipFree(p);
+// the growth policy of the batch-sized buffers: powers of two from 1024
+static int64_t pow2_cap(int64_t n) {
+    int64_t c = 1024;
+    while (c < n) c <<= 1;
+    return c;
 }
 
 struct Prof {
@@ -222,87 +228,40 @@ static int drain_profile(tfr_model* m) {
     return TFR_OK;
 }
 
-static void free_workspace(tfr_model* m) {
-    dfree(m->d_u); dfree(m->d_i); dfree(m->d_r); dfree(m->d_logits); dfree(m->d_g);
-    dfree(m->ks_u); dfree(m->ps_u); dfree(m->ks_i); dfree(m->ps_i);
-    dfree(m->ks2_u); dfree(m->ps2_u); dfree(m->ks2_i); dfree(m->ps2_i); dfree(m->gq); dfree(m->gp); dfree(m->gbq); dfree(m->gbp);
-    dfree(m->partials); dfree(m->lrank_u); dfree(m->lrank_i); dfree(m->hist_u); dfree(m->hist_i);
-    dfree(m->offs_u); dfree(m->offs_i); dfree(m->binbase_u); dfree(m->binbase_i);
-    dfree(m->blocktot_u); dfree(m->blocktot_i);
-    dfree(m->osel); m->osel = nullptr;
-    for (int pz = 0; pz < 2; ++pz) for (int sd = 0; sd < 2; ++sd) { dfree(m->srt[pz][sd]); m->srt[pz][sd] = nullptr; }
-    dfree(m->d_in); m->d_in = nullptr;
-    if (m->h_in) (void)hipHostFree(m->h_in);
-    if (m->h_out) (void)hipHostFree(m->h_out);
-    if (m->h_err) (void)hipHostFree(m->h_err);
-    m->h_err = nullptr;
-    m->h_in = nullptr; m->h_out = nullptr; m->stage_cap = 0;
-    dfree(m->alt.d_u); dfree(m->alt.d_i); dfree(m->alt.d_r); dfree(m->alt.ks_u); dfree(m->alt.ps_u); dfree(m->alt.ks_i); dfree(m->alt.ps_i);
-    m->alt = tfr_model::SortSet(); m->alt_cap = 0;
-    m->pf_valid = false;
-    m->blocktot_u = m->blocktot_i = nullptr;
-    m->lrank_u = m->lrank_i = m->hist_u = m->hist_i = nullptr;
-    m->offs_u = m->offs_i = m->binbase_u = m->binbase_i = nullptr;
-    m->d_u = m->d_i = nullptr; m->d_r = m->d_logits = m->d_g = nullptr;
-    m->ks_u = m->ps_u = m->ks_i = m->ps_i = nullptr;
-    m->ks2_u = m->ps2_u = m->ks2_i = m->ps2_i = nullptr; m->gq = m->gp = m->gbq = m->gbp = nullptr; m->partials = nullptr;
-    m->cap = 0;
-}
-
 static int ensure_capacity(tfr_model* m, int64_t B) {
     if (B <= m->cap) return TFR_OK;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    free_workspace(m);
-    int64_t cap = 1024;
-    while (cap < B) cap <<= 1;
+    const int64_t cap = pow2_cap(B);
     if (cap > (int64_t)1 << 30) return fail(TFR_ERR_ARG, "batch %lld too large", (long long)B);
-    int rc;
-    if ((rc = dmalloc(&m->d_u, cap))) return rc;
-    if ((rc = dmalloc(&m->d_i, cap))) return rc;
-    if ((rc = dmalloc(&m->d_r, cap))) return rc;
-    if ((rc = dmalloc(&m->d_logits, cap + 4))) return rc;          // + {loss, reg, sum g, error flag} behind the logits
-    if ((rc = dmalloc(&m->d_g, cap))) return rc;
-    if ((rc = dmalloc(&m->ks_u, cap))) return rc;
-    if ((rc = dmalloc(&m->ps_u, cap))) return rc;
-    if ((rc = dmalloc(&m->ks_i, cap))) return rc;
-    if ((rc = dmalloc(&m->ps_i, cap))) return rc;
-    if ((rc = dmalloc(&m->ks2_u, cap))) return rc;
-    if ((rc = dmalloc(&m->ps2_u, cap))) return rc;
-    if ((rc = dmalloc(&m->ks2_i, cap))) return rc;
-    if ((rc = dmalloc(&m->ps2_i, cap))) return rc;
+    hipStream_t s = m->stream;
+    m->cap = 0;
+    m->pf_valid = false;
+    HIPCHK(reserve_each(cap, s, m->d_u, m->d_i, m->d_r));
+    HIPCHK(m->d_logits.reserve(cap + 4, s));          // + {loss, reg, sum g, error flag} behind the logits
+    HIPCHK(reserve_each(cap, s, m->d_g, m->ks_u, m->ps_u, m->ks_i, m->ps_i, m->ks2_u, m->ps2_u, m->ks2_i, m->ps2_i));
     const bool tf1_ws = m->o.optimizer == TFR_OPT_ADAM && m->o.adam_mode == TFR_ADAM_TF1;
     // non-tf1: second third of gq parks the pieces of split user runs, the last third the
     // per-entry copies of pre-update item rows the fused user side reads
-    if ((rc = dmalloc(&m->gq, (size_t)cap * m->D * (tf1_ws ? 1 : 3)))) return rc;
-    if ((rc = dmalloc(&m->gbq, cap))) return rc;
-    for (int pz = 0; pz < 2; ++pz)
-        for (int sd = 0; sd < 2; ++sd)
-            if ((rc = dmalloc(&m->srt[pz][sd], cap))) return rc;
-    m->pf_valid = false;
-    if ((rc = dmalloc(&m->gbp, cap))) return rc;
-    if (tf1_ws)
-        if ((rc = dmalloc(&m->gp, (size_t)cap * m->D))) return rc;
+    HIPCHK(m->gq.reserve(cap * m->D * (tf1_ws ? 1 : 3), s));
+    HIPCHK(reserve_each(cap, s, m->gbq, m->srt[0][0], m->srt[0][1], m->srt[1][0], m->srt[1][1], m->gbp));
+    if (tf1_ws) HIPCHK(m->gp.reserve(cap * m->D, s));
     {   // per-block {loss, reg, sum g}: the forward launches <= 8192 blocks, the reduce with the
         // forward fused in one block per 1024/G sorted entries
-        const size_t nb = (size_t)(cap + 1024 / m->G - 1) / (1024 / m->G);
-        if ((rc = dmalloc(&m->partials, (nb > 8192 ? nb : 8192) * 4))) return rc;
+        const int64_t nb = (cap + 1024 / m->G - 1) / (1024 / m->G);
+        HIPCHK(m->partials.reserve((nb > 8192 ? nb : 8192) * 4, s));
     }
     {
-        const size_t ntiles = (size_t)(cap + CSORT_TILE - 1) / CSORT_TILE;
+        const int64_t ntiles = (cap + CSORT_TILE - 1) / CSORT_TILE;
         const bool small = (1 << (m->bits_u > m->bits_i ? m->bits_u : m->bits_i)) <= CSORT_MAX_BINS;
-        const size_t hu = (small ? ((size_t)1 << m->bits_u) : 256) * ntiles;
-        const size_t hi = (small ? ((size_t)1 << m->bits_i) : 256) * ntiles;
-        if ((rc = dmalloc(&m->osel, cap))) return rc;
-        if ((rc = dmalloc(&m->lrank_u, cap))) return rc;
-        if ((rc = dmalloc(&m->lrank_i, cap))) return rc;
-        if ((rc = dmalloc(&m->hist_u, hu > 256 * ntiles ? hu : 256 * ntiles))) return rc;
-        if ((rc = dmalloc(&m->hist_i, hi > 256 * ntiles ? hi : 256 * ntiles))) return rc;
-        if ((rc = dmalloc(&m->offs_u, hu > 256 * ntiles ? hu : 256 * ntiles))) return rc;
-        if ((rc = dmalloc(&m->offs_i, hi > 256 * ntiles ? hi : 256 * ntiles))) return rc;
-        if ((rc = dmalloc(&m->binbase_u, small ? (size_t)1 << m->bits_u : 1))) return rc;
-        if ((rc = dmalloc(&m->binbase_i, small ? (size_t)1 << m->bits_i : 1))) return rc;
-        if ((rc = dmalloc(&m->blocktot_u, 64 + 256 * ntiles / 4096))) return rc;
-        if ((rc = dmalloc(&m->blocktot_i, 64 + 256 * ntiles / 4096))) return rc;
+        const int64_t hu = std::max((small ? ((int64_t)1 << m->bits_u) : 256) * ntiles, 256 * ntiles);
+        const int64_t hi = std::max((small ? ((int64_t)1 << m->bits_i) : 256) * ntiles, 256 * ntiles);
+        HIPCHK(reserve_each(cap, s, m->osel, m->lrank_u, m->lrank_i));
+        HIPCHK(m->hist_u.reserve(hu, s));
+        HIPCHK(m->hist_i.reserve(hi, s));
+        HIPCHK(m->offs_u.reserve(hu, s));
+        HIPCHK(m->offs_i.reserve(hi, s));
+        HIPCHK(m->binbase_u.reserve(small ? (int64_t)1 << m->bits_u : 1, s));
+        HIPCHK(m->binbase_i.reserve(small ? (int64_t)1 << m->bits_i : 1, s));
+        HIPCHK(reserve_each(64 + 256 * ntiles / 4096, s, m->blocktot_u, m->blocktot_i));
         m->csort_ok = small;
     }
     m->cap = cap;
@@ -311,39 +270,29 @@ static int ensure_capacity(tfr_model* m, int64_t B) {
 
 static int cancel_run_ahead(tfr_model* m);
 
-static int ensure_step_out(tfr_model* m, int64_t nsteps) {
-    if (nsteps <= m->step_out_cap) return TFR_OK;
+// clear the device error flag e (just read back) and name its cause
+static int device_error(tfr_model* m, int32_t e) {
+    HIPCHK(hipMemsetAsync(m->d_err, 0, sizeof(int32_t), m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
-    dfree(m->step_out);
-    m->step_out = nullptr;
-    m->step_out_cap = 0;
-    int rc;
-    if ((rc = dmalloc(&m->step_out, (size_t)nsteps * 4))) return rc;
-    m->step_out_cap = nsteps;
-    return TFR_OK;
+    if (e & 1) return fail(TFR_ERR_OOB, "user/item id out of range [0,%lld) / [0,%lld)",
+                           (long long)m->U, (long long)m->I);
+    if (e == 8) return fail(TFR_ERR_OOB, "row-sharded step: another rank voided the step (capacity exceeded or id out of range there) - "
+                                         "it was void on every rank; that rank's sync names the cause");
+    if (e == 16) return fail(TFR_ERR_ARG, "top-K exclusion CSR: a row is not non-decreasing (or indptr is)");
+    if (e & 4) return fail(TFR_ERR_OOB, "row-sharded step: more local samples or distinct items per owner than the fixed capacities "
+                                        "(sample_cap / slot_cap) hold - the step was void; raise the slack");
+    return fail(TFR_ERR_OOB, "store index out of range [0,%lld)", (long long)m->N);
 }
 
 // read + clear the device error flag (stream must be idle or this call synchronises)
 static int check_device_error(tfr_model* m) {
     // the flag lands in pinned memory: a pageable destination turns the 4-byte copy into a staged, blocking one
-    if (!m->h_err) HIPCHK(hipHostMalloc((void**)&m->h_err, 64, hipHostMallocDefault));
+    HIPCHK(m->h_err.reserve(16, m->stream));
     *m->h_err = 0;
     HIPCHK(hipMemcpyAsync(m->h_err, m->d_err, sizeof(int32_t), hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     const int32_t e = *m->h_err;
-    if (e) {
-        HIPCHK(hipMemsetAsync(m->d_err, 0, sizeof(int32_t), m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));
-        if (e & 1) return fail(TFR_ERR_OOB, "user/item id out of range [0,%lld) / [0,%lld)",
-                               (long long)m->U, (long long)m->I);
-        if (e == 8) return fail(TFR_ERR_OOB, "row-sharded step: another rank voided the step (capacity exceeded or id out of range there) - "
-                                             "it was void on every rank; that rank's sync names the cause");
-        if (e == 16) return fail(TFR_ERR_ARG, "top-K exclusion CSR: a row is not non-decreasing (or indptr is)");
-        if (e & 4) return fail(TFR_ERR_OOB, "row-sharded step: more local samples or distinct items per owner than the fixed capacities "
-                                            "(sample_cap / slot_cap) hold - the step was void; raise the slack");
-        return fail(TFR_ERR_OOB, "store index out of range [0,%lld)", (long long)m->N);
-    }
-    return TFR_OK;
+    return e ? device_error(m, e) : TFR_OK;
 }
 
 #define MODEL_ENTER(m)                                                \
@@ -405,9 +354,8 @@ int tfr_device_copy_rate(int32_t device, int64_t bytes, int32_t reps, double* be
     if (bytes < (1 << 20) || reps < 1 || reps > 1000 || !best_gbs) return fail(TFR_ERR_ARG, "tfr_device_copy_rate: bad argument");
     HIPCHK(hipSetDevice(device));
     const int64_t n4 = bytes / 16;
-    copy_f4 *a = nullptr, *b = nullptr;
-    HIPCHK(hipMalloc(&a, n4 * 16));
-    if (hipMalloc(&b, n4 * 16) != hipSuccess) { (void)hipFree(a); return fail(TFR_ERR_NOMEM, "tfr_device_copy_rate: out of memory"); }
+    DevBuf<copy_f4> a, b;                                // freed on return, with `device` current
+    if (reserve_each(n4, nullptr, a, b) != hipSuccess) return fail(TFR_ERR_NOMEM, "tfr_device_copy_rate: out of memory");
     hipStream_t st;
     HIPCHK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     (void)hipMemsetAsync(a, 1, n4 * 16, st);
@@ -431,8 +379,6 @@ int tfr_device_copy_rate(int32_t device, int64_t bytes, int32_t reps, double* be
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     (void)hipStreamDestroy(st);
-    (void)hipFree(a);
-    (void)hipFree(b);
     *best_gbs = best;
     if (mean_gbs) *mean_gbs = sum / reps;
     return TFR_OK;
@@ -440,38 +386,62 @@ int tfr_device_copy_rate(int32_t device, int64_t bytes, int32_t reps, double* be
 
 int tfr_destroy(tfr_model* m) {
     if (!m) return TFR_OK;
-    (void)hipSetDevice(m->device);
+    (void)hipSetDevice(m->device);                       // the buffers are freed with the model's device current
     if (m->stream) (void)hipStreamSynchronize(m->stream);
+    if (m->stream2) (void)hipStreamSynchronize(m->stream2);
+    if (m->stream3) (void)hipStreamSynchronize(m->stream3);
     for (auto& e : m->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-    free_workspace(m);
-    for (int t = 0; t < 5; ++t) { dfree(m->w[t]); dfree(m->m[t]); dfree(m->v[t]); }
-    dfree(m->q_alt); dfree(m->q_sel);
-    dfree(m->map_u); dfree(m->map_i); dfree(m->dg_p); dfree(m->dg_q); dfree(m->dg_bu); dfree(m->dg_bi); dfree(m->scalars); dfree(m->step_out); dfree(m->d_err);
-    dfree(m->store); dfree(m->d_auc);
-    dfree(m->d_ids); dfree(m->ev_u); dfree(m->ev_i); dfree(m->ev_r);
-    if (m->stream2) { (void)hipStreamSynchronize(m->stream2); (void)hipStreamDestroy(m->stream2); }
-    if (m->stream3) { (void)hipStreamSynchronize(m->stream3); (void)hipStreamDestroy(m->stream3); }
     for (auto e : m->chunk_ev) (void)hipEventDestroy(e);
     if (m->ev_ids_free) (void)hipEventDestroy(m->ev_ids_free);
-    dfree(m->d_rng); dfree(m->d_ring); dfree(m->d_ids_alt); dfree(m->d_rng_snap);
-    dfree(m->rb[0].recs); dfree(m->rb[1].recs);
-    dfree(m->rng_ws.raw); dfree(m->rng_ws.counts); dfree(m->rng_ws.hdr);
-    for (auto& R : m->rt) {
-        dfree(R.mine); dfree(R.u); dfree(R.it); dfree(R.r); dfree(R.slot); dfree(R.counts);
-        dfree(R.ks_u); dfree(R.ps_u); dfree(R.ks_i); dfree(R.ps_i); dfree(R.akeys); dfree(R.aks); dfree(R.aps);
-    }
-    dfree(m->tk_part); dfree(m->tk_users); dfree(m->tk_indptr); dfree(m->tk_excl); dfree(m->tk_items); dfree(m->tk_scores);
-    dfree(m->tk_bad);
-    dfree(m->ft_buf);
     if (m->spec_ev) (void)hipEventDestroy(m->spec_ev);
-    if (m->h_ring) (void)hipHostFree(m->h_ring);
     for (int z = 0; z < tfr_model::HRING; ++z) if (m->ring_ev[z]) (void)hipEventDestroy(m->ring_ev[z]);
     for (int z = 0; z < 2; ++z) { if (m->ev_sorted[z]) (void)hipEventDestroy(m->ev_sorted[z]); if (m->ev_free[z]) (void)hipEventDestroy(m->ev_free[z]); }
     if (m->ev_first) (void)hipEventDestroy(m->ev_first);
     if (m->ev_mid) (void)hipEventDestroy(m->ev_mid);
     for (auto& e : m->draw_evs) if (e) (void)hipEventDestroy(e);
+    if (m->stream2) (void)hipStreamDestroy(m->stream2);
+    if (m->stream3) (void)hipStreamDestroy(m->stream3);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
     delete m;
+    return TFR_OK;
+}
+
+// the tables (zeroed), their optimiser slots and the per-model scratch
+static int alloc_model(tfr_model* m) {
+    hipStream_t s = m->stream;
+    const int64_t U = m->U, I = m->I, D = m->D;
+    const bool adam = m->o.optimizer == TFR_OPT_ADAM;
+    for (int t = 0; t < 5; ++t) {
+        HIPCHK(m->w[t].reserve(m->n[t], s));
+        HIPCHK(hipMemsetAsync(m->w[t], 0, (size_t)m->n[t] * 4, s));
+        if (adam) {
+            HIPCHK(reserve_each(m->n[t], s, m->m[t], m->v[t]));
+            HIPCHK(hipMemsetAsync(m->m[t], 0, (size_t)m->n[t] * 4, s));
+            HIPCHK(hipMemsetAsync(m->v[t], 0, (size_t)m->n[t] * 4, s));
+        }
+    }
+    if (adam && m->o.adam_mode == TFR_ADAM_TF1) {
+        HIPCHK(m->map_u.reserve(U, s));
+        HIPCHK(m->map_i.reserve(I, s));
+        HIPCHK(hipMemsetAsync(m->map_u, 0, (size_t)U * 4, s));
+        HIPCHK(hipMemsetAsync(m->map_i, 0, (size_t)I * 4, s));
+        // dense per-row gradient buffers for the TF1 sweep, while they stay small (<= 256 MB)
+        if ((size_t)(U + I) * (D + 1) * 4 <= ((size_t)256 << 20)) {
+            HIPCHK(m->dg_p.reserve(U * D, s));
+            HIPCHK(m->dg_q.reserve(I * D, s));
+            HIPCHK(m->dg_bu.reserve(U, s));
+            HIPCHK(m->dg_bi.reserve(I, s));
+            HIPCHK(hipMemsetAsync(m->dg_p, 0, (size_t)U * D * 4, s));
+            HIPCHK(hipMemsetAsync(m->dg_q, 0, (size_t)I * D * 4, s));
+            HIPCHK(hipMemsetAsync(m->dg_bu, 0, (size_t)U * 4, s));
+            HIPCHK(hipMemsetAsync(m->dg_bi, 0, (size_t)I * 4, s));
+        }
+    }
+    HIPCHK(m->scalars.reserve(4, s));
+    HIPCHK(m->d_err.reserve(1, s));
+    HIPCHK(hipMemsetAsync(m->scalars, 0, 16, s));
+    HIPCHK(hipMemsetAsync(m->d_err, 0, 4, s));
+    HIPCHK(hipStreamSynchronize(s));
     return TFR_OK;
 }
 
@@ -507,58 +477,12 @@ int tfr_create(tfr_model** out, int64_t U, int64_t I, int32_t D, const tfr_opts*
     memset(m->prof_ms, 0, sizeof(m->prof_ms));
     memset(m->prof_n, 0, sizeof(m->prof_n));
     int rc = TFR_OK;
-    do {
-        if (hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) != hipSuccess) {
-            rc = fail(TFR_ERR_HIP, "hipStreamCreate failed");
-            break;
-        }
+    if (hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking) != hipSuccess) {
+        rc = fail(TFR_ERR_HIP, "hipStreamCreate failed");
+    } else {
         m->stream = m->own_stream;
-        const bool adam = opts->optimizer == TFR_OPT_ADAM;
-        for (int t = 0; t < 5 && rc == TFR_OK; ++t) {
-            rc = dmalloc(&m->w[t], (size_t)m->n[t]);
-            if (rc == TFR_OK && hipMemsetAsync(m->w[t], 0, (size_t)m->n[t] * 4, m->stream) != hipSuccess)
-                rc = fail(TFR_ERR_HIP, "memset failed");
-            if (rc == TFR_OK && adam) {
-                rc = dmalloc(&m->m[t], (size_t)m->n[t]);
-                if (rc == TFR_OK) rc = dmalloc(&m->v[t], (size_t)m->n[t]);
-                if (rc == TFR_OK && (hipMemsetAsync(m->m[t], 0, (size_t)m->n[t] * 4, m->stream) != hipSuccess ||
-                                     hipMemsetAsync(m->v[t], 0, (size_t)m->n[t] * 4, m->stream) != hipSuccess))
-                    rc = fail(TFR_ERR_HIP, "memset failed");
-            }
-        }
-        if (rc) break;
-        if (adam && opts->adam_mode == TFR_ADAM_TF1) {
-            if ((rc = dmalloc(&m->map_u, (size_t)U))) break;
-            if ((rc = dmalloc(&m->map_i, (size_t)I))) break;
-            if (hipMemsetAsync(m->map_u, 0, (size_t)U * 4, m->stream) != hipSuccess ||
-                hipMemsetAsync(m->map_i, 0, (size_t)I * 4, m->stream) != hipSuccess) {
-                rc = fail(TFR_ERR_HIP, "memset failed");
-                break;
-            }
-            // dense per-row gradient buffers for the TF1 sweep, while they stay small (<= 256 MB)
-            if ((size_t)(U + I) * (D + 1) * 4 <= ((size_t)256 << 20)) {
-                if ((rc = dmalloc(&m->dg_p, (size_t)U * D))) break;
-                if ((rc = dmalloc(&m->dg_q, (size_t)I * D))) break;
-                if ((rc = dmalloc(&m->dg_bu, (size_t)U))) break;
-                if ((rc = dmalloc(&m->dg_bi, (size_t)I))) break;
-                if (hipMemsetAsync(m->dg_p, 0, (size_t)U * D * 4, m->stream) != hipSuccess ||
-                    hipMemsetAsync(m->dg_q, 0, (size_t)I * D * 4, m->stream) != hipSuccess ||
-                    hipMemsetAsync(m->dg_bu, 0, (size_t)U * 4, m->stream) != hipSuccess ||
-                    hipMemsetAsync(m->dg_bi, 0, (size_t)I * 4, m->stream) != hipSuccess) {
-                    rc = fail(TFR_ERR_HIP, "memset failed");
-                    break;
-                }
-            }
-        }
-        if ((rc = dmalloc(&m->scalars, 4))) break;
-        if ((rc = dmalloc(&m->d_err, 1))) break;
-        if (hipMemsetAsync(m->scalars, 0, 16, m->stream) != hipSuccess ||
-            hipMemsetAsync(m->d_err, 0, 4, m->stream) != hipSuccess ||
-            hipStreamSynchronize(m->stream) != hipSuccess) {
-            rc = fail(TFR_ERR_HIP, "init failed: %s", hipGetErrorString(hipGetLastError()));
-            break;
-        }
-    } while (0);
+        rc = alloc_model(m);
+    }
     if (rc) {
         char keep[512];
         strncpy(keep, g_err, sizeof(keep));
@@ -931,46 +855,36 @@ static int front_and_sort(tfr_model* m, const int32_t*& du, const int32_t*& di, 
 // resident store): was this batch's tile sort published by the previous launch?  Is there a next
 // batch to sort in this one?  The packed tables and the sorted records are double-buffered by step
 // parity (hist_* / offs_* serve as the two tables).  *par_out = which table set k_dense_tiles reads.
-// ---- record buffers (tfr_model::RecBuf) ----------------------------------------------------------------
+// ---- store records beside the id buffers (IdBuf) ---------------------------------------------------------
 static bool recs_on() {                                  // TFR_RECS=0: A/B switch
     static int on = -1;
     if (on < 0) { const char* e = getenv("TFR_RECS"); on = (e && e[0] == '0') ? 0 : 1; }
     return on == 1;
 }
-static void recs_forget(tfr_model* m) { m->rb[0].n = 0; m->rb[1].n = 0; }      // the store changed / an id buffer was rewritten elsewhere
-// the record buffer that goes with the id buffer at `base` (capacity `cap` ids); a slot whose id buffer is gone is reused
-static tfr_model::RecBuf* recs_slot(tfr_model* m, const int64_t* base, int64_t cap) {
-    if (!recs_on() || !base) return nullptr;
-    tfr_model::RecBuf* r = nullptr;
-    for (int k = 0; k < 2; ++k) if (m->rb[k].ids_base == base) r = &m->rb[k];
-    if (!r) {
-        for (int k = 0; k < 2 && !r; ++k)
-            if (m->rb[k].ids_base != m->d_ids && m->rb[k].ids_base != m->d_ids_alt) r = &m->rb[k];
-        if (!r) return nullptr;
-        r->ids_base = base; r->n = 0;
-    }
-    if (r->cap < cap) {                                  // the old records' readers: the id buffer they went with was freed after a sync
-        dfree(r->recs);
-        r->recs = nullptr; r->cap = 0; r->n = 0;
-        if (hipMalloc((void**)&r->recs, (size_t)cap * sizeof(int4)) != hipSuccess) { (void)hipGetLastError(); r->ids_base = nullptr; return nullptr; }
-        r->cap = cap;
-    }
-    return r;
+static void recs_forget(tfr_model* m) { m->ids.n_recs = 0; m->ids_alt.n_recs = 0; }      // the store changed
+// does [p, p + n) overlap the id buffer b?
+static bool ids_overlap(const IdBuf& b, const int64_t* p, int64_t n) {
+    const int64_t* base = b.ids;
+    return base && p < base + b.ids.capacity() && base < p + n;
 }
-// after a run of ids [off, off + count) of the buffer at `base` was written on stream `st`: gather their records behind it
-static void recs_follow(tfr_model* m, const int64_t* base, int64_t cap, int64_t off, int64_t count, hipStream_t st) {
-    tfr_model::RecBuf* r = recs_slot(m, base, cap);
-    if (!r) return;
-    if (off > r->n) { r->n = 0; return; }                // a gap: nothing before `off` is known to have records
-    launch_gather_recs(base + off, m->store, r->recs + off, count, m->N, st);
-    r->n = off + count;
-}
-static const int4* recs_for(tfr_model* m, const int64_t* ids, int64_t B) {
-    if (!ids || !recs_on()) return nullptr;
-    for (int k = 0; k < 2; ++k) {
-        const tfr_model::RecBuf& r = m->rb[k];
-        if (r.recs && r.ids_base && ids >= r.ids_base && (ids - r.ids_base) + B <= r.n) return r.recs + (ids - r.ids_base);
+// after a run of ids [off, off + count) of b was written on stream `st`: gather their records behind it.  Without room
+// for the records (allocation failed) the step reads ids -> store as without them.
+static void recs_follow(tfr_model* m, IdBuf& b, int64_t off, int64_t count, hipStream_t st) {
+    if (!recs_on()) return;
+    if (b.recs.capacity() < b.ids.capacity()) {          // the old records' readers: the id buffer they went with was freed after a sync
+        b.n_recs = 0;
+        b.recs.reset();
+        if (b.recs.reserve(b.ids.capacity(), st) != hipSuccess) { (void)hipGetLastError(); return; }
     }
+    if (off > b.n_recs) { b.n_recs = 0; return; }        // a gap: nothing before `off` is known to have records
+    launch_gather_recs(b.ids + off, m->store, b.recs + off, count, m->N, st);
+    b.n_recs = off + count;
+}
+// the records of ids [p, p + B) when p points into one of the model's id buffers and they are all there
+static const int4* recs_for(tfr_model* m, const int64_t* p, int64_t B) {
+    if (!p || !recs_on()) return nullptr;
+    for (const IdBuf* b : {&m->ids, &m->ids_alt})
+        if (ids_overlap(*b, p, 1) && (p - b->ids.get()) + B <= b->n_recs) return b->recs + (p - b->ids.get());
     return nullptr;
 }
 
@@ -1009,9 +923,9 @@ static int tile_step_launch(tfr_model* m, const int32_t* du, const int32_t* di, 
     *nblk_out = ts.ntiles * m->G;            // one {loss, reg, sum g} slot per piece
     static int dbg_on = -1;                  // TFR_TILE_DEBUG=1: per-block start / end stamps of every launch on stderr (synchronises)
     if (dbg_on < 0) { const char* e = getenv("TFR_TILE_DEBUG"); dbg_on = (e && e[0] == '1') ? 1 : 0; }
-    static unsigned long long* d_dbg = nullptr;
-    if (dbg_on && !d_dbg) (void)hipMalloc((void**)&d_dbg, 2048 * 64);
-    if (dbg_on && d_dbg && 2 * (ts.next_ntiles + ts.ntiles * m->G) <= 2048) { (void)hipMemsetAsync(d_dbg, 0, 2048 * 64, m->stream); ts.dbg = d_dbg; }
+    if (dbg_on && m->tile_dbg.reserve(2048 * 8, m->stream) != hipSuccess) (void)hipGetLastError();
+    unsigned long long* d_dbg = m->tile_dbg;
+    if (d_dbg && 2 * (ts.next_ntiles + ts.ntiles * m->G) <= 2048) { (void)hipMemsetAsync(d_dbg, 0, 2048 * 64, m->stream); ts.dbg = d_dbg; }
     {
         Prof p(m, TFR_K_REDUCE_ITEM);
         launch_tile_step(ts, m->G, m->VEC, m->stream);
@@ -1082,9 +996,15 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
         static int dualq = -1;
         if (dualq < 0) { const char* e = getenv("TFR_DUALQ"); dualq = (e && e[0] == '0') ? 0 : 1; }
         const bool dual = fwd_fused && dualq;
-        if (dual && !m->q_alt) {
-            if ((rc = dmalloc(&m->q_alt, (size_t)m->n[TFR_Q])) || (rc = dmalloc(&m->q_sel, (size_t)m->I))) return rc;
-            HIPCHK(hipMemsetAsync(m->q_sel, 0, (size_t)m->I * 4, s));
+        if (dual && !(m->q_alt && m->q_sel)) {           // both tables or neither
+            hipError_t e = m->q_alt.reserve(m->n[TFR_Q], s);
+            if (e == hipSuccess) e = m->q_sel.reserve(m->I, s);
+            if (e == hipSuccess) e = hipMemsetAsync(m->q_sel, 0, (size_t)m->I * 4, s);
+            if (e != hipSuccess) {
+                m->q_alt.reset();
+                m->q_sel.reset();
+                return fail(e == hipErrorOutOfMemory ? TFR_ERR_NOMEM : TFR_ERR_HIP, "two-table step: %s", hipGetErrorString(e));
+            }
         }
         if (!dual && (rc = settle_q(m))) return rc;
         static int split_tiles = -1;   // TFR_TILE_SPLIT=1: the three-launch form (k_front + k_seg_reduce), kept for A/B
@@ -1301,27 +1221,11 @@ static void rollback_step(tfr_model* m, int64_t step0, float b1p0, float b2p0) {
 // pinned staging for host-fed batches up to 1M ratings (larger ones take the plain copies)
 static const int64_t STAGE_MAX = 1 << 20;
 static int ensure_staging(tfr_model* m, int64_t B) {
-    if (B <= m->stage_cap) return TFR_OK;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    dfree(m->d_in); m->d_in = nullptr;
-    if (m->h_in) (void)hipHostFree(m->h_in);
-    if (m->h_out) (void)hipHostFree(m->h_out);
-    m->h_in = nullptr; m->h_out = nullptr; m->stage_cap = 0;
-    int64_t cap = 1024;
-    while (cap < B) cap *= 2;
-    int rc;
-    if ((rc = dmalloc(&m->d_in, (size_t)3 * cap))) return rc;
-    HIPCHK(hipHostMalloc((void**)&m->h_in, (size_t)3 * cap * 4, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&m->h_out, (size_t)(cap + 4) * 4, hipHostMallocDefault));
-    m->stage_cap = cap;
+    const int64_t cap = pow2_cap(B);
+    HIPCHK(m->d_in.reserve(3 * cap, m->stream));
+    HIPCHK(m->h_in.reserve(3 * cap, m->stream));
+    HIPCHK(m->h_out.reserve(cap + 4, m->stream));
     return TFR_OK;
-}
-
-static int report_device_error(tfr_model* m, int32_t e) {
-    HIPCHK(hipMemsetAsync(m->d_err, 0, sizeof(int32_t), m->stream));
-    HIPCHK(hipStreamSynchronize(m->stream));
-    if (e & 1) return fail(TFR_ERR_OOB, "user/item id out of range [0,%lld) / [0,%lld)", (long long)m->U, (long long)m->I);
-    return fail(TFR_ERR_OOB, "store index out of range [0,%lld)", (long long)m->N);
 }
 
 static int check_batch(const void* u, const void* i, int64_t B) {
@@ -1372,7 +1276,7 @@ int tfr_forward(tfr_model* m, const int32_t* u, const int32_t* i, int64_t B, flo
 static int auc_device(tfr_model* m, const float* d_score, const float* d_label, int64_t n, double* auc_out) {
     int rc;
     if ((rc = ensure_capacity(m, n))) return rc;
-    if (!m->d_auc) { if ((rc = dmalloc(&m->d_auc, 2))) return rc; }
+    HIPCHK(m->d_auc.reserve(2, m->stream));
     hipStream_t s = m->stream;
     HIPCHK(hipMemsetAsync(m->d_auc, 0, 16, s));
     launch_auc_keys(d_score, m->d_i, n, s);              // d_i: batch-sized int scratch
@@ -1434,19 +1338,14 @@ int tfr_upload_eval_triples(tfr_model* m, const int32_t* u, const int32_t* i, co
     MODEL_ENTER(m);
     if (N < 1 || !u || !i || !r) return fail(TFR_ERR_ARG, "upload_eval_triples: need n >= 1 and non-null columns");
     HIPCHK(hipStreamSynchronize(m->stream));
-    dfree(m->ev_u); dfree(m->ev_i); dfree(m->ev_r);
-    m->ev_u = m->ev_i = nullptr; m->ev_r = nullptr; m->ev_n = 0;
-    int rc;
-    if ((rc = dmalloc(&m->ev_u, (size_t)N))) return rc;
-    if ((rc = dmalloc(&m->ev_i, (size_t)N))) return rc;
-    if ((rc = dmalloc(&m->ev_r, (size_t)N))) return rc;
+    m->ev_n = 0;
+    HIPCHK(reserve_each(N, m->stream, m->ev_u, m->ev_i, m->ev_r));
     HIPCHK(hipMemcpyAsync(m->ev_u, u, (size_t)N * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(m->ev_i, i, (size_t)N * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(m->ev_r, r, (size_t)N * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     m->ev_n = N;
-    if ((rc = ensure_capacity(m, 1))) return rc;
-    return TFR_OK;
+    return ensure_capacity(m, 1);
 }
 
 /* the fork's epoch line on the device (svd_train_val.py:94-98,170-178): accuracy count, summed sigmoid
@@ -1530,7 +1429,7 @@ int tfr_train_step(tfr_model* m, const int32_t* u, const int32_t* i, const float
         const int32_t e = (int32_t)m->h_out[nl + 3];
         if (e) {                                         // a bad batch never advances the step
             rollback_step(m, step0, b1p0, b2p0);
-            return report_device_error(m, e);
+            return device_error(m, e);
         }
         if (logits_out) memcpy(logits_out, m->h_out, (size_t)B * 4);
         sc[0] = m->h_out[nl]; sc[1] = m->h_out[nl + 1];
@@ -1565,7 +1464,7 @@ int tfr_train_steps_repeat(tfr_model* m, const int32_t* u, const int32_t* i, con
     if (nsteps < 0) return fail(TFR_ERR_ARG, "bad nsteps");
     if (nsteps == 0) return TFR_OK;
     if ((rc = ensure_capacity(m, B))) return rc;
-    if (loss_out && (rc = ensure_step_out(m, nsteps))) return rc;
+    if (loss_out) HIPCHK(m->step_out.reserve((int64_t)nsteps * 4, m->stream));
     const int64_t step0 = m->step;
     const float b1p0 = m->b1p, b2p0 = m->b2p;
     m->last_r = nullptr;
@@ -1610,23 +1509,17 @@ int tfr_last_batch_auc(tfr_model* m, double* auc_out) {
 static int build_store(tfr_model* m, const int32_t* u, const int32_t* i, const float* r, int64_t N, bool on_device) {
     HIPCHK(hipStreamSynchronize(m->stream));
     if (m->spec_valid) { int rc0 = cancel_run_ahead(m); if (rc0) return rc0; }     // ids drawn ahead were for the old store size
-    dfree(m->store);
-    m->store = nullptr; m->N = 0; m->pf_valid = false;
+    m->N = 0; m->pf_valid = false;
     recs_forget(m);
-    int rc;
-    if ((rc = dmalloc(&m->store, (size_t)N))) return rc;
+    HIPCHK(m->store.reserve(N, m->stream));
     if (on_device) {
         launch_pack_triples(u, i, r, m->store, N, m->stream);
         HIPCHK(hipGetLastError());
     } else {
         const int64_t chunk = (int64_t)1 << 24;
-        int32_t *tu = nullptr, *ti = nullptr;
-        float* tr = nullptr;
-        const int64_t c0 = N < chunk ? N : chunk;
-        if ((rc = dmalloc(&tu, (size_t)c0)) || (rc = dmalloc(&ti, (size_t)c0)) || (rc = dmalloc(&tr, (size_t)c0))) {
-            dfree(tu); dfree(ti); dfree(tr);
-            return rc;
-        }
+        DevBuf<int32_t> tu, ti;
+        DevBuf<float> tr;
+        HIPCHK(reserve_each(N < chunk ? N : chunk, m->stream, tu, ti, tr));
         hipError_t e = hipSuccess;
         for (int64_t off = 0; off < N && e == hipSuccess; off += chunk) {
             const int64_t n = (N - off < chunk) ? N - off : chunk;
@@ -1638,7 +1531,6 @@ static int build_store(tfr_model* m, const int32_t* u, const int32_t* i, const f
                 e = hipStreamSynchronize(m->stream);
             }
         }
-        dfree(tu); dfree(ti); dfree(tr);
         if (e != hipSuccess) return fail(TFR_ERR_HIP, "upload_triples: %s", hipGetErrorString(e));
     }
     HIPCHK(hipStreamSynchronize(m->stream));
@@ -1686,16 +1578,9 @@ static const int64_t IDS_MIN_CAP = (int64_t)1 << 24;   // 128 MB: a 900-step cal
 // room for n staged ids (contents undefined afterwards); the stream must be idle
 static int ensure_ids(tfr_model* m, int64_t n) {
     m->n_ids = 0; m->pf_valid = false;
-    if (n > m->d_ids_cap) {
-        if (m->stream3) HIPCHK(hipStreamSynchronize(m->stream3));
-        dfree(m->d_ids);
-        m->d_ids = nullptr; m->d_ids_cap = 0;
-        int rc;
-        const int64_t want = n < IDS_MIN_CAP ? IDS_MIN_CAP : n;      // allocations are slow: never size for a short call only
-        if ((rc = dmalloc(&m->d_ids, (size_t)want))) return rc;
-        m->d_ids_cap = want;
-    }
-    for (int k = 0; k < 2; ++k) if (m->rb[k].ids_base == m->d_ids) m->rb[k].n = 0;      // (a new buffer may sit at an old one's address)
+    m->ids.n_recs = 0;
+    // allocations are slow: never size for a short call only
+    HIPCHK(m->ids.ids.reserve(n < IDS_MIN_CAP ? IDS_MIN_CAP : n, m->stream3 ? m->stream3 : m->stream));
     return TFR_OK;
 }
 
@@ -1705,9 +1590,8 @@ int tfr_stage_ids(tfr_model* m, const int64_t* ids, int64_t n) {
     HIPCHK(hipStreamSynchronize(m->stream));
     int rc;
     if ((rc = ensure_ids(m, n))) return rc;
-    HIPCHK(hipMemcpyAsync(m->d_ids, ids, (size_t)n * 8, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(m->ids.ids, ids, (size_t)n * 8, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
-    for (int k = 0; k < 2; ++k) if (m->rb[k].ids_base == m->d_ids) m->rb[k].n = 0;
     m->n_ids = n;
     return TFR_OK;
 }
@@ -1732,16 +1616,8 @@ static void swap_sortset(tfr_model* m) {
 }
 
 static int ensure_lookahead(tfr_model* m) {
-    int rc;
-    if (m->alt_cap < m->cap) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        dfree(m->alt.d_u); dfree(m->alt.d_i); dfree(m->alt.d_r); dfree(m->alt.ks_u); dfree(m->alt.ps_u); dfree(m->alt.ks_i); dfree(m->alt.ps_i);
-        m->alt = tfr_model::SortSet(); m->alt_cap = 0;
-        if ((rc = dmalloc(&m->alt.d_u, m->cap)) || (rc = dmalloc(&m->alt.d_i, m->cap)) || (rc = dmalloc(&m->alt.d_r, m->cap)) ||
-            (rc = dmalloc(&m->alt.ks_u, m->cap)) || (rc = dmalloc(&m->alt.ps_u, m->cap)) ||
-            (rc = dmalloc(&m->alt.ks_i, m->cap)) || (rc = dmalloc(&m->alt.ps_i, m->cap))) return rc;
-        m->alt_cap = m->cap;
-    }
+    tfr_model::SortSet& A = m->alt;
+    HIPCHK(reserve_each(m->cap, m->stream, A.d_u, A.d_i, A.d_r, A.ks_u, A.ps_u, A.ks_i, A.ps_i));
     if (!m->stream2) {
         // (tried, one gpurun call each, C3 step: a high-priority look-ahead stream - no change; the look-ahead stream
         // confined to 8 / 16 / 32 / 64 CUs by hipExtStreamCreateWithCUMask - 1070 / 717 / 584 / 487 us against 497-504)
@@ -1819,8 +1695,8 @@ struct IdsReady {
             hipEvent_t pa = nullptr, pb = nullptr;
             if (m->prof && hipEventCreate(&pa) == hipSuccess && hipEventCreate(&pb) == hipSuccess) (void)hipEventRecord(pa, m->stream3);
             if (rng != 0) {
-                launch_mt_draw(m->d_rng, m->d_ids + s0 * B, (s1 - s0) * B, rng, mask_for(rng), m->stream3, nullptr, &m->rng_ws);
-                recs_follow(m, m->d_ids, m->d_ids_cap, s0 * B, (s1 - s0) * B, m->stream3);
+                launch_mt_draw(m->d_rng, m->ids.ids + s0 * B, (s1 - s0) * B, rng, mask_for(rng), m->stream3, nullptr, &m->rng_ws);
+                recs_follow(m, m->ids, s0 * B, (s1 - s0) * B, m->stream3);
             }
             if (pa && pb) { (void)hipEventRecord(pb, m->stream3); m->events.push_back({pa, pb, TFR_K_DRAW}); }
             if (hipGetLastError() != hipSuccess || hipEventRecord(m->chunk_ev[c], m->stream3) != hipSuccess)
@@ -1862,7 +1738,7 @@ static int staged_steps_lookahead(tfr_model* m, int64_t first_step, int64_t B, i
     auto sort_batch = [&](int64_t step) -> int {           // into the buffer set the model currently points at
         const int32_t* du = m->d_u; const int32_t* di = m->d_i; const float* dr = m->d_r;
         if (ready) { const int e = ready->need(first_step + step, m->stream, m->stream == main_s ? 0 : 1); if (e) return e; }
-        return front_and_sort(m, du, di, dr, B, nullptr, m->d_ids + (first_step + step) * B, fdummy, nb0, fd0, false, true);
+        return front_and_sort(m, du, di, dr, B, nullptr, m->ids.ids + (first_step + step) * B, fdummy, nb0, fd0, false, true);
     };
     if ((rc = sort_batch(0))) return rc;
     HIPCHK(hipEventRecord(m->ev_first, main_s));
@@ -1877,7 +1753,7 @@ static int staged_steps_lookahead(tfr_model* m, int64_t first_step, int64_t B, i
             const int z = s & 1;
             if (s > 0) HIPCHK(hipStreamWaitEvent(main_s, m->ev_sorted[z], 0));
             if ((rc = run_train_step(m, m->d_u, m->d_i, m->d_r, B, nullptr, loss_out ? m->step_out + (size_t)s * 4 : nullptr,
-                                     m->d_ids + (first_step + s) * B, nullptr, true)))
+                                     m->ids.ids + (first_step + s) * B, nullptr, true)))
                 break;
             HIPCHK(hipEventRecord(m->ev_free[z], main_s));
             if (ready && (rc = ready->feed(first_step + s))) break;
@@ -1909,7 +1785,7 @@ static int staged_steps_lookahead(tfr_model* m, int64_t first_step, int64_t B, i
         }
         if (s > 0) HIPCHK(hipStreamWaitEvent(main_s, m->ev_sorted[z], 0));
         if ((rc = run_train_step(m, m->d_u, m->d_i, m->d_r, B, nullptr, loss_out ? m->step_out + (size_t)s * 4 : nullptr,
-                                 m->d_ids + (first_step + s) * B, nullptr, true)))
+                                 m->ids.ids + (first_step + s) * B, nullptr, true)))
             return rc;
         HIPCHK(hipEventRecord(m->ev_free[z], main_s));
         if (ready && (rc = ready->feed(first_step + s))) return rc;
@@ -1922,7 +1798,7 @@ static int staged_steps_lookahead(tfr_model* m, int64_t first_step, int64_t B, i
 static int staged_steps(tfr_model* m, int64_t first_step, int64_t B, int32_t nsteps, float* loss_out, IdsReady* ready = nullptr) {
     int rc;
     if ((rc = ensure_capacity(m, B))) return rc;
-    if (loss_out && (rc = ensure_step_out(m, nsteps))) return rc;
+    if (loss_out) HIPCHK(m->step_out.reserve((int64_t)nsteps * 4, m->stream));
     const int64_t step0 = m->step;
     const float b1p0 = m->b1p, b2p0 = m->b2p;
     static int no_ahead = -1;                              // TFR_NO_LOOKAHEAD=1: A/B switch
@@ -1937,10 +1813,10 @@ static int staged_steps(tfr_model* m, int64_t first_step, int64_t B, int32_t nst
         if (ready && (rc = ready->need(first_step + s + ((first_step + s + 2) * B <= m->n_ids ? 1 : 0), m->stream, 0))) return rc;
         // look ahead past the end of this call too when more staged batches follow: the
         // next call then starts presorted (the sort is free, hidden in this launch)
-        const int64_t* nxt = (first_step + s + 2) * B <= m->n_ids ? m->d_ids + (first_step + s + 1) * B : nullptr;
+        const int64_t* nxt = (first_step + s + 2) * B <= m->n_ids ? m->ids.ids + (first_step + s + 1) * B : nullptr;
         if ((rc = run_train_step(m, m->d_u, m->d_i, m->d_r, B, nullptr,
                                  loss_out ? m->step_out + (size_t)s * 4 : nullptr,
-                                 m->d_ids + (first_step + s) * B, nxt))) {
+                                 m->ids.ids + (first_step + s) * B, nxt))) {
             m->pf_valid = false;
             return rc;
         }
@@ -1963,7 +1839,7 @@ static int staged_steps(tfr_model* m, int64_t first_step, int64_t B, int32_t nst
 int tfr_train_steps_staged(tfr_model* m, int64_t first_step, int64_t B, int32_t nsteps, float* loss_out) {
     MODEL_ENTER(m);
     if (!m->N) return fail(TFR_ERR_STATE, "no resident triples: call tfr_upload_triples first");
-    if (!m->d_ids) return fail(TFR_ERR_STATE, "no staged ids: call tfr_stage_ids first");
+    if (!m->ids.ids) return fail(TFR_ERR_STATE, "no staged ids: call tfr_stage_ids first");
     if (B < 1 || nsteps < 0 || first_step < 0) return fail(TFR_ERR_ARG, "bad batch/nsteps/first_step");
     if ((first_step + nsteps) * B > m->n_ids)
         return fail(TFR_ERR_ARG, "steps [%lld,%lld) x batch %lld exceed the %lld staged ids", (long long)first_step,
@@ -1986,18 +1862,14 @@ int tfr_train_steps_resident(tfr_model* m, const int64_t* ids, int64_t B, int32_
 
 // ---- device id draw (rng.hip) ------------------------------------------------------------
 static int ensure_rng(tfr_model* m) {
-    if (!m->d_rng) {
-        int rc;
-        if ((rc = dmalloc(&m->d_rng, 625))) return rc;
-        if ((rc = dmalloc(&m->d_rng_snap, 625))) return rc;
-        // scratch of the wide draw; TFR_RNG_WIDE=0 keeps every draw on the one-workgroup kernel (A/B)
-        const char* e = getenv("TFR_RNG_WIDE");
-        if (!(e && e[0] == '0')) {
-            if ((rc = dmalloc(&m->rng_ws.raw, (size_t)MT_WIDE_BLOCKS * 624))) return rc;
-            if ((rc = dmalloc(&m->rng_ws.counts, (size_t)MT_WIDE_BLOCKS))) return rc;
-            if ((rc = dmalloc(&m->rng_ws.hdr, 4))) return rc;
-            m->rng_ws.cap_blocks = MT_WIDE_BLOCKS;
-        }
+    HIPCHK(reserve_each(625, m->stream, m->d_rng, m->d_rng_snap));
+    // scratch of the wide draw; TFR_RNG_WIDE=0 keeps every draw on the one-workgroup kernel (A/B)
+    const char* e = getenv("TFR_RNG_WIDE");
+    if (!(e && e[0] == '0')) {
+        HIPCHK(m->rng_raw.reserve(MT_WIDE_BLOCKS * 624, m->stream));
+        HIPCHK(m->rng_counts.reserve(MT_WIDE_BLOCKS, m->stream));
+        HIPCHK(m->rng_hdr.reserve(4, m->stream));
+        m->rng_ws = {m->rng_raw, m->rng_counts, m->rng_hdr, MT_WIDE_BLOCKS};
     }
     if (!m->stream3) {
         HIPCHK(hipStreamCreateWithFlags(&m->stream3, hipStreamNonBlocking));
@@ -2067,11 +1939,11 @@ int tfr_draw_ids(tfr_model* m, int64_t high, int64_t count, int64_t* ids_out) {
     if (count == 0) return TFR_OK;
     if (high == 1) { memset(ids_out, 0, (size_t)count * 8); return TFR_OK; }    // rng == 0: no draw is consumed
     if ((rc = cancel_run_ahead(m))) return rc;
-    int64_t* d = nullptr;
-    if ((rc = dmalloc(&d, (size_t)count))) return rc;
+    DevBuf<int64_t> d;
+    HIPCHK(d.reserve(count, m->stream3));
     const uint32_t rng = (uint32_t)(high - 1);
-    unsigned long long* dbg = nullptr;
-    if (getenv("TFR_RNG_DEBUG")) (void)hipMalloc((void**)&dbg, 16);           // diagnostic: in-kernel clock of the generator
+    DevBuf<unsigned long long> dbg;
+    if (getenv("TFR_RNG_DEBUG") && dbg.reserve(2, m->stream3) != hipSuccess) (void)hipGetLastError();   // diagnostic: in-kernel clock of the generator
     launch_mt_draw(m->d_rng, d, count, rng, mask_for(rng), m->stream3, dbg, &m->rng_ws);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(ids_out, d, (size_t)count * 8, hipMemcpyDeviceToHost, m->stream3);
@@ -2083,8 +1955,6 @@ int tfr_draw_ids(tfr_model* m, int64_t high, int64_t count, int64_t* ids_out) {
                 (long long)count, h[0], h[1] / 100.0, h[1] ? h[0] * 100.0 / h[1] : 0.0,
                 h[0] / ((double)count * ((double)mask_for(rng) + 1.0) / ((double)rng + 1.0) / 624.0), mask_for(rng), rng);
     }
-    dfree(dbg);
-    dfree(d);
     if (e != hipSuccess) return fail(TFR_ERR_HIP, "draw_ids: %s", hipGetErrorString(e));
     return TFR_OK;
 }
@@ -2110,6 +1980,11 @@ int tfr_draw_ids_dev(tfr_model* m, int64_t high, int64_t count, int64_t* d_ids_o
     }
     HIPCHK(hipEventRecord(dev, m->stream3));
     m->draw_count += 1;
+    for (IdBuf* b : {&m->ids, &m->ids_alt}) {              // a draw into one of the model's id buffers rewrites it
+        if (!ids_overlap(*b, d_ids_out, count)) continue;
+        b->n_recs = 0;
+        if (m->pf_valid && ids_overlap(*b, m->pf_ids, 1)) m->pf_valid = false;
+    }
     return TFR_OK;
 }
 
@@ -2139,26 +2014,24 @@ int tfr_join_draw(tfr_model* m, int64_t ordinal) {
 
 // run ahead: the next call's first batches, drawn into the other id buffer (last read by the call before the current one)
 static int enqueue_run_ahead(tfr_model* m, int64_t B, int64_t nsteps, uint32_t rng) {
-    int rc;
     if (rng != 0) {
         int64_t spec = 131072 / B;
         if (spec > 8) spec = 8;
         if (spec > nsteps) spec = nsteps;
         if (spec < 1) spec = 1;
-        if (spec * B > m->d_ids_alt_cap || m->d_ids_alt_cap < m->d_ids_cap) {   // keep both buffers the same size: a repeat of this call then fits
+        DevBuf<int64_t>& alt = m->ids_alt.ids;
+        const int64_t cap = m->ids.ids.capacity();
+        if (spec * B > alt.capacity() || alt.capacity() < cap) {   // keep both buffers the same size: a repeat of this call then fits
             HIPCHK(hipStreamSynchronize(m->stream));       // the old alternate buffer may still be read by queued steps
-            HIPCHK(hipStreamSynchronize(m->stream3));
-            dfree(m->d_ids_alt);
-            m->d_ids_alt = nullptr; m->d_ids_alt_cap = 0;
-            int64_t want = spec * B > m->d_ids_cap ? spec * B : m->d_ids_cap;
+            m->ids_alt.n_recs = 0;
+            int64_t want = spec * B > cap ? spec * B : cap;
             if (want < IDS_MIN_CAP) want = IDS_MIN_CAP;
-            if ((rc = dmalloc(&m->d_ids_alt, (size_t)want))) return rc;
-            m->d_ids_alt_cap = want;
+            HIPCHK(alt.reserve(want, m->stream3));
         }
         HIPCHK(hipStreamWaitEvent(m->stream3, m->ev_ids_free, 0));  // the alternate buffer's last readers (before this call) are done
         HIPCHK(hipMemcpyAsync(m->d_rng_snap, m->d_rng, 625 * 4, hipMemcpyDeviceToDevice, m->stream3));
-        launch_mt_draw(m->d_rng, m->d_ids_alt, spec * B, rng, mask_for(rng), m->stream3, nullptr, &m->rng_ws);
-        recs_follow(m, m->d_ids_alt, m->d_ids_alt_cap, 0, spec * B, m->stream3);
+        launch_mt_draw(m->d_rng, alt, spec * B, rng, mask_for(rng), m->stream3, nullptr, &m->rng_ws);
+        recs_follow(m, m->ids_alt, 0, spec * B, m->stream3);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(m->spec_ev, m->stream3));
         m->spec_valid = true; m->spec_B = B; m->spec_N = m->N; m->spec_steps = spec;
@@ -2182,28 +2055,26 @@ int tfr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* loss_o
         // the previous call left the first spec_steps batches of this one in the alternate buffer
         pre = m->spec_steps;
         m->spec_valid = false;
-        std::swap(m->d_ids, m->d_ids_alt);
-        std::swap(m->d_ids_cap, m->d_ids_alt_cap);
-        if (total > m->d_ids_cap) {                        // grow, keeping the head (rare: a longer call than ever before)
+        std::swap(m->ids, m->ids_alt);                     // (each id buffer with its records)
+        if (total > m->ids.ids.capacity()) {               // grow, keeping the head (rare: a longer call than ever before)
             HIPCHK(hipStreamSynchronize(m->stream3));
-            int64_t* bigger = nullptr;
-            if ((rc = dmalloc(&bigger, (size_t)total))) return rc;         // total > capacity >= IDS_MIN_CAP
-            HIPCHK(hipMemcpy(bigger, m->d_ids, (size_t)pre * B * 8, hipMemcpyDeviceToDevice));
-            dfree(m->d_ids);
-            m->d_ids = bigger; m->d_ids_cap = total;
-            recs_follow(m, m->d_ids, m->d_ids_cap, 0, pre * B, m->stream3);
+            IdBuf bigger;
+            HIPCHK(bigger.ids.reserve(total, m->stream3));  // total > capacity >= IDS_MIN_CAP
+            HIPCHK(hipMemcpy(bigger.ids, m->ids.ids, (size_t)pre * B * 8, hipMemcpyDeviceToDevice));
+            m->ids = std::move(bigger);
+            recs_follow(m, m->ids, 0, pre * B, m->stream3);
         }
         HIPCHK(hipEventRecord(m->ev_ids_free, m->stream));          // everything queued so far: the earlier calls' steps
     } else {
         if ((rc = cancel_run_ahead(m))) return rc;
-        if (total > m->d_ids_cap) {                        // (re)allocation: nothing may still read the old buffer
+        if (total > m->ids.ids.capacity()) {               // (re)allocation: nothing may still read the old buffer
             HIPCHK(hipStreamSynchronize(m->stream));
             if ((rc = ensure_ids(m, total))) return rc;
         }
         // the draws overwrite the id buffer: they may start once every step already queued has read it
         HIPCHK(hipEventRecord(m->ev_ids_free, m->stream));
         HIPCHK(hipStreamWaitEvent(m->stream3, m->ev_ids_free, 0));
-        for (int k = 0; k < 2; ++k) if (m->rb[k].ids_base == m->d_ids) m->rb[k].n = 0;
+        m->ids.n_recs = 0;
     }
     m->pf_valid = false;                                   // the buffer's contents change: no published look-ahead sort survives
     m->n_ids = total;
@@ -2211,8 +2082,8 @@ int tfr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* loss_o
     ready.m = m; ready.B = B; ready.nsteps = nsteps; ready.rng = rng;
     ready.plan(B >= 65536 ? 1 : (65536 / B < 16 ? 65536 / B : 16), pre);     // a chunk holds at most ~64K ids / 16 steps
     if (rng == 0) {                                        // one-rating store: no draw consumed
-        HIPCHK(hipMemsetAsync(m->d_ids, 0, (size_t)total * 8, m->stream3));
-        for (int k = 0; k < 2; ++k) if (m->rb[k].ids_base == m->d_ids) m->rb[k].n = 0;
+        HIPCHK(hipMemsetAsync(m->ids.ids, 0, (size_t)total * 8, m->stream3));
+        m->ids.n_recs = 0;
     }
     tr.mark(pre ? "ids drawn ahead taken" : "no ids drawn ahead");
     if ((rc = staged_steps(m, 0, B, nsteps, loss_out, &ready))) return rc;
@@ -2297,15 +2168,10 @@ int tfr_lds_bytes(int32_t kernel, int32_t dim, int64_t batch, int64_t user_num, 
 
 static int ensure_ring(tfr_model* m, int64_t B) {
     if (B <= m->ring_cap) return TFR_OK;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    dfree(m->d_ring); m->d_ring = nullptr;
-    if (m->h_ring) (void)hipHostFree(m->h_ring);
-    m->h_ring = nullptr; m->ring_cap = 0;
-    int64_t cap = 1024;
-    while (cap < B) cap *= 2;
-    int rc;
-    if ((rc = dmalloc(&m->d_ring, (size_t)cap * tfr_model::HRING))) return rc;
-    HIPCHK(hipHostMalloc((void**)&m->h_ring, (size_t)cap * tfr_model::HRING * 8, hipHostMallocDefault));
+    const int64_t cap = pow2_cap(B);
+    m->ring_cap = 0;
+    HIPCHK(m->d_ring.reserve(cap * tfr_model::HRING, m->stream));
+    HIPCHK(m->h_ring.reserve(cap * tfr_model::HRING, m->stream));
     for (int z = 0; z < tfr_model::HRING; ++z)
         if (!m->ring_ev[z]) HIPCHK(hipEventCreateWithFlags(&m->ring_ev[z], hipEventDisableTiming));
     m->ring_cap = cap;
@@ -2386,18 +2252,8 @@ static int shard_route_core(tfr_model* m, const int32_t* d_user, const int32_t* 
     const int64_t need = sample_cap > (int64_t)world * slot_cap ? sample_cap : (int64_t)world * slot_cap;
     if ((rc = ensure_capacity(m, need > Bg ? need : (Bg > 0 ? Bg : 1)))) return rc;
     tfr_model::RouteSet& R = m->rt[m->rt_sel];
-    if (sample_cap > R.cap || world > R.cap_world) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        dfree(R.mine); dfree(R.u); dfree(R.it); dfree(R.r); dfree(R.slot); dfree(R.counts);
-        dfree(R.ks_u); dfree(R.ps_u); dfree(R.ks_i); dfree(R.ps_i);
-        R.mine = R.u = R.it = R.slot = R.counts = R.ks_u = R.ps_u = R.ks_i = R.ps_i = nullptr; R.r = nullptr; R.cap = 0;
-        if ((rc = dmalloc(&R.mine, (size_t)sample_cap)) || (rc = dmalloc(&R.u, (size_t)sample_cap)) ||
-            (rc = dmalloc(&R.it, (size_t)sample_cap)) || (rc = dmalloc(&R.r, (size_t)sample_cap)) ||
-            (rc = dmalloc(&R.slot, (size_t)sample_cap)) || (rc = dmalloc(&R.counts, (size_t)world + 4)) ||
-            (rc = dmalloc(&R.ks_u, (size_t)sample_cap)) || (rc = dmalloc(&R.ps_u, (size_t)sample_cap)) ||
-            (rc = dmalloc(&R.ks_i, (size_t)sample_cap)) || (rc = dmalloc(&R.ps_i, (size_t)sample_cap))) return rc;
-        R.cap = sample_cap; R.cap_world = world;
-    }
+    HIPCHK(reserve_each(sample_cap, m->stream, R.mine, R.u, R.it, R.r, R.slot, R.ks_u, R.ps_u, R.ks_i, R.ps_i));
+    HIPCHK(R.counts.reserve(world + 4, m->stream));
     R.B = sample_cap; R.slots = world * slot_cap; R.world = world;
     R.sorted_fwd = false; R.sorted_req = nullptr;
     hipStream_t s = m->stream;
@@ -2745,13 +2601,7 @@ int tfr_shard_presort(tfr_model* m, const int32_t* d_req_recv, int64_t n) {
         R.sorted_fwd = true;
     }
     if (n > 0) {
-        if (n > R.acap) {
-            HIPCHK(hipStreamSynchronize(m->stream));
-            dfree(R.akeys); dfree(R.aks); dfree(R.aps);
-            R.akeys = R.aks = R.aps = nullptr; R.acap = 0;
-            if ((rc = dmalloc(&R.akeys, (size_t)n)) || (rc = dmalloc(&R.aks, (size_t)n)) || (rc = dmalloc(&R.aps, (size_t)n))) return rc;
-            R.acap = n;
-        }
+        HIPCHK(reserve_each(n, m->stream, R.akeys, R.aks, R.aps));
         launch_pad_keys(d_req_recv, R.akeys, n, (int32_t)m->I, R.counts + R.world + 2, m->stream);
         HIPCHK(hipGetLastError());
         const int32_t* keys[2] = {R.akeys, nullptr};
@@ -2953,7 +2803,7 @@ int tfr_dp_apply(tfr_model* m, float* d_flat) {
 
 int tfr_staged_ids_devptr(tfr_model* m, void** ptr, int64_t* n) {
     MODEL_ENTER(m);
-    if (ptr) *ptr = m->d_ids;
+    if (ptr) *ptr = m->ids.ids;
     if (n) *n = m->n_ids;
     return TFR_OK;
 }
@@ -2966,11 +2816,10 @@ int tfr_staged_ids_devptr(tfr_model* m, void** ptr, int64_t* n) {
 // the fused SGD / lazy-Adam apply unchanged.
 struct tfr_fm {
     tfr_model* m = nullptr;
-    int64_t cap_rows = 0, cap_nnz = 0, s_cap = 0;
-    int64_t* d_indptr = nullptr;
-    int32_t* d_indices = nullptr;
-    float *d_data = nullptr, *d_y = nullptr, *d_out = nullptr, *s_rows = nullptr;
-    int4* ent = nullptr; int64_t ent_cap = 0;            // per non-zero {row, g x, lam - g x^2, -} of the training step
+    DevBuf<int64_t> d_indptr;
+    DevBuf<int32_t> d_indices;
+    DevBuf<float> d_data, d_y, d_out, s_rows;
+    DevBuf<int4> ent;                                    // per non-zero {row, g x, lam - g x^2, -} of the training step
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -2982,25 +2831,9 @@ static int fm_stage_csr(tfr_fm* f, const int64_t* indptr, const int32_t* indices
     for (int64_t r = 0; r < n_rows; ++r)
         if (indptr[r + 1] < indptr[r]) return fail(TFR_ERR_ARG, "indptr must be non-decreasing");
     if (nnz > 0 && (!indices || !data)) return fail(TFR_ERR_ARG, "null indices/data");
-    if (n_rows > f->cap_rows) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        dfree(f->d_indptr); dfree(f->d_out); dfree(f->d_y);
-        f->d_indptr = nullptr; f->d_out = nullptr; f->d_y = nullptr; f->cap_rows = 0;
-        int rc;
-        if ((rc = dmalloc(&f->d_indptr, (size_t)n_rows + 1))) return rc;
-        if ((rc = dmalloc(&f->d_out, (size_t)n_rows))) return rc;
-        if ((rc = dmalloc(&f->d_y, (size_t)n_rows))) return rc;
-        f->cap_rows = n_rows;
-    }
-    if (nnz > f->cap_nnz) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        dfree(f->d_indices); dfree(f->d_data);
-        f->d_indices = nullptr; f->d_data = nullptr; f->cap_nnz = 0;
-        int rc;
-        if ((rc = dmalloc(&f->d_indices, (size_t)nnz))) return rc;
-        if ((rc = dmalloc(&f->d_data, (size_t)nnz))) return rc;
-        f->cap_nnz = nnz;
-    }
+    HIPCHK(f->d_indptr.reserve(n_rows + 1, m->stream));
+    HIPCHK(reserve_each(n_rows, m->stream, f->d_out, f->d_y));
+    HIPCHK(reserve_each(nnz, m->stream, f->d_indices, f->d_data));
     HIPCHK(hipMemcpyAsync(f->d_indptr, indptr, (size_t)(n_rows + 1) * 8, hipMemcpyHostToDevice, m->stream));
     if (nnz > 0) {
         HIPCHK(hipMemcpyAsync(f->d_indices, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, m->stream));
@@ -3045,20 +2878,8 @@ static int fm_train_core(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_in
     if (adam && o.adam_mode != TFR_ADAM_LAZY) return fail(TFR_ERR_STATE, "FM training supports SGD and lazy Adam");
     int rc;
     if ((rc = ensure_capacity(m, nnz > 0 ? nnz : 1))) return rc;
-    if (n_rows * m->D > f->s_cap) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        dfree(f->s_rows);
-        f->s_rows = nullptr; f->s_cap = 0;
-        if ((rc = dmalloc(&f->s_rows, (size_t)n_rows * m->D))) return rc;
-        f->s_cap = n_rows * m->D;
-    }
-    if (nnz > f->ent_cap) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        dfree(f->ent);
-        f->ent = nullptr; f->ent_cap = 0;
-        if ((rc = dmalloc(&f->ent, (size_t)nnz))) return rc;
-        f->ent_cap = nnz;
-    }
+    HIPCHK(f->s_rows.reserve(n_rows * m->D, m->stream));
+    HIPCHK(f->ent.reserve(nnz, m->stream));
     const float alpha = adam ? o.lr * sqrtf(1.f - m->b2p) / (1.f - m->b1p) : 0.f;
     hipStream_t s = m->stream;
     FmArgs a;
@@ -3139,16 +2960,15 @@ const char* tfr_fm_last_error(void) { return g_err; }
 
 int tfr_fm_destroy(tfr_fm* f) {
     if (!f) return TFR_OK;
-    if (f->m) {
-        (void)hipSetDevice(f->m->device);
-        (void)hipStreamSynchronize(f->m->stream);
+    tfr_model* m = f->m;
+    if (m) {
+        (void)hipSetDevice(m->device);
+        (void)hipStreamSynchronize(m->stream);
     }
-    dfree(f->d_indptr); dfree(f->d_indices); dfree(f->d_data); dfree(f->d_y); dfree(f->d_out); dfree(f->s_rows); dfree(f->ent);
     if (f->ev0) (void)hipEventDestroy(f->ev0);
     if (f->ev1) (void)hipEventDestroy(f->ev1);
-    tfr_destroy(f->m);
-    delete f;
-    return TFR_OK;
+    delete f;                                            // the FM buffers go first, under the wrapped model's device
+    return tfr_destroy(m);
 }
 
 int tfr_fm_create(tfr_fm** out, int64_t n_features, int32_t dim, const tfr_opts* opts) {
@@ -3277,21 +3097,6 @@ int tfr_fm_sync(tfr_fm* f, float* last_kernel_ms) {
 }  // extern "C"
 
 // ---- top-K recommendation (topk.hip) ----------------------------------------------------------------------------------------
-template <typename T>
-static int tk_grow(tfr_model* m, T** p, int64_t* cap, int64_t need) {
-    if (need <= *cap) return TFR_OK;
-    HIPCHK(hipStreamSynchronize(m->stream));
-    dfree(*p);
-    *p = nullptr;
-    *cap = 0;
-    int64_t c = 1024;
-    while (c < need) c <<= 1;
-    const int rc = dmalloc(p, (size_t)c);
-    if (rc) return rc;
-    *cap = c;
-    return TFR_OK;
-}
-
 struct TopkTables { const float *P, *bu, *Q, *bi, *mu; int64_t U, n_items; int32_t item_abs; };
 
 static TopkTables svd_topk_tables(const tfr_model* m) {
@@ -3301,8 +3106,7 @@ static TopkTables svd_topk_tables(const tfr_model* m) {
 // one chunk of rows, all pointers on the device: scoring (item slices) -> merge into items_out / scores_out
 static int topk_chunk(tfr_model* m, const TopkTables& t, const TopkPlan& p, const int32_t* d_users, int64_t rows, int32_t k,
                       const int64_t* d_indptr, const int32_t* d_excl, int32_t* d_items, float* d_scores) {
-    int rc;
-    if ((rc = tk_grow(m, &m->tk_part, &m->tk_part_cap, rows * p.slices * k))) return rc;
+    HIPCHK(m->tk_part.reserve(pow2_cap(rows * p.slices * k), m->stream));
     TopkArgs a;
     memset(&a, 0, sizeof(a));
     a.P = t.P; a.bu = t.bu; a.Q = t.Q; a.bi = t.bi; a.mu = t.mu;
@@ -3322,10 +3126,7 @@ static int topk_chunk(tfr_model* m, const TopkTables& t, const TopkPlan& p, cons
 
 static int topk_prepare(tfr_model* m, int32_t k, int64_t n, int64_t n_items, TopkPlan* p) {
     if (!topk_plan(k, n, n_items, p)) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
-    if (!m->tk_bad) {
-        int rc = dmalloc(&m->tk_bad, 1);
-        if (rc) return rc;
-    }
+    HIPCHK(m->tk_bad.reserve(1, m->stream));
     HIPCHK(hipMemsetAsync(m->tk_bad, 0, sizeof(int32_t), m->stream));
     return settle_q(m);                                  // item rows the fused big-table step left in q_alt come back first
 }
@@ -3357,9 +3158,9 @@ static int topk_host(tfr_model* m, const TopkTables& t, const int32_t* users, in
     TopkPlan p;
     int rc = topk_prepare(m, k, n, t.n_items, &p);
     if (rc) return rc;
-    if ((rc = tk_grow(m, &m->tk_users, &m->tk_users_cap, p.chunk))) return rc;
-    if ((rc = tk_grow(m, &m->tk_items, &m->tk_out_cap, p.chunk * k))) return rc;
-    if (scores_out && (rc = tk_grow(m, &m->tk_scores, &m->tk_scores_cap, p.chunk * k))) return rc;
+    HIPCHK(m->tk_users.reserve(pow2_cap(p.chunk), m->stream));
+    HIPCHK(m->tk_items.reserve(pow2_cap(p.chunk * k), m->stream));
+    if (scores_out) HIPCHK(m->tk_scores.reserve(pow2_cap(p.chunk * k), m->stream));
     std::vector<int64_t> rebased;
     for (int64_t c0 = 0; c0 < n; c0 += p.chunk) {
         const int64_t rows = n - c0 < p.chunk ? n - c0 : p.chunk;
@@ -3370,8 +3171,8 @@ static int topk_host(tfr_model* m, const TopkTables& t, const int32_t* users, in
             const int64_t e0 = indptr[c0], nnz = indptr[c0 + rows] - e0;
             rebased.resize((size_t)rows + 1);
             for (int64_t r = 0; r <= rows; ++r) rebased[(size_t)r] = indptr[c0 + r] - e0;
-            if ((rc = tk_grow(m, &m->tk_indptr, &m->tk_indptr_cap, rows + 1))) return rc;
-            if ((rc = tk_grow(m, &m->tk_excl, &m->tk_excl_cap, nnz))) return rc;
+            HIPCHK(m->tk_indptr.reserve(pow2_cap(rows + 1), m->stream));
+            if (nnz > 0) HIPCHK(m->tk_excl.reserve(pow2_cap(nnz), m->stream));
             HIPCHK(hipMemcpyAsync(m->tk_indptr, rebased.data(), (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, m->stream));
             if (nnz > 0) HIPCHK(hipMemcpyAsync(m->tk_excl, excl + e0, (size_t)nnz * 4, hipMemcpyHostToDevice, m->stream));
             d_ip = m->tk_indptr;
@@ -3583,15 +3384,7 @@ int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, cons
                  o_pre = take((size_t)n_rounds * 4), o_bpow = take(bpow.size() * 4), o_order = take((size_t)n_users * 4),
                  o_askout = take((size_t)n_rounds * 4), o_loss = take(round_loss_out ? (size_t)n_rounds * 4 : 0),
                  o_final = take(final_logits_out ? (size_t)n_rows * 4 : 0);
-    if ((int64_t)off > m->ft_cap) {
-        HIPCHK(hipStreamSynchronize(m->stream));
-        dfree(m->ft_buf);
-        m->ft_buf = nullptr;
-        m->ft_cap = 0;
-        int rc = dmalloc(&m->ft_buf, off);
-        if (rc) return rc;
-        m->ft_cap = (int64_t)off;
-    }
+    HIPCHK(m->ft_buf.reserve((int64_t)off, m->stream));
     int rc = settle_q(m);                                // item rows the fused big-table step left in q_alt come back first
     if (rc) return rc;
     char* b = m->ft_buf;
