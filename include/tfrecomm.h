@@ -367,6 +367,34 @@ int tfr_fm_topk(tfr_fm* m, const int32_t* user_features, int64_t n_users, int64_
 int tfr_topk_plan(int32_t dim, int32_t k, int64_t n_users, int64_t item_num,
                   int64_t* lds_bytes, int32_t* users_per_block, int32_t* item_slices, int64_t* user_chunk);
 
+/* ---- held-out ranking over the whole catalogue: the ranking form of the reference's AUC (svd_train_val.py:97,141,
+ *      non_adaptive_test.py:121, fm.py:164) - DESIGN §13 ---------------------------------------------------------------------
+ *      Row r ranks the target items T = tgt_items[tgt_indptr[r], tgt_indptr[r+1]) (strictly increasing) of user u = users[r]
+ *      among the eligible items E = [0, n_items) minus the row's exclusions X (optional CSR aligned with users, rows
+ *      non-decreasing, as tfr_topk).  key(u, i) = the tfr_topk key: the order-preserving uint32 of
+ *      score = ((dot + mu) + bu[u]) + bi[i] (dot the f32 fmaf chain over f ascending from +0, |Q| under item_abs), then ~i.
+ *          rank(t) = #{ i in E : score(u,i) not NaN and key(u,i) > key(u,t) }   if t in E and score(u,t) is not NaN
+ *          rank(t) = -1                                                           otherwise (unranked)
+ *      0-based, counting the other targets, distinct within a row (ties by item id).  For every K <= 256, 0 <= rank(t) < K
+ *      exactly when t is in tfr_topk(users, K, X)[r], and rank(t) is its position there.  Integer counts: bit-identical
+ *      run to run and whatever the batch, duplicates, chunking, slicing and row order.
+ *      ranks_out[e - tgt_indptr[0]] = rank of tgt_items[e].  Ids and the CSR shapes are checked on the host before any
+ *      device work (TFR_ERR_OOB for an id out of range, TFR_ERR_ARG otherwise; ranks_out untouched).  n_users = 0 and rows
+ *      without targets are no-ops.  Reads the five tables only; runs on the model's stream and synchronises. */
+int tfr_rank_items(tfr_model* m, const int32_t* users, int64_t n_users,
+                   const int64_t* tgt_indptr /* [n_users+1] */, const int32_t* tgt_items,
+                   const int64_t* excl_indptr /* [n_users+1] or NULL */, const int32_t* excl_items,
+                   int32_t* ranks_out /* [tgt_indptr[n_users] - tgt_indptr[0]] */);
+/* FM (tfr_fm): the tables of tfr_fm_topk; target and excluded ids relative to item_lo. */
+int tfr_fm_rank_items(tfr_fm* m, const int32_t* user_features, int64_t n_users, int64_t item_lo, int64_t item_hi,
+                      const int64_t* tgt_indptr, const int32_t* tgt_items, const int64_t* excl_indptr,
+                      const int32_t* excl_items, int32_t* ranks_out);
+/* host-only, no device: what the launcher will do for n_users rows holding n_targets targets in all (at most
+ * min(n_targets, n_users + n_targets / targets_per_piece) pieces) - LDS bytes per workgroup (the larger of the target and
+ * the counting kernel), pieces per counting workgroup, item slices, targets per piece, pieces per chunk */
+int tfr_rank_plan(int32_t dim, int64_t n_users, int64_t n_targets, int64_t item_num, int64_t* lds_bytes,
+                  int32_t* pieces_per_block, int32_t* item_slices, int32_t* targets_per_piece, int64_t* piece_chunk);
+
 /* ---- batched per-user fine-tuning: every user of adaptive_test.py:87-116 / non_adaptive_test.py:56-87 in one launch -----------
  *      A schedule: for user u = users[x] (each at most once), training rows items / rates [row_ptr[x], row_ptr[x+1]) and rounds
  *      [round_ptr[x], round_ptr[x+1]).  Round k first predicts ask_items[k] with the parameters of the moment (its logit, the

@@ -11,6 +11,8 @@ from .engine import SvdModel, device_copy_rate, rated_matrix
 from . import dataio, graph, ops, config, cats, adaptive_test, finetune
 from .fm import FmModel
 from .als import MangakiALS3
+from . import ranking
+from .ranking import ranking_metrics, evaluate_ranking
 
 __all__ = ["SvdModel", "device_copy_rate", "rated_matrix", "TfrError", "OutOfRangeError", "_lib", "dataio", "graph", "ops", "config", "cats", "adaptive_test", "finetune",
-           "FmModel", "MangakiALS3"]
+           "FmModel", "MangakiALS3", "ranking", "ranking_metrics", "evaluate_ranking"]

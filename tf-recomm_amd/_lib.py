@@ -141,6 +141,9 @@ SIGNATURES = {
     "tfr_topk_dev": (C.c_int, [_p, _p, C.c_int64, C.c_int32, _p, _p, _p, _p]),
     "tfr_fm_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
     "tfr_topk_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, _i64p, _i32p, _i32p, _i64p]),
+    "tfr_rank_items": (C.c_int, [_p, _i32p, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
+    "tfr_fm_rank_items": (C.c_int, [_p, _i32p, C.c_int64, C.c_int64, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
+    "tfr_rank_plan": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, _i64p, _i32p, _i32p, _i32p, _i64p]),
     "tfr_finetune_users": (C.c_int, [_p, C.c_int64, _i32p, _i64p, _i32p, _f32p, _i64p, _i32p, _i32p, _i64p, C.c_int32,
                                      _f32p, _f32p, _f32p]),
     "tfr_finetune_plan": (C.c_int, [C.c_int32, C.c_int64, _i64p, _i32p, _i32p]),

@@ -17,6 +17,7 @@
 #include "tfrecomm.h"
 #include "svd_kernels.h"
 #include "topk.h"
+#include "rank.h"
 #include "finetune.h"
 #include "devbuf.h"
 
@@ -160,6 +161,11 @@ struct tfr_model {
     DevBuf<int32_t> tk_items;
     DevBuf<float> tk_scores;
     DevBuf<int32_t> tk_bad;
+    // held-out ranking (tfr_rank_items*): one piece chunk's staged pieces, targets and exclusions, and its per-piece state
+    DevBuf<RankPiece> rk_pieces;
+    DevBuf<int32_t> rk_tgt, rk_excl, rk_ranks;
+    DevBuf<uint64_t> rk_keys;
+    DevBuf<int32_t> rk_order, rk_bins, rk_nr;
     // batched fine-tuning (tfr_finetune_users): one device buffer for a call's schedule and outputs
     DevBuf<char> ft_buf;
     // profiling
@@ -3248,6 +3254,134 @@ int tfr_fm_topk(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_
     const TopkTables t = {m->w[TFR_P], m->w[TFR_BU], m->w[TFR_P] + item_lo * m->D, m->w[TFR_BU] + item_lo, m->w[TFR_MU],
                           m->U, item_hi - item_lo, 0};
     return topk_host(m, t, user_features, n_users, k, excl_indptr, excl_items, items_out, scores_out);
+}
+
+}  // extern "C"
+
+// ---- held-out ranking (rank.hip) --------------------------------------------------------------------------------------------
+// the host entries: ids, the target rows and the exclusion CSR are checked here, before any device work; the rows are cut
+// into pieces of at most RANK_CAP targets and ranked chunk by chunk of pieces.  ranks_out is written only when every check
+// passed.
+static int rank_host(tfr_model* m, const TopkTables& t, const int32_t* users, int64_t n, const int64_t* tip,
+                     const int32_t* tit, const int64_t* xip, const int32_t* xit, int32_t* ranks_out) {
+    if (n < 0) return fail(TFR_ERR_ARG, "rank: negative n_users");
+    if (n == 0) return TFR_OK;
+    if (!users || !tip) return fail(TFR_ERR_ARG, "rank: null users / target indptr");
+    if (tip[0] < 0) return fail(TFR_ERR_ARG, "rank: target indptr starts below 0");
+    for (int64_t r = 0; r < n; ++r)
+        if (tip[r + 1] < tip[r]) return fail(TFR_ERR_ARG, "rank: target indptr decreases at row %lld", (long long)r);
+    const int64_t n_tgt = tip[n] - tip[0];
+    if (n_tgt > 0 && (!tit || !ranks_out)) return fail(TFR_ERR_ARG, "rank: null target items / ranks_out");
+    if (xip && !xit && xip[n] > xip[0]) return fail(TFR_ERR_ARG, "rank: exclusion indptr without items");
+    for (int64_t r = 0; r < n; ++r)
+        if (users[r] < 0 || (int64_t)users[r] >= t.U)
+            return fail(TFR_ERR_OOB, "rank: user id %d outside [0, %lld)", users[r], (long long)t.U);
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t e = tip[r]; e < tip[r + 1]; ++e) {
+            if (tit[e] < 0 || (int64_t)tit[e] >= t.n_items)
+                return fail(TFR_ERR_OOB, "rank: target item %d outside [0, %lld)", tit[e], (long long)t.n_items);
+            if (e > tip[r] && tit[e - 1] >= tit[e])
+                return fail(TFR_ERR_ARG, "rank: target row %lld is not strictly increasing", (long long)r);
+        }
+    if (xip) {
+        if (xip[0] < 0) return fail(TFR_ERR_ARG, "rank: exclusion indptr starts below 0");
+        for (int64_t r = 0; r < n; ++r) {
+            if (xip[r + 1] < xip[r]) return fail(TFR_ERR_ARG, "rank: exclusion indptr decreases at row %lld", (long long)r);
+            for (int64_t e = xip[r]; e < xip[r + 1]; ++e) {
+                if (xit[e] < 0 || (int64_t)xit[e] >= t.n_items)
+                    return fail(TFR_ERR_OOB, "rank: excluded item %d outside [0, %lld)", xit[e], (long long)t.n_items);
+                if (e > xip[r] && xit[e - 1] > xit[e])
+                    return fail(TFR_ERR_ARG, "rank: exclusion row %lld is not sorted", (long long)r);
+            }
+        }
+    }
+    if (n_tgt == 0) return TFR_OK;
+    // pieces in row order: tlo absolute into tit, xlo / xhi absolute into xit (rebased per chunk below); prow = their rows
+    std::vector<RankPiece> pieces;
+    std::vector<int64_t> prow;
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t e = tip[r]; e < tip[r + 1]; e += RANK_CAP) {
+            const int64_t nt = tip[r + 1] - e < RANK_CAP ? tip[r + 1] - e : RANK_CAP;
+            pieces.push_back({e, xip ? xip[r] : 0, xip ? xip[r + 1] : 0, users[r], (int32_t)nt});
+            prow.push_back(r);
+        }
+    const int64_t np = (int64_t)pieces.size();
+    RankPlan p;
+    if (!rank_plan(np, t.n_items, &p)) return fail(TFR_ERR_ARG, "rank: no plan for %lld pieces", (long long)np);
+    int rc = settle_q(m);                                // item rows the fused big-table step left in q_alt come back first
+    if (rc) return rc;
+    hipStream_t s = m->stream;
+    HIPCHK(m->rk_pieces.reserve(pow2_cap(p.chunk), s));
+    HIPCHK(reserve_each(pow2_cap(p.chunk * RANK_CAP), s, m->rk_tgt, m->rk_ranks, m->rk_order, m->rk_bins));
+    HIPCHK(m->rk_keys.reserve(pow2_cap(p.chunk * RANK_CAP), s));
+    HIPCHK(m->rk_nr.reserve(pow2_cap(p.chunk), s));
+    std::vector<RankPiece> staged;
+    for (int64_t c0 = 0; c0 < np; c0 += p.chunk) {
+        const int64_t cnt = np - c0 < p.chunk ? np - c0 : p.chunk;
+        const int64_t t0 = pieces[(size_t)c0].tlo;
+        const int64_t t1 = pieces[(size_t)(c0 + cnt - 1)].tlo + pieces[(size_t)(c0 + cnt - 1)].nt;
+        const int64_t x0 = xip ? xip[prow[(size_t)c0]] : 0;
+        const int64_t x1 = xip ? xip[prow[(size_t)(c0 + cnt - 1)] + 1] : 0;
+        staged.assign(pieces.begin() + c0, pieces.begin() + c0 + cnt);
+        for (auto& q : staged) { q.tlo -= t0; q.xlo -= x0; q.xhi -= x0; }
+        HIPCHK(hipMemcpyAsync(m->rk_pieces, staged.data(), (size_t)cnt * sizeof(RankPiece), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(m->rk_tgt, tit + t0, (size_t)(t1 - t0) * 4, hipMemcpyHostToDevice, s));
+        if (x1 > x0) {
+            HIPCHK(m->rk_excl.reserve(pow2_cap(x1 - x0), s));
+            HIPCHK(hipMemcpyAsync(m->rk_excl, xit + x0, (size_t)(x1 - x0) * 4, hipMemcpyHostToDevice, s));
+        }
+        RankArgs a;
+        memset(&a, 0, sizeof(a));
+        a.P = t.P; a.bu = t.bu; a.Q = t.Q; a.bi = t.bi; a.mu = t.mu;
+        a.pieces = m->rk_pieces; a.tgt = m->rk_tgt; a.excl = m->rk_excl;
+        a.keys = m->rk_keys; a.order = m->rk_order; a.nr = m->rk_nr; a.bins = m->rk_bins; a.ranks = m->rk_ranks;
+        a.n_pieces = cnt; a.n_items = t.n_items;
+        a.D = m->D; a.slices = p.slices; a.item_abs = t.item_abs;
+        launch_rank(a, p, s);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ranks_out + (t0 - tip[0]), m->rk_ranks, (size_t)(t1 - t0) * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));                 // the staged inputs are rewritten by the next chunk
+    }
+    return check_device_error(m);
+}
+
+extern "C" {
+
+int tfr_rank_plan(int32_t dim, int64_t n_users, int64_t n_targets, int64_t item_num, int64_t* lds_bytes,
+                  int32_t* pieces_per_block, int32_t* item_slices, int32_t* targets_per_piece, int64_t* piece_chunk) {
+    int G, VEC;
+    if (!geometry(dim, &G, &VEC)) return fail(TFR_ERR_ARG, "unsupported dim %d", dim);
+    if (n_users < 0 || n_targets < 0 || item_num < 1)
+        return fail(TFR_ERR_ARG, "rank plan: n_users >= 0, n_targets >= 0 and item_num >= 1");
+    RankPlan p;
+    if (!rank_plan(rank_pieces_bound(n_users, n_targets), item_num, &p)) return fail(TFR_ERR_ARG, "rank plan: no plan");
+    if (lds_bytes) *lds_bytes = (int64_t)(p.lds_count > p.lds_targets ? p.lds_count : p.lds_targets);
+    if (pieces_per_block) *pieces_per_block = p.ppb;
+    if (item_slices) *item_slices = p.slices;
+    if (targets_per_piece) *targets_per_piece = p.cap;
+    if (piece_chunk) *piece_chunk = p.chunk;
+    return TFR_OK;
+}
+
+int tfr_rank_items(tfr_model* m, const int32_t* users, int64_t n_users, const int64_t* tgt_indptr, const int32_t* tgt_items,
+                   const int64_t* excl_indptr, const int32_t* excl_items, int32_t* ranks_out) {
+    MODEL_ENTER(m);
+    return rank_host(m, svd_topk_tables(m), users, n_users, tgt_indptr, tgt_items, excl_indptr, excl_items, ranks_out);
+}
+
+int tfr_fm_rank_items(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_t item_lo, int64_t item_hi,
+                      const int64_t* tgt_indptr, const int32_t* tgt_items, const int64_t* excl_indptr,
+                      const int32_t* excl_items, int32_t* ranks_out) {
+    if (!f) return fail(TFR_ERR_ARG, "null model");
+    tfr_model* m = f->m;
+    HIPCHK(hipSetDevice(m->device));
+    if (item_lo < 0 || item_hi <= item_lo || item_hi > m->U)
+        return fail(TFR_ERR_ARG, "rank: item feature range [%lld, %lld) not inside [0, %lld)", (long long)item_lo,
+                    (long long)item_hi, (long long)m->U);
+    // the tables of tfr_fm_topk: V / W of the wrapped model, items are features [item_lo, item_hi)
+    const TopkTables t = {m->w[TFR_P], m->w[TFR_BU], m->w[TFR_P] + item_lo * m->D, m->w[TFR_BU] + item_lo, m->w[TFR_MU],
+                          m->U, item_hi - item_lo, 0};
+    return rank_host(m, t, user_features, n_users, tgt_indptr, tgt_items, excl_indptr, excl_items, ranks_out);
 }
 
 }  // extern "C"

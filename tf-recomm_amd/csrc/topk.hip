@@ -10,41 +10,10 @@
 // k_topk_check_excl: the device entry's range / order check of the exclusion CSR.
 #include <hip/hip_runtime.h>
 #include "svd_kernels.h"
+#include "score_tile.h"
 #include "topk.h"
 
 namespace tfr {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ uint64_t topk_key(float s, int64_t item) {
-    const uint32_t b = __float_as_uint(s);
-    const uint32_t o = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    return ((uint64_t)o << 32) | (uint32_t)~(uint32_t)item;
-}
-
-__device__ __forceinline__ float topk_key_score(uint64_t key) {
-    const uint32_t o = (uint32_t)(key >> 32);
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
-// descending bitonic sort of q[0..CAP) by one wave
-template <int CAP>
-__device__ __forceinline__ void wave_sort_desc(uint64_t* q, int lane) {
-    for (int size = 2; size <= CAP; size <<= 1) {
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-#pragma unroll
-            for (int t0 = 0; t0 < CAP / 2; t0 += 64) {
-                const int t = t0 + lane;
-                const int i = 2 * t - (t & (stride - 1));
-                const int j = i + stride;
-                const uint64_t x = q[i], y = q[j];
-                const bool desc = (i & size) == 0;
-                if ((x < y) == desc) { q[i] = y; q[j] = x; }
-            }
-            wave_lds_sync();
-        }
-    }
-}
 
 // sort user u's queue, keep its k best, raise its threshold (one wave; cnt / thr / queue are LDS)
 template <int CAP>
@@ -59,27 +28,6 @@ __device__ __forceinline__ void topk_compact(uint64_t* q, int32_t* cnt, uint64_t
         *thr = keep == k ? q[k - 1] : 0;
     }
     wave_lds_sync();
-}
-
-__device__ __forceinline__ bool topk_excluded(const int32_t* x, int64_t lo, int64_t hi, int32_t item) {
-    const int64_t end = hi;
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (x[mid] < item) lo = mid + 1; else hi = mid;
-    }
-    return lo < end && x[lo] == item;
-}
-
-template <bool V4>
-__device__ __forceinline__ float4 topk_load4(const float* row, int t, int D) {
-    if (V4) return *reinterpret_cast<const float4*>(row + 4 * t);
-    const int f = 4 * t;
-    float4 v;
-    v.x = f < D ? row[f] : 0.f;
-    v.y = f + 1 < D ? row[f + 1] : 0.f;
-    v.z = f + 2 < D ? row[f + 2] : 0.f;
-    v.w = f + 3 < D ? row[f + 3] : 0.f;
-    return v;
 }
 
 template <int UPB, int CAP, bool V4>
@@ -120,34 +68,13 @@ __global__ __launch_bounds__(256) void k_topk_score(TopkArgs a) {
     const int64_t s_lo = (int64_t)slice * per;
     const int64_t s_hi = s_lo + per < a.n_items ? s_lo + per : a.n_items;
     const int64_t rounds = s_hi > s_lo ? (s_hi - s_lo + TOPK_ROUND - 1) / TOPK_ROUND : 0;
-    const int DP4 = (a.D + 3) >> 2;
 
     for (int64_t rd = 0; rd < rounds; ++rd) {
         const int64_t base = s_lo + rd * TOPK_ROUND + wave * TOPK_SUB;
         int64_t my_item = base + c;                    // A row = item; past the slice: a row inside it, result dropped
         if (my_item >= s_hi) my_item = s_hi - 1;
         const float* qrow = a.Q + my_item * a.D;
-        f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-        // lane (c, h) gives A[item c][f] and B[f][user c] for f = 2s + h of step s: elements h and h + 2 of float4 t = s / 2
-        for (int t0 = 0; t0 < DP4; t0 += 4) {
-            float4 qa[4], pb[4];
-#pragma unroll
-            for (int z = 0; z < 4; ++z)
-                if (t0 + z < DP4) { qa[z] = topk_load4<V4>(qrow, t0 + z, a.D); pb[z] = topk_load4<V4>(prow, t0 + z, a.D); }
-#pragma unroll
-            for (int z = 0; z < 4; ++z) {
-                if (t0 + z < DP4) {
-                    float4 q = qa[z];
-                    if (a.item_abs) { q.x = fabsf(q.x); q.y = fabsf(q.y); q.z = fabsf(q.z); q.w = fabsf(q.w); }
-                    const float a0 = h ? q.y : q.x, a1 = h ? q.w : q.z;
-                    const float b0 = h ? pb[z].y : pb[z].x, b1 = h ? pb[z].w : pb[z].z;
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc, 0, 0, 0);
-                }
-            }
-        }
+        const f32x16 acc = mfma_tile_dot<V4>(qrow, prow, a.D, a.item_abs, h);
         // C[item row][user column]: this lane holds user j, items base + (r&3) + 8(r>>2) + 4h
         const uint64_t th = thr[j];
         if (live) {

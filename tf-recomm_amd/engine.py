@@ -57,6 +57,52 @@ def exclusion_csr(exclude, rows):
     return np.ascontiguousarray(x.indptr, np.int64), np.ascontiguousarray(x.indices, np.int32)
 
 
+def target_csr(targets, rows):
+    """``targets`` as the C-ABI's target rows: (indptr int64 from 0, items int32 with every row strictly increasing, order).
+    ``targets`` is an (indptr, items) pair aligned with ``rows`` (a row in any order; ``order`` is the permutation that sorted
+    it: sorted position ``j`` holds the caller's item ``order[j]``; None when the rows were already strictly increasing) or a
+    ``scipy.sparse`` matrix whose row ``r`` lists the targets of id ``r`` (gathered for ``rows``; ``order`` None, the ranks
+    follow the gathered rows' sorted indices).
+    A repeated item in a row raises ValueError."""
+    if isinstance(targets, tuple):
+        indptr, items = targets
+        indptr = np.asarray(indptr, np.int64).reshape(-1)
+        items = L.as_i32(items, "target items").reshape(-1)
+        if indptr.size != len(rows) + 1:
+            raise ValueError("target indptr must hold n_users + 1 entries")
+        if indptr.size and (indptr[0] < 0 or np.any(np.diff(indptr) < 0) or indptr[-1] > items.size):
+            raise ValueError("target indptr must be non-decreasing and inside its items")
+        items = items[indptr[0]:indptr[-1]]
+        indptr = indptr - indptr[0]
+        row = np.repeat(np.arange(len(rows), dtype=np.int64), np.diff(indptr))
+        order = None
+        if items.size > 1 and np.any((items[1:] <= items[:-1]) & (row[1:] == row[:-1])):
+            order = np.lexsort((items, row))           # rows not yet strictly increasing: sort them, remember how
+            items = np.ascontiguousarray(items[order])
+    else:
+        x = targets.tocsr()[np.asarray(rows, np.int64)]
+        x.sort_indices()
+        indptr, items, order = np.asarray(x.indptr, np.int64), np.ascontiguousarray(x.indices, np.int32), None
+        row = np.repeat(np.arange(len(rows), dtype=np.int64), np.diff(indptr))
+    if items.size > 1 and np.any((items[1:] == items[:-1]) & (row[1:] == row[:-1])):
+        raise ValueError("a target row repeats an item")
+    return np.ascontiguousarray(indptr, np.int64), items, order
+
+
+def rank_call(fn, rows, targets, exclude):
+    """Shared body of ``SvdModel.rank_items`` / ``FmModel.rank_items``: fn(indptr, items, x_indptr, x_items, out) -> rc."""
+    indptr, items, order = target_csr(targets, rows)
+    xp, xi = exclusion_csr(exclude, rows)
+    out = np.empty(items.size, np.int32)
+    fn(L.ptr_i64(indptr), L.ptr_i32(items), None if xp is None else L.ptr_i64(xp), None if xi is None else L.ptr_i32(xi),
+       L.ptr_i32(out))
+    if order is None:
+        return out
+    ranks = np.empty_like(out)
+    ranks[order] = out
+    return ranks
+
+
 class SvdModel:
     """The five trainables of ops.py:8-12,29-32 (+ optimiser slots) resident in HBM."""
 
@@ -308,6 +354,20 @@ class SvdModel:
                                        None if scores is None else scores.data_ptr()))
         cur.wait_stream(mine)                          # (so no record_stream: the tensors' next users on `cur` come after)
         return (items, scores) if return_scores else items
+
+    # -- held-out ranking (include/tfrecomm.h tfr_rank_items; tfrecomm_amd.ranking for the metrics) -------------
+    def rank_items(self, users, targets, exclude=None):
+        """0-based rank of each target item of each of ``users`` among all items not in ``exclude``: the number of eligible
+        items with a non-NaN score whose key (score descending, then item id ascending, as ``recommend``) beats the target's.
+        -1 for a target that is excluded or scores NaN.  ``rank < k`` exactly when the target is in ``recommend(users, k,
+        exclude)``, at that position.  ``targets``: an (indptr, items) pair aligned with ``users`` (ranks aligned with those
+        items) or a ``scipy.sparse`` ``[user_num, item_num]`` matrix (ranks aligned with its rows for ``users``, indices
+        sorted); ``exclude`` as in ``recommend``.  Returns int32 ranks."""
+        u = L.as_i32(users, "user ids").reshape(-1)
+
+        def call(ip, it, xp, xi, out):
+            L.check(self._lib.tfr_rank_items(self._h, L.ptr_i32(u), u.size, ip, it, xp, xi, out))
+        return rank_call(call, u, targets, exclude)
 
     # -- resident store -----------------------------------------------------------
     def upload_triples(self, users, items, rates):

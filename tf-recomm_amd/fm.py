@@ -113,6 +113,17 @@ class FmModel(object):
                                           L.ptr_i32(items), None if scores is None else L.ptr_f32(scores)))
         return (items, scores) if return_scores else items
 
+    def rank_items(self, user_features, item_lo, item_hi, targets, exclude=None):
+        """``SvdModel.rank_items`` for the ``topk`` scores: item features ``[item_lo, item_hi)``, ids (in ``targets`` and
+        ``exclude``) relative to ``item_lo``; a sparse ``targets`` / ``exclude`` is indexed by user feature."""
+        from .engine import rank_call
+        u = L.as_i32(user_features, "user features").reshape(-1)
+
+        def call(ip, it, xp, xi, out):
+            self._check(self._lib.tfr_fm_rank_items(self._h, L.ptr_i32(u), u.size, int(item_lo), int(item_hi), ip, it, xp,
+                                                    xi, out))
+        return rank_call(call, u, targets, exclude)
+
     def get_ranking(self, encoded_user_id, user_num, item_num, k=50, exclude=None):
         """forward.py:47-61 ``get_ranking``: the reference's design rows put user ``u`` at feature ``u`` and item ``i`` at
         feature ``user_num + i``; returns (items [k] best first, their scores)."""
