@@ -305,12 +305,20 @@ def test_all_identical_ids_long_segment():
         _check_tables(m, orc.tables(), "identical", RTOL)
 
 
-def test_frozen_tables_var_list():
-    """var_list=[user_bias, user_features] (adaptive_test.py:28): the other three never move."""
-    U, I, D, B = 60, 50, 20, 200
+FROZEN_ITEM_SIDE = (1 << L.MU) | (1 << L.BI) | (1 << L.Q)      # var_list=[user_bias, user_features] (adaptive_test.py:28)
+FROZEN_USER_SIDE = (1 << L.BU) | (1 << L.P)
+
+
+# 60 x 50: the small-table tile path; 17000 rows a side (past CSORT_MAX_BINS): the fused big-table step (lazy Adam, SGD) and
+# the radix sort + dense sweeps (TF1)
+@pytest.mark.parametrize("U, I", [(60, 50), (17000, 17000)], ids=["tiles", "big"])
+@pytest.mark.parametrize("frozen", [FROZEN_ITEM_SIDE, FROZEN_USER_SIDE], ids=["item_side", "user_side"])
+def test_frozen_tables_var_list(frozen, U, I):
+    """Frozen tables never move; the others follow the oracle."""
+    D, B = 20, 200
     rs = np.random.RandomState(4)
     t = rand_tables(rs, U, I, D)
-    frozen = (1 << L.MU) | (1 << L.BI) | (1 << L.Q)
+    moving = L.Q if frozen >> L.P & 1 else L.P
     for kw in (dict(optimizer="adam", adam_mode="tf1"), dict(optimizer="adam", adam_mode="lazy"), dict(optimizer="sgd")):
         orc = make_oracle(U, I, D, t, frozen=frozen, **kw)
         with model_from(U, I, D, t, frozen=frozen, **kw) as m:
@@ -320,9 +328,10 @@ def test_frozen_tables_var_list():
                 m.train_step(u, i, r)
                 orc.train_step(u, i, r)
             after = m.tables()
-            assert np.array_equal(after[L.Q], t["Q"]) and np.array_equal(after[L.BI], t["bi"])
-            assert float(after[L.MU]) == float(t["mu"])
-            assert not np.array_equal(after[L.P], t["P"])
+            for tid in TIDS:
+                if frozen >> tid & 1:
+                    assert np.array_equal(np.ravel(after[tid]), np.ravel(t[TABLE_NAMES[tid]])), (TABLE_NAMES[tid], kw)
+            assert not np.array_equal(after[moving], t[TABLE_NAMES[moving]])
             _check_tables(m, orc.tables(), "frozen", 3 * RTOL)
 
 

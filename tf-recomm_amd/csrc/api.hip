@@ -663,23 +663,78 @@ int tfr_profile_read(tfr_model* m, int32_t kernel, double* total_ms, int64_t* la
 }  // extern "C"
 
 // ---------------------------------------------------------------------------------------
-// forward on device-resident ids
-static int run_forward(tfr_model* m, int mode, const int32_t* du, const int32_t* di, const float* dr,
-                       int64_t B, float* d_logits, float* d_g, int* nblk_out,
-                       const int64_t* d_store_ids = nullptr) {
-    { const int rcq = settle_q(m); if (rcq) return rcq; }
+// A training update's view of the model, written once for every step path.
+// One side of the factorisation: side = TFR_P (users: P, user_bias) or TFR_Q (items: Q, item_bias).  The side's tables,
+// their Adam slots and frozen bits go into the fields every update struct names alike; `w` is where the rows are written.
+template <typename A>
+static void bind_side_tables(A& a, float*& w, const tfr_model* m, int side) {
+    const int b = side == TFR_P ? TFR_BU : TFR_BI;
+    w = m->w[side]; a.m = m->m[side]; a.v = m->v[side];
+    a.bias_w = m->w[b]; a.bias_m = m->m[b]; a.bias_v = m->v[b];
+    a.frozen_rows = (m->frozen >> side) & 1; a.frozen_bias = (m->frozen >> b) & 1;
+}
+static void bind_side(RedArgs& a, const tfr_model* m, int side) { bind_side_tables(a, a.own_w, m, side); }
+static void bind_side(ApplyArgs& a, const tfr_model* m, int side) { bind_side_tables(a, a.w, m, side); }
+template <typename A>                    // DenseArgs, TileDenseArgs: the sweeps also cover every row of the side
+static void bind_side(A& a, const tfr_model* m, int side) {
+    bind_side_tables(a, a.w, m, side);
+    a.rows = side == TFR_P ? m->U : m->I;
+}
+
+// the optimiser at the model's current step
+struct OptStep { bool adam, tf1; float alpha, b1, b2, eps, lr; };
+static OptStep opt_step(const tfr_model* m) {
+    const tfr_opts& o = m->o;
+    const bool adam = o.optimizer == TFR_OPT_ADAM;
+    // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), float32 like the TF graph [TF1-lib]
+    return {adam, adam && o.adam_mode == TFR_ADAM_TF1, adam ? o.lr * sqrtf(1.f - m->b2p) / (1.f - m->b1p) : 0.f,
+            o.beta1, o.beta2, o.eps, o.lr};
+}
+template <typename A>
+static void set_hyper(A& a, const OptStep& k) { a.alpha = k.alpha; a.b1 = k.b1; a.b2 = k.b2; a.eps = k.eps; a.lr = k.lr; }
+
+// K4 with the bias_global update; partials and nblk are the caller's
+static FinArgs mu_fin(const tfr_model* m, const OptStep& k, bool update_mu, float* out) {
+    FinArgs f;
+    memset(&f, 0, sizeof(f));
+    f.scalars = m->scalars; f.out = out; f.err = m->d_err;
+    f.mu = m->w[TFR_MU]; f.mu_m = m->m[TFR_MU]; f.mu_v = m->v[TFR_MU];
+    f.update_mu = update_mu ? 1 : 0; f.opt = k.adam ? 0 : 1;
+    set_hyper(f, k);
+    return f;
+}
+
+// after a step's applies: the beta-power accumulators advance [TF1-lib], then the step count
+static void advance_step(tfr_model* m) {
+    if (m->o.optimizer == TFR_OPT_ADAM) {
+        m->b1p *= m->o.beta1;
+        m->b2p *= m->o.beta2;
+    }
+    m->step += 1;
+}
+
+// the forward's tables, batch and outputs; with d_store_ids the batch is gathered from the resident store
+static FwdArgs fwd_args(const tfr_model* m, const int32_t* du, const int32_t* di, const float* dr, int64_t B,
+                        float* d_logits, float* d_g, const int64_t* d_store_ids) {
     FwdArgs a;
     memset(&a, 0, sizeof(a));
     a.P = m->w[TFR_P]; a.Q = m->w[TFR_Q]; a.bu = m->w[TFR_BU]; a.bi = m->w[TFR_BI]; a.mu = m->w[TFR_MU];
     a.u = du; a.it = di; a.r = dr;
     a.logits = d_logits; a.g = d_g; a.partials = m->partials; a.err = m->d_err;
     a.B = B; a.U = m->U; a.I = m->I; a.N = m->N;
-    if (d_store_ids) {                 // fused gather from the resident store
-        a.ids = d_store_ids; a.store = m->store;
-        a.u_out = m->d_u; a.it_out = m->d_i;
-    }
-    { static int lr = -1; if (lr < 0) { const char* e = getenv("TFR_LDS_REDUCE"); lr = (e && e[0] == '1') ? 1 : 0; } a.lds_reduce = lr; }
+    if (d_store_ids) { a.ids = d_store_ids; a.store = m->store; }
     a.D = m->D; a.loss = m->o.loss; a.item_abs = m->o.item_abs; a.reg_bias = m->o.reg_bias;
+    return a;
+}
+
+// forward on device-resident ids
+static int run_forward(tfr_model* m, int mode, const int32_t* du, const int32_t* di, const float* dr,
+                       int64_t B, float* d_logits, float* d_g, int* nblk_out,
+                       const int64_t* d_store_ids = nullptr) {
+    { const int rcq = settle_q(m); if (rcq) return rcq; }
+    FwdArgs a = fwd_args(m, du, di, dr, B, d_logits, d_g, d_store_ids);
+    if (d_store_ids) { a.u_out = m->d_u; a.it_out = m->d_i; }     // the gathered ids, for the backward
+    { static int lr = -1; if (lr < 0) { const char* e = getenv("TFR_LDS_REDUCE"); lr = (e && e[0] == '1') ? 1 : 0; } a.lds_reduce = lr; }
     const int grid = forward_grid(B, m->G, mode);
     if (nblk_out) *nblk_out = grid;
     {
@@ -784,7 +839,6 @@ static int front_and_sort(tfr_model* m, const int32_t*& du, const int32_t*& di, 
                           float* d_logits, const int64_t* d_store_ids, FinArgs& f, int& nblk, bool& fin_done,
                           bool tiles = false, bool sort_only = false) {
     m->pf_valid = false;                                 // the sort scratch doubles as the published tables of the tile step
-    const tfr_opts& o = m->o;
     hipStream_t s = m->stream;
     int rc;
     if (sort_only) {
@@ -813,13 +867,7 @@ static int front_and_sort(tfr_model* m, const int32_t*& du, const int32_t*& di, 
         // scan (+K4) and scatter
         FrontArgs fa;
         memset(&fa, 0, sizeof(fa));
-        FwdArgs& fw = fa.f;
-        fw.P = m->w[TFR_P]; fw.Q = m->w[TFR_Q]; fw.bu = m->w[TFR_BU]; fw.bi = m->w[TFR_BI]; fw.mu = m->w[TFR_MU];
-        fw.u = du; fw.it = di; fw.r = dr;
-        fw.logits = d_logits; fw.g = m->d_g; fw.partials = m->partials; fw.err = m->d_err;
-        fw.B = B; fw.U = m->U; fw.I = m->I; fw.N = m->N;
-        fw.D = m->D; fw.loss = o.loss; fw.item_abs = o.item_abs; fw.reg_bias = o.reg_bias;
-        if (d_store_ids) { fw.ids = d_store_ids; fw.store = m->store; }     // rank blocks publish the ids
+        fa.f = fwd_args(m, du, di, dr, B, d_logits, m->d_g, d_store_ids);     // with store ids the rank blocks publish them
         CSortArgs& c = fa.c;
         c.keys[0] = d_store_ids ? m->d_u : du; c.keys[1] = d_store_ids ? m->d_i : di;
         c.ks[0] = m->ks_u; c.ks[1] = m->ks_i; c.ps[0] = m->ps_u; c.ps[1] = m->ps_i;
@@ -981,19 +1029,13 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
                           float* d_logits, float* out3, const int64_t* d_store_ids = nullptr,
                           const int64_t* next_store_ids = nullptr, bool presorted_big = false, bool out_err = false) {
     const tfr_opts& o = m->o;
-    const bool adam = o.optimizer == TFR_OPT_ADAM;
-    const bool tf1 = adam && o.adam_mode == TFR_ADAM_TF1;
-    // lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), float32 like the TF graph [TF1-lib]
-    const float alpha = adam ? o.lr * sqrtf(1.f - m->b2p) / (1.f - m->b1p) : 0.f;
+    const OptStep k = opt_step(m);
+    const bool adam = k.adam, tf1 = k.tf1;
     int nblk = 0;
     hipStream_t s = m->stream;
     bool fin_done = false, tiles = false;
-    FinArgs f;
-    memset(&f, 0, sizeof(f));
-    f.partials = m->partials; f.scalars = m->scalars; f.out = out3; f.out_err = out_err ? 1 : 0;
-    f.mu = m->w[TFR_MU]; f.mu_m = m->m[TFR_MU]; f.mu_v = m->v[TFR_MU]; f.err = m->d_err;
-    f.update_mu = !((m->frozen >> TFR_MU) & 1); f.opt = adam ? 0 : 1;
-    f.alpha = alpha; f.b1 = o.beta1; f.b2 = o.beta2; f.eps = o.eps; f.lr = o.lr;
+    FinArgs f = mu_fin(m, k, !((m->frozen >> TFR_MU) & 1), out3);
+    f.partials = m->partials; f.out_err = out_err ? 1 : 0;
     if (B > 0) {
         int rc;
         tiles = tiles_eligible(m, B);
@@ -1052,19 +1094,15 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
             memset(&d, 0, sizeof(d));
             d.err = m->d_err; d.D = m->D; d.ntiles = (int32_t)((B + CSORT_TILE - 1) / CSORT_TILE);
             d.opt = adam ? 0 : 1; d.skip_untouched = tf1 ? 0 : 1;
-            d.alpha = alpha; d.b1 = o.beta1; d.b2 = o.beta2; d.eps = o.eps; d.lr = o.lr;
+            set_hyper(d, k);
             L.a[0] = d;                // items
-            L.a[0].tab = par ? m->offs_i : m->hist_i; L.a[0].nbins = 1 << m->bits_i; L.a[0].rows = m->I;
+            bind_side(L.a[0], m, TFR_Q);
+            L.a[0].tab = par ? m->offs_i : m->hist_i; L.a[0].nbins = 1 << m->bits_i;
             L.a[0].grad_rows = m->gq; L.a[0].grad_bias = m->gbq;
-            L.a[0].w = m->w[TFR_Q]; L.a[0].m = m->m[TFR_Q]; L.a[0].v = m->v[TFR_Q];
-            L.a[0].bias_w = m->w[TFR_BI]; L.a[0].bias_m = m->m[TFR_BI]; L.a[0].bias_v = m->v[TFR_BI];
-            L.a[0].frozen_rows = (m->frozen >> TFR_Q) & 1; L.a[0].frozen_bias = (m->frozen >> TFR_BI) & 1;
             L.a[1] = d;                // users
-            L.a[1].tab = par ? m->offs_u : m->hist_u; L.a[1].nbins = 1 << m->bits_u; L.a[1].rows = m->U;
+            bind_side(L.a[1], m, TFR_P);
+            L.a[1].tab = par ? m->offs_u : m->hist_u; L.a[1].nbins = 1 << m->bits_u;
             L.a[1].grad_rows = pr.a[1].grad_rows; L.a[1].grad_bias = m->gbp;
-            L.a[1].w = m->w[TFR_P]; L.a[1].m = m->m[TFR_P]; L.a[1].v = m->v[TFR_P];
-            L.a[1].bias_w = m->w[TFR_BU]; L.a[1].bias_m = m->m[TFR_BU]; L.a[1].bias_v = m->v[TFR_BU];
-            L.a[1].frozen_rows = (m->frozen >> TFR_P) & 1; L.a[1].frozen_bias = (m->frozen >> TFR_BU) & 1;
             L.f = f;
             {
                 Prof p(m, TFR_K_APPLY);
@@ -1076,8 +1114,8 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
         RedArgs r;
         memset(&r, 0, sizeof(r));
         r.g = m->d_g; r.err = m->d_err; r.B = B; r.D = m->D;
-        r.item_abs = o.item_abs; r.reg_bias = o.reg_bias;
-        r.lam = o.reg; r.alpha = alpha; r.b1 = o.beta1; r.b2 = o.beta2; r.eps = o.eps; r.lr = o.lr;
+        r.item_abs = o.item_abs; r.reg_bias = o.reg_bias; r.lam = o.reg;
+        set_hyper(r, k);
         // big tables: every row of this step is touched once and cannot stay cached - non-temporal loads / stores for the
         // rows, default policy only for reading back the pre-update copies (A/B in one gpurun call, TFR_NT=<bits>:
         // 523-548 us/step with 0, 498 with 23; bits in svd_kernels.h RedArgs::nt)
@@ -1093,10 +1131,8 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
         ru.side = 0;
         ru.ks = m->ks_u; ru.ps = m->ps_u; ru.other = di;
         ru.own = m->w[TFR_P]; ru.partner = m->w[TFR_Q]; ru.own_bias = m->w[TFR_BU];
-        ru.own_w = m->w[TFR_P]; ru.m = m->m[TFR_P]; ru.v = m->v[TFR_P];
-        ru.bias_w = m->w[TFR_BU]; ru.bias_m = m->m[TFR_BU]; ru.bias_v = m->v[TFR_BU];
+        bind_side(ru, m, TFR_P);
         ru.grad_bias = m->gbp; ru.map = tf1 ? m->map_u : nullptr;
-        ru.frozen_rows = (m->frozen >> TFR_P) & 1; ru.frozen_bias = (m->frozen >> TFR_BU) & 1;
         if (tf1) {
             // both sides only read the tables: one launch
             ru.grad_rows = m->gp;
@@ -1114,9 +1150,7 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
             // side, which then updates P; pieces of runs cut by a block boundary are parked in
             // the first (items) and second (users) third of gq and finished by k_apply_rows.
             float* qcopy = m->gq + 2 * (size_t)m->cap * m->D;
-            ri.own_w = m->w[TFR_Q]; ri.m = m->m[TFR_Q]; ri.v = m->v[TFR_Q];
-            ri.bias_w = m->w[TFR_BI]; ri.bias_m = m->m[TFR_BI]; ri.bias_v = m->v[TFR_BI];
-            ri.frozen_rows = (m->frozen >> TFR_Q) & 1; ri.frozen_bias = (m->frozen >> TFR_BI) & 1;
+            bind_side(ri, m, TFR_Q);
             if (dual) {
                 // the updated item row goes to the table the row is NOT in, so the user side still finds the pre-update row where
                 // it was: no copy written (4D per rating) and none read
@@ -1152,19 +1186,15 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
             ApplyArgs ap;
             memset(&ap, 0, sizeof(ap));
             ap.err = m->d_err; ap.B = B; ap.D = m->D; ap.only_split = 1;
-            ap.alpha = alpha; ap.b1 = o.beta1; ap.b2 = o.beta2; ap.eps = o.eps; ap.lr = o.lr;
+            set_hyper(ap, k);
             ApplyPair app;
             app.a[0] = ap;
+            bind_side(app.a[0], m, TFR_Q);
             app.a[0].ks = m->ks_i; app.a[0].grad_rows = m->gq; app.a[0].grad_bias = m->gbq;
-            app.a[0].w = m->w[TFR_Q]; app.a[0].m = m->m[TFR_Q]; app.a[0].v = m->v[TFR_Q];
-            app.a[0].bias_w = m->w[TFR_BI]; app.a[0].bias_m = m->m[TFR_BI]; app.a[0].bias_v = m->v[TFR_BI];
-            app.a[0].frozen_rows = ri.frozen_rows; app.a[0].frozen_bias = ri.frozen_bias;
             if (dual) { app.a[0].w_alt = m->q_alt; app.a[0].sel = m->q_sel; }
             app.a[1] = ap;
+            bind_side(app.a[1], m, TFR_P);
             app.a[1].ks = m->ks_u; app.a[1].grad_rows = ru.grad_rows; app.a[1].grad_bias = m->gbp;
-            app.a[1].w = m->w[TFR_P]; app.a[1].m = m->m[TFR_P]; app.a[1].v = m->v[TFR_P];
-            app.a[1].bias_w = m->w[TFR_BU]; app.a[1].bias_m = m->m[TFR_BU]; app.a[1].bias_v = m->v[TFR_BU];
-            app.a[1].frozen_rows = ru.frozen_rows; app.a[1].frozen_bias = ru.frozen_bias;
             if (!fin_done) {           // K4 rides in the same launch (one launch and ~6 us fewer per big-table step)
                 f.nblk = nblk;
                 app.f = f; app.with_fin = 1;
@@ -1184,22 +1214,16 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
         DenseArgs d;
         memset(&d, 0, sizeof(d));
         d.err = m->d_err; d.D = m->D; d.B = B;
-        d.alpha = alpha; d.b1 = o.beta1; d.b2 = o.beta2; d.eps = o.eps;
+        set_hyper(d, k);
         DensePair dp;
         dp.a[0] = d;
+        bind_side(dp.a[0], m, TFR_P);
         dp.a[0].map = m->map_u; dp.a[0].ks = m->ks_u; dp.a[0].grad_rows = m->gp; dp.a[0].grad_bias = m->gbp;
         dp.a[0].dense_grad = m->dg_p; dp.a[0].dense_gbias = m->dg_bu;
-        dp.a[0].rows = m->U;
-        dp.a[0].w = m->w[TFR_P]; dp.a[0].m = m->m[TFR_P]; dp.a[0].v = m->v[TFR_P];
-        dp.a[0].bias_w = m->w[TFR_BU]; dp.a[0].bias_m = m->m[TFR_BU]; dp.a[0].bias_v = m->v[TFR_BU];
-        dp.a[0].frozen_rows = (m->frozen >> TFR_P) & 1; dp.a[0].frozen_bias = (m->frozen >> TFR_BU) & 1;
         dp.a[1] = d;
+        bind_side(dp.a[1], m, TFR_Q);
         dp.a[1].map = m->map_i; dp.a[1].ks = m->ks_i; dp.a[1].grad_rows = m->gq; dp.a[1].grad_bias = m->gbq;
         dp.a[1].dense_grad = m->dg_q; dp.a[1].dense_gbias = m->dg_bi;
-        dp.a[1].rows = m->I;
-        dp.a[1].w = m->w[TFR_Q]; dp.a[1].m = m->m[TFR_Q]; dp.a[1].v = m->v[TFR_Q];
-        dp.a[1].bias_w = m->w[TFR_BI]; dp.a[1].bias_m = m->m[TFR_BI]; dp.a[1].bias_v = m->v[TFR_BI];
-        dp.a[1].frozen_rows = (m->frozen >> TFR_Q) & 1; dp.a[1].frozen_bias = (m->frozen >> TFR_BI) & 1;
         // the sweep also consumes (clears) the row->slot maps, so it always runs on both tables
         launch_adam_dense(dp, 2, m->G, m->VEC, s);
         HIPCHK(hipGetLastError());
@@ -1210,11 +1234,7 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
         launch_finalize(f, s);
     }
     HIPCHK(hipGetLastError());
-    if (adam) {                       // beta-power accumulators advance after the applies [TF1-lib]
-        m->b1p *= o.beta1;
-        m->b2p *= o.beta2;
-    }
-    m->step += 1;
+    advance_step(m);
     return TFR_OK;
 }
 
@@ -2370,21 +2390,20 @@ static int shard_forward_reduce_part(tfr_model* m, const float* d_item_rows, flo
     int rc;
     if ((rc = ensure_capacity(m, B > nI ? B : nI))) return rc;
     const tfr_opts& o = m->o;
-    const bool adam = o.optimizer == TFR_OPT_ADAM;
-    const bool tf1 = adam && o.adam_mode == TFR_ADAM_TF1;
-    const float alpha = adam ? o.lr * sqrtf(1.f - m->b2p) / (1.f - m->b1p) : 0.f;
+    const OptStep k = opt_step(m);
+    const bool adam = k.adam, tf1 = k.tf1;
     hipStream_t s = m->stream;
     int nblk = (int)((B + 1024 / m->G - 1) / (1024 / m->G));
     RedArgs r;
     memset(&r, 0, sizeof(r));
     r.g = m->d_g; r.err = m->d_err; r.B = B; r.D = m->D; r.dB = dB;
-    r.item_abs = o.item_abs; r.reg_bias = o.reg_bias;
-    r.lam = o.reg; r.alpha = alpha; r.b1 = o.beta1; r.b2 = o.beta2; r.eps = o.eps; r.lr = o.lr;
+    r.item_abs = o.item_abs; r.reg_bias = o.reg_bias; r.lam = o.reg;
+    set_hyper(r, k);
     RedPair pr;
     ApplyArgs ap;
     memset(&ap, 0, sizeof(ap));
     ap.err = m->d_err; ap.B = B; ap.D = m->D; ap.dB = dB;
-    ap.alpha = alpha; ap.b1 = o.beta1; ap.b2 = o.beta2; ap.eps = o.eps; ap.lr = o.lr;
+    set_hyper(ap, k);
     ApplyPair app;
     if (part & 1) {
         // a peer that had to void this step (capacity overflow, id out of range) said so beside its rows: void it here too, before
@@ -2445,11 +2464,9 @@ static int shard_forward_reduce_part(tfr_model* m, const float* d_item_rows, flo
         if (!R.fks_u) return fail(TFR_ERR_STATE, "shard_reduce_users: call tfr_shard_forward_items on this routed batch first");
         ru.ks = R.fks_u; ru.ps = R.fps_u; ru.other = dslot;
         ru.own = m->w[TFR_P]; ru.partner = d_item_rows; ru.pstride = DS; ru.own_bias = m->w[TFR_BU];
-        ru.own_w = m->w[TFR_P]; ru.m = m->m[TFR_P]; ru.v = m->v[TFR_P];
-        ru.bias_w = m->w[TFR_BU]; ru.bias_m = m->m[TFR_BU]; ru.bias_v = m->v[TFR_BU];
+        bind_side(ru, m, TFR_P);
         ru.grad_bias = m->gbp; ru.map = tf1 ? m->map_u : nullptr;
         ru.grad_rows = tf1 ? m->gp : m->gq + (size_t)m->cap * m->D;
-        ru.frozen_rows = (m->frozen >> TFR_P) & 1; ru.frozen_bias = (m->frozen >> TFR_BU) & 1;
         pr.a[0] = ru;
         {
             Prof p(m, TFR_K_REDUCE_USER);
@@ -2459,10 +2476,8 @@ static int shard_forward_reduce_part(tfr_model* m, const float* d_item_rows, flo
         if (!tf1) {
             app.a[0] = ap;
             app.a[0].only_split = 1;
+            bind_side(app.a[0], m, TFR_P);
             app.a[0].ks = R.fks_u; app.a[0].grad_rows = ru.grad_rows; app.a[0].grad_bias = m->gbp;
-            app.a[0].w = m->w[TFR_P]; app.a[0].m = m->m[TFR_P]; app.a[0].v = m->v[TFR_P];
-            app.a[0].bias_w = m->w[TFR_BU]; app.a[0].bias_m = m->m[TFR_BU]; app.a[0].bias_v = m->v[TFR_BU];
-            app.a[0].frozen_rows = ru.frozen_rows; app.a[0].frozen_bias = ru.frozen_bias;
             Prof p(m, TFR_K_APPLY);
             launch_apply_rows(app, 1, adam ? 0 : 1, m->G, m->VEC, s);
         }
@@ -2473,11 +2488,9 @@ static int shard_forward_reduce_part(tfr_model* m, const float* d_item_rows, flo
         memset(&dp, 0, sizeof(dp));
         DenseArgs& d = dp.a[0];
         d.err = m->d_err; d.D = m->D; d.B = B;
-        d.alpha = alpha; d.b1 = o.beta1; d.b2 = o.beta2; d.eps = o.eps;
-        d.map = m->map_u; d.ks = R.fks_u; d.grad_rows = m->gp; d.grad_bias = m->gbp; d.rows = m->U;
-        d.w = m->w[TFR_P]; d.m = m->m[TFR_P]; d.v = m->v[TFR_P];
-        d.bias_w = m->w[TFR_BU]; d.bias_m = m->m[TFR_BU]; d.bias_v = m->v[TFR_BU];
-        d.frozen_rows = (m->frozen >> TFR_P) & 1; d.frozen_bias = (m->frozen >> TFR_BU) & 1;
+        set_hyper(d, k);
+        bind_side(d, m, TFR_P);
+        d.map = m->map_u; d.ks = R.fks_u; d.grad_rows = m->gp; d.grad_bias = m->gbp;
         Prof p(m, TFR_K_APPLY);
         launch_adam_dense(dp, 1, m->G, m->VEC, s);
         HIPCHK(hipGetLastError());
@@ -2508,10 +2521,8 @@ int tfr_shard_apply_items(tfr_model* m, const int32_t* d_req_recv, const float* 
     int rc;
     if ((rc = settle_q(m))) return rc;
     if ((rc = ensure_capacity(m, n > 0 ? n : 1))) return rc;
-    const tfr_opts& o = m->o;
-    const bool adam = o.optimizer == TFR_OPT_ADAM;
-    const bool tf1 = adam && o.adam_mode == TFR_ADAM_TF1;
-    const float alpha = adam ? o.lr * sqrtf(1.f - m->b2p) / (1.f - m->b1p) : 0.f;
+    const OptStep k = opt_step(m);
+    const bool adam = k.adam, tf1 = k.tf1;
     const int DS = shard_stride(m);
     hipStream_t s = m->stream;
     int32_t* d_nvalid = R.counts + R.world + 2;           // requests actually received (unused slots excluded)
@@ -2534,13 +2545,11 @@ int tfr_shard_apply_items(tfr_model* m, const int32_t* d_req_recv, const float* 
         RedArgs& r = pr.a[0];
         memset(&r, 0, sizeof(r));
         r.err = m->d_err; r.B = n; r.D = m->D; r.side = 1; r.dB = d_nvalid;
-        r.alpha = alpha; r.b1 = o.beta1; r.b2 = o.beta2; r.eps = o.eps; r.lr = o.lr;
+        set_hyper(r, k);
+        bind_side(r, m, TFR_Q);
         r.ks = aks; r.ps = aps; r.rows_in = d_grad_recv; r.rstride = DS; r.bias_in = d_grad_recv + m->D; r.rbstride = DS;
         r.own = m->w[TFR_Q]; r.own_bias = m->w[TFR_BI];
-        r.own_w = m->w[TFR_Q]; r.m = m->m[TFR_Q]; r.v = m->v[TFR_Q];
-        r.bias_w = m->w[TFR_BI]; r.bias_m = m->m[TFR_BI]; r.bias_v = m->v[TFR_BI];
         r.grad_rows = m->gq; r.grad_bias = m->gbq; r.map = tf1 ? m->map_i : nullptr;
-        r.frozen_rows = (m->frozen >> TFR_Q) & 1; r.frozen_bias = (m->frozen >> TFR_BI) & 1;
         {
             Prof p(m, TFR_K_REDUCE_ITEM);
             launch_seg_reduce(pr, 1, tf1 ? RMODE_SCRATCH : (adam ? RMODE_ADAM : RMODE_SGD), m->G, m->VEC, s);
@@ -2551,11 +2560,9 @@ int tfr_shard_apply_items(tfr_model* m, const int32_t* d_req_recv, const float* 
             ApplyArgs& ap = app.a[0];
             memset(&ap, 0, sizeof(ap));
             ap.err = m->d_err; ap.B = n; ap.D = m->D; ap.only_split = 1; ap.dB = d_nvalid;
-            ap.alpha = alpha; ap.b1 = o.beta1; ap.b2 = o.beta2; ap.eps = o.eps; ap.lr = o.lr;
+            set_hyper(ap, k);
+            bind_side(ap, m, TFR_Q);
             ap.ks = aks; ap.grad_rows = m->gq; ap.grad_bias = m->gbq;
-            ap.w = m->w[TFR_Q]; ap.m = m->m[TFR_Q]; ap.v = m->v[TFR_Q];
-            ap.bias_w = m->w[TFR_BI]; ap.bias_m = m->m[TFR_BI]; ap.bias_v = m->v[TFR_BI];
-            ap.frozen_rows = r.frozen_rows; ap.frozen_bias = r.frozen_bias;
             Prof p(m, TFR_K_APPLY);
             launch_apply_rows(app, 1, adam ? 0 : 1, m->G, m->VEC, s);
         }
@@ -2566,11 +2573,9 @@ int tfr_shard_apply_items(tfr_model* m, const int32_t* d_req_recv, const float* 
         memset(&dp, 0, sizeof(dp));
         DenseArgs& d = dp.a[0];
         d.err = m->d_err; d.D = m->D; d.B = n;
-        d.alpha = alpha; d.b1 = o.beta1; d.b2 = o.beta2; d.eps = o.eps;
-        d.map = m->map_i; d.ks = aks; d.grad_rows = m->gq; d.grad_bias = m->gbq; d.rows = m->I;
-        d.w = m->w[TFR_Q]; d.m = m->m[TFR_Q]; d.v = m->v[TFR_Q];
-        d.bias_w = m->w[TFR_BI]; d.bias_m = m->m[TFR_BI]; d.bias_v = m->v[TFR_BI];
-        d.frozen_rows = (m->frozen >> TFR_Q) & 1; d.frozen_bias = (m->frozen >> TFR_BI) & 1;
+        set_hyper(d, k);
+        bind_side(d, m, TFR_Q);
+        d.map = m->map_i; d.ks = aks; d.grad_rows = m->gq; d.grad_bias = m->gbq;
         Prof p(m, TFR_K_APPLY);
         launch_adam_dense(dp, 1, m->G, m->VEC, s);
         HIPCHK(hipGetLastError());
@@ -2623,25 +2628,14 @@ int tfr_shard_presort(tfr_model* m, const int32_t* d_req_recv, int64_t n) {
 int tfr_shard_finish_step(tfr_model* m, const float* d_scalars4) {
     MODEL_ENTER(m);
     if (!d_scalars4) return fail(TFR_ERR_ARG, "shard_finish_step: null scalars");
-    const tfr_opts& o = m->o;
-    const bool adam = o.optimizer == TFR_OPT_ADAM;
-    const float alpha = adam ? o.lr * sqrtf(1.f - m->b2p) / (1.f - m->b1p) : 0.f;
-    FinArgs f;
-    memset(&f, 0, sizeof(f));
-    f.partials = d_scalars4; f.nblk = 1; f.scalars = m->scalars; f.out = nullptr;
-    f.mu = m->w[TFR_MU]; f.mu_m = m->m[TFR_MU]; f.mu_v = m->v[TFR_MU]; f.err = m->d_err;
-    f.update_mu = !((m->frozen >> TFR_MU) & 1); f.opt = adam ? 0 : 1;
-    f.alpha = alpha; f.b1 = o.beta1; f.b2 = o.beta2; f.eps = o.eps; f.lr = o.lr;
+    FinArgs f = mu_fin(m, opt_step(m), !((m->frozen >> TFR_MU) & 1), nullptr);
+    f.partials = d_scalars4; f.nblk = 1;
     {
         Prof p(m, TFR_K_FINALIZE);
         launch_finalize(f, m->stream);
     }
     HIPCHK(hipGetLastError());
-    if (adam) {
-        m->b1p *= o.beta1;
-        m->b2p *= o.beta2;
-    }
-    m->step += 1;
+    advance_step(m);
     return TFR_OK;
 }
 
@@ -2760,11 +2754,8 @@ int tfr_dp_local_grads(tfr_model* m, const int32_t* du, const int32_t* di, const
 int tfr_dp_apply(tfr_model* m, float* d_flat) {
     MODEL_ENTER(m);
     if (!d_flat) return fail(TFR_ERR_ARG, "dp_apply: null buffer");
-    const tfr_opts& o = m->o;
-    const bool adam = o.optimizer == TFR_OPT_ADAM;
-    if (adam && o.adam_mode != TFR_ADAM_TF1)
-        return fail(TFR_ERR_STATE, "data-parallel steps need dense semantics: Adam tf1 or SGD");
-    const float alpha = adam ? o.lr * sqrtf(1.f - m->b2p) / (1.f - m->b1p) : 0.f;
+    const OptStep k = opt_step(m);
+    if (k.adam && !k.tf1) return fail(TFR_ERR_STATE, "data-parallel steps need dense semantics: Adam tf1 or SGD");
     { const int rcq = settle_q(m); if (rcq) return rcq; }
     float* gP = d_flat;
     float* gQ = gP + m->U * m->D;
@@ -2775,35 +2766,23 @@ int tfr_dp_apply(tfr_model* m, float* d_flat) {
     memset(&dp, 0, sizeof(dp));
     DenseArgs d;
     memset(&d, 0, sizeof(d));
-    d.err = m->d_err; d.D = m->D; d.opt = adam ? 0 : 1;
-    d.alpha = alpha; d.b1 = o.beta1; d.b2 = o.beta2; d.eps = o.eps; d.lr = o.lr;
+    d.err = m->d_err; d.D = m->D; d.opt = k.adam ? 0 : 1;
+    set_hyper(d, k);
     dp.a[0] = d;
-    dp.a[0].dense_grad = gP; dp.a[0].dense_gbias = gbu; dp.a[0].rows = m->U;
-    dp.a[0].w = m->w[TFR_P]; dp.a[0].m = m->m[TFR_P]; dp.a[0].v = m->v[TFR_P];
-    dp.a[0].bias_w = m->w[TFR_BU]; dp.a[0].bias_m = m->m[TFR_BU]; dp.a[0].bias_v = m->v[TFR_BU];
-    dp.a[0].frozen_rows = (m->frozen >> TFR_P) & 1; dp.a[0].frozen_bias = (m->frozen >> TFR_BU) & 1;
+    bind_side(dp.a[0], m, TFR_P);
+    dp.a[0].dense_grad = gP; dp.a[0].dense_gbias = gbu;
     dp.a[1] = d;
-    dp.a[1].dense_grad = gQ; dp.a[1].dense_gbias = gbi; dp.a[1].rows = m->I;
-    dp.a[1].w = m->w[TFR_Q]; dp.a[1].m = m->m[TFR_Q]; dp.a[1].v = m->v[TFR_Q];
-    dp.a[1].bias_w = m->w[TFR_BI]; dp.a[1].bias_m = m->m[TFR_BI]; dp.a[1].bias_v = m->v[TFR_BI];
-    dp.a[1].frozen_rows = (m->frozen >> TFR_Q) & 1; dp.a[1].frozen_bias = (m->frozen >> TFR_BI) & 1;
-    FinArgs f;                         // bias_global from the all-reduced {loss, reg, sum g}; rides in the sweep
-    memset(&f, 0, sizeof(f));
-    f.partials = tail; f.nblk = 1; f.scalars = m->scalars; f.out = nullptr;
-    f.mu = m->w[TFR_MU]; f.mu_m = m->m[TFR_MU]; f.mu_v = m->v[TFR_MU]; f.err = m->d_err;
-    f.update_mu = !((m->frozen >> TFR_MU) & 1); f.opt = adam ? 0 : 1;
-    f.alpha = alpha; f.b1 = o.beta1; f.b2 = o.beta2; f.eps = o.eps; f.lr = o.lr;
-    f.clear_partials = 1;                                        // scalars consumed: clean for the next step
+    bind_side(dp.a[1], m, TFR_Q);
+    dp.a[1].dense_grad = gQ; dp.a[1].dense_gbias = gbi;
+    FinArgs f = mu_fin(m, k, !((m->frozen >> TFR_MU) & 1), nullptr);   // bias_global from the all-reduced {loss, reg, sum g}
+    f.partials = tail; f.nblk = 1;                                       // rides in the sweep
+    f.clear_partials = 1;                                                // scalars consumed: clean for the next step
     {
         Prof p(m, TFR_K_APPLY);
         launch_adam_dense(dp, 2, m->G, m->VEC, m->stream, &f);
     }
     HIPCHK(hipGetLastError());
-    if (adam) {
-        m->b1p *= o.beta1;
-        m->b2p *= o.beta2;
-    }
-    m->step += 1;
+    advance_step(m);
     return TFR_OK;
 }
 
@@ -2880,13 +2859,13 @@ static int fm_train_core(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_in
                          const float* d_y, int64_t n_rows, int64_t nnz, float* d_pred, float* out3) {
     tfr_model* m = f->m;
     const tfr_opts& o = m->o;
-    const bool adam = o.optimizer == TFR_OPT_ADAM;
+    const OptStep k = opt_step(m);
+    const bool adam = k.adam;
     if (adam && o.adam_mode != TFR_ADAM_LAZY) return fail(TFR_ERR_STATE, "FM training supports SGD and lazy Adam");
     int rc;
     if ((rc = ensure_capacity(m, nnz > 0 ? nnz : 1))) return rc;
     HIPCHK(f->s_rows.reserve(n_rows * m->D, m->stream));
     HIPCHK(f->ent.reserve(nnz, m->stream));
-    const float alpha = adam ? o.lr * sqrtf(1.f - m->b2p) / (1.f - m->b1p) : 0.f;
     hipStream_t s = m->stream;
     FmArgs a;
     memset(&a, 0, sizeof(a));
@@ -2914,12 +2893,11 @@ static int fm_train_core(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_in
         RedPair pr;
         RedArgs& r = pr.a[0];
         memset(&r, 0, sizeof(r));
-        r.err = m->d_err; r.B = nnz; r.D = m->D; r.side = 0; r.reg_bias = 1;
-        r.lam = o.reg; r.alpha = alpha; r.b1 = o.beta1; r.b2 = o.beta2; r.eps = o.eps; r.lr = o.lr;
+        r.err = m->d_err; r.B = nnz; r.D = m->D; r.side = 0; r.reg_bias = 1; r.lam = o.reg;
+        set_hyper(r, k);
+        bind_side(r, m, TFR_P);          // V and W: the wrapped model's user side (its frozen mask stays 0)
         r.ks = m->ks_u; r.ps = m->ps_u; r.ent = f->ent;
         r.own = m->w[TFR_P]; r.partner = f->s_rows; r.own_bias = m->w[TFR_BU];
-        r.own_w = m->w[TFR_P]; r.m = m->m[TFR_P]; r.v = m->v[TFR_P];
-        r.bias_w = m->w[TFR_BU]; r.bias_m = m->m[TFR_BU]; r.bias_v = m->v[TFR_BU];
         r.grad_rows = m->gq + (size_t)m->cap * m->D; r.grad_bias = m->gbp;
         {
             Prof p(m, TFR_K_REDUCE_USER);
@@ -2930,33 +2908,24 @@ static int fm_train_core(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_in
         ApplyArgs& ap = app.a[0];
         memset(&ap, 0, sizeof(ap));
         ap.err = m->d_err; ap.B = nnz; ap.D = m->D; ap.only_split = 1;
-        ap.alpha = alpha; ap.b1 = o.beta1; ap.b2 = o.beta2; ap.eps = o.eps; ap.lr = o.lr;
+        set_hyper(ap, k);
+        bind_side(ap, m, TFR_P);
         ap.ks = m->ks_u; ap.grad_rows = r.grad_rows; ap.grad_bias = m->gbp;
-        ap.w = m->w[TFR_P]; ap.m = m->m[TFR_P]; ap.v = m->v[TFR_P];
-        ap.bias_w = m->w[TFR_BU]; ap.bias_m = m->m[TFR_BU]; ap.bias_v = m->v[TFR_BU];
         {
             Prof p(m, TFR_K_APPLY);
             launch_apply_rows(app, 1, adam ? 0 : 1, m->G, m->VEC, s);
         }
         HIPCHK(hipGetLastError());
     }
-    FinArgs fin;
-    memset(&fin, 0, sizeof(fin));
-    fin.partials = m->partials; fin.nblk = grid; fin.scalars = m->scalars; fin.out = out3;
-    fin.mu = m->w[TFR_MU]; fin.mu_m = m->m[TFR_MU]; fin.mu_v = m->v[TFR_MU]; fin.err = m->d_err;
-    fin.update_mu = 1; fin.opt = adam ? 0 : 1;
-    fin.alpha = alpha; fin.b1 = o.beta1; fin.b2 = o.beta2; fin.eps = o.eps; fin.lr = o.lr;
+    FinArgs fin = mu_fin(m, k, true, out3);
+    fin.partials = m->partials; fin.nblk = grid;
     {
         Prof p(m, TFR_K_FINALIZE);
         launch_finalize(fin, s);
     }
     (void)hipEventRecord(f->ev1, s);
     HIPCHK(hipGetLastError());
-    if (adam) {
-        m->b1p *= o.beta1;
-        m->b2p *= o.beta2;
-    }
-    m->step += 1;
+    advance_step(m);
     return TFR_OK;
 }
 
@@ -3109,6 +3078,43 @@ static TopkTables svd_topk_tables(const tfr_model* m) {
     return {m->w[TFR_P], m->w[TFR_BU], m->w[TFR_Q], m->w[TFR_BI], m->w[TFR_MU], m->U, m->I, m->o.item_abs};
 }
 
+// FM: V / W of the wrapped model are the users' and the items' features, mu its bias_global; items are features
+// [item_lo, item_hi).  `who` prefixes the error.
+static int fm_topk_tables(const tfr_model* m, const char* who, int64_t item_lo, int64_t item_hi, TopkTables* t) {
+    if (item_lo < 0 || item_hi <= item_lo || item_hi > m->U)
+        return fail(TFR_ERR_ARG, "%s: item feature range [%lld, %lld) not inside [0, %lld)", who, (long long)item_lo,
+                    (long long)item_hi, (long long)m->U);
+    *t = {m->w[TFR_P], m->w[TFR_BU], m->w[TFR_P] + item_lo * m->D, m->w[TFR_BU] + item_lo, m->w[TFR_MU], m->U, item_hi - item_lo, 0};
+    return TFR_OK;
+}
+
+// host ids: every ids[0..n) inside [0, rows)
+static int check_ids(const char* who, const char* what, const int32_t* ids, int64_t n, int64_t rows) {
+    for (int64_t r = 0; r < n; ++r)
+        if (ids[r] < 0 || (int64_t)ids[r] >= rows)
+            return fail(TFR_ERR_OOB, "%s: %s %d outside [0, %lld)", who, what, ids[r], (long long)rows);
+    return TFR_OK;
+}
+
+// a host CSR of n item rows, targets (each row strictly increasing) or exclusions (each row sorted): indptr non-decreasing from
+// >= 0, checked whole before any item is read, and items inside [0, n_items)
+static int check_csr(const char* who, bool targets, const int64_t* ip, const int32_t* it, int64_t n, int64_t n_items) {
+    const char* what = targets ? "target" : "exclusion";
+    if (ip[0] < 0) return fail(TFR_ERR_ARG, "%s: %s indptr starts below 0", who, what);
+    for (int64_t r = 0; r < n; ++r)
+        if (ip[r + 1] < ip[r]) return fail(TFR_ERR_ARG, "%s: %s indptr decreases at row %lld", who, what, (long long)r);
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t e = ip[r]; e < ip[r + 1]; ++e) {
+            if (it[e] < 0 || (int64_t)it[e] >= n_items)
+                return fail(TFR_ERR_OOB, "%s: %s item %d outside [0, %lld)", who, targets ? "target" : "excluded", it[e],
+                            (long long)n_items);
+            if (e > ip[r] && (targets ? it[e - 1] >= it[e] : it[e - 1] > it[e]))
+                return fail(TFR_ERR_ARG, "%s: %s row %lld is not %s", who, what, (long long)r,
+                            targets ? "strictly increasing" : "sorted");
+        }
+    return TFR_OK;
+}
+
 // one chunk of rows, all pointers on the device: scoring (item slices) -> merge into items_out / scores_out
 static int topk_chunk(tfr_model* m, const TopkTables& t, const TopkPlan& p, const int32_t* d_users, int64_t rows, int32_t k,
                       const int64_t* d_indptr, const int32_t* d_excl, int32_t* d_items, float* d_scores) {
@@ -3146,24 +3152,10 @@ static int topk_host(tfr_model* m, const TopkTables& t, const int32_t* users, in
     if (n == 0) return TFR_OK;
     if (!users || !items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
     if (indptr && !excl && indptr[n] > indptr[0]) return fail(TFR_ERR_ARG, "top-K: exclusion indptr without items");
-    for (int64_t r = 0; r < n; ++r)
-        if (users[r] < 0 || (int64_t)users[r] >= t.U)
-            return fail(TFR_ERR_OOB, "top-K: user id %d outside [0, %lld)", users[r], (long long)t.U);
-    if (indptr) {
-        if (indptr[0] < 0) return fail(TFR_ERR_ARG, "top-K: exclusion indptr starts below 0");
-        for (int64_t r = 0; r < n; ++r) {
-            if (indptr[r + 1] < indptr[r]) return fail(TFR_ERR_ARG, "top-K: exclusion indptr decreases at row %lld", (long long)r);
-            for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
-                if (excl[e] < 0 || (int64_t)excl[e] >= t.n_items)
-                    return fail(TFR_ERR_OOB, "top-K: excluded item %d outside [0, %lld)", excl[e], (long long)t.n_items);
-                if (e > indptr[r] && excl[e - 1] > excl[e])
-                    return fail(TFR_ERR_ARG, "top-K: exclusion row %lld is not sorted", (long long)r);
-            }
-        }
-    }
+    int rc = check_ids("top-K", "user id", users, n, t.U);
+    if (rc || (indptr && (rc = check_csr("top-K", false, indptr, excl, n, t.n_items)))) return rc;
     TopkPlan p;
-    int rc = topk_prepare(m, k, n, t.n_items, &p);
-    if (rc) return rc;
+    if ((rc = topk_prepare(m, k, n, t.n_items, &p))) return rc;
     HIPCHK(m->tk_users.reserve(pow2_cap(p.chunk), m->stream));
     HIPCHK(m->tk_items.reserve(pow2_cap(p.chunk * k), m->stream));
     if (scores_out) HIPCHK(m->tk_scores.reserve(pow2_cap(p.chunk * k), m->stream));
@@ -3247,13 +3239,9 @@ int tfr_fm_topk(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_
     tfr_model* m = f->m;
     HIPCHK(hipSetDevice(m->device));
     if (k < 1 || k > TOPK_KMAX) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
-    if (item_lo < 0 || item_hi <= item_lo || item_hi > m->U)
-        return fail(TFR_ERR_ARG, "top-K: item feature range [%lld, %lld) not inside [0, %lld)", (long long)item_lo,
-                    (long long)item_hi, (long long)m->U);
-    // V = the wrapped model's user_features, W = its user_bias, mu = its bias_global; items are features [item_lo, item_hi)
-    const TopkTables t = {m->w[TFR_P], m->w[TFR_BU], m->w[TFR_P] + item_lo * m->D, m->w[TFR_BU] + item_lo, m->w[TFR_MU],
-                          m->U, item_hi - item_lo, 0};
-    return topk_host(m, t, user_features, n_users, k, excl_indptr, excl_items, items_out, scores_out);
+    TopkTables t;
+    const int rc = fm_topk_tables(m, "top-K", item_lo, item_hi, &t);
+    return rc ? rc : topk_host(m, t, user_features, n_users, k, excl_indptr, excl_items, items_out, scores_out);
 }
 
 }  // extern "C"
@@ -3267,34 +3255,12 @@ static int rank_host(tfr_model* m, const TopkTables& t, const int32_t* users, in
     if (n < 0) return fail(TFR_ERR_ARG, "rank: negative n_users");
     if (n == 0) return TFR_OK;
     if (!users || !tip) return fail(TFR_ERR_ARG, "rank: null users / target indptr");
-    if (tip[0] < 0) return fail(TFR_ERR_ARG, "rank: target indptr starts below 0");
-    for (int64_t r = 0; r < n; ++r)
-        if (tip[r + 1] < tip[r]) return fail(TFR_ERR_ARG, "rank: target indptr decreases at row %lld", (long long)r);
     const int64_t n_tgt = tip[n] - tip[0];
     if (n_tgt > 0 && (!tit || !ranks_out)) return fail(TFR_ERR_ARG, "rank: null target items / ranks_out");
     if (xip && !xit && xip[n] > xip[0]) return fail(TFR_ERR_ARG, "rank: exclusion indptr without items");
-    for (int64_t r = 0; r < n; ++r)
-        if (users[r] < 0 || (int64_t)users[r] >= t.U)
-            return fail(TFR_ERR_OOB, "rank: user id %d outside [0, %lld)", users[r], (long long)t.U);
-    for (int64_t r = 0; r < n; ++r)
-        for (int64_t e = tip[r]; e < tip[r + 1]; ++e) {
-            if (tit[e] < 0 || (int64_t)tit[e] >= t.n_items)
-                return fail(TFR_ERR_OOB, "rank: target item %d outside [0, %lld)", tit[e], (long long)t.n_items);
-            if (e > tip[r] && tit[e - 1] >= tit[e])
-                return fail(TFR_ERR_ARG, "rank: target row %lld is not strictly increasing", (long long)r);
-        }
-    if (xip) {
-        if (xip[0] < 0) return fail(TFR_ERR_ARG, "rank: exclusion indptr starts below 0");
-        for (int64_t r = 0; r < n; ++r) {
-            if (xip[r + 1] < xip[r]) return fail(TFR_ERR_ARG, "rank: exclusion indptr decreases at row %lld", (long long)r);
-            for (int64_t e = xip[r]; e < xip[r + 1]; ++e) {
-                if (xit[e] < 0 || (int64_t)xit[e] >= t.n_items)
-                    return fail(TFR_ERR_OOB, "rank: excluded item %d outside [0, %lld)", xit[e], (long long)t.n_items);
-                if (e > xip[r] && xit[e - 1] > xit[e])
-                    return fail(TFR_ERR_ARG, "rank: exclusion row %lld is not sorted", (long long)r);
-            }
-        }
-    }
+    int rc = check_ids("rank", "user id", users, n, t.U);
+    if (rc || (rc = check_csr("rank", true, tip, tit, n, t.n_items)) || (xip && (rc = check_csr("rank", false, xip, xit, n, t.n_items))))
+        return rc;
     if (n_tgt == 0) return TFR_OK;
     // pieces in row order: tlo absolute into tit, xlo / xhi absolute into xit (rebased per chunk below); prow = their rows
     std::vector<RankPiece> pieces;
@@ -3308,8 +3274,7 @@ static int rank_host(tfr_model* m, const TopkTables& t, const int32_t* users, in
     const int64_t np = (int64_t)pieces.size();
     RankPlan p;
     if (!rank_plan(np, t.n_items, &p)) return fail(TFR_ERR_ARG, "rank: no plan for %lld pieces", (long long)np);
-    int rc = settle_q(m);                                // item rows the fused big-table step left in q_alt come back first
-    if (rc) return rc;
+    if ((rc = settle_q(m))) return rc;                   // item rows the fused big-table step left in q_alt come back first
     hipStream_t s = m->stream;
     HIPCHK(m->rk_pieces.reserve(pow2_cap(p.chunk), s));
     HIPCHK(reserve_each(pow2_cap(p.chunk * RANK_CAP), s, m->rk_tgt, m->rk_ranks, m->rk_order, m->rk_bins));
@@ -3375,13 +3340,9 @@ int tfr_fm_rank_items(tfr_fm* f, const int32_t* user_features, int64_t n_users, 
     if (!f) return fail(TFR_ERR_ARG, "null model");
     tfr_model* m = f->m;
     HIPCHK(hipSetDevice(m->device));
-    if (item_lo < 0 || item_hi <= item_lo || item_hi > m->U)
-        return fail(TFR_ERR_ARG, "rank: item feature range [%lld, %lld) not inside [0, %lld)", (long long)item_lo,
-                    (long long)item_hi, (long long)m->U);
-    // the tables of tfr_fm_topk: V / W of the wrapped model, items are features [item_lo, item_hi)
-    const TopkTables t = {m->w[TFR_P], m->w[TFR_BU], m->w[TFR_P] + item_lo * m->D, m->w[TFR_BU] + item_lo, m->w[TFR_MU],
-                          m->U, item_hi - item_lo, 0};
-    return rank_host(m, t, user_features, n_users, tgt_indptr, tgt_items, excl_indptr, excl_items, ranks_out);
+    TopkTables t;
+    const int rc = fm_topk_tables(m, "rank", item_lo, item_hi, &t);
+    return rc ? rc : rank_host(m, t, user_features, n_users, tgt_indptr, tgt_items, excl_indptr, excl_items, ranks_out);
 }
 
 }  // extern "C"
@@ -3457,15 +3418,10 @@ int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, cons
     if (n_rounds > 0 && (!ask_items || !prefix_len)) return fail(TFR_ERR_ARG, "fine-tune: null ask_items / prefix_len");
     if (n_rounds > INT64_MAX / nsteps) return fail(TFR_ERR_ARG, "fine-tune: n_rounds x nsteps overflows");
     if (n_users > INT32_MAX) return fail(TFR_ERR_ARG, "fine-tune: too many users");
-    for (int64_t u = 0; u < n_users; ++u)
-        if (users[u] < 0 || (int64_t)users[u] >= m->U)
-            return fail(TFR_ERR_OOB, "fine-tune: user id %d outside [0, %lld)", users[u], (long long)m->U);
-    for (int64_t r = 0; r < n_rows; ++r)
-        if (items[r] < 0 || (int64_t)items[r] >= m->I)
-            return fail(TFR_ERR_OOB, "fine-tune: item id %d outside [0, %lld)", items[r], (long long)m->I);
-    for (int64_t k = 0; k < n_rounds; ++k)
-        if (ask_items[k] < 0 || (int64_t)ask_items[k] >= m->I)
-            return fail(TFR_ERR_OOB, "fine-tune: asked item id %d outside [0, %lld)", ask_items[k], (long long)m->I);
+    int rc;
+    if ((rc = check_ids("fine-tune", "user id", users, n_users, m->U)) || (rc = check_ids("fine-tune", "item id", items, n_rows, m->I)) ||
+        (rc = check_ids("fine-tune", "asked item id", ask_items, n_rounds, m->I)))
+        return rc;
     {
         // two waves on one user row would race: every user at most once
         std::vector<int32_t> sorted(users, users + n_users);
@@ -3519,8 +3475,7 @@ int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, cons
                  o_askout = take((size_t)n_rounds * 4), o_loss = take(round_loss_out ? (size_t)n_rounds * 4 : 0),
                  o_final = take(final_logits_out ? (size_t)n_rows * 4 : 0);
     HIPCHK(m->ft_buf.reserve((int64_t)off, m->stream));
-    int rc = settle_q(m);                                // item rows the fused big-table step left in q_alt come back first
-    if (rc) return rc;
+    if ((rc = settle_q(m))) return rc;                   // item rows the fused big-table step left in q_alt come back first
     char* b = m->ft_buf;
     hipStream_t s = m->stream;
     auto up = [&](size_t at, const void* src, size_t bytes) -> int {
