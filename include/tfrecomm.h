@@ -422,6 +422,56 @@ int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, cons
  * memory), waves (users) per workgroup */
 int tfr_finetune_plan(int32_t dim, int64_t max_rows, int64_t* lds_bytes, int32_t* rows_staged, int32_t* waves_per_block);
 
+/* ---- SVD++ (Koren, "Factorization Meets the Neighborhood", KDD 2008): the third model of the reference README - DESIGN §14 ----
+ *      A tfr_svdpp wraps a tfr_model (its five tables, optimiser, hyper-parameters, step and stream) and adds Y [I, D], the
+ *      implicit item factors, with their Adam slots, and the implicit sets N(u): a CSR [U, I] given by the caller.
+ *          s_u = 1/sqrt(|N(u)|), z_u = s_u * sum_{j in N(u)} Y[j] (z_u = 0 for an empty row),  e = P[u] + z_u
+ *          logit = ((dot(e, Q'[i]) + mu) + bu[u]) + bi[i]          (Q' = |Q| under item_abs; the SVD forward's add order)
+ *      Loss and heads are the SVD model's; the regulariser adds, per batch entry, 1/2 sum_{j in N(u)} ||Y[j]||^2.  Gradients
+ *      per occurrence with g = d loss / d logit: dP = g Q' + lam P, dQ = g e (x sign(Q) under item_abs) + lam Q, biases and mu
+ *      as in SVD, and dY[j] += g s_u Q'[i] + lam Y[j] for every j in N(u).  SGD or lazy Adam (touched rows); tf1 Adam is
+ *      refused (TFR_ERR_STATE).  Every quantity uses the tables before the step.  Sums have a fixed order: bit-identical
+ *      run to run.  Table ids: TFR_MU..TFR_Q and TFR_Y, each + TFR_SLOT_M / TFR_SLOT_V; frozen bit TFR_Y freezes Y.
+ *      Ids of a batch out of range void the step (every table) and the next synchronising call returns TFR_ERR_OOB, as the
+ *      SVD step.  Training, forward, top-K and ranking before tfr_svdpp_set_implicit return TFR_ERR_STATE. */
+typedef struct tfr_svdpp tfr_svdpp;
+enum { TFR_Y = 5 };
+int tfr_svdpp_create(tfr_svdpp** out, int64_t user_num, int64_t item_num, int32_t dim, const tfr_opts* opts);
+int tfr_svdpp_destroy(tfr_svdpp* m);
+int tfr_svdpp_set_table(tfr_svdpp* m, int32_t which, const float* host, int64_t n);
+int tfr_svdpp_get_table(tfr_svdpp* m, int32_t which, float* host, int64_t n);
+/* tfr_init_tables of the wrapped model plus Y ~ truncated normal(feature_stddev); zeroes Y's slots */
+int tfr_svdpp_init(tfr_svdpp* m, uint64_t seed, float feature_stddev, float bias_stddev);
+/* N(u): indptr [user_num + 1] from 0, non-decreasing; items with every row strictly increasing.  Checked on the host before
+ * any device work: an item outside [0, item_num) gives TFR_ERR_OOB, anything else malformed TFR_ERR_ARG.  Resident (with its
+ * transpose) until replaced; synchronises. */
+int tfr_svdpp_set_implicit(tfr_svdpp* m, const int64_t* indptr, const int32_t* items);
+int tfr_svdpp_set_frozen(tfr_svdpp* m, uint32_t mask);
+int tfr_svdpp_set_hyper(tfr_svdpp* m, float lr, float reg);
+int tfr_svdpp_get_step(tfr_svdpp* m, int64_t* step, float* beta1_power, float* beta2_power);
+int tfr_svdpp_set_step(tfr_svdpp* m, int64_t step, float beta1_power, float beta2_power);
+int tfr_svdpp_forward(tfr_svdpp* m, const int32_t* user, const int32_t* item, int64_t batch, float* logits_out);
+int tfr_svdpp_forward_dev(tfr_svdpp* m, const int32_t* d_user, const int32_t* d_item, int64_t batch, float* d_logits);
+/* sum_k (infer_k - rate_k)^2 and the count of infer == rate, as tfr_eval */
+int tfr_svdpp_eval(tfr_svdpp* m, const int32_t* user, const int32_t* item, const float* rate, int64_t batch,
+                   double* sum_sq_err_out, int64_t* n_equal_out);
+/* one minibatch: pre-update logits (may be NULL), data loss and regulariser, as tfr_train_step */
+int tfr_svdpp_train_step(tfr_svdpp* m, const int32_t* user, const int32_t* item, const float* rate, int64_t batch,
+                         float* logits_out, float* loss_out, float* reg_out);
+int tfr_svdpp_train_step_dev(tfr_svdpp* m, const int32_t* d_user, const int32_t* d_item, const float* d_rate, int64_t batch,
+                             float* d_logits /* may be NULL */);
+/* tfr_topk / tfr_topk_dev / tfr_rank_items with e = P[u] + z_u in place of P[u]: the same keys, so rank < K exactly when
+ * tfr_svdpp_topk(K) returns the item, at that position */
+int tfr_svdpp_topk(tfr_svdpp* m, const int32_t* users, int64_t n_users, int32_t k, const int64_t* excl_indptr,
+                   const int32_t* excl_items, int32_t* items_out, float* scores_out);
+int tfr_svdpp_topk_dev(tfr_svdpp* m, const int32_t* d_users, int64_t n_users, int32_t k, const int64_t* d_excl_indptr,
+                       const int32_t* d_excl_items, int32_t* d_items_out, float* d_scores_out);
+int tfr_svdpp_rank_items(tfr_svdpp* m, const int32_t* users, int64_t n_users, const int64_t* tgt_indptr,
+                         const int32_t* tgt_items, const int64_t* excl_indptr, const int32_t* excl_items, int32_t* ranks_out);
+int tfr_svdpp_get_stream(tfr_svdpp* m, void** hip_stream);
+int tfr_svdpp_sync(tfr_svdpp* m);            /* drains the stream; reports deferred TFR_ERR_OOB */
+const char* tfr_svdpp_last_error(void);
+
 /* ---- per-kernel timing with HIP events on the model's stream (bench.py roofline) -------- */
 enum {
     TFR_K_FORWARD = 0,        /* gather-dot forward (+ fused loss/grad when training)       */

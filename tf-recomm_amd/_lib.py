@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libtfrecomm_hip.so")
 ABI_VERSION = 3       # include/tfrecomm.h TFR_ABI_VERSION this binding was written against (checked at load)
 OK, ERR_ARG, ERR_OOB, ERR_HIP, ERR_STATE, ERR_NOMEM = 0, -1, -2, -3, -4, -5
 MU, BU, BI, P, Q = 0, 1, 2, 3, 4
+Y = 5                 # SVD++ implicit item factors (tfr_svdpp_* only)
 SLOT_M, SLOT_V = 8, 16
 LOSS = {"mse": 0, "nll": 1}
 OPTIMIZER = {"adam": 0, "sgd": 1}
@@ -147,6 +148,27 @@ SIGNATURES = {
     "tfr_finetune_users": (C.c_int, [_p, C.c_int64, _i32p, _i64p, _i32p, _f32p, _i64p, _i32p, _i32p, _i64p, C.c_int32,
                                      _f32p, _f32p, _f32p]),
     "tfr_finetune_plan": (C.c_int, [C.c_int32, C.c_int64, _i64p, _i32p, _i32p]),
+    "tfr_svdpp_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_int32, C.POINTER(TfrOpts)]),
+    "tfr_svdpp_destroy": (C.c_int, [_p]),
+    "tfr_svdpp_set_table": (C.c_int, [_p, C.c_int32, _f32p, C.c_int64]),
+    "tfr_svdpp_get_table": (C.c_int, [_p, C.c_int32, _f32p, C.c_int64]),
+    "tfr_svdpp_init": (C.c_int, [_p, C.c_uint64, C.c_float, C.c_float]),
+    "tfr_svdpp_set_implicit": (C.c_int, [_p, _i64p, _i32p]),
+    "tfr_svdpp_set_frozen": (C.c_int, [_p, C.c_uint32]),
+    "tfr_svdpp_set_hyper": (C.c_int, [_p, C.c_float, C.c_float]),
+    "tfr_svdpp_get_step": (C.c_int, [_p, _i64p, _f32p, _f32p]),
+    "tfr_svdpp_set_step": (C.c_int, [_p, C.c_int64, C.c_float, C.c_float]),
+    "tfr_svdpp_forward": (C.c_int, [_p, _i32p, _i32p, C.c_int64, _f32p]),
+    "tfr_svdpp_forward_dev": (C.c_int, [_p, _p, _p, C.c_int64, _p]),
+    "tfr_svdpp_eval": (C.c_int, [_p, _i32p, _i32p, _f32p, C.c_int64, _f64p, _i64p]),
+    "tfr_svdpp_train_step": (C.c_int, [_p, _i32p, _i32p, _f32p, C.c_int64, _f32p, _f32p, _f32p]),
+    "tfr_svdpp_train_step_dev": (C.c_int, [_p, _p, _p, _p, C.c_int64, _p]),
+    "tfr_svdpp_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
+    "tfr_svdpp_topk_dev": (C.c_int, [_p, _p, C.c_int64, C.c_int32, _p, _p, _p, _p]),
+    "tfr_svdpp_rank_items": (C.c_int, [_p, _i32p, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
+    "tfr_svdpp_get_stream": (C.c_int, [_p, C.POINTER(_p)]),
+    "tfr_svdpp_sync": (C.c_int, [_p]),
+    "tfr_svdpp_last_error": (C.c_char_p, []),
     "tfr_sync": (C.c_int, [_p]),
     "tfr_last_error": (C.c_char_p, []),
     "tfr_version": (C.c_int, []),

@@ -3186,6 +3186,30 @@ static int topk_host(tfr_model* m, const TopkTables& t, const int32_t* users, in
     return check_device_error(m);
 }
 
+// the device entry: every pointer on the device, the exclusion CSR checked there; no synchronisation
+static int topk_dev(tfr_model* m, const TopkTables& t, const int32_t* d_users, int64_t n, int32_t k,
+                    const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t* d_items_out, float* d_scores_out) {
+    if (n < 0) return fail(TFR_ERR_ARG, "top-K: negative n_users");
+    if (k < 1 || k > TOPK_KMAX) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
+    if (n == 0) return TFR_OK;
+    if (!d_users || !d_items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
+    if (d_excl_indptr && !d_excl_items) return fail(TFR_ERR_ARG, "top-K: exclusion indptr without items");
+    TopkPlan p;
+    int rc = topk_prepare(m, k, n, t.n_items, &p);
+    if (rc) return rc;
+    if (d_excl_indptr) {
+        launch_topk_check_excl(d_excl_indptr, d_excl_items, n, t.n_items, m->tk_bad, m->d_err, m->stream);
+        HIPCHK(hipGetLastError());
+    }
+    for (int64_t c0 = 0; c0 < n; c0 += p.chunk) {
+        const int64_t rows = n - c0 < p.chunk ? n - c0 : p.chunk;
+        if ((rc = topk_chunk(m, t, p, d_users + c0, rows, k, d_excl_indptr ? d_excl_indptr + c0 : nullptr, d_excl_items,
+                             d_items_out + c0 * k, d_scores_out ? d_scores_out + c0 * k : nullptr)))
+            return rc;
+    }
+    return TFR_OK;
+}
+
 extern "C" {
 
 int tfr_topk_plan(int32_t dim, int32_t k, int64_t n_users, int64_t item_num, int64_t* lds_bytes, int32_t* users_per_block,
@@ -3211,26 +3235,7 @@ int tfr_topk(tfr_model* m, const int32_t* users, int64_t n_users, int32_t k, con
 int tfr_topk_dev(tfr_model* m, const int32_t* d_users, int64_t n, int32_t k, const int64_t* d_excl_indptr,
                  const int32_t* d_excl_items, int32_t* d_items_out, float* d_scores_out) {
     MODEL_ENTER(m);
-    if (n < 0) return fail(TFR_ERR_ARG, "top-K: negative n_users");
-    if (k < 1 || k > TOPK_KMAX) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
-    if (n == 0) return TFR_OK;
-    if (!d_users || !d_items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
-    if (d_excl_indptr && !d_excl_items) return fail(TFR_ERR_ARG, "top-K: exclusion indptr without items");
-    const TopkTables t = svd_topk_tables(m);
-    TopkPlan p;
-    int rc = topk_prepare(m, k, n, t.n_items, &p);
-    if (rc) return rc;
-    if (d_excl_indptr) {
-        launch_topk_check_excl(d_excl_indptr, d_excl_items, n, t.n_items, m->tk_bad, m->d_err, m->stream);
-        HIPCHK(hipGetLastError());
-    }
-    for (int64_t c0 = 0; c0 < n; c0 += p.chunk) {
-        const int64_t rows = n - c0 < p.chunk ? n - c0 : p.chunk;
-        if ((rc = topk_chunk(m, t, p, d_users + c0, rows, k, d_excl_indptr ? d_excl_indptr + c0 : nullptr, d_excl_items,
-                             d_items_out + c0 * k, d_scores_out ? d_scores_out + c0 * k : nullptr)))
-            return rc;
-    }
-    return TFR_OK;
+    return topk_dev(m, svd_topk_tables(m), d_users, n, k, d_excl_indptr, d_excl_items, d_items_out, d_scores_out);
 }
 
 int tfr_fm_topk(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_t item_lo, int64_t item_hi, int32_t k,
@@ -3517,3 +3522,6 @@ int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, cons
 }
 
 }  // extern "C"
+
+// ---- SVD++ (tfr_svdpp*, svdpp.hip): the wrapped model's internals are shared, so its entry points live in this unit
+#include "svdpp_api.inc.h"

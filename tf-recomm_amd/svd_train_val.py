@@ -149,6 +149,43 @@ def svd_resident(train, test, *, user_num=None, item_num=None, dim=None, batch_s
     return rows
 
 
+def svdpp(train, test, *, user_num=None, item_num=None, dim=None, batch_size=None, epoch_max=None,
+          learning_rate=None, reg=None, device=None, optimizer="adam", log=print):
+    """The ``svd`` run with the SVD++ model: N(u) = the items u rated in the training frame; the same
+    minibatch stream, evaluation points and README epoch rows.  Returns the list of (epoch, train_error, val_error,
+    seconds) rows."""
+    from .engine import rated_matrix
+    from .svdpp import SvdppModel
+    user_num, item_num = user_num or C.USER_NUM, item_num or C.ITEM_NUM
+    dim, batch_size = dim or C.DIM, batch_size or C.BATCH_SIZE
+    epoch_max = C.EPOCH_MAX if epoch_max is None else epoch_max
+    learning_rate = C.LEARNING_RATE if learning_rate is None else learning_rate
+    reg = C.LAMBDA_REG if reg is None else reg
+    device = C.DEVICE if device is None else device
+    nb_batches = len(train["user"]) // batch_size                       # svd_train_val.py:24
+    iter_train = dataio.ShuffleIterator([train["user"], train["item"], train["outcome"]], batch_size=batch_size)
+    rows = []
+    with SvdppModel(user_num, item_num, dim, optimizer=optimizer, lr=learning_rate, reg=reg, device=device) as m:
+        m.init_tables(seed=C.SEED)
+        m.set_implicit(rated_matrix(train["user"], train["item"], user_num, item_num))
+        log("{} {} {} {}".format("epoch", "train_error", "val_error", "elapsed_time"))
+        train_se = deque(maxlen=nb_batches)
+        start = time.time()
+        for i in range(epoch_max * nb_batches):
+            users, items, rates = next(iter_train)
+            logits, _, _ = m.train_step(users, items, rates)
+            train_se.append(np.power(rates - logits, 2))
+            if i % nb_batches == 0:                                     # :106 (also at i=0, after ONE step)
+                sse, _ = m.eval(test["user"], test["item"], test["outcome"])
+                end = time.time()
+                row = (i // nb_batches, float(np.sqrt(np.mean(train_se))), float(np.sqrt(sse / max(1, len(test["user"])))),
+                       end - start)
+                rows.append(row)
+                log("{:3d} {:f} {:f} {:f}(s)".format(*row))
+                start = end
+    return rows
+
+
 def synthetic_frames(user_num, item_num, n, seed=C.SEED):
     """ML-1M-shaped ratings from a low-rank ground truth (no dataset ships; no network)."""
     rs = np.random.RandomState(seed)
@@ -169,6 +206,7 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--batch", type=int, default=C.BATCH_SIZE)
     ap.add_argument("--dim", type=int, default=C.DIM)
+    ap.add_argument("--model", choices=("svd", "svdpp"), default="svd", help="svdpp: Koren's SVD++ with N(u) = training items")
     a = ap.parse_args(argv)
     np.random.seed(C.SEED)                                              # svd_train_val.py:15
     if a.data:
@@ -184,8 +222,11 @@ def main(argv=None):
     else:
         un, inum = C.USER_NUM, C.ITEM_NUM
         df_train, df_val = synthetic_frames(un, inum, 1000209)
-    svd(df_train, df_val, user_num=un, item_num=inum, dim=a.dim, batch_size=a.batch, epoch_max=a.epochs,
-        save_path=os.path.join(os.getcwd(), "fm.ckpt"))
+    if a.model == "svdpp":
+        svdpp(df_train, df_val, user_num=un, item_num=inum, dim=a.dim, batch_size=a.batch, epoch_max=a.epochs)
+    else:
+        svd(df_train, df_val, user_num=un, item_num=inum, dim=a.dim, batch_size=a.batch, epoch_max=a.epochs,
+            save_path=os.path.join(os.getcwd(), "fm.ckpt"))
     print("Done!")
 
 
