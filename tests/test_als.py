@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle.als_oracle import AlsOracle
+from tests import widths
 
 CASES = ("small", "d8")
 
@@ -62,9 +63,20 @@ def test_gpu_als_matches_reference_run(golden, name):
 
 @pytest.mark.gpu
 def test_gpu_als_larger_vs_oracle_and_deterministic():
+    _check_larger_vs_oracle(20)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d", widths.ALS)
+def test_gpu_als_larger_vs_oracle_at_both_ends_of_the_cholesky(d):
+    """d = 1 (one lane) and d = ALS_MAXD (every lane of the wave owns a row)"""
+    _check_larger_vs_oracle(d)
+
+
+def _check_larger_vs_oracle(d):
     import tfrecomm_amd as T
     rs = np.random.RandomState(3)
-    U, W, n, d = 700, 500, 60000, 20
+    U, W, n = 700, 500, 60000
     X = np.stack([rs.randint(0, U, n), rs.randint(0, W, n)], 1)
     y = rs.randint(1, 6, n).astype(np.float64)
     Xt = np.stack([rs.randint(0, U, 1000), rs.randint(0, W, 1000)], 1)
@@ -91,9 +103,19 @@ def test_gpu_als_larger_vs_oracle_and_deterministic():
 def test_gpu_als_long_lists_are_chunked_and_match_oracle():
     """One work holds a third of all ratings and one user a tenth: their lists are far longer than the
     chunk size, so their normal equations come from several blocks' partial sums."""
+    _check_long_lists(12)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("d", widths.ALS_CHUNKED)
+def test_gpu_als_long_lists_at_the_widest_d(d):
+    _check_long_lists(d)
+
+
+def _check_long_lists(d):
     import tfrecomm_amd as T
     rs = np.random.RandomState(5)
-    U, W, n, d = 400, 300, 40000, 12
+    U, W, n = 400, 300, 40000
     u = rs.randint(0, U, n); w = rs.randint(0, W, n)
     w[rs.rand(n) < 0.33] = 7                      # ~13000 ratings of one work
     u[rs.rand(n) < 0.10] = 3                      # ~4000 ratings of one user

@@ -14,6 +14,7 @@ from tfrecomm_amd import adaptive_test as AT
 from tfrecomm_amd import finetune as FT
 from tests.finetune_ref import OracleDriverModel, per_user_frame
 from tests.util import assert_close, rand_tables
+from tests import widths as W
 
 pytestmark = pytest.mark.gpu
 
@@ -52,6 +53,21 @@ CASES = [  # driver, D, opt, loss, item_abs, reg_bias
 
 @pytest.mark.parametrize("driver,D,opt,loss,item_abs,reg_bias", CASES)
 def test_batched_drivers_match_the_sequential_hip_drivers_and_the_oracle(driver, D, opt, loss, item_abs, reg_bias):
+    _check_batched_drivers(driver, D, opt, loss, item_abs, reg_bias)
+
+
+# at each width both drivers, each with its own optimiser, the optimisers swapping from one width to the next
+WIDTH_CASES = [(drv, D, ("sgd", "lazy")[(x + y) % 2], ("mse", "nll")[x % 2], bool(y), x % 3 == 0)
+               for x, D in enumerate(W.FINETUNE) for y, drv in enumerate(("non_adaptive", "adaptive"))]
+
+
+@pytest.mark.parametrize("driver,D,opt,loss,item_abs,reg_bias", WIDTH_CASES)
+def test_batched_drivers_at_every_register_width(driver, D, opt, loss, item_abs, reg_bias):
+    """k_finetune<NJ> at every NJ = ceil(D / 64), last register full and partial"""
+    _check_batched_drivers(driver, D, opt, loss, item_abs, reg_bias)
+
+
+def _check_batched_drivers(driver, D, opt, loss, item_abs, reg_bias):
     U, I = 40, 70
     rs = np.random.RandomState(D)
     t = rand_tables(rs, U, I, D, scale=0.3 / np.sqrt(D / 8.0))
@@ -114,7 +130,7 @@ def _powers_at(b1p, b2p, b1, b2, n):
     return float(b1p), float(b2p)
 
 
-@pytest.mark.parametrize("opt,D", [("sgd", 20), ("lazy", 5), ("lazy", 64), ("lazy", 256)])
+@pytest.mark.parametrize("opt,D", [("sgd", 20), ("lazy", 5), ("lazy", 64), ("lazy", 256), ("lazy", 192)])
 def test_a_user_alone_and_among_1000_others_is_bit_identical(opt, D):
     U, I = 1200, 500
     rs = np.random.RandomState(4)
@@ -157,16 +173,29 @@ def test_a_user_alone_and_among_1000_others_is_bit_identical(opt, D):
 
 @pytest.mark.parametrize("opt", ["sgd", "lazy"])
 def test_a_heavy_user_streamed_from_global_memory_matches_the_oracle(opt):
-    U, I, D = 50, 4000, 20
+    _check_streamed(opt, 20, lambda staged: 12)
+
+
+@pytest.mark.parametrize("opt", ["sgd", "lazy"])
+@pytest.mark.parametrize("D", W.FINETUNE_STREAMED)
+def test_staged_and_streamed_users_in_one_call_at_every_register_count(opt, D):
+    """k_finetune<NJ> with STAGED true and false in one launch at every NJ; the staged user has exactly as many rows as
+    tfr_finetune_plan stages at this width, the next user one more"""
+    _check_streamed(opt, D, lambda staged: staged, lambda staged: staged + 1)
+
+
+def _check_streamed(opt, D, light_rows, mid_rows=lambda staged: 500):
+    U, I = 50, 4000
     rs = np.random.RandomState(12)
-    t = rand_tables(rs, U, I, D, scale=0.05)
+    t = rand_tables(rs, U, I, D, scale=0.05 * np.sqrt(20.0 / D))
     kw, tol = _kw(opt, "nll")
     kw["lr"] = kw["lr"] / 30                        # thousands of rows per step
     users = np.array([17, 3, 40], np.int32)
-    s = _schedule(rs, users, I, [3000, 12, 500], 3, max_rounds=3)
     lds, staged, wpb = C.c_int64(), C.c_int32(), C.c_int32()
     assert L.load().tfr_finetune_plan(D, 3000, C.byref(lds), C.byref(staged), C.byref(wpb)) == L.OK
-    assert staged.value < 500                       # users 17 and 40 stream, user 3 is staged
+    light, mid = light_rows(staged.value), mid_rows(staged.value)
+    assert 1 <= light <= staged.value < mid < 3000  # users 17 and 40 stream, user 3 is staged
+    s = _schedule(rs, users, I, [3000, light, mid], 3, max_rounds=3)
     orc = OracleDriverModel(U, I, D, t, **kw)
     orc.set_frozen(AT.FROZEN_BUT_USER)
     want = orc.finetune_users(*s)

@@ -7,6 +7,7 @@ import scipy.sparse as sp
 import tfrecomm_amd as T
 from oracle import svd_oracle as so
 from tests.util import assert_close
+from tests import widths as W
 
 pytestmark = pytest.mark.gpu
 
@@ -27,6 +28,16 @@ def test_fm_golden(golden):
 
 @pytest.mark.parametrize("F,D,n,nnz", [(5000, 64, 3000, 8), (777, 15, 500, 3), (100000, 128, 4096, 12), (64, 4, 10, 64)])
 def test_fm_random_csr_matches_oracle_and_scipy_path(F, D, n, nnz):
+    _check_random_csr(F, D, n, nnz)
+
+
+@pytest.mark.parametrize("D", W.FM)
+def test_fm_random_csr_at_every_row_geometry(D):
+    """k_fm_forward at every (G, VEC)"""
+    _check_random_csr(300, D, 200, 6)
+
+
+def _check_random_csr(F, D, n, nnz):
     rs = np.random.RandomState(F + D)
     V = rs.normal(0, 0.1, (F, D)).astype(np.float32)
     W = rs.normal(0, 0.1, F).astype(np.float32)
@@ -116,6 +127,17 @@ def _random_design(rs, n, F, nnz, hot=20):
 @pytest.mark.parametrize("optimizer", ["sgd", "adam"])
 @pytest.mark.parametrize("F,D,n,nnz", [(400, 16, 700, 6), (5000, 64, 3000, 8), (90, 5, 257, 4)])
 def test_fm_training_matches_oracle(loss, optimizer, F, D, n, nnz):
+    _check_training(loss, optimizer, F, D, n, nnz)
+
+
+@pytest.mark.parametrize("D", W.FM)
+def test_fm_training_at_every_row_geometry(D):
+    """k_fm_forward (training form), the FM backward and its apply at every (G, VEC); loss and optimiser rotate"""
+    x = W.FM.index(D)
+    _check_training(("mse", "nll")[x % 2], ("sgd", "adam")[(x >> 1) % 2], 400, D, 700, 6)
+
+
+def _check_training(loss, optimizer, F, D, n, nnz):
     rs = np.random.RandomState(F + n)
     V0 = rs.normal(0, 0.1, (F, D)).astype(np.float32)
     W0 = rs.normal(0, 0.1, F).astype(np.float32)

@@ -8,6 +8,7 @@ import tfrecomm_amd as T
 from tfrecomm_amd import _lib as L
 from oracle import svd_oracle as so
 from tests.util import RTOL, assert_close, dup_heavy_ids, make_oracle, rand_tables, rel_err, TABLE_NAMES
+from tests import widths as W
 
 pytestmark = pytest.mark.gpu
 
@@ -510,6 +511,68 @@ def test_random_shapes_two_steps(case):
             run = 7.0 * B / max(1, min(U, I))
             # Adam's first steps amplify fp32 rounding of near-cancelling gradient elements (see the
             # full-size test); SGD through the same kernels stays at 4e-5
+            base = 2e-4 if opt == "adam" else 4 * RTOL
+            assert_close(got[tid], orc.tables()[tid], rtol=base * max(1.0, np.sqrt(run / 64)),
+                         what="table %s" % TABLE_NAMES[tid])
+
+
+# ------------------------------------------------------------------ every row geometry (G, VEC), both step paths
+# The optimiser and the loss form rotate across the widths (tests/widths.py; tests/test_width_coverage.py checks the lists).
+OPTS = [("adam", "tf1"), ("adam", "lazy"), ("sgd", "tf1")]
+
+
+def _rotation(widths, D):
+    x = widths.index(D)
+    return OPTS[x % 3], ("mse", "nll")[x % 2], bool((x >> 1) & 1), bool((x >> 2) & 1)
+
+
+@pytest.mark.parametrize("D", W.SVD_SMALL)
+def test_small_table_forward_and_five_steps_at_every_row_geometry(D):
+    """k_forward and k_tile_step at every (G, VEC) against the float64 oracle, at the seeded trajectory's tolerances"""
+    (opt, mode), loss, item_abs, reg_bias = _rotation(W.SVD_SMALL, D)
+    U, I, B = 500, 300, 700
+    rs = np.random.RandomState(300 + D)
+    t = rand_tables(rs, U, I, D, scale=0.3 / np.sqrt(max(D, 16) / 16))
+    kw = dict(loss=loss, item_abs=item_abs, reg_bias=reg_bias, optimizer=opt, adam_mode=mode, lr=2e-3, reg=0.03)
+    orc = make_oracle(U, I, D, t, **kw)
+    with model_from(U, I, D, t, **kw) as m:
+        u, i = dup_heavy_ids(rs, U, B), dup_heavy_ids(rs, I, B)
+        assert_close(m.forward(u, i), orc.forward(u, i), what="forward")
+        for s in range(5):
+            u, i = dup_heavy_ids(rs, U, B), dup_heavy_ids(rs, I, B)
+            r = (rs.rand(B) < 0.5).astype(np.float32) if loss == "nll" else rs.randint(1, 6, B).astype(np.float32)
+            logits, lossv, regv = m.train_step(u, i, r)
+            wl, wloss, wreg = orc.train_step(u, i, r)
+            tol = RTOL * (s + 1)
+            assert_close(logits, wl, rtol=tol, what="step %d logits" % s)
+            assert_close(lossv, wloss, rtol=tol, what="step %d loss" % s)
+            assert_close(regv, wreg, rtol=tol, what="step %d reg" % s)
+        _check_tables(m, orc.tables(), "final", RTOL * 10)
+
+
+@pytest.mark.parametrize("D", W.SVD_BIG)
+def test_big_table_step_at_every_row_geometry(D):
+    """U just above CSORT_MAX_BINS rows: the radix sort, k_seg_reduce, k_apply_rows and the fused in-place forms at every
+    (G, VEC), two steps against the float64 oracle at the sweep's tolerances"""
+    (opt, mode), loss, item_abs, reg_bias = _rotation(W.SVD_BIG, D)
+    U, I, B = 16384 + 77, 300, 3000
+    rs = np.random.RandomState(400 + D)
+    t = rand_tables(rs, U, I, D, scale=0.3 / np.sqrt(max(D, 16) / 16))
+    kw = dict(loss=loss, item_abs=item_abs, reg_bias=reg_bias, optimizer=opt, adam_mode=mode, lr=3e-3, reg=0.02)
+    orc = make_oracle(U, I, D, t, **kw)
+    with model_from(U, I, D, t, **kw) as m:
+        for s in range(2):
+            u, i = dup_heavy_ids(rs, U, B), dup_heavy_ids(rs, I, B)
+            r = (rs.rand(B) < 0.5).astype(np.float32) if loss == "nll" else rs.randint(1, 6, B).astype(np.float32)
+            logits, lossv, regv = m.train_step(u, i, r)
+            wl, wloss, wreg = orc.train_step(u, i, r)
+            tol = 2 * RTOL * (s + 1)
+            assert_close(logits, wl, rtol=tol, what="logits")
+            assert_close(lossv, wloss, rtol=tol, what="loss")
+            assert_close(regv, wreg, rtol=tol, what="reg")
+        got = m.tables()
+        for tid in TIDS:
+            run = 7.0 * B / max(1, min(U, I))
             base = 2e-4 if opt == "adam" else 4 * RTOL
             assert_close(got[tid], orc.tables()[tid], rtol=base * max(1.0, np.sqrt(run / 64)),
                          what="table %s" % TABLE_NAMES[tid])

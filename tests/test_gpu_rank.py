@@ -10,6 +10,7 @@ from tfrecomm_amd import _lib as L
 from tests.rank_ref import rank_ref
 from tests.topk_ref import svd_scores
 from tests.test_gpu_topk import dyadic, make, random_excl
+from tests import widths as W
 
 pytestmark = pytest.mark.gpu
 
@@ -40,7 +41,7 @@ def ref_ranks(m, t, users, trows, xrows=None):
     return rank_ref(S, trows, xrows)
 
 
-@pytest.mark.parametrize("D", DIMS)
+@pytest.mark.parametrize("D", sorted(set(DIMS) | set(W.RANK)))
 def test_exact_on_dyadic_tables(D):
     rs = np.random.RandomState(100 + D)
     U, I = 70, 900
@@ -56,7 +57,7 @@ def test_exact_on_dyadic_tables(D):
         m.close()
 
 
-@pytest.mark.parametrize("D", DIMS)
+@pytest.mark.parametrize("D", sorted(set(DIMS) | set(W.RANK_RANDOM)))
 def test_rank_is_position_in_recommend_on_random_tables(D):
     rs = np.random.RandomState(200 + D)
     U, I, K = 50, 2000, 256
@@ -242,9 +243,19 @@ def test_errors_leave_output_untouched():
 
 @pytest.mark.parametrize("dyad", [True, False])
 def test_fm_rank_items(dyad):
+    _check_fm_rank_items(dyad, 16)
+
+
+@pytest.mark.parametrize("dyad", [True, False])
+@pytest.mark.parametrize("D", W.FM_TOPK)
+def test_fm_rank_items_at_other_widths(dyad, D):
+    _check_fm_rank_items(dyad, D)
+
+
+def _check_fm_rank_items(dyad, D):
     from tests.test_gpu_topk import fm_two_hot
     rs = np.random.RandomState(10)
-    Un, In, D = 40, 500, 16
+    Un, In = 40, 500
     F = Un + In
     fm = T.FmModel(F, D)
     if dyad:

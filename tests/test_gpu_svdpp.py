@@ -6,6 +6,7 @@ import tfrecomm_amd as T
 from tfrecomm_amd import _lib as L
 from oracle import svd_oracle as so
 from tests import svdpp_ref as R
+from tests import widths as W
 
 pytestmark = pytest.mark.gpu
 
@@ -51,7 +52,7 @@ def got_tables(m):
     return {k: np.asarray(g[k], np.float64) for k in ORDER}
 
 
-@pytest.mark.parametrize("D", [1, 5, 16, 64, 128, 256])
+@pytest.mark.parametrize("D", sorted({1, 5, 16, 64, 128, 256} | set(W.SVDPP)))
 @pytest.mark.parametrize("item_abs", [False, True])
 def test_forward_matches_reference(D, item_abs):
     rs = np.random.RandomState(D + 7 * item_abs)
@@ -66,11 +67,25 @@ def test_forward_matches_reference(D, item_abs):
     np.testing.assert_allclose(x, want, rtol=2e-5, atol=2e-5 * max(1.0, np.abs(want).max()))
 
 
-@pytest.mark.parametrize("loss,item_abs,reg_bias", [("mse", False, False), ("nll", True, True), ("mse", True, False)])
+GRAD_CASES = [("mse", False, False), ("nll", True, True), ("mse", True, False)]
+
+
+@pytest.mark.parametrize("loss,item_abs,reg_bias", GRAD_CASES)
 def test_one_step_gradients_of_all_six_tables(loss, item_abs, reg_bias):
     """SGD with lr = 1: every table moves by exactly minus its gradient; hot Y rows (a column over several pieces) included."""
+    _one_step_gradients(16, loss, item_abs, reg_bias)
+
+
+@pytest.mark.parametrize("D", W.SVDPP)
+def test_one_step_gradients_at_every_register_width(D):
+    """the same at every NJ = ceil(D / 64), last register full and partial: k_pp_users (TRAIN), k_pp_items, k_pp_ygrad and
+    k_pp_yapply at every instantiation; the loss form rotates across the widths"""
+    _one_step_gradients(D, *GRAD_CASES[W.SVDPP.index(D) % len(GRAD_CASES)])
+
+
+def _one_step_gradients(D, loss, item_abs, reg_bias):
     rs = np.random.RandomState(3)
-    U, I, D, B = 600, 200, 16, 3000
+    U, I, B = 600, 200, 3000
     N = implicit(U, I, rs, long_users=(5,), long_len=190, hot_item=11, hot_users=tuple(range(1, 600, 2)))
     t = tables(U, I, D, rs, 0.2)
     u = rs.randint(0, U, B).astype(np.int32)
@@ -96,8 +111,20 @@ def test_one_step_gradients_of_all_six_tables(loss, item_abs, reg_bias):
 @pytest.mark.parametrize("optimizer", ["sgd", "adam"])
 @pytest.mark.parametrize("loss,reg_bias", [("mse", False), ("nll", True)])
 def test_trajectory_of_twenty_steps(optimizer, loss, reg_bias):
+    _trajectory(32, optimizer, loss, reg_bias)
+
+
+@pytest.mark.parametrize("optimizer", ["sgd", "adam"])
+@pytest.mark.parametrize("D", W.SVDPP)
+def test_trajectory_at_every_register_width(D, optimizer):
+    """both optimisers at every NJ, last register full and partial; the loss alternates across the widths"""
+    loss, reg_bias = [("mse", False), ("nll", True)][W.SVDPP.index(D) % 2]
+    _trajectory(D, optimizer, loss, reg_bias)
+
+
+def _trajectory(D, optimizer, loss, reg_bias):
     rs = np.random.RandomState(11)
-    U, I, D, B = 300, 250, 32, 800
+    U, I, B = 300, 250, 800
     N = implicit(U, I, rs, long_users=(3,), long_len=200)
     t = tables(U, I, D, rs, 0.1)
     lr = 1e-4 if optimizer == "sgd" else 1e-3              # SGD sums the batch: lr * B stays below one

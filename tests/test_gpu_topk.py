@@ -8,6 +8,7 @@ import scipy.sparse as sp
 import tfrecomm_amd as T
 from tfrecomm_amd import _lib as L
 from tests.topk_ref import svd_scores, topk_ref, csr_rows
+from tests import widths as W
 
 pytestmark = pytest.mark.gpu
 
@@ -39,14 +40,14 @@ def random_excl(rs, n, I, frac=0.2):
     return (indptr, np.concatenate(rows).astype(np.int32) if rows else np.zeros(0, np.int32)), rows
 
 
-@pytest.mark.parametrize("D", [1, 5, 15, 16, 64, 128, 256])
+@pytest.mark.parametrize("D", sorted({1, 5, 15, 16, 64, 128, 256} | set(W.TOPK)))
 def test_exact_on_dyadic_tables(D):
     rs = np.random.RandomState(D)
     U, I = 70, 900
     for item_abs in (False, True):
         m, t = make(U, I, D, rs, item_abs=item_abs)
         users = rs.randint(0, U, 40).astype(np.int32)
-        for k in (1, 10, 100, 256):
+        for k in W.TOPK_KS:
             for with_excl in (False, True):
                 ex, rows = random_excl(rs, users.size, I) if with_excl else (None, None)
                 items, scores = m.recommend(users, k, exclude=ex)
@@ -256,8 +257,18 @@ def fm_two_hot(user, user_num, item_num):
 
 @pytest.mark.parametrize("dyad", [True, False])
 def test_fm_get_ranking(dyad):
+    _check_fm_get_ranking(dyad, 16)
+
+
+@pytest.mark.parametrize("dyad", [True, False])
+@pytest.mark.parametrize("D", W.FM_TOPK)
+def test_fm_get_ranking_at_other_widths(dyad, D):
+    _check_fm_get_ranking(dyad, D)
+
+
+def _check_fm_get_ranking(dyad, D):
     rs = np.random.RandomState(10)
-    Un, In, D = 40, 500, 16
+    Un, In = 40, 500
     F = Un + In
     fm = T.FmModel(F, D)
     if dyad:

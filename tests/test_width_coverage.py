@@ -1,0 +1,105 @@
+"""Every instantiation a supported row width can reach is run by the GPU tests (tests/widths.py).
+
+Each kernel family picks a template instantiation from D.  The rules are restated here in a few lines each, next to the
+source they restate; the tests enumerate what every supported D reaches and check that the family's width list reaches all
+of it.  A new width-templated kernel, or a change to a dispatch rule, belongs here together with its width list."""
+import pytest
+
+from tests import widths as W
+
+
+def supported(D):
+    """a row width the models accept: geometry() rejects lanes > 64 (csrc/svd_kernels.h geometry)"""
+    return 1 <= D <= 64 or (D % 4 == 0 and D <= 256)
+
+
+SUPPORTED = [D for D in range(1, 257) if supported(D)]
+
+
+def geometry(D):
+    """(G, VEC) of the SVD step and forward and of the FM kernels (csrc/svd_kernels.h geometry, fm_kernels.hip launch_fm)"""
+    vec = 4 if D % 4 == 0 else 1
+    lanes = -(-D // vec)
+    g = 4
+    while g < lanes:
+        g *= 2
+    return g, vec
+
+
+def registers(D):
+    """(NJ, last register full): NJ = ceil(D / 64) features per lane, f = lane + 64 j guarded by f < D
+    (csrc/svdpp.hip pp_nj, csrc/finetune.hip launch_finetune)"""
+    return -(-D // 64), D % 64 == 0
+
+
+def tile(D):
+    """(V4, where the last group ends): mfma_tile_dot walks DP4 = ceil(D / 4) float4s in groups of four and masks the last
+    group; V4 = (D % 4 == 0) picks the vector loads (csrc/score_tile.h mfma_tile_dot, topk.hip launch_score_v, rank.hip).
+    The first group alone, or DP4 % 4 once past it.  tfr_topk_plan / tfr_rank_plan pick no template argument from D."""
+    dp4 = -(-D // 4)
+    return D % 4 == 0, "first group" if dp4 <= 4 else "DP4 %% 4 = %d" % (dp4 % 4)
+
+
+TOPK_ROUND = 4 * 32                                        # csrc/topk.h TOPK_WAVES * TOPK_SUB
+
+
+def topk_queue(k):
+    """(users per block, queue size) of k_topk_score (csrc/topk.h topk_cap, topk_upb)"""
+    return (32, 256) if k + TOPK_ROUND <= 256 else (16, 512)
+
+
+ALS_MAXD = 32                                              # csrc/als_kernels.hip
+
+
+def _check(name, rule, listed, reachable):
+    bad = [D for D in listed if not supported(D)]
+    assert not bad, "%s: unsupported widths %s" % (name, bad)
+    covered = {rule(D) for D in listed}
+    missing = sorted(set(reachable) - covered, key=str)
+    assert not missing, "%s: no width reaches %s (widths %s)" % (name, ", ".join(map(str, missing)), list(listed))
+
+
+def test_there_are_ten_row_geometries():
+    assert len({geometry(D) for D in SUPPORTED}) == 10
+    assert {registers(D) for D in SUPPORTED} == {(nj, full) for nj in (1, 2, 3, 4) for full in (False, True)}
+    assert len({tile(D) for D in SUPPORTED}) == 10
+
+
+@pytest.mark.parametrize("name", ["SVD_SMALL", "SVD_BIG", "FM"])
+def test_every_row_geometry(name):
+    _check(name, geometry, getattr(W, name), {geometry(D) for D in SUPPORTED})
+
+
+@pytest.mark.parametrize("name", ["SVDPP", "FINETUNE"])
+def test_every_register_count_full_and_partial(name):
+    _check(name, registers, getattr(W, name), {registers(D) for D in SUPPORTED})
+
+
+def test_streamed_fine_tuning_at_every_register_count():
+    nj = lambda D: registers(D)[0]
+    _check("FINETUNE_STREAMED", nj, W.FINETUNE_STREAMED, {nj(D) for D in SUPPORTED})
+
+
+@pytest.mark.parametrize("name", ["TOPK", "RANK"])
+def test_every_tile_load_and_last_group(name):
+    _check(name, tile, getattr(W, name), {tile(D) for D in SUPPORTED})
+
+
+def test_topk_k_reaches_both_queue_sizes():
+    got = {topk_queue(k) for k in W.TOPK_KS}
+    assert got == {topk_queue(k) for k in range(1, 257)}, got
+
+
+def test_random_rank_and_fm_ranking_widths():
+    v4 = lambda D: D % 4 == 0
+    _check("RANK_RANDOM", v4, W.RANK_RANDOM, {False, True})
+    _check("FM_TOPK", v4, W.FM_TOPK, {False, True})
+    assert max(W.FM_TOPK) > 128, "FM_TOPK: no width above 128"
+
+
+def test_als_reaches_both_ends_of_the_one_wave_cholesky():
+    for name in ("ALS", "ALS_CHUNKED"):
+        listed = getattr(W, name)
+        assert all(1 <= d <= ALS_MAXD for d in listed), (name, listed)
+    assert {1, ALS_MAXD} <= set(W.ALS), "ALS: d = 1 and d = %d not both listed" % ALS_MAXD
+    assert ALS_MAXD in W.ALS_CHUNKED, "ALS_CHUNKED: no chunked long list at d = %d" % ALS_MAXD

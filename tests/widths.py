@@ -1,0 +1,27 @@
+"""The row widths D the GPU tests run each kernel family at.
+
+Every kernel is templated on something D picks (see tests/test_width_coverage.py, which restates each dispatch rule and
+checks that each list below reaches every instantiation a supported D can reach).  Each list holds one width per
+instantiation it must reach, so that removing a width leaves an instantiation untested and the guard names it.  Tests
+that ran at a hand-picked list before keep that list and add these."""
+
+# SVD forward and step, FM forward and training: geometry(D) -> (G, VEC), ten pairs
+SVD_SMALL = (2, 5, 15, 16, 25, 28, 61, 64, 128, 200)       # small tables: k_tile_step
+SVD_BIG = (3, 7, 9, 12, 31, 32, 33, 36, 100, 252)          # a side above CSORT_MAX_BINS rows: radix sort, k_seg_reduce, ...
+FM = (2, 6, 13, 8, 25, 28, 61, 44, 100, 200)
+
+# SVD++ kernels and batched fine-tuning: NJ = ceil(D / 64) registers per lane, the last one full or partial
+SVDPP = (33, 64, 100, 128, 132, 192, 252, 256)
+FINETUNE = (20, 64, 68, 128, 132, 192, 252, 256)
+FINETUNE_STREAMED = (20, 100, 132, 252)                    # one call stages some users and streams others, each NJ
+
+# top-K and rank: V4 = (D % 4 == 0) crossed with where mfma_tile_dot's last group of four float4s ends
+TOPK = (4, 5, 27, 33, 38, 63, 68, 104, 128, 252)
+TOPK_KS = (1, 10, 100, 256)                                # both queue sizes (k + TOPK_ROUND <= 256, and above)
+RANK = (3, 8, 17, 20, 28, 31, 32, 43, 54, 200)
+RANK_RANDOM = (43, 200)                                    # rank == position in recommend, on random tables
+FM_TOPK = (25, 200)                                        # FM get_ranking / rank_items: a V1 width, a width above 128
+
+# ALS: one-wave Cholesky, lane r owns row r, 1 <= d <= ALS_MAXD
+ALS = (1, 32)
+ALS_CHUNKED = (32,)
