@@ -472,6 +472,54 @@ int tfr_svdpp_get_stream(tfr_svdpp* m, void** hip_stream);
 int tfr_svdpp_sync(tfr_svdpp* m);            /* drains the stream; reports deferred TFR_ERR_OOB */
 const char* tfr_svdpp_last_error(void);
 
+/* ---- BPR (Rendle et al., "BPR: Bayesian Personalized Ranking from Implicit Feedback", UAI 2009) - DESIGN §15 ----------
+ *      A BPR step trains the SVD model's own tables (tables, optimiser, hyper-parameters, step counter and stream of the
+ *      tfr_model) on triples (u, i, j): i a positive of u, j a negative.  For a triple, with Q' = |Q| under item_abs,
+ *          s(u, k) = dot(P[u], Q'[k]) + bi[k]      dot: per-lane f32 fmaf chains over f = lane + 64 t, then a butterfly sum
+ *          x = s(u, i) - s(u, j)                   (mu and bu cancel: a BPR step never reads or writes them)
+ *          data = sum_b softplus(-x_b)             (max(-x, 0) + log1p(exp(-|x|)))
+ *          reg  = 1/2 sum_b (||P[u_b]||^2 + ||Q[i_b]||^2 + ||Q[j_b]||^2)  (+ 1/2 (bi[i_b]^2 + bi[j_b]^2) with reg_bias)
+ *          cost = data + lam reg                   (loss_out = data, reg_out = reg, as tfr_train_step)
+ *      Per triple, g = -sigmoid(-x): dP[u] = g (Q'[i] - Q'[j]) + lam P[u]; dQ[i] = g P[u] (x sign Q[i] under item_abs)
+ *      + lam Q[i]; dQ[j] = -g P[u] (x sign Q[j]) + lam Q[j]; dbi[i] = g, dbi[j] = -g (each + lam bi with reg_bias).  An
+ *      item that is the positive of one triple and the negative of another sums both roles.  Every quantity uses the tables
+ *      as they were before the step.  SGD or lazy Adam on the touched rows (the SVD step's sparse Adam); tf1 Adam gives
+ *      TFR_ERR_STATE.  Frozen bits TFR_BI, TFR_P, TFR_Q are honoured.  The step counter and the beta powers advance once
+ *      per step.  The model's loss option does not apply.  Sums run in a fixed order: bit-identical run to run, and a
+ *      user's rows get the same bits whichever other users (touching none of its rows) share the batch.  An id out of range
+ *      voids the step (every table) and the next synchronising call returns TFR_ERR_OOB, as the SVD step.
+ *
+ *      Negative sampler, counter-based (all arithmetic mod 2^64):
+ *          mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ *          k   = mix(mix(seed ^ 0x9E3779B97F4A7C15) ^ step)     step = the model's step counter before this step
+ *          r_a = mix(k ^ ((b << 6) | a))                      b = position in the batch, a = attempt, 0 <= a < attempts <= 64
+ *          j_a = ((r_a >> 32) * item_num) >> 32
+ *      j = the first j_a not in row u of the positives.  If every attempt lands on a positive the triple is skipped: it is
+ *      absent from the batch (no data, no regulariser, no gradient, no lazy-Adam touch) and its negative reads -1.
+ *      Defaults: seed 0, attempts 16.  Negatives given by the caller are used as given: checked as ids, never rejected,
+ *      j == i legal.
+ *
+ *      Positives: a CSR [user_num, item_num], indptr from 0, non-decreasing, each row strictly increasing; checked on the
+ *      host before any device work (TFR_ERR_OOB for an item out of range, TFR_ERR_ARG otherwise); resident until replaced;
+ *      the call synchronises.  Sampling and training calls before it return TFR_ERR_STATE. */
+int tfr_bpr_set_positives(tfr_model* m, const int64_t* indptr /* [user_num + 1] */, const int32_t* items);
+/* seed and attempts (1..64) of the sampler; kept until changed */
+int tfr_bpr_set_sampler(tfr_model* m, uint64_t seed, int32_t attempts);
+/* the sampler alone, at counter `step`, for host users (checked on the host: TFR_ERR_OOB); synchronises */
+int tfr_bpr_negatives(tfr_model* m, const int32_t* user, int64_t batch, int64_t step, int32_t* neg_out);
+/* one BPR step on host columns; neg NULL = sample.  neg_out [batch] receives the negatives used (-1 = skipped),
+ * n_skipped_out the number of skipped triples.  Any output may be NULL; synchronises. */
+int tfr_bpr_train_step(tfr_model* m, const int32_t* user, const int32_t* pos, const int32_t* neg /* NULL = sample */,
+                       int64_t batch, int32_t* neg_out, float* loss_out, float* reg_out, int64_t* n_skipped_out);
+/* the same on device columns, asynchronous (id errors surface at the next synchronising call) */
+int tfr_bpr_train_step_dev(tfr_model* m, const int32_t* d_user, const int32_t* d_pos, const int32_t* d_neg /* NULL = sample */,
+                           int64_t batch, int32_t* d_neg_out /* may be NULL */);
+/* nsteps x { e = np.random.randint(0, nnz, batch) from the model's MT19937 stream (as tfr_train_steps_drawn draws);
+ * (u, i) = entry e of the positives CSR; one BPR step with sampled negatives }, all on the device.  Cancels the SVD
+ * path's run-ahead draw first and draws into its own buffer.  loss_out[nsteps] (may be NULL; then the call does not
+ * synchronise): data term per step. */
+int tfr_bpr_train_steps_drawn(tfr_model* m, int64_t batch, int32_t nsteps, float* loss_out);
+
 /* ---- per-kernel timing with HIP events on the model's stream (bench.py roofline) -------- */
 enum {
     TFR_K_FORWARD = 0,        /* gather-dot forward (+ fused loss/grad when training)       */

@@ -169,6 +169,12 @@ SIGNATURES = {
     "tfr_svdpp_get_stream": (C.c_int, [_p, C.POINTER(_p)]),
     "tfr_svdpp_sync": (C.c_int, [_p]),
     "tfr_svdpp_last_error": (C.c_char_p, []),
+    "tfr_bpr_set_positives": (C.c_int, [_p, _i64p, _i32p]),
+    "tfr_bpr_set_sampler": (C.c_int, [_p, C.c_uint64, C.c_int32]),
+    "tfr_bpr_negatives": (C.c_int, [_p, _i32p, C.c_int64, C.c_int64, _i32p]),
+    "tfr_bpr_train_step": (C.c_int, [_p, _i32p, _i32p, _i32p, C.c_int64, _i32p, _f32p, _f32p, _i64p]),
+    "tfr_bpr_train_step_dev": (C.c_int, [_p, _p, _p, _p, C.c_int64, _p]),
+    "tfr_bpr_train_steps_drawn": (C.c_int, [_p, C.c_int64, C.c_int32, _f32p]),
     "tfr_sync": (C.c_int, [_p]),
     "tfr_last_error": (C.c_char_p, []),
     "tfr_version": (C.c_int, []),

@@ -52,6 +52,8 @@ struct IdBuf {
     int64_t n_recs = 0;
 };
 
+struct BprState;                                        // bpr_api.inc.h
+
 struct tfr_model {
     int64_t U = 0, I = 0;
     int32_t D = 0, G = 0, VEC = 0;
@@ -168,6 +170,8 @@ struct tfr_model {
     DevBuf<int32_t> rk_order, rk_bins, rk_nr;
     // batched fine-tuning (tfr_finetune_users): one device buffer for a call's schedule and outputs
     DevBuf<char> ft_buf;
+    // BPR steps (tfr_bpr_*): the positives, the sampler's settings and the step's buffers; created by the first BPR call
+    BprState* bpr = nullptr;
     // profiling
     bool prof = false;
     std::vector<ProfEvent> events;
@@ -390,6 +394,8 @@ int tfr_device_copy_rate(int32_t device, int64_t bytes, int32_t reps, double* be
     return TFR_OK;
 }
 
+static void bpr_release(tfr_model* m);
+
 int tfr_destroy(tfr_model* m) {
     if (!m) return TFR_OK;
     (void)hipSetDevice(m->device);                       // the buffers are freed with the model's device current
@@ -407,6 +413,7 @@ int tfr_destroy(tfr_model* m) {
     for (auto& e : m->draw_evs) if (e) (void)hipEventDestroy(e);
     if (m->stream2) (void)hipStreamDestroy(m->stream2);
     if (m->stream3) (void)hipStreamDestroy(m->stream3);
+    bpr_release(m);
     if (m->own_stream) (void)hipStreamDestroy(m->own_stream);
     delete m;
     return TFR_OK;
@@ -750,6 +757,7 @@ static int run_forward(tfr_model* m, int mode, const int32_t* du, const int32_t*
 static int radix_sort_columns(tfr_model* m, int ncols, const int32_t* const* keys, const int* bits,
                               int32_t* const* ks_out, int32_t* const* ps_out, int64_t B,
                               const int64_t* limits = nullptr, const int64_t* store_ids = nullptr) {
+    m->pf_valid = false;                                 // the sort scratch doubles as the published tables of the tile step
     int maxbits = bits[0];
     if (ncols > 1 && bits[1] > maxbits) maxbits = bits[1];
     const int passes = (maxbits + 7) / 8;
@@ -796,6 +804,7 @@ static int sort_columns(tfr_model* m, const int32_t* du, const int32_t* di, int6
                         const FinArgs* fin = nullptr, bool* fin_done = nullptr, bool validate = false,
                         const int64_t* store_ids = nullptr) {
     Prof p(m, TFR_K_SORT);
+    m->pf_valid = false;                                 // the sort scratch doubles as the published tables of the tile step
     if (m->csort_ok && csort_eligible(B, m->bits_u, m->bits_i)) {
         CSortArgs c;
         c.keys[0] = du; c.keys[1] = di;
@@ -3525,3 +3534,5 @@ int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, cons
 
 // ---- SVD++ (tfr_svdpp*, svdpp.hip): the wrapped model's internals are shared, so its entry points live in this unit
 #include "svdpp_api.inc.h"
+// ---- BPR steps (tfr_bpr_*, bpr.hip) on the model's own tables
+#include "bpr_api.inc.h"

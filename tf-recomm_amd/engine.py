@@ -467,6 +467,65 @@ class SvdModel:
         L.check(self._lib.tfr_sort_segments(self._h, side, L.ptr_i32(a), a.size, L.ptr_i32(ks), L.ptr_i32(ps)))
         return ks, ps
 
+    # -- BPR on implicit feedback (include/tfrecomm.h tfr_bpr_*) ------------------------------------------
+    def set_positives(self, csr):
+        """The positives of the BPR steps: a ``scipy.sparse`` ``[user_num, item_num]`` matrix (e.g. ``rated_matrix``; its
+        stored entries) or an (indptr, items) pair with strictly increasing rows.  Checked before any device work."""
+        from .svdpp import implicit_csr
+        indptr, items = implicit_csr(csr, self.user_num, self.item_num)
+        L.check(self._lib.tfr_bpr_set_positives(self._h, L.ptr_i64(indptr), L.ptr_i32(items)))
+
+    def set_bpr_sampler(self, seed=0, attempts=16):
+        L.check(self._lib.tfr_bpr_set_sampler(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(attempts)))
+
+    def bpr_negatives(self, users, step=None):
+        """The sampler alone for ``users`` at counter ``step`` (default: the model's step counter, i.e. what the next
+        step would draw).  int32 negatives, -1 where every attempt landed on a positive."""
+        u = L.as_i32(users, "user ids").reshape(-1)
+        out = np.empty(u.size, np.int32)
+        L.check(self._lib.tfr_bpr_negatives(self._h, L.ptr_i32(u), u.size, self.step if step is None else int(step),
+                                            L.ptr_i32(out)))
+        return out
+
+    def train_bpr_step(self, users, pos_items, neg_items=None):
+        """One BPR step on host columns; ``neg_items`` None = sample on the device.  Returns (negatives used, data loss,
+        regulariser, number of skipped triples)."""
+        u, i = L.as_i32(users, "user ids").reshape(-1), L.as_i32(pos_items, "item ids").reshape(-1)
+        j = None if neg_items is None else L.as_i32(neg_items, "item ids").reshape(-1)
+        if u.shape != i.shape or (j is not None and j.shape != u.shape):
+            raise ValueError("batches must be 1-D and of equal length")
+        neg = np.empty(u.size, np.int32)
+        loss, reg, skipped = C.c_float(), C.c_float(), C.c_int64()
+        L.check(self._lib.tfr_bpr_train_step(self._h, L.ptr_i32(u), L.ptr_i32(i), None if j is None else L.ptr_i32(j),
+                                             u.size, L.ptr_i32(neg), C.byref(loss), C.byref(reg), C.byref(skipped)))
+        return neg, loss.value, reg.value, skipped.value
+
+    def train_bpr_step_dev(self, users, pos_items, neg_items=None, want_negatives=False):
+        """One BPR step on torch int32 device tensors, asynchronous: ordered after torch's current stream, and that stream
+        after it; an id error surfaces at the next ``sync()``.  Returns the negatives as a device tensor when asked."""
+        import torch
+        cols = [users.contiguous(), pos_items.contiguous()] + ([] if neg_items is None else [neg_items.contiguous()])
+        if any(c.dtype != torch.int32 or c.dim() != 1 or c.shape != cols[0].shape for c in cols):
+            raise TypeError("users / items must be 1-D int32 tensors of equal length")
+        n = cols[0].numel()
+        neg = torch.empty(n, dtype=torch.int32, device=cols[0].device) if want_negatives else None
+        mine = torch.cuda.ExternalStream(self.get_stream(), device=cols[0].device)
+        cur = torch.cuda.current_stream(cols[0].device)
+        mine.wait_stream(cur)
+        L.check(self._lib.tfr_bpr_train_step_dev(self._h, cols[0].data_ptr(), cols[1].data_ptr(),
+                                                 None if neg_items is None else cols[2].data_ptr(), n,
+                                                 None if neg is None else neg.data_ptr()))
+        cur.wait_stream(mine)
+        return neg
+
+    def train_bpr_steps_drawn(self, batch, nsteps, want_loss=False):
+        """nsteps x { e = np.random.randint(0, nnz, batch) (the device generator, as ``train_steps_drawn``); (u, i) =
+        entry e of the positives; one BPR step with sampled negatives }, all on the device.  Per-step data loss if asked."""
+        loss = np.empty(nsteps, np.float32) if want_loss else None
+        L.check(self._lib.tfr_bpr_train_steps_drawn(self._h, int(batch), int(nsteps),
+                                                    L.ptr_f32(loss) if want_loss else None))
+        return loss
+
     # -- device-pointer plumbing --------------------------------------------------
     def forward_dev(self, d_user, d_item, batch, d_logits):
         L.check(self._lib.tfr_forward_dev(self._h, d_user, d_item, batch, d_logits))

@@ -186,6 +186,43 @@ def svdpp(train, test, *, user_num=None, item_num=None, dim=None, batch_size=Non
     return rows
 
 
+def bpr(train, test, *, user_num=None, item_num=None, dim=None, batch_size=None, epoch_max=None, learning_rate=0.01,
+        reg=0.005, device=None, log=print):
+    """BPR on implicit feedback: the positives are the training frame's (user, item) pairs; each epoch runs
+    nnz / batch drawn steps (pairs drawn with the ShuffleIterator's randint, negatives sampled on the device), then ranks
+    the validation pairs over the whole catalogue with the training positives excluded.  Lazy Adam.  Returns the list of
+    (epoch, mean BPR loss per triple, recall@10, ndcg@10, auc, seconds) rows."""
+    from . import _lib as L
+    from .engine import SvdModel, rated_matrix
+    from .ranking import evaluate_ranking
+    user_num, item_num = user_num or C.USER_NUM, item_num or C.ITEM_NUM
+    dim, batch_size = dim or C.DIM, batch_size or C.BATCH_SIZE
+    epoch_max = C.EPOCH_MAX if epoch_max is None else epoch_max
+    device = C.DEVICE if device is None else device
+    pos = rated_matrix(train["user"], train["item"], user_num, item_num)
+    steps = max(1, pos.nnz // batch_size)
+    rows = []
+    with SvdModel(user_num, item_num, dim, optimizer="adam", adam_mode="lazy", lr=learning_rate, reg=reg,
+                  device=device) as m:
+        m.init_tables(seed=C.SEED, feature_stddev=0.1)
+        m.set_table(L.BI, np.zeros(item_num, np.float32))
+        m.set_positives(pos)
+        m.rng_from_numpy()                                              # the ShuffleIterator's generator
+        log("{} {} {} {} {} {}".format("epoch", "bpr_loss", "recall@10", "ndcg@10", "auc", "elapsed_time"))
+        start = time.time()
+        for epoch in range(epoch_max):
+            loss = m.train_bpr_steps_drawn(batch_size, steps, want_loss=True)
+            ev = evaluate_ranking(m, test["user"], test["item"], exclude=pos, ks=(10,))["mean"]
+            end = time.time()
+            row = (epoch, float(np.mean(loss)) / batch_size, float(ev["recall@10"]), float(ev["ndcg@10"]),
+                   float(ev["auc"]), end - start)
+            rows.append(row)
+            log("{:3d} {:f} {:f} {:f} {:f} {:f}(s)".format(*row))
+            start = end
+        m.rng_to_numpy()
+    return rows
+
+
 def synthetic_frames(user_num, item_num, n, seed=C.SEED):
     """ML-1M-shaped ratings from a low-rank ground truth (no dataset ships; no network)."""
     rs = np.random.RandomState(seed)
@@ -206,7 +243,8 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--batch", type=int, default=C.BATCH_SIZE)
     ap.add_argument("--dim", type=int, default=C.DIM)
-    ap.add_argument("--model", choices=("svd", "svdpp"), default="svd", help="svdpp: Koren's SVD++ with N(u) = training items")
+    ap.add_argument("--model", choices=("svd", "svdpp", "bpr"), default="svd",
+                    help="svdpp: Koren's SVD++ with N(u) = training items; bpr: BPR on the training pairs as implicit feedback")
     a = ap.parse_args(argv)
     np.random.seed(C.SEED)                                              # svd_train_val.py:15
     if a.data:
@@ -222,7 +260,9 @@ def main(argv=None):
     else:
         un, inum = C.USER_NUM, C.ITEM_NUM
         df_train, df_val = synthetic_frames(un, inum, 1000209)
-    if a.model == "svdpp":
+    if a.model == "bpr":
+        bpr(df_train, df_val, user_num=un, item_num=inum, dim=a.dim, batch_size=a.batch, epoch_max=a.epochs)
+    elif a.model == "svdpp":
         svdpp(df_train, df_val, user_num=un, item_num=inum, dim=a.dim, batch_size=a.batch, epoch_max=a.epochs)
     else:
         svd(df_train, df_val, user_num=un, item_num=inum, dim=a.dim, batch_size=a.batch, epoch_max=a.epochs,
