@@ -1001,7 +1001,8 @@ static int tile_step_launch(tfr_model* m, const int32_t* du, const int32_t* di, 
         unsigned long long t0 = ~0ull, t1 = 0;
         for (size_t k = 0; k < h.size(); k += 8) if (h[k]) { if (h[k] < t0) t0 = h[k]; if (h[k + 1] > t1) t1 = h[k + 1]; }
         const int nsort = ts.next_ids ? 2 * ts.next_ntiles : 0;
-        const size_t gridx = (size_t)nsort + (size_t)ts.ntiles * (m->G / tile_step_epg(ts.ntiles, m->G, m->VEC));
+        const int64_t epb = 1024 / m->G, epg = tile_step_epg(ts.ntiles, m->G, m->VEC);
+        const size_t nblk_u = (size_t)((B + epb * epg - 1) / (epb * epg));   // grid: sort blocks, user side, item side
         double ahead_end = 0, ahead_dur = 0, comp_end = 0, comp_dur = 0, ph[8] = {0, 0, 0, 0, 0, 0, 0, 0}, phl[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int longest_y = -1; size_t longest_k = 0;
         int nblocks = 0, ncomp = 0;
@@ -1010,12 +1011,12 @@ static int tile_step_launch(tfr_model* m, const int32_t* du, const int32_t* di, 
             if (!b[0]) continue;
             ++nblocks;
             const double st = (b[0] - t0) / 100.0, en = (b[1] - t0) / 100.0;
-            const bool ah = k < gridx && (int)k < nsort;                // blockIdx.y == 0 and blockIdx.x < nsort
+            const bool ah = (int)k < nsort;
             if (ah) { if (en > ahead_end) ahead_end = en; if (en - st > ahead_dur) ahead_dur = en - st; }
             else {
                 if (en > comp_end) comp_end = en;
                 if (en - st > comp_dur) {
-                    comp_dur = en - st; longest_k = k; longest_y = (int)(k / gridx);
+                    comp_dur = en - st; longest_y = k < nsort + nblk_u ? 0 : 1; longest_k = k - nsort - (longest_y ? nblk_u : 0);
                     if (b[2] && b[6]) { for (int q = 2; q <= 6; ++q) phl[q] = (b[q] - b[0]) / 100.0; phl[7] = en - st; }
                 }
                 if (b[2] && b[6]) { ++ncomp; for (int q = 2; q <= 6; ++q) ph[q] += (b[q] - b[0]) / 100.0; ph[7] += en - st; }
@@ -1027,7 +1028,7 @@ static int tile_step_launch(tfr_model* m, const int32_t* du, const int32_t* di, 
                 ph[2] / (ncomp ? ncomp : 1), ph[3] / (ncomp ? ncomp : 1), ph[4] / (ncomp ? ncomp : 1), ph[5] / (ncomp ? ncomp : 1),
                 ph[6] / (ncomp ? ncomp : 1), ph[7] / (ncomp ? ncomp : 1));
         fprintf(stderr, "[k_tile_step] longest step block: side %d, block %zu of its side: records %.2f, rows+contributions %.2f, wave sums staged %.2f, "
-                        "partials %.2f, wave rounds %.2f, end %.2f\n", longest_y, longest_k % gridx, phl[2], phl[3], phl[4], phl[5], phl[6], phl[7]);
+                        "partials %.2f, wave rounds %.2f, end %.2f\n", longest_y, longest_k, phl[2], phl[3], phl[4], phl[5], phl[6], phl[7]);
     }
     return TFR_OK;
 }

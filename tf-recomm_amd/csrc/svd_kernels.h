@@ -139,6 +139,17 @@ struct DenseArgs {
 struct DensePair { DenseArgs a[2]; FinArgs f; };
 
 
+// write-through (sc1) stores of what only the next dependent launch reads, by hand-off (TFR_WT=<bits>, A/B; tile_step_wt())
+enum : int32_t {
+    TFR_WT_ROWS = 1,        // k_dense_tiles: the updated table rows
+    TFR_WT_MOMENTS = 2,     // k_dense_tiles: the rows' Adam m and v
+    TFR_WT_BIAS = 4,        // k_dense_tiles: the biases and their m and v
+    TFR_WT_PIECES = 8,      // k_tile_step: the piece sums (grad_rows, grad_bias)
+    TFR_WT_PUBLISH = 16,    // k_tile_step: the packed lookup tables and the look-ahead's sorted records
+};
+constexpr int32_t TFR_WT_DEFAULT = TFR_WT_ROWS | TFR_WT_MOMENTS | TFR_WT_BIAS | TFR_WT_PIECES | TFR_WT_PUBLISH;
+int tile_step_wt();
+
 // small-table sweep over per-tile partial gradients (k_dense_tiles)
 struct TileDenseArgs {
     const int32_t* tab;                            // [ntiles * nbins]: (count << 16) | offset, from the tile-local sort
@@ -150,7 +161,7 @@ struct TileDenseArgs {
     int32_t D, nbins, ntiles, frozen_rows, frozen_bias, opt, skip_untouched;
     float alpha, b1, b2, eps, lr;
 };
-struct TileDenseLaunch { TileDenseArgs a[2]; FinArgs f; int32_t with_fin; };
+struct TileDenseLaunch { TileDenseArgs a[2]; FinArgs f; int32_t with_fin; int32_t wt; };
 void launch_dense_tiles(const TileDenseLaunch& L, bool write, bool with_fin, int G, int VEC, hipStream_t s);
 
 // one-pass stable counting sort of both id columns (small tables: all bins fit in LDS)
@@ -210,6 +221,9 @@ struct TileStepArgs {
     const int64_t* next_ids; int64_t next_B; int32_t next_ntiles;
     int32_t* next_tab[2]; int4* next_srt[2];
     unsigned long long* dbg;                                 // TFR_TILE_DEBUG: {start, end} of every block, 100 MHz ticks
+    int32_t epg_item;                                        // pieces per item-side block: EPG or EPG / 2 (launch_tile_step sets it)
+    int32_t one_barrier;                                     // piece sums across waves after one barrier (TFR_ONE_BARRIER=1)
+    int32_t wt;                                              // TFR_WT_* bits: which hand-offs are stored write-through
 };
 void launch_tile_step(const TileStepArgs& a, int G, int VEC, hipStream_t s);
 void launch_gather_recs(const int64_t* ids, const void* store, void* recs, int64_t n, int64_t N, hipStream_t s);
@@ -230,7 +244,9 @@ constexpr size_t seg_reduce_static_lds(int G, int VEC, bool fwd) {
     // (an upper bound over the instantiations: the three-round item side with the forward inside also parks the own rows in LDS)
     return (size_t)1024 * VEC * 4 + (size_t)2 * (1024 / G) * 4 + (fwd ? (size_t)(2 * (1024 / G) + 1024) * 4 + 16 * 3 * 4 + (size_t)1024 * VEC * 4 : 4);
 }
-int tile_step_epg(int ntiles, int G, int VEC);       // pieces per block k_tile_step will use (grid = ntiles * G / epg per side)
+int tile_step_epg(int ntiles, int G, int VEC);       // pieces per block of k_tile_step's user side (the item side's <= this; sizes the LDS)
+int tile_step_item_epg(int64_t B, int G, int VEC, int nsort);   // pieces per block of its item side
+int tile_step_one_barrier();                         // TFR_ONE_BARRIER=1: the cross-wave piece sums after one barrier
 
 // row geometry for a dim: returns false if unsupported
 inline bool geometry(int D, int* G, int* VEC) {

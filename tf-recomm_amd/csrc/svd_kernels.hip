@@ -88,6 +88,36 @@ __device__ __forceinline__ void store_frag_h(float* __restrict__ row, int d0, in
     }
 }
 
+// write-through (sc1) vector stores for bytes whose only reader is the next dependent launch: the line is written
+// on to memory and dropped from the XCD's L2 instead of being left dirty there, so the kernel boundary has less
+// to write back (TFR_WT bits, A/B).  Through a buffer resource on a block-uniform base; `off` counts floats from
+// it and stays below 2^29 (small tables: at most 16384 rows / 16 tiles of 1024 entries, D <= 256).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wt_rsrc(const void* base) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);   // 32-bit data format
+}
+template <int VEC>
+__device__ __forceinline__ void store_frag_wt(__amdgpu_buffer_rsrc_t r, size_t off, int d0, int D, const Frag<VEC>& f) {
+    if (d0 < D) {
+        if constexpr (VEC == 4) {
+            typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+            uintx4 t;
+            t.x = __float_as_uint(f.v[0]); t.y = __float_as_uint(f.v[1]); t.z = __float_as_uint(f.v[2]); t.w = __float_as_uint(f.v[3]);
+            __builtin_amdgcn_raw_buffer_store_b128(t, r, (int)((off + d0) * 4), 0, 16);      // aux 16: sc1
+        } else {
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(f.v[0]), r, (int)((off + d0) * 4), 0, 16);
+        }
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void store_frag_p(float* base, size_t off, int d0, int D, const Frag<VEC>& f, bool wt) {
+    if (wt) store_frag_wt<VEC>(wt_rsrc(base), off, d0, D, f);
+    else store_frag<VEC>(base + off, d0, D, f);
+}
+__device__ __forceinline__ void store_word_p(void* base, size_t idx, uint32_t x, bool wt) {
+    if (wt) __builtin_amdgcn_raw_buffer_store_b32(x, wt_rsrc(base), (int)(idx * 4), 0, 16);
+    else reinterpret_cast<uint32_t*>(base)[idx] = x;
+}
+
 template <int G>
 __device__ __forceinline__ float group_sum(float x) {
     // butterfly over the G lanes of a group (G is a power of two <= 64); every lane of the
@@ -536,8 +566,21 @@ __device__ __forceinline__ void tile_sort(int32_t* cnt_, int32_t* rec_u_, int32_
     __syncthreads();
 }
 
-// grid = (nsort + ntiles * G / EPG, 2).
-//  * blocks [0, nsort), y == 0: look-ahead - tile_sort one (side, tile) of the NEXT batch and publish its
+struct TileStamp {                                       // diagnostic (TFR_TILE_DEBUG): when did this block start, pass its phases, end?
+    unsigned long long* p; unsigned long long t0;
+    __device__ void mark(int k) const { if (p && threadIdx.x == 0) p[k] = __builtin_amdgcn_s_memrealtime(); }
+    __device__ ~TileStamp() { if (p && threadIdx.x == 0) { p[0] = t0; p[1] = __builtin_amdgcn_s_memrealtime(); } }
+};
+
+template <int G, int VEC, int EPG>
+__device__ __forceinline__ void tile_pieces(const TileStepArgs& a, int32_t* dyn, const int32_t* rec_u, const int32_t* rec_i,
+                                            const float* rec_r, const int32_t* srt_key, const int32_t* srt_pos, float* lds_gb,
+                                            int32_t* lds_key, float* lds_stage, const TileStamp& stamp, int side, int bx, int slice,
+                                            int64_t tile0, int nvalid, bool presorted);
+
+// grid = nsort + nblk_u + nblk_i, one dimension: the look-ahead sort blocks, then the user side's blocks, then the
+// item side's, each side cut to the blocks that hold entries (ceil(B / entries per block)).
+//  * blocks [0, nsort): look-ahead - tile_sort one (side, tile) of the NEXT batch and publish its
 //    packed table and its sorted records; that work has no dependence on the tables, so it rides
 //    here, in the shadow of this step's reduce, instead of heading the next step's critical path.
 //  * the other blocks: block (tile, slice, side) owns EPG pieces of 1024/G consecutive entries of the
@@ -546,42 +589,44 @@ __device__ __forceinline__ void tile_sort(int32_t* cnt_, int32_t* rec_u_, int32_
 //    two more dependent memory round trips).  One lane group per entry loads P[u], Q[i] once, forms
 //    the logit and g = dcost/dlogit exactly as K1 does (both sides compute the same g from the same
 //    registers), and the runs inside each piece are summed in two levels - inside a wave in registers,
-//    across the piece's 16 waves through LDS - always by doubling, i.e. in a fixed tree order (K3).
-//    Piece sums land at the tile-sorted position.  The item side also writes the logits and the
-//    per-piece {loss, reg, sum g}.  EPG is chosen so that the grid stays within one block per CU.
+//    across the piece's 16 waves through LDS - always by doubling, i.e. in a fixed tree order (K3).  Piece sums land at the tile-sorted position.  The item side also writes the
+//    logits and the per-piece {loss, reg, sum g}.  The user side takes EPG pieces per block, the item
+//    side a.epg_item = EPG, or EPG / 2 where the grid has room for it (TFR_ITEM_SPLIT=1, tile_step_item_epg);
+//    the grid stays within one block per CU.
 template <int G, int VEC, int EPG>
-__global__ __launch_bounds__(1024) void k_tile_step(TileStepArgs a, int nsort) {
+__global__ __launch_bounds__(1024) void k_tile_step(TileStepArgs a, int nsort, int nblk_u) {
     warm_args(a);
     constexpr int EPB = 1024 / G;                        // entries per piece = lane groups per block
-    constexpr int EPS = EPB * EPG;                       // entries per block
-    constexpr int NSL = 1024 / EPS;                      // blocks per tile
-    extern __shared__ int32_t dyn[];                     // sort: cnt[nbins]; then the wave-level sums (ping-pong)
+    extern __shared__ __attribute__((aligned(16))) int32_t dyn[];   // sort: cnt[nbins]; then the wave-level sums
     __shared__ int32_t rec_u[1024], rec_i[1024], srt_key[1024], srt_pos[1024];
     __shared__ float rec_r[1024];
-    __shared__ float lds_gb[2 * EPG * 16];
-    __shared__ int32_t lds_key[EPG * 16];
+    __shared__ __attribute__((aligned(16))) float lds_gb[2 * EPG * 16];
+    __shared__ __attribute__((aligned(16))) int32_t lds_key[EPG * 16];
     __shared__ float lds_stage[EPG * (2 * EPB + 1024)];
     __shared__ int32_t wtot[16];
     static_assert(sizeof(rec_u) + sizeof(rec_i) + sizeof(srt_key) + sizeof(srt_pos) + sizeof(rec_r) + sizeof(lds_gb) + sizeof(lds_key) +
                   sizeof(lds_stage) + sizeof(wtot) == tile_step_static_lds(G, EPG), "tile_step_static_lds() is out of date");
     static_assert(tile_step_static_lds(G, EPG) + 64 * 1024 <= LDS_PER_CU, "static LDS leaves no room for 16384 sort bins");
-    struct Stamp {                                       // diagnostic (TFR_TILE_DEBUG): when did this block start, pass its phases, end?
-        unsigned long long* p; unsigned long long t0;
-        __device__ void mark(int k) const { if (p && threadIdx.x == 0) p[k] = __builtin_amdgcn_s_memrealtime(); }
-        __device__ ~Stamp() { if (p && threadIdx.x == 0) { p[0] = t0; p[1] = __builtin_amdgcn_s_memrealtime(); } }
-    } stamp = {a.dbg ? a.dbg + 8 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x) : nullptr, a.dbg ? __builtin_amdgcn_s_memrealtime() : 0ull};
+    TileStamp stamp = {a.dbg ? a.dbg + 8 * (size_t)blockIdx.x : nullptr, a.dbg ? __builtin_amdgcn_s_memrealtime() : 0ull};
     const int tid = threadIdx.x;
     const bool ahead = (int)blockIdx.x < nsort;          // look-ahead block: sort (side, tile) of the next batch
-    if (ahead && blockIdx.y) return;
-    const int bx = ahead ? 0 : (int)blockIdx.x - nsort;
-    const int side = ahead ? (int)blockIdx.x / a.next_ntiles : (int)blockIdx.y;      // 0: user rows, 1: item rows
+    const int b0 = (int)blockIdx.x - nsort;
+    const int side = ahead ? (int)blockIdx.x / a.next_ntiles : (b0 < nblk_u ? 0 : 1);   // 0: user rows, 1: item rows
+    const int bx = ahead ? 0 : (side ? b0 - nblk_u : b0);
+    const int epg = side ? a.epg_item : EPG;
+    const int EPS = EPB * epg;                           // entries per block
+    const int NSL = 1024 / EPS;                          // blocks per tile
     const int tile = ahead ? (int)blockIdx.x % a.next_ntiles : bx / NSL;
     const int slice = bx % NSL;
     const int64_t tile0 = (int64_t)tile * 1024;
     const int64_t Bt = ahead ? a.next_B : a.B;
     const int nvalid = (Bt - tile0 < 1024) ? (int)(Bt - tile0) : 1024;
+    if (!ahead && side == 1 && (int64_t)(bx + 1) * EPS >= a.B) {   // the item side's last block: the pieces past the
+        const int np = a.ntiles * G;                     // batch's end have no block - their {loss, reg, sum g} are zero
+        for (int k = (bx + 1) * epg * 4 + tid; k < np * 4; k += 1024) a.partials[k] = 0.f;
+    }
     if (!ahead && slice * EPS >= nvalid) {               // a short last tile: nothing in this slice
-        if (side == 1 && tid < 4 * EPG) a.partials[(size_t)bx * EPG * 4 + tid] = 0.f;
+        if (side == 1 && tid < 4 * epg) a.partials[(size_t)bx * epg * 4 + tid] = 0.f;
         return;
     }
     const bool presorted = a.srt[0] != nullptr;
@@ -589,20 +634,48 @@ __global__ __launch_bounds__(1024) void k_tile_step(TileStepArgs a, int nsort) {
     if (ahead || !presorted) {
         tile_sort(dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, wtot, ahead ? a.next_ids : a.ids, a.store, ahead ? a.next_recs : a.recs,
                   a.u, a.it, a.r, tile0, nvalid, side, nb, a.N, a.U, a.I, a.err);
+        const bool wt = a.wt & TFR_WT_PUBLISH;
         if (ahead) {                                     // publish the packed table and the sorted records
-            for (int b = tid; b < nb; b += 1024) a.next_tab[side][(size_t)tile * nb + b] = dyn[b];
+            int32_t* nt = a.next_tab[side];
+            for (int b = tid; b < nb; b += 1024) store_word_p(nt, (size_t)tile * nb + b, (uint32_t)dyn[b], wt);
             if (tid < nvalid) {
                 const int pl = srt_pos[tid];
-                a.next_srt[side][tile0 + tid] = make_int4(rec_u[pl], rec_i[pl], __float_as_int(rec_r[pl]), pl);
+                const int4 rec = make_int4(rec_u[pl], rec_i[pl], __float_as_int(rec_r[pl]), pl);
+                if (wt) {
+                    typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+                    uintx4 t; t.x = (unsigned)rec.x; t.y = (unsigned)rec.y; t.z = (unsigned)rec.z; t.w = (unsigned)rec.w;
+                    __builtin_amdgcn_raw_buffer_store_b128(t, wt_rsrc(a.next_srt[side]), (int)((tile0 + tid) * 16), 0, 16);
+                } else {
+                    a.next_srt[side][tile0 + tid] = rec;
+                }
             }
             return;
         }
         // the tile's packed lookup table, written once: its bins are dealt round the tile's active blocks
         const int nact = (nvalid + EPS - 1) / EPS;
-        for (int b = slice * 1024 + tid; b < nb; b += nact * 1024) a.tab[side][(size_t)tile * nb + b] = dyn[b];
+        for (int b = slice * 1024 + tid; b < nb; b += nact * 1024) store_word_p(a.tab[side], (size_t)tile * nb + b, (uint32_t)dyn[b], wt);
         __syncthreads();                                 // cnt is dead from here: its memory takes the contributions
     }
+    if constexpr (EPG > 1) {
+        if (epg != EPG) {
+            tile_pieces<G, VEC, EPG / 2>(a, dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, lds_gb, lds_key, lds_stage, stamp, side, bx, slice,
+                                         tile0, nvalid, presorted);
+            return;
+        }
+    }
+    tile_pieces<G, VEC, EPG>(a, dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, lds_gb, lds_key, lds_stage, stamp, side, bx, slice, tile0,
+                             nvalid, presorted);
+}
 
+// the step part of k_tile_step for one block of EPG pieces (see above)
+template <int G, int VEC, int EPG>
+__device__ __forceinline__ void tile_pieces(const TileStepArgs& a, int32_t* dyn, const int32_t* rec_u, const int32_t* rec_i,
+                                            const float* rec_r, const int32_t* srt_key, const int32_t* srt_pos, float* lds_gb,
+                                            int32_t* lds_key, float* lds_stage, const TileStamp& stamp, int side, int bx, int slice,
+                                            int64_t tile0, int nvalid, bool presorted) {
+    constexpr int EPB = 1024 / G;                        // entries per piece = lane groups per block
+    constexpr int EPS = EPB * EPG;                       // entries per block
+    const int tid = threadIdx.x;
     // ---- this block's entries (EPG per lane group, one from each piece): forward + contribution
     const int grp = tid / G, gl = tid % G, d0 = gl * VEC;
     const int D = a.D;
@@ -734,13 +807,16 @@ __global__ __launch_bounds__(1024) void k_tile_step(TileStepArgs a, int nsort) {
         }
     }
     if (a.dbg) { if (gb[0] == -12345.f) return; stamp.mark(3); }      // rows have arrived, contributions formed
-    // ---- K3 inside each piece, in two levels, every sum in a fixed tree order (bit-identical run to
+    // ---- K3 inside each piece, in two levels, every sum in a fixed order (bit-identical run to
     //      run however long the runs are):
     //      1. a wave holds GPW consecutive entries of the piece: suffix sums within runs by doubling,
     //         in registers (cross-lane moves, no LDS memory, no barrier);
     //      2. the 16 waves' leading-run sums: the same doubling over 16 values per piece through LDS
     //         (a value whose run ends within reach is final and drops out);
     //      3. an entry whose run reaches the end of its wave adds the next wave's total.
+    //      TFR_ONE_BARRIER=1 (A/B, measured slower: DESIGN.md §8): instead of 2 and 3, after the one barrier that
+    //      stages the wave values, a run head whose run reaches the end of its wave reads the keys of the piece's
+    //      later waves and all their staged sums, and adds those of the waves its run covers, left to right.
     constexpr int GPW = 64 / G;
     const int wv = tid >> 6, gw = grp % GPW;
 #pragma unroll
@@ -782,44 +858,83 @@ __global__ __launch_bounds__(1024) void k_tile_step(TileStepArgs a, int nsort) {
     else __syncthreads();
     stamp.mark(5);
     int cur = 0;
-#pragma unroll
-    for (int d = 1; d < 16; d <<= 1) {
+    if (a.one_barrier) {
 #pragma unroll
         for (int h = 0; h < EPG; ++h) {
-            if (live[h]) {
-                const int w0 = h * 16 + wv;
-                const bool take = row[h] >= 0 && wv + d < 16 && lds_key[w0 + d] == row[h];
-                if (take) {
+            if (pstart[h] && reach[h] && wv + 1 < 16) {  // at most one lane group per wave and piece
+                const int32_t* kp = lds_key + h * 16;
+                const float* gp = wgb[0] + h * 16;
+                int32_t key[16];
+                float xgb[16];
 #pragma unroll
-                    for (int e = 0; e < VEC; ++e) tacc[h].v[e] += wbuf[cur][((w0 + d) * G + gl) * VEC + e];
-                    tgb[h] += wgb[cur][w0 + d];
-                } else {
-                    live[h] = false;
+                for (int q = 0; q < 4; ++q) {
+                    const int4 k4 = reinterpret_cast<const int4*>(kp)[q];
+                    const float4 g4 = reinterpret_cast<const float4*>(gp)[q];
+                    key[4 * q] = k4.x; key[4 * q + 1] = k4.y; key[4 * q + 2] = k4.z; key[4 * q + 3] = k4.w;
+                    xgb[4 * q] = g4.x; xgb[4 * q + 1] = g4.y; xgb[4 * q + 2] = g4.z; xgb[4 * q + 3] = g4.w;
                 }
+                Frag<VEC> x[15];
 #pragma unroll
-                for (int e = 0; e < VEC; ++e) wbuf[cur ^ 1][(w0 * G + gl) * VEC + e] = tacc[h].v[e];
-                if (gl == 0) wgb[cur ^ 1][w0] = tgb[h];
+                for (int k = 1; k < 16; ++k) {
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) x[k - 1].v[e] = wbuf[0][((h * 16 + k) * G + gl) * VEC + e];
+                }
+                bool run = true;                         // the waves after this one whose leading run is this run
+#pragma unroll
+                for (int k = 1; k < 16; ++k) {
+                    if (k > wv) {
+                        run = run && key[k] == row[h];
+                        if (run) {
+#pragma unroll
+                            for (int e = 0; e < VEC; ++e) acc[h].v[e] += x[k - 1].v[e];
+                            gb[h] += xgb[k];
+                        }
+                    }
+                }
             }
         }
-        __syncthreads();
-        cur ^= 1;
-    }
-    stamp.mark(6);                                       // the four doubling rounds over the waves
+        stamp.mark(6);                                   // the staged sums added
+    } else {
 #pragma unroll
-    for (int h = 0; h < EPG; ++h) {
-        const int w1 = h * 16 + wv + 1;
-        if (reach[h] && wv + 1 < 16 && lds_key[w1] == row[h]) {
+        for (int d = 1; d < 16; d <<= 1) {
 #pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[h].v[e] += wbuf[cur][(w1 * G + gl) * VEC + e];
-            gb[h] += wgb[cur][w1];
+            for (int h = 0; h < EPG; ++h) {
+                if (live[h]) {
+                    const int w0 = h * 16 + wv;
+                    const bool take = row[h] >= 0 && wv + d < 16 && lds_key[w0 + d] == row[h];
+                    if (take) {
+#pragma unroll
+                        for (int e = 0; e < VEC; ++e) tacc[h].v[e] += wbuf[cur][((w0 + d) * G + gl) * VEC + e];
+                        tgb[h] += wgb[cur][w0 + d];
+                    } else {
+                        live[h] = false;
+                    }
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e) wbuf[cur ^ 1][(w0 * G + gl) * VEC + e] = tacc[h].v[e];
+                    if (gl == 0) wgb[cur ^ 1][w0] = tgb[h];
+                }
+            }
+            __syncthreads();
+            cur ^= 1;
+        }
+        stamp.mark(6);                                   // the four doubling rounds over the waves
+#pragma unroll
+        for (int h = 0; h < EPG; ++h) {
+            const int w1 = h * 16 + wv + 1;
+            if (reach[h] && wv + 1 < 16 && lds_key[w1] == row[h]) {
+#pragma unroll
+                for (int e = 0; e < VEC; ++e) acc[h].v[e] += wbuf[cur][(w1 * G + gl) * VEC + e];
+                gb[h] += wgb[cur][w1];
+            }
         }
     }
+    const bool wt = a.wt & TFR_WT_PIECES;
 #pragma unroll
     for (int h = 0; h < EPG; ++h) {
         if (pstart[h]) {
             const int64_t j = tile0 + jl[h];
-            store_frag<VEC>(a.grad_rows[side] + (size_t)j * D, d0, D, acc[h]);
-            if (gl == 0) a.grad_bias[side][j] = gb[h];
+            store_frag_p<VEC>(a.grad_rows[side], (size_t)j * D, d0, D, acc[h], wt);
+            if (gl == 0) store_word_p(a.grad_bias[side], (size_t)j, __float_as_uint(gb[h]), wt);
         }
     }
 }
@@ -1663,27 +1778,29 @@ __global__ __launch_bounds__(256) void k_dense_tiles(TileDenseLaunch L) {
             }
         } else {
             if (!touched && a.skip_untouched) continue;
+            const int wt = L.wt;                         // write-through: read only by the next launches (TFR_WT)
             if (!a.frozen_rows) {
                 if (a.opt == 0) {
 #pragma unroll
                     for (int q = 0; q < VEC; ++q) adam_sparse(w.v[q], mrow.v[q], vrow.v[q], tot.v[q], c);
-                    store_frag<VEC>(a.m + roff, d0, D, mrow);
-                    store_frag<VEC>(a.v + roff, d0, D, vrow);
+                    store_frag_p<VEC>(a.m, roff, d0, D, mrow, wt & TFR_WT_MOMENTS);
+                    store_frag_p<VEC>(a.v, roff, d0, D, vrow, wt & TFR_WT_MOMENTS);
                 } else {
 #pragma unroll
                     for (int q = 0; q < VEC; ++q) w.v[q] = w.v[q] - a.lr * tot.v[q];
                 }
-                store_frag<VEC>(a.w + roff, d0, D, w);
+                store_frag_p<VEC>(a.w, roff, d0, D, w, wt & TFR_WT_ROWS);
             }
             if (gl == 0 && !a.frozen_bias) {
+                const bool wb = wt & TFR_WT_BIAS;
                 if (a.opt == 0) {
                     adam_sparse(bw, mb, vb, gb, c);
-                    a.bias_m[row] = mb;
-                    a.bias_v[row] = vb;
+                    store_word_p(a.bias_m, (size_t)row, __float_as_uint(mb), wb);
+                    store_word_p(a.bias_v, (size_t)row, __float_as_uint(vb), wb);
                 } else {
                     bw = bw - a.lr * gb;
                 }
-                a.bias_w[row] = bw;
+                store_word_p(a.bias_w, (size_t)row, __float_as_uint(bw), wb);
             }
         }
     }
@@ -1836,14 +1953,44 @@ int tile_step_epg(int ntiles, int G, int VEC) {
     return epg;
 }
 
-void launch_tile_step(const TileStepArgs& a, int G, int VEC, hipStream_t s) {
-    const int nbmax = a.nbins[0] > a.nbins[1] ? a.nbins[0] : a.nbins[1];
-    const int epg = tile_step_epg(a.ntiles, G, VEC);
+// the item side's pieces per block: half the user side's where the grid - look-ahead sort blocks, the user side's
+// blocks and the item side's, each side cut to the blocks that hold entries - still fits one block per CU (256 CUs).
+// At the headline shape (B = 10000, G = 16, 20 sort blocks) that is 20 + 79 + 157 = 256 blocks.  Measured no faster
+// than one EPG for both sides: off unless TFR_ITEM_SPLIT=1 (A/B).
+int tile_step_item_epg(int64_t B, int G, int VEC, int nsort) {
+    const int epg = tile_step_epg((int)((B + 1023) / 1024), G, VEC);
+    static int split = -1;
+    if (split < 0) { const char* e = getenv("TFR_ITEM_SPLIT"); split = (e && e[0] == '1') ? 1 : 0; }
+    if (!split || epg < 2) return epg;
+    const int64_t epb = 1024 / G;
+    const int64_t nu = (B + epb * epg - 1) / (epb * epg), ni = (B + epb * (epg / 2) - 1) / (epb * (epg / 2));
+    return nsort + nu + ni <= 256 ? epg / 2 : epg;
+}
+int tile_step_one_barrier() {                            // TFR_ONE_BARRIER=1: A/B switch, measured slower
+    static int on = -1;
+    if (on < 0) { const char* e = getenv("TFR_ONE_BARRIER"); on = (e && e[0] == '1') ? 1 : 0; }
+    return on;
+}
+int tile_step_wt() {                                     // TFR_WT=<bits>: A/B switch (TFR_WT_* in svd_kernels.h)
+    static int wt = -1;
+    if (wt < 0) { const char* e = getenv("TFR_WT"); wt = e ? (atoi(e) & 31) : TFR_WT_DEFAULT; }
+    return wt;
+}
+
+void launch_tile_step(const TileStepArgs& a0, int G, int VEC, hipStream_t s) {
+    const int nbmax = a0.nbins[0] > a0.nbins[1] ? a0.nbins[0] : a0.nbins[1];
+    const int epg = tile_step_epg(a0.ntiles, G, VEC);
     size_t dyn = (size_t)nbmax * 4;                       // bins during the sort, contributions afterwards
     if (dyn < (size_t)2 * epg * 16 * G * VEC * 4) dyn = (size_t)2 * epg * 16 * G * VEC * 4;   // wave-level ping-pong buffers of the reduce
     if (tile_step_static_lds(G, epg) + dyn > LDS_PER_CU) return;  // cannot happen for a shape tile_step_epg() admits (tests/test_lds_budget.py)
-    const int nsort = a.next_ids ? 2 * a.next_ntiles : 0;         // look-ahead sort blocks come first
-    const dim3 grid(nsort + a.ntiles * (G / epg), 2);
+    const int nsort = a0.next_ids ? 2 * a0.next_ntiles : 0;       // look-ahead sort blocks come first
+    TileStepArgs a = a0;
+    a.epg_item = tile_step_item_epg(a.B, G, VEC, nsort);  // <= epg: the LDS above covers it
+    a.one_barrier = tile_step_one_barrier();
+    a.wt = tile_step_wt();
+    const int64_t epb = 1024 / G;
+    const int nblk_u = (int)((a.B + epb * epg - 1) / (epb * epg)), nblk_i = (int)((a.B + epb * a.epg_item - 1) / (epb * a.epg_item));
+    const dim3 grid(nsort + nblk_u + nblk_i);
 #define TFR_TS_LAUNCH(g, v, e)                                                                        \
     {                                                                                                 \
         static size_t attr = 0;              /* static + dynamic LDS must stay within 160 KB: ask for what is needed */ \
@@ -1853,7 +2000,7 @@ void launch_tile_step(const TileStepArgs& a, int G, int VEC, hipStream_t s) {
                 return;                      /* leaves the error for the caller's hipGetLastError() */ \
             attr = dyn;                                                                               \
         }                                                                                             \
-        hipLaunchKernelGGL((k_tile_step<g, v, e>), grid, dim3(1024), dyn, s, a, nsort);               \
+        hipLaunchKernelGGL((k_tile_step<g, v, e>), grid, dim3(1024), dyn, s, a, nsort, nblk_u);       \
     }
 #define TFR_TS_CASE(g, v)                                                                             \
     if (G == g && VEC == v) {                                                                         \
@@ -1953,6 +2100,7 @@ void launch_dense_tiles(const TileDenseLaunch& L, bool write, bool with_fin, int
     const dim3 grid((int)nb + 1, 2);                     // + one block column for K4
     TileDenseLaunch LL = L;
     LL.with_fin = with_fin ? 1 : 0;
+    LL.wt = tile_step_wt() & (TFR_WT_ROWS | TFR_WT_MOMENTS | TFR_WT_BIAS);
 #define TFR_DT_LAUNCH(g, v, wr, nt) hipLaunchKernelGGL((k_dense_tiles<g, v, wr, nt>), grid, dim3(256), 0, s, LL)
 #define TFR_DT_CASE(g, v)                                                                         \
     if (G == g && VEC == v) {                                                                     \
