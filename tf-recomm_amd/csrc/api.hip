@@ -79,7 +79,6 @@ struct tfr_model {
     // two-table form of the fused big-table step (RedArgs::sel): the alternate item table, the per-row "which table" word,
     // the per-entry {partner row | old table} words of the current batch; q_dirty = some row may live in q_alt
     DevBuf<float> q_alt; DevBuf<int32_t> q_sel, osel; bool q_dirty = false;
-    bool csort_ok = false;
     DevBuf<float> gq, gp, gbq, gbp;
     DevBuf<int32_t> map_u, map_i;
     DevBuf<float> dg_p, dg_q, dg_bu, dg_bi;   // tf1: dense per-row gradients
@@ -238,6 +237,22 @@ static int drain_profile(tfr_model* m) {
     return TFR_OK;
 }
 
+// Adam in TF1 mode: the reduce leaves every touched row's sum in scratch, a dense sweep moves every row
+static bool tf1_mode(const tfr_model* m) { return m->o.optimizer == TFR_OPT_ADAM && m->o.adam_mode == TFR_ADAM_TF1; }
+
+// small tables: the bins of both id columns fit the counting sort's LDS (bits_u / bits_i are fixed at tfr_create)
+static bool small_tables(const tfr_model* m) { return (1 << std::max(m->bits_u, m->bits_i)) <= CSORT_MAX_BINS; }
+// a batch of B entries is sorted by the counting sort (otherwise by the radix sort)
+static bool csort_path(const tfr_model* m, int64_t B) { return small_tables(m) && csort_eligible(B, m->bits_u, m->bits_i); }
+
+// The reduce's gradient scratch, as ensure_capacity lays it out in cap*D-float parts.  TF1 mode: gq holds the item side's rows,
+// gp the user side's.  Otherwise gq = [item side | user side | per-entry copies of the pre-update item rows]; only the pieces of
+// runs cut by a block boundary land in the two sides' parts, and the fused user side reads the copies.
+static float* user_grad_rows(const tfr_model* m) { return tf1_mode(m) ? m->gp.get() : m->gq + (size_t)m->cap * m->D; }
+static float* item_copy_rows(const tfr_model* m) { return m->gq + 2 * (size_t)m->cap * m->D; }
+static float* grad_rows(const tfr_model* m, int side) { return side == TFR_P ? user_grad_rows(m) : m->gq.get(); }
+static float* grad_bias(const tfr_model* m, int side) { return side == TFR_P ? m->gbp.get() : m->gbq.get(); }
+
 static int ensure_capacity(tfr_model* m, int64_t B) {
     if (B <= m->cap) return TFR_OK;
     const int64_t cap = pow2_cap(B);
@@ -248,9 +263,8 @@ static int ensure_capacity(tfr_model* m, int64_t B) {
     HIPCHK(reserve_each(cap, s, m->d_u, m->d_i, m->d_r));
     HIPCHK(m->d_logits.reserve(cap + 4, s));          // + {loss, reg, sum g, error flag} behind the logits
     HIPCHK(reserve_each(cap, s, m->d_g, m->ks_u, m->ps_u, m->ks_i, m->ps_i, m->ks2_u, m->ps2_u, m->ks2_i, m->ps2_i));
-    const bool tf1_ws = m->o.optimizer == TFR_OPT_ADAM && m->o.adam_mode == TFR_ADAM_TF1;
-    // non-tf1: second third of gq parks the pieces of split user runs, the last third the
-    // per-entry copies of pre-update item rows the fused user side reads
+    const bool tf1_ws = tf1_mode(m);
+    // the layout user_grad_rows / item_copy_rows read
     HIPCHK(m->gq.reserve(cap * m->D * (tf1_ws ? 1 : 3), s));
     HIPCHK(reserve_each(cap, s, m->gbq, m->srt[0][0], m->srt[0][1], m->srt[1][0], m->srt[1][1], m->gbp));
     if (tf1_ws) HIPCHK(m->gp.reserve(cap * m->D, s));
@@ -261,7 +275,7 @@ static int ensure_capacity(tfr_model* m, int64_t B) {
     }
     {
         const int64_t ntiles = (cap + CSORT_TILE - 1) / CSORT_TILE;
-        const bool small = (1 << (m->bits_u > m->bits_i ? m->bits_u : m->bits_i)) <= CSORT_MAX_BINS;
+        const bool small = small_tables(m);
         const int64_t hu = std::max((small ? ((int64_t)1 << m->bits_u) : 256) * ntiles, 256 * ntiles);
         const int64_t hi = std::max((small ? ((int64_t)1 << m->bits_i) : 256) * ntiles, 256 * ntiles);
         HIPCHK(reserve_each(cap, s, m->osel, m->lrank_u, m->lrank_i));
@@ -272,7 +286,6 @@ static int ensure_capacity(tfr_model* m, int64_t B) {
         HIPCHK(m->binbase_u.reserve(small ? (int64_t)1 << m->bits_u : 1, s));
         HIPCHK(m->binbase_i.reserve(small ? (int64_t)1 << m->bits_i : 1, s));
         HIPCHK(reserve_each(64 + 256 * ntiles / 4096, s, m->blocktot_u, m->blocktot_i));
-        m->csort_ok = small;
     }
     m->cap = cap;
     return TFR_OK;
@@ -700,15 +713,97 @@ static OptStep opt_step(const tfr_model* m) {
 template <typename A>
 static void set_hyper(A& a, const OptStep& k) { a.alpha = k.alpha; a.b1 = k.b1; a.b2 = k.b2; a.eps = k.eps; a.lr = k.lr; }
 
+// the optimiser as the kernels' mode arguments: the reduce's (scratch in TF1 mode, else the update fused in) and the
+// applies' (also the `opt` field of FinArgs / DenseArgs / TileDenseArgs)
+static int reduce_mode(const OptStep& k) { return k.tf1 ? RMODE_SCRATCH : k.adam ? RMODE_ADAM : RMODE_SGD; }
+static int apply_mode(const OptStep& k) { return k.adam ? 0 : 1; }
+// launch_apply_rows: write the reduced rows (and biases) out to w / bias_w instead of updating a table
+static const int APPLY_EMIT_ROWS = 2;
+
 // K4 with the bias_global update; partials and nblk are the caller's
 static FinArgs mu_fin(const tfr_model* m, const OptStep& k, bool update_mu, float* out) {
     FinArgs f;
     memset(&f, 0, sizeof(f));
     f.scalars = m->scalars; f.out = out; f.err = m->d_err;
     f.mu = m->w[TFR_MU]; f.mu_m = m->m[TFR_MU]; f.mu_v = m->v[TFR_MU];
-    f.update_mu = update_mu ? 1 : 0; f.opt = k.adam ? 0 : 1;
+    f.update_mu = update_mu ? 1 : 0; f.opt = apply_mode(k);
     set_hyper(f, k);
     return f;
+}
+
+// K4 without the bias_global update: the local {loss, reg, sum g} into out (data-parallel and row-sharded steps, where
+// bias_global waits for the all-reduce); nblk is the caller's
+static FinArgs local_fin(const tfr_model* m, float* out) {
+    FinArgs f;
+    memset(&f, 0, sizeof(f));
+    f.partials = m->partials; f.scalars = m->scalars; f.out = out; f.err = m->d_err;
+    f.mu = m->w[TFR_MU];
+    return f;
+}
+
+// ---- the phases of a training step: one builder per argument struct -----------------------------------------------
+// Each sets what every caller sets alike; what a path does differently stays an assignment at its call site.
+
+// one side of the segmented reduce over the sorted order ks / ps of B entries: `own` is the side's table, the sums go to
+// the side's scratch
+static RedArgs reduce_side(const tfr_model* m, int side, const int32_t* ks, const int32_t* ps, int64_t B) {
+    RedArgs r;
+    memset(&r, 0, sizeof(r));
+    r.side = side == TFR_Q ? 1 : 0; r.ks = ks; r.ps = ps;
+    r.own = m->w[side]; r.own_bias = m->w[side == TFR_P ? TFR_BU : TFR_BI];
+    r.grad_rows = grad_rows(m, side); r.grad_bias = grad_bias(m, side);
+    r.err = m->d_err; r.B = B; r.D = m->D;
+    return r;
+}
+// ... of a rating batch: the partner rows are the other table's, by the other id column; g comes from the forward
+static RedArgs rating_side(const tfr_model* m, int side, const int32_t* ks, const int32_t* ps, const int32_t* other, int64_t B) {
+    RedArgs r = reduce_side(m, side, ks, ps, B);
+    r.other = other; r.partner = m->w[side == TFR_P ? TFR_Q : TFR_P]; r.g = m->d_g;
+    r.item_abs = m->o.item_abs; r.reg_bias = m->o.reg_bias; r.lam = m->o.reg;
+    return r;
+}
+
+// k_apply_rows on the runs of one side that the reduce cut into several pieces (the whole runs are done)
+static ApplyArgs apply_split(const tfr_model* m, int side, const int32_t* ks, int64_t B) {
+    ApplyArgs a;
+    memset(&a, 0, sizeof(a));
+    a.ks = ks; a.grad_rows = grad_rows(m, side); a.grad_bias = grad_bias(m, side);
+    a.err = m->d_err; a.B = B; a.D = m->D; a.only_split = 1;
+    return a;
+}
+
+// the dense sweep of one side (every row moves); with ks, the touched rows' sums come from the reduce's scratch, found
+// through the side's row -> slot map
+static DenseArgs dense_side(const tfr_model* m, const OptStep& k, int side, const int32_t* ks = nullptr, int64_t B = 0) {
+    DenseArgs d;
+    memset(&d, 0, sizeof(d));
+    bind_side(d, m, side);
+    set_hyper(d, k);
+    d.err = m->d_err; d.D = m->D; d.opt = apply_mode(k);
+    if (ks) {
+        d.map = side == TFR_P ? m->map_u : m->map_i;
+        d.ks = ks; d.B = B; d.grad_rows = grad_rows(m, side); d.grad_bias = grad_bias(m, side);
+    }
+    return d;
+}
+
+// k_dense_tiles over both sides' per-tile piece sums of a B-entry batch (tile tables of parity par), K4 `f` riding along;
+// a[0] items, a[1] users
+static TileDenseLaunch tile_dense(const tfr_model* m, int64_t B, int par, const FinArgs& f) {
+    TileDenseLaunch L;
+    memset(&L, 0, sizeof(L));
+    for (int j = 0; j < 2; ++j) {
+        const int side = j == 0 ? TFR_Q : TFR_P;
+        TileDenseArgs& d = L.a[j];
+        d.tab = j == 0 ? (par ? m->offs_i : m->hist_i) : (par ? m->offs_u : m->hist_u);
+        d.nbins = 1 << (j == 0 ? m->bits_i : m->bits_u);
+        d.ntiles = (int32_t)((B + CSORT_TILE - 1) / CSORT_TILE);
+        d.grad_rows = grad_rows(m, side); d.grad_bias = grad_bias(m, side);
+        d.rows = side == TFR_P ? m->U : m->I;
+        d.err = m->d_err; d.D = m->D;
+    }
+    L.f = f;
+    return L;
 }
 
 // after a step's applies: the beta-power accumulators advance [TF1-lib], then the step count
@@ -805,7 +900,7 @@ static int sort_columns(tfr_model* m, const int32_t* du, const int32_t* di, int6
                         const int64_t* store_ids = nullptr) {
     Prof p(m, TFR_K_SORT);
     m->pf_valid = false;                                 // the sort scratch doubles as the published tables of the tile step
-    if (m->csort_ok && csort_eligible(B, m->bits_u, m->bits_i)) {
+    if (csort_path(m, B)) {
         CSortArgs c;
         c.keys[0] = du; c.keys[1] = di;
         c.ks[0] = m->ks_u; c.ks[1] = m->ks_i; c.ps[0] = m->ps_u; c.ps[1] = m->ps_i;
@@ -831,8 +926,7 @@ static int sort_columns(tfr_model* m, const int32_t* du, const int32_t* di, int6
 // big tables with a touched-rows optimiser: the forward is computed inside the item-side reduce,
 // which needs the sorted order first - so the step starts with (gather +) sort
 static bool fwd_in_reduce(const tfr_model* m, int64_t B) {
-    const bool tf1 = m->o.optimizer == TFR_OPT_ADAM && m->o.adam_mode == TFR_ADAM_TF1;
-    return B > 0 && !tf1 && !(m->csort_ok && csort_eligible(B, m->bits_u, m->bits_i));
+    return B > 0 && !tf1_mode(m) && !csort_path(m, B);
 }
 
 static int gather_batch(tfr_model* m, const int64_t* d_ids, int64_t lo, int64_t B);
@@ -841,7 +935,7 @@ static int gather_batch(tfr_model* m, const int64_t* d_ids, int64_t lo, int64_t 
 // (`f`) rides in the csort scan launch when that path is taken (fin_done).  du/di are updated
 // to where the batch ids live afterwards.
 static bool tiles_eligible(const tfr_model* m, int64_t B) {
-    return B > 0 && m->csort_ok && csort_eligible(B, m->bits_u, m->bits_i) && (B + CSORT_TILE - 1) / CSORT_TILE <= 16;
+    return B > 0 && csort_path(m, B) && (B + CSORT_TILE - 1) / CSORT_TILE <= 16;
 }
 
 static int front_and_sort(tfr_model* m, const int32_t*& du, const int32_t*& di, const float*& dr, int64_t B,
@@ -851,7 +945,7 @@ static int front_and_sort(tfr_model* m, const int32_t*& du, const int32_t*& di, 
     hipStream_t s = m->stream;
     int rc;
     if (sort_only) {
-        const bool radix = !(m->csort_ok && csort_eligible(B, m->bits_u, m->bits_i));
+        const bool radix = !csort_path(m, B);
         static int fuse = -1;                            // TFR_FUSE_GATHER=0: A/B switch (separate k_gather_triples launch)
         if (fuse < 0) { const char* e = getenv("TFR_FUSE_GATHER"); fuse = (e && e[0] == '0') ? 0 : 1; }
         if (d_store_ids && radix && fuse) {                      // the radix sort's first pass gathers the batch itself (one launch less)
@@ -871,7 +965,7 @@ static int front_and_sort(tfr_model* m, const int32_t*& du, const int32_t*& di, 
         d_store_ids = nullptr;
         du = m->d_u; di = m->d_i; dr = m->d_r;
     }
-    if (m->csort_ok && csort_eligible(B, m->bits_u, m->bits_i)) {
+    if (csort_path(m, B)) {
         // small tables: forward and the counting sort's rank pass share one launch, then
         // scan (+K4) and scatter
         FrontArgs fa;
@@ -953,7 +1047,7 @@ static const int4* recs_for(tfr_model* m, const int64_t* p, int64_t B) {
 
 static int tile_step_launch(tfr_model* m, const int32_t* du, const int32_t* di, const float* dr, int64_t B,
                             float* d_logits, const int64_t* d_store_ids, const int64_t* next_store_ids,
-                            float* gp_rows, int* par_out, int* nblk_out) {
+                            int* par_out, int* nblk_out) {
     const tfr_opts& o = m->o;
     TileStepArgs ts;
     memset(&ts, 0, sizeof(ts));
@@ -975,8 +1069,8 @@ static int tile_step_launch(tfr_model* m, const int32_t* du, const int32_t* di, 
         ts.next_srt[0] = m->srt[par ^ 1][0]; ts.next_srt[1] = m->srt[par ^ 1][1];
         m->pf_valid = true; m->pf_ids = next_store_ids; m->pf_B = B; m->pf_par = par ^ 1;
     }
-    ts.grad_rows[0] = gp_rows; ts.grad_rows[1] = m->gq;
-    ts.grad_bias[0] = m->gbp; ts.grad_bias[1] = m->gbq;
+    ts.grad_rows[0] = grad_rows(m, TFR_P); ts.grad_rows[1] = grad_rows(m, TFR_Q);
+    ts.grad_bias[0] = grad_bias(m, TFR_P); ts.grad_bias[1] = grad_bias(m, TFR_Q);
     ts.B = B; ts.U = m->U; ts.I = m->I; ts.N = m->N;
     ts.D = m->D; ts.loss = o.loss; ts.item_abs = o.item_abs; ts.reg_bias = o.reg_bias;
     ts.ntiles = (int32_t)((B + CSORT_TILE - 1) / CSORT_TILE);
@@ -1033,27 +1127,158 @@ static int tile_step_launch(tfr_model* m, const int32_t* du, const int32_t* di, 
     return TFR_OK;
 }
 
+// The three paths of a training step after its forward and sort (front_and_sort); `f` is the step's K4, nblk included.
+
+// small tables: per-tile sorted order -> piece sums per tile -> one sweep that combines a row's per-tile partials, applies
+// the optimiser to both tables and runs K4.  one_launch: gather + tile-local sort + forward + per-tile reduce of both sides
+// in one launch (k_tile_step); otherwise the reduce follows front_and_sort's forward and sort
+static int step_small_tiles(tfr_model* m, const OptStep& k, const int32_t* du, const int32_t* di, const float* dr, int64_t B,
+                            float* d_logits, const int64_t* d_store_ids, const int64_t* next_store_ids, bool one_launch,
+                            FinArgs f) {
+    hipStream_t s = m->stream;
+    int par = 0;
+    if (one_launch) {
+        int nblk = 0, rc;
+        if ((rc = tile_step_launch(m, du, di, dr, B, d_logits, d_store_ids, next_store_ids, &par, &nblk))) return rc;
+        f.nblk = nblk;
+    } else {
+        RedPair pr;
+        pr.a[0] = rating_side(m, TFR_Q, m->ks_i, m->ps_i, du, B);
+        pr.a[1] = rating_side(m, TFR_P, m->ks_u, m->ps_u, di, B);
+        pr.a[0].tile = pr.a[1].tile = CSORT_TILE;
+        Prof p(m, TFR_K_REDUCE_ITEM);
+        launch_seg_reduce(pr, 2, RMODE_SCRATCH, m->G, m->VEC, s);
+    }
+    HIPCHK(hipGetLastError());
+    TileDenseLaunch L = tile_dense(m, B, par, f);
+    for (int j = 0; j < 2; ++j) {
+        TileDenseArgs& d = L.a[j];
+        bind_side(d, m, j == 0 ? TFR_Q : TFR_P);
+        set_hyper(d, k);
+        d.opt = apply_mode(k); d.skip_untouched = k.tf1 ? 0 : 1;
+    }
+    {
+        Prof p(m, TFR_K_APPLY);
+        launch_dense_tiles(L, false, true, m->G, m->VEC, s);
+    }
+    HIPCHK(hipGetLastError());
+    return TFR_OK;
+}
+
+// big tables, Adam in TF1 mode: both sides' sums into scratch in one launch (both only read the tables), then the dense
+// sweeps - every row of every unfrozen table moves.  B = 0: the sweeps alone
+static int step_big_tf1(tfr_model* m, const OptStep& k, const int32_t* du, const int32_t* di, int64_t B) {
+    hipStream_t s = m->stream;
+    if (B > 0) {
+        RedPair pr = {{rating_side(m, TFR_Q, m->ks_i, m->ps_i, du, B), rating_side(m, TFR_P, m->ks_u, m->ps_u, di, B)}};
+        RedArgs& ri = pr.a[0];
+        RedArgs& ru = pr.a[1];
+        bind_side(ru, m, TFR_P);
+        set_hyper(ri, k); set_hyper(ru, k);
+        ri.map = m->map_i; ru.map = m->map_u;
+        if (m->dg_p) {
+            ri.dense_rows = m->dg_q; ri.dense_bias = m->dg_bi;
+            ru.dense_rows = m->dg_p; ru.dense_bias = m->dg_bu;
+        }
+        {
+            Prof p(m, TFR_K_REDUCE_ITEM);
+            launch_seg_reduce(pr, 2, reduce_mode(k), m->G, m->VEC, s);
+        }
+        HIPCHK(hipGetLastError());
+    }
+    Prof p(m, TFR_K_APPLY);
+    DensePair dp;
+    memset(&dp, 0, sizeof(dp));
+    dp.a[0] = dense_side(m, k, TFR_P, m->ks_u, B);
+    dp.a[0].dense_grad = m->dg_p; dp.a[0].dense_gbias = m->dg_bu;
+    dp.a[1] = dense_side(m, k, TFR_Q, m->ks_i, B);
+    dp.a[1].dense_grad = m->dg_q; dp.a[1].dense_gbias = m->dg_bi;
+    // the sweep also consumes (clears) the row->slot maps, so it always runs on both tables
+    launch_adam_dense(dp, 2, m->G, m->VEC, s);
+    HIPCHK(hipGetLastError());
+    return TFR_OK;
+}
+
+// big tables, lazy Adam / SGD: both sides fused (reduce + update in place).  The item side goes first; the user side then
+// updates P and reads the pre-update Q rows - from the table the item side did not write (dual) or from the per-entry copy
+// the item side leaves.  fwd_fused: K1 runs inside the item side.  Pieces of runs cut by a block boundary are parked in
+// the sides' scratch and finished by k_apply_rows, which also carries K4 unless the sort did (fin_done)
+static int step_big_fused(tfr_model* m, const OptStep& k, const int32_t* du, const int32_t* di, const float* dr, int64_t B,
+                          float* d_logits, bool fwd_fused, bool dual, FinArgs f, bool fin_done) {
+    hipStream_t s = m->stream;
+    RedArgs ri = rating_side(m, TFR_Q, m->ks_i, m->ps_i, du, B);
+    RedArgs ru = rating_side(m, TFR_P, m->ks_u, m->ps_u, di, B);
+    bind_side(ri, m, TFR_Q); bind_side(ru, m, TFR_P);
+    set_hyper(ri, k); set_hyper(ru, k);
+    // big tables: every row of this step is touched once and cannot stay cached - non-temporal loads / stores for the
+    // rows, default policy only for reading back the pre-update copies (A/B, TFR_NT=<bits>:
+    // 523-548 us/step with 0, 498 with 23; bits in svd_kernels.h RedArgs::nt)
+    { static int nt = -1; if (nt < 0) { const char* e = getenv("TFR_NT"); nt = e ? atoi(e) : 23; } ri.nt = ru.nt = fwd_fused ? nt : 0; }
+    if (dual) {
+        // the updated item row goes to the table the row is NOT in, so the user side still finds the pre-update row where
+        // it was: no copy written (4D per rating) and none read
+        ri.own_alt = m->q_alt; ri.own_w_alt = m->q_alt; ri.sel = m->q_sel; ri.osel_out = m->osel;
+        ru.osel_in = m->osel; ru.partner_alt = m->q_alt;
+        m->q_dirty = true;
+    } else {
+        ri.own_copy_out = item_copy_rows(m);
+        ru.partner_by_pos = item_copy_rows(m);
+    }
+    if (fwd_fused) {           // K1 inside the item side: logits, g, per-block {loss, reg, sum g}
+        ri.partner_bias = m->w[TFR_BU]; ri.mu = m->w[TFR_MU]; ri.r = dr; ri.loss = m->o.loss;
+        ri.g_out = m->d_g; ri.logits_out = d_logits; ri.partials = m->partials;
+        { static int st = -1; if (st < 0) { const char* e = getenv("TFR_STAGE_SUM"); st = (e && e[0] == '0') ? 0 : 1; } ri.stage_sum = st; }
+        const int epb = 1024 / m->G;
+        f.nblk = (int)((B + epb - 1) / epb);
+    }
+    RedPair pr;
+    pr.a[0] = ri;
+    {
+        Prof p(m, TFR_K_REDUCE_ITEM);
+        launch_seg_reduce(pr, 1, reduce_mode(k), m->G, m->VEC, s, fwd_fused);
+    }
+    HIPCHK(hipGetLastError());
+    if (m->ev_mid_on) HIPCHK(hipEventRecord(m->ev_mid, s));
+    pr.a[0] = ru;
+    {
+        Prof p(m, TFR_K_REDUCE_USER);
+        launch_seg_reduce(pr, 1, reduce_mode(k), m->G, m->VEC, s);
+    }
+    HIPCHK(hipGetLastError());
+    ApplyPair app;
+    app.a[0] = apply_split(m, TFR_Q, m->ks_i, B);
+    app.a[1] = apply_split(m, TFR_P, m->ks_u, B);
+    bind_side(app.a[0], m, TFR_Q); bind_side(app.a[1], m, TFR_P);
+    set_hyper(app.a[0], k); set_hyper(app.a[1], k);
+    if (dual) { app.a[0].w_alt = m->q_alt; app.a[0].sel = m->q_sel; }
+    if (!fin_done) { app.f = f; app.with_fin = 1; }     // K4 rides in the same launch (one launch and ~6 us fewer per big-table step)
+    {
+        Prof p(m, TFR_K_APPLY);
+        launch_apply_rows(app, 2, apply_mode(k), m->G, m->VEC, s);
+    }
+    HIPCHK(hipGetLastError());
+    return TFR_OK;
+}
+
 // one minibatch on device-resident (u, i, r) - or, with d_store_ids, on rows of the resident
 // store gathered inside the forward kernel; out3 = optional device {loss, reg, sum_g} slot
 static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, const float* dr, int64_t B,
                           float* d_logits, float* out3, const int64_t* d_store_ids = nullptr,
                           const int64_t* next_store_ids = nullptr, bool presorted_big = false, bool out_err = false) {
-    const tfr_opts& o = m->o;
     const OptStep k = opt_step(m);
-    const bool adam = k.adam, tf1 = k.tf1;
-    int nblk = 0;
+    int nblk = 0, rc;
     hipStream_t s = m->stream;
-    bool fin_done = false, tiles = false;
+    bool fin_done = false;
     FinArgs f = mu_fin(m, k, !((m->frozen >> TFR_MU) & 1), out3);
     f.partials = m->partials; f.out_err = out_err ? 1 : 0;
+    const bool tiles = tiles_eligible(m, B);
+    const bool fwd_fused = fwd_in_reduce(m, B);
+    bool dual = false, one_launch = false;
     if (B > 0) {
-        int rc;
-        tiles = tiles_eligible(m, B);
-        const bool fwd_fused = fwd_in_reduce(m, B);
         // two-table form of the fused big-table step (no per-entry copy of the pre-update item rows): TFR_DUALQ=0 restores the copy
         static int dualq = -1;
         if (dualq < 0) { const char* e = getenv("TFR_DUALQ"); dualq = (e && e[0] == '0') ? 0 : 1; }
-        const bool dual = fwd_fused && dualq;
+        dual = fwd_fused && dualq;
         if (dual && !(m->q_alt && m->q_sel)) {           // both tables or neither
             hipError_t e = m->q_alt.reserve(m->n[TFR_Q], s);
             if (e == hipSuccess) e = m->q_sel.reserve(m->I, s);
@@ -1067,176 +1292,18 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
         if (!dual && (rc = settle_q(m))) return rc;
         static int split_tiles = -1;   // TFR_TILE_SPLIT=1: the three-launch form (k_front + k_seg_reduce), kept for A/B
         if (split_tiles < 0) { const char* e = getenv("TFR_TILE_SPLIT"); split_tiles = (e && e[0] == '1') ? 1 : 0; }
-        const bool one_launch = tiles && !split_tiles;
+        one_launch = tiles && !split_tiles;
         if (!one_launch && !(presorted_big && fwd_fused))     // presorted_big: gathered + sorted ahead, on the second stream
             if ((rc = front_and_sort(m, du, di, dr, B, d_logits, d_store_ids, f, nblk, fin_done, tiles, fwd_fused))) return rc;
-        if (tiles) {
-            // small tables: per-tile sorted order -> piece sums per tile -> one sweep that combines a
-            // row's per-tile partials, applies the optimiser to both tables and runs K4
-            float* gp_rows = m->gp ? m->gp : m->gq + (size_t)m->cap * m->D;
-            int par = 0;
-            if (one_launch) {
-                // gather + tile-local sort + forward + per-tile reduce of both sides: one launch
-                if ((rc = tile_step_launch(m, du, di, dr, B, d_logits, d_store_ids, next_store_ids, gp_rows, &par, &nblk))) return rc;
-                f.nblk = nblk;
-            }
-            RedArgs r;
-            memset(&r, 0, sizeof(r));
-            r.g = m->d_g; r.err = m->d_err; r.B = B; r.D = m->D; r.tile = CSORT_TILE;
-            r.item_abs = o.item_abs; r.reg_bias = o.reg_bias; r.lam = o.reg;
-            RedPair pr;
-            pr.a[0] = r;
-            pr.a[0].side = 1; pr.a[0].ks = m->ks_i; pr.a[0].ps = m->ps_i; pr.a[0].other = du;
-            pr.a[0].own = m->w[TFR_Q]; pr.a[0].partner = m->w[TFR_P]; pr.a[0].own_bias = m->w[TFR_BI];
-            pr.a[0].grad_rows = m->gq; pr.a[0].grad_bias = m->gbq;
-            pr.a[1] = r;
-            pr.a[1].side = 0; pr.a[1].ks = m->ks_u; pr.a[1].ps = m->ps_u; pr.a[1].other = di;
-            pr.a[1].own = m->w[TFR_P]; pr.a[1].partner = m->w[TFR_Q]; pr.a[1].own_bias = m->w[TFR_BU];
-            pr.a[1].grad_rows = gp_rows; pr.a[1].grad_bias = m->gbp;
-            if (!one_launch) {
-                Prof p(m, TFR_K_REDUCE_ITEM);
-                launch_seg_reduce(pr, 2, RMODE_SCRATCH, m->G, m->VEC, s);
-            }
-            HIPCHK(hipGetLastError());
-            TileDenseLaunch L;
-            memset(&L, 0, sizeof(L));
-            TileDenseArgs d;
-            memset(&d, 0, sizeof(d));
-            d.err = m->d_err; d.D = m->D; d.ntiles = (int32_t)((B + CSORT_TILE - 1) / CSORT_TILE);
-            d.opt = adam ? 0 : 1; d.skip_untouched = tf1 ? 0 : 1;
-            set_hyper(d, k);
-            L.a[0] = d;                // items
-            bind_side(L.a[0], m, TFR_Q);
-            L.a[0].tab = par ? m->offs_i : m->hist_i; L.a[0].nbins = 1 << m->bits_i;
-            L.a[0].grad_rows = m->gq; L.a[0].grad_bias = m->gbq;
-            L.a[1] = d;                // users
-            bind_side(L.a[1], m, TFR_P);
-            L.a[1].tab = par ? m->offs_u : m->hist_u; L.a[1].nbins = 1 << m->bits_u;
-            L.a[1].grad_rows = pr.a[1].grad_rows; L.a[1].grad_bias = m->gbp;
-            L.f = f;
-            {
-                Prof p(m, TFR_K_APPLY);
-                launch_dense_tiles(L, false, true, m->G, m->VEC, s);
-            }
-            HIPCHK(hipGetLastError());
-            fin_done = true;
-        } else {
-        RedArgs r;
-        memset(&r, 0, sizeof(r));
-        r.g = m->d_g; r.err = m->d_err; r.B = B; r.D = m->D;
-        r.item_abs = o.item_abs; r.reg_bias = o.reg_bias; r.lam = o.reg;
-        set_hyper(r, k);
-        // big tables: every row of this step is touched once and cannot stay cached - non-temporal loads / stores for the
-        // rows, default policy only for reading back the pre-update copies (A/B in one gpurun call, TFR_NT=<bits>:
-        // 523-548 us/step with 0, 498 with 23; bits in svd_kernels.h RedArgs::nt)
-        { static int nt = -1; if (nt < 0) { const char* e = getenv("TFR_NT"); nt = e ? atoi(e) : 23; } r.nt = fwd_fused ? nt : 0; }
-        // item side -> scratch (reads the pre-update user rows)
-        RedArgs ri = r;
-        ri.side = 1;
-        ri.ks = m->ks_i; ri.ps = m->ps_i; ri.other = du;
-        ri.own = m->w[TFR_Q]; ri.partner = m->w[TFR_P]; ri.own_bias = m->w[TFR_BI];
-        ri.grad_rows = m->gq; ri.grad_bias = m->gbq; ri.map = tf1 ? m->map_i : nullptr;
-        // user side: fused update (lazy Adam / SGD) or scratch (TF1 Adam)
-        RedArgs ru = r;
-        ru.side = 0;
-        ru.ks = m->ks_u; ru.ps = m->ps_u; ru.other = di;
-        ru.own = m->w[TFR_P]; ru.partner = m->w[TFR_Q]; ru.own_bias = m->w[TFR_BU];
-        bind_side(ru, m, TFR_P);
-        ru.grad_bias = m->gbp; ru.map = tf1 ? m->map_u : nullptr;
-        if (tf1) {
-            // both sides only read the tables: one launch
-            ru.grad_rows = m->gp;
-            if (m->dg_p) {
-                ri.dense_rows = m->dg_q; ri.dense_bias = m->dg_bi;
-                ru.dense_rows = m->dg_p; ru.dense_bias = m->dg_bu;
-            }
-            RedPair pr;
-            pr.a[0] = ri; pr.a[1] = ru;
-            Prof p(m, TFR_K_REDUCE_ITEM);
-            launch_seg_reduce(pr, 2, RMODE_SCRATCH, m->G, m->VEC, s);
-        } else {
-            // both sides fused (reduce + lazy Adam / SGD in place).  The item side goes first and
-            // leaves a per-entry copy of the pre-update Q rows (last third of gq) for the user
-            // side, which then updates P; pieces of runs cut by a block boundary are parked in
-            // the first (items) and second (users) third of gq and finished by k_apply_rows.
-            float* qcopy = m->gq + 2 * (size_t)m->cap * m->D;
-            bind_side(ri, m, TFR_Q);
-            if (dual) {
-                // the updated item row goes to the table the row is NOT in, so the user side still finds the pre-update row where
-                // it was: no copy written (4D per rating) and none read
-                ri.own_alt = m->q_alt; ri.own_w_alt = m->q_alt; ri.sel = m->q_sel; ri.osel_out = m->osel;
-                ru.osel_in = m->osel; ru.partner_alt = m->q_alt;
-                m->q_dirty = true;
-            } else {
-                ri.own_copy_out = qcopy;
-                ru.partner_by_pos = qcopy;
-            }
-            ru.grad_rows = m->gq + (size_t)m->cap * m->D;
-            if (fwd_fused) {           // K1 inside the item side: logits, g, per-block {loss, reg, sum g}
-                ri.partner_bias = m->w[TFR_BU]; ri.mu = m->w[TFR_MU]; ri.r = dr; ri.loss = o.loss;
-                ri.g_out = m->d_g; ri.logits_out = d_logits; ri.partials = m->partials;
-                { static int st = -1; if (st < 0) { const char* e = getenv("TFR_STAGE_SUM"); st = (e && e[0] == '0') ? 0 : 1; } ri.stage_sum = st; }
-                const int epb = 1024 / m->G;
-                nblk = (int)((B + epb - 1) / epb);
-            }
-            RedPair pr;
-            pr.a[0] = ri;
-            {
-                Prof p(m, TFR_K_REDUCE_ITEM);
-                launch_seg_reduce(pr, 1, adam ? RMODE_ADAM : RMODE_SGD, m->G, m->VEC, s, fwd_fused);
-            }
-            HIPCHK(hipGetLastError());
-            if (m->ev_mid_on) HIPCHK(hipEventRecord(m->ev_mid, s));
-            pr.a[0] = ru;
-            {
-                Prof p(m, TFR_K_REDUCE_USER);
-                launch_seg_reduce(pr, 1, adam ? RMODE_ADAM : RMODE_SGD, m->G, m->VEC, s);
-            }
-            HIPCHK(hipGetLastError());
-            ApplyArgs ap;
-            memset(&ap, 0, sizeof(ap));
-            ap.err = m->d_err; ap.B = B; ap.D = m->D; ap.only_split = 1;
-            set_hyper(ap, k);
-            ApplyPair app;
-            app.a[0] = ap;
-            bind_side(app.a[0], m, TFR_Q);
-            app.a[0].ks = m->ks_i; app.a[0].grad_rows = m->gq; app.a[0].grad_bias = m->gbq;
-            if (dual) { app.a[0].w_alt = m->q_alt; app.a[0].sel = m->q_sel; }
-            app.a[1] = ap;
-            bind_side(app.a[1], m, TFR_P);
-            app.a[1].ks = m->ks_u; app.a[1].grad_rows = ru.grad_rows; app.a[1].grad_bias = m->gbp;
-            if (!fin_done) {           // K4 rides in the same launch (one launch and ~6 us fewer per big-table step)
-                f.nblk = nblk;
-                app.f = f; app.with_fin = 1;
-                fin_done = true;
-            }
-            {
-                Prof p(m, TFR_K_APPLY);
-                launch_apply_rows(app, 2, adam ? 0 : 1, m->G, m->VEC, s);
-            }
-        }
-        HIPCHK(hipGetLastError());
-        }
     }
-    if (tf1 && !tiles) {
-        // dense sweeps: every row of every unfrozen table moves; one launch
-        Prof p(m, TFR_K_APPLY);
-        DenseArgs d;
-        memset(&d, 0, sizeof(d));
-        d.err = m->d_err; d.D = m->D; d.B = B;
-        set_hyper(d, k);
-        DensePair dp;
-        dp.a[0] = d;
-        bind_side(dp.a[0], m, TFR_P);
-        dp.a[0].map = m->map_u; dp.a[0].ks = m->ks_u; dp.a[0].grad_rows = m->gp; dp.a[0].grad_bias = m->gbp;
-        dp.a[0].dense_grad = m->dg_p; dp.a[0].dense_gbias = m->dg_bu;
-        dp.a[1] = d;
-        bind_side(dp.a[1], m, TFR_Q);
-        dp.a[1].map = m->map_i; dp.a[1].ks = m->ks_i; dp.a[1].grad_rows = m->gq; dp.a[1].grad_bias = m->gbq;
-        dp.a[1].dense_grad = m->dg_q; dp.a[1].dense_gbias = m->dg_bi;
-        // the sweep also consumes (clears) the row->slot maps, so it always runs on both tables
-        launch_adam_dense(dp, 2, m->G, m->VEC, s);
-        HIPCHK(hipGetLastError());
+    if (tiles) {
+        if ((rc = step_small_tiles(m, k, du, di, dr, B, d_logits, d_store_ids, next_store_ids, one_launch, f))) return rc;
+        fin_done = true;
+    } else if (k.tf1) {
+        if ((rc = step_big_tf1(m, k, du, di, B))) return rc;
+    } else if (B > 0) {
+        if ((rc = step_big_fused(m, k, du, di, dr, B, d_logits, fwd_fused, dual, f, fin_done))) return rc;
+        fin_done = true;
     }
     if (!fin_done) {
         f.nblk = nblk;
@@ -2136,30 +2203,26 @@ int tfr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* loss_o
 int tfr_kernel_plan(tfr_model* m, int64_t B, char* buf, int64_t buflen) {
     MODEL_ENTER(m);
     if (!buf || buflen < 64 || B < 1) return fail(TFR_ERR_ARG, "kernel_plan: need a buffer of >= 64 bytes and batch >= 1");
-    const tfr_opts& o = m->o;
-    const bool adam = o.optimizer == TFR_OPT_ADAM;
-    const bool tf1 = adam && o.adam_mode == TFR_ADAM_TF1;
+    const OptStep k = opt_step(m);
     const int G = m->G, V = m->VEC;
-    const bool small = (1 << (m->bits_u > m->bits_i ? m->bits_u : m->bits_i)) <= CSORT_MAX_BINS;
-    const bool csort = small && csort_eligible(B, m->bits_u, m->bits_i);
     const int64_t ntiles = (B + CSORT_TILE - 1) / CSORT_TILE;
     char tmp[1024];
-    if (csort && ntiles <= 16) {
+    if (tiles_eligible(m, B)) {
         const int nt = ntiles <= 4 ? 4 : ntiles <= 8 ? 8 : ntiles <= 10 ? 10 : ntiles <= 12 ? 12 : 16;
         snprintf(tmp, sizeof(tmp), "reduce_item=k_tile_step<%d, %d, %d>;apply=k_dense_tiles<%d, %d, false, %d>", G, V,
                  tile_step_epg((int)ntiles, G, V), G, V, nt);
-    } else if (!tf1 && !csort) {
-        const int rm = adam ? RMODE_ADAM : RMODE_SGD;
+    } else if (fwd_in_reduce(m, B)) {
+        const int rm = reduce_mode(k);
         // the sixth argument: the three-round load form (launch_seg_reduce picks it for the two-table step on full-width rows)
         const char* e1 = getenv("TFR_DUALQ"); const char* e2 = getenv("TFR_FAST"); const char* e3 = getenv("TFR_LEAN");
         const bool fast = !(e1 && e1[0] == '0') && !(e2 && e2[0] == '0') && !(e3 && e3[0] == '0') && m->D == G * V;
         snprintf(tmp, sizeof(tmp), "sort=%s x%d passes (the first gathers the batch);reduce_item=k_seg_reduce<%d, %d, %d, true, true, %s>;"
                  "reduce_user=k_seg_reduce<%d, %d, %d, false, true, %s>;apply=k_apply_rows<%d, %d, %d>",   // K4 rides in the apply launch
                  rsortw_eligible(B) ? "k_rsortw_hist/k_rsort_scan/k_rsortw_scatter" : "k_rsort_rank/scan/scatter",
-                 ((m->bits_u > m->bits_i ? m->bits_u : m->bits_i) + 7) / 8, G, V, rm, fast ? "true" : "false", G, V, rm, fast ? "true" : "false", G, V, adam ? 0 : 1);
-    } else if (csort) {
+                 ((m->bits_u > m->bits_i ? m->bits_u : m->bits_i) + 7) / 8, G, V, rm, fast ? "true" : "false", G, V, rm, fast ? "true" : "false", G, V, apply_mode(k));
+    } else if (csort_path(m, B)) {
         snprintf(tmp, sizeof(tmp), "forward=k_front<%d, %d>;sort=k_csort_scan/scatter;reduce_item=k_seg_reduce<%d, %d, %d, false, true, false>;apply=%s",
-                 G, V, G, V, tf1 ? RMODE_SCRATCH : (adam ? RMODE_ADAM : RMODE_SGD), tf1 ? "k_adam_dense" : "k_apply_rows");
+                 G, V, G, V, reduce_mode(k), k.tf1 ? "k_adam_dense" : "k_apply_rows");
     } else {
         snprintf(tmp, sizeof(tmp), "forward=k_forward<%d, %d, 1, 4, false>;sort=k_rsort_rank/scan/scatter;reduce_item=k_seg_reduce<%d, %d, 0, false, true, false>;apply=k_adam_dense<%d, %d>;finalize=k_finalize",
                  G, V, G, V, G, V);
@@ -2399,21 +2462,10 @@ static int shard_forward_reduce_part(tfr_model* m, const float* d_item_rows, flo
     const int32_t* dB = R.counts;                         // the local batch size, on the device
     int rc;
     if ((rc = ensure_capacity(m, B > nI ? B : nI))) return rc;
-    const tfr_opts& o = m->o;
     const OptStep k = opt_step(m);
-    const bool adam = k.adam, tf1 = k.tf1;
     hipStream_t s = m->stream;
     int nblk = (int)((B + 1024 / m->G - 1) / (1024 / m->G));
-    RedArgs r;
-    memset(&r, 0, sizeof(r));
-    r.g = m->d_g; r.err = m->d_err; r.B = B; r.D = m->D; r.dB = dB;
-    r.item_abs = o.item_abs; r.reg_bias = o.reg_bias; r.lam = o.reg;
-    set_hyper(r, k);
     RedPair pr;
-    ApplyArgs ap;
-    memset(&ap, 0, sizeof(ap));
-    ap.err = m->d_err; ap.B = B; ap.D = m->D; ap.dB = dB;
-    set_hyper(ap, k);
     ApplyPair app;
     if (part & 1) {
         // a peer that had to void this step (capacity overflow, id out of range) said so beside its rows: void it here too, before
@@ -2433,35 +2485,31 @@ static int shard_forward_reduce_part(tfr_model* m, const float* d_item_rows, flo
             if ((rc = radix_sort_columns(m, 2, keys, bits, ks, ps, B))) return rc;
             R.fks_u = m->ks_u; R.fps_u = m->ps_u; R.fks_i = m->ks_i; R.fps_i = m->ps_i;
         }
-        RedArgs ri = r;                 // item side: own = the fetched rows, indexed by slot
-        ri.side = 1;
-        ri.ks = R.fks_i; ri.ps = R.fps_i; ri.other = du;
-        ri.own = d_item_rows; ri.ostride = DS; ri.own_bias = d_item_rows + m->D; ri.obstride = DS; ri.partner = m->w[TFR_P];
-        ri.grad_rows = m->gq; ri.grad_bias = m->gbq;
+        RedArgs& ri = pr.a[0];          // item side: own = the fetched rows, indexed by slot
+        ri = rating_side(m, TFR_Q, R.fks_i, R.fps_i, du, B);
+        ri.dB = dB; set_hyper(ri, k);
+        ri.own = d_item_rows; ri.ostride = DS; ri.own_bias = d_item_rows + m->D; ri.obstride = DS;
         // a slot whose samples lie in one block of the sorted order (nearly all) goes straight into the exchange buffer;
         // k_apply_rows then only finishes the slots cut by a block boundary (it emitted every slot before: 102 us)
         ri.dense_rows = d_item_grad; ri.dstride = DS; ri.dense_bias = d_item_grad + m->D; ri.dbstride = DS;
-        ri.partner_bias = m->w[TFR_BU]; ri.mu = m->w[TFR_MU]; ri.r = dr; ri.loss = o.loss;
+        ri.partner_bias = m->w[TFR_BU]; ri.mu = m->w[TFR_MU]; ri.r = dr; ri.loss = m->o.loss;
         ri.g_out = m->d_g; ri.logits_out = d_logits; ri.partials = m->partials; ri.stage_sum = 1;
-        pr.a[0] = ri;
         {
             Prof p(m, TFR_K_REDUCE_ITEM);
             launch_seg_reduce(pr, 1, RMODE_SCRATCH, m->G, m->VEC, s, true);
         }
         HIPCHK(hipGetLastError());
-        app.a[0] = ap;                  // reduced gradient row (+ bias gradient) of the split slots, in the exchange layout
-        app.a[0].only_split = 1;
-        app.a[0].ks = R.fks_i; app.a[0].grad_rows = m->gq; app.a[0].grad_bias = m->gbq;
-        app.a[0].w = d_item_grad; app.a[0].wstride = DS; app.a[0].bias_w = d_item_grad + m->D; app.a[0].wbstride = DS;
+        ApplyArgs& ap = app.a[0];       // reduced gradient row (+ bias gradient) of the split slots, in the exchange layout
+        ap = apply_split(m, TFR_Q, R.fks_i, B);
+        ap.dB = dB; set_hyper(ap, k);
+        ap.w = d_item_grad; ap.wstride = DS; ap.bias_w = d_item_grad + m->D; ap.wbstride = DS;
         {
             Prof p(m, TFR_K_APPLY);
-            launch_apply_rows(app, 1, 2, m->G, m->VEC, s);
+            launch_apply_rows(app, 1, APPLY_EMIT_ROWS, m->G, m->VEC, s);
         }
         HIPCHK(hipGetLastError());
-        FinArgs f;                      // local {loss, reg, sum g}; bias_global waits for the all-reduce
-        memset(&f, 0, sizeof(f));
-        f.partials = m->partials; f.nblk = nblk; f.scalars = m->scalars; f.out = d_scalars4; f.err = m->d_err;
-        f.mu = m->w[TFR_MU];
+        FinArgs f = local_fin(m, d_scalars4);
+        f.nblk = nblk;
         {
             Prof p(m, TFR_K_FINALIZE);
             launch_finalize(f, s);
@@ -2469,38 +2517,30 @@ static int shard_forward_reduce_part(tfr_model* m, const float* d_item_rows, flo
         HIPCHK(hipGetLastError());
     }
     if (part & 2) {
-        RedArgs ru = r;                 // user side: rows are local; partner = fetched item rows
-        ru.side = 0;
         if (!R.fks_u) return fail(TFR_ERR_STATE, "shard_reduce_users: call tfr_shard_forward_items on this routed batch first");
-        ru.ks = R.fks_u; ru.ps = R.fps_u; ru.other = dslot;
-        ru.own = m->w[TFR_P]; ru.partner = d_item_rows; ru.pstride = DS; ru.own_bias = m->w[TFR_BU];
-        bind_side(ru, m, TFR_P);
-        ru.grad_bias = m->gbp; ru.map = tf1 ? m->map_u : nullptr;
-        ru.grad_rows = tf1 ? m->gp : m->gq + (size_t)m->cap * m->D;
-        pr.a[0] = ru;
+        RedArgs& ru = pr.a[0];          // user side: rows are local; partner = fetched item rows
+        ru = rating_side(m, TFR_P, R.fks_u, R.fps_u, dslot, B);
+        ru.dB = dB; set_hyper(ru, k); bind_side(ru, m, TFR_P);
+        ru.partner = d_item_rows; ru.pstride = DS;
+        ru.map = k.tf1 ? m->map_u : nullptr;
         {
             Prof p(m, TFR_K_REDUCE_USER);
-            launch_seg_reduce(pr, 1, tf1 ? RMODE_SCRATCH : (adam ? RMODE_ADAM : RMODE_SGD), m->G, m->VEC, s);
+            launch_seg_reduce(pr, 1, reduce_mode(k), m->G, m->VEC, s);
         }
         HIPCHK(hipGetLastError());
-        if (!tf1) {
-            app.a[0] = ap;
-            app.a[0].only_split = 1;
-            bind_side(app.a[0], m, TFR_P);
-            app.a[0].ks = R.fks_u; app.a[0].grad_rows = ru.grad_rows; app.a[0].grad_bias = m->gbp;
+        if (!k.tf1) {
+            ApplyArgs& ap = app.a[0];
+            ap = apply_split(m, TFR_P, R.fks_u, B);
+            ap.dB = dB; set_hyper(ap, k); bind_side(ap, m, TFR_P);
             Prof p(m, TFR_K_APPLY);
-            launch_apply_rows(app, 1, adam ? 0 : 1, m->G, m->VEC, s);
+            launch_apply_rows(app, 1, apply_mode(k), m->G, m->VEC, s);
         }
         HIPCHK(hipGetLastError());
     }
-    if (tf1 && (part & 2)) {            // dense sweep of the local user rows (every row moves)
+    if (k.tf1 && (part & 2)) {          // dense sweep of the local user rows (every row moves)
         DensePair dp;
         memset(&dp, 0, sizeof(dp));
-        DenseArgs& d = dp.a[0];
-        d.err = m->d_err; d.D = m->D; d.B = B;
-        set_hyper(d, k);
-        bind_side(d, m, TFR_P);
-        d.map = m->map_u; d.ks = R.fks_u; d.grad_rows = m->gp; d.grad_bias = m->gbp;
+        dp.a[0] = dense_side(m, k, TFR_P, R.fks_u, B);
         Prof p(m, TFR_K_APPLY);
         launch_adam_dense(dp, 1, m->G, m->VEC, s);
         HIPCHK(hipGetLastError());
@@ -2532,7 +2572,6 @@ int tfr_shard_apply_items(tfr_model* m, const int32_t* d_req_recv, const float* 
     if ((rc = settle_q(m))) return rc;
     if ((rc = ensure_capacity(m, n > 0 ? n : 1))) return rc;
     const OptStep k = opt_step(m);
-    const bool adam = k.adam, tf1 = k.tf1;
     const int DS = shard_stride(m);
     hipStream_t s = m->stream;
     int32_t* d_nvalid = R.counts + R.world + 2;           // requests actually received (unused slots excluded)
@@ -2552,40 +2591,30 @@ int tfr_shard_apply_items(tfr_model* m, const int32_t* d_req_recv, const float* 
             if ((rc = radix_sort_columns(m, 1, keys, bits, ks, ps, n))) return rc;
         }
         RedPair pr;
-        RedArgs& r = pr.a[0];
-        memset(&r, 0, sizeof(r));
-        r.err = m->d_err; r.B = n; r.D = m->D; r.side = 1; r.dB = d_nvalid;
-        set_hyper(r, k);
-        bind_side(r, m, TFR_Q);
-        r.ks = aks; r.ps = aps; r.rows_in = d_grad_recv; r.rstride = DS; r.bias_in = d_grad_recv + m->D; r.rbstride = DS;
-        r.own = m->w[TFR_Q]; r.own_bias = m->w[TFR_BI];
-        r.grad_rows = m->gq; r.grad_bias = m->gbq; r.map = tf1 ? m->map_i : nullptr;
+        RedArgs& r = pr.a[0];           // the received gradient rows, reduced by item row
+        r = reduce_side(m, TFR_Q, aks, aps, n);
+        r.dB = d_nvalid; set_hyper(r, k); bind_side(r, m, TFR_Q);
+        r.rows_in = d_grad_recv; r.rstride = DS; r.bias_in = d_grad_recv + m->D; r.rbstride = DS;
+        r.map = k.tf1 ? m->map_i : nullptr;
         {
             Prof p(m, TFR_K_REDUCE_ITEM);
-            launch_seg_reduce(pr, 1, tf1 ? RMODE_SCRATCH : (adam ? RMODE_ADAM : RMODE_SGD), m->G, m->VEC, s);
+            launch_seg_reduce(pr, 1, reduce_mode(k), m->G, m->VEC, s);
         }
         HIPCHK(hipGetLastError());
-        if (!tf1) {
+        if (!k.tf1) {
             ApplyPair app;
             ApplyArgs& ap = app.a[0];
-            memset(&ap, 0, sizeof(ap));
-            ap.err = m->d_err; ap.B = n; ap.D = m->D; ap.only_split = 1; ap.dB = d_nvalid;
-            set_hyper(ap, k);
-            bind_side(ap, m, TFR_Q);
-            ap.ks = aks; ap.grad_rows = m->gq; ap.grad_bias = m->gbq;
+            ap = apply_split(m, TFR_Q, aks, n);
+            ap.dB = d_nvalid; set_hyper(ap, k); bind_side(ap, m, TFR_Q);
             Prof p(m, TFR_K_APPLY);
-            launch_apply_rows(app, 1, adam ? 0 : 1, m->G, m->VEC, s);
+            launch_apply_rows(app, 1, apply_mode(k), m->G, m->VEC, s);
         }
         HIPCHK(hipGetLastError());
     }
-    if (tf1) {
+    if (k.tf1) {
         DensePair dp;
         memset(&dp, 0, sizeof(dp));
-        DenseArgs& d = dp.a[0];
-        d.err = m->d_err; d.D = m->D; d.B = n;
-        set_hyper(d, k);
-        bind_side(d, m, TFR_Q);
-        d.map = m->map_i; d.ks = aks; d.grad_rows = m->gq; d.grad_bias = m->gbq;
+        dp.a[0] = dense_side(m, k, TFR_Q, aks, n);
         Prof p(m, TFR_K_APPLY);
         launch_adam_dense(dp, 1, m->G, m->VEC, s);
         HIPCHK(hipGetLastError());
@@ -2670,8 +2699,7 @@ int tfr_dp_local_grads(tfr_model* m, const int32_t* du, const int32_t* di, const
     if (!d_flat || B < 0) return fail(TFR_ERR_ARG, "dp_local_grads: bad arguments");
     if (!d_store_ids && B > 0 && (!du || !di || !dr)) return fail(TFR_ERR_ARG, "dp_local_grads: null batch pointers");
     if (d_store_ids && !m->N) return fail(TFR_ERR_STATE, "no resident triples: call tfr_upload_triples first");
-    const tfr_opts& o = m->o;
-    if (o.optimizer == TFR_OPT_ADAM && o.adam_mode != TFR_ADAM_TF1)
+    if (m->o.optimizer == TFR_OPT_ADAM && !tf1_mode(m))
         return fail(TFR_ERR_STATE, "data-parallel steps need dense semantics: Adam tf1 or SGD");
     int rc;
     if ((rc = settle_q(m))) return rc;
@@ -2686,30 +2714,17 @@ int tfr_dp_local_grads(tfr_model* m, const int32_t* du, const int32_t* di, const
     hipStream_t s = m->stream;
     int nblk = 0;
     bool fin_done = false;
-    FinArgs f;                         // local {loss, reg, sum g} -> tail of the flat buffer; no mu update yet
-    memset(&f, 0, sizeof(f));
-    f.partials = m->partials; f.scalars = m->scalars; f.out = tail; f.err = m->d_err;
-    f.mu = m->w[TFR_MU];
+    FinArgs f = local_fin(m, tail);    // local {loss, reg, sum g} -> tail of the flat buffer; no mu update yet
     if (B > 0 && tiles_eligible(m, B)) {
         // small tables: k_tile_step (look-ahead sort of the hinted next batch included), then one sweep that
         // writes every touched row's gradient into the flat buffer and reduces the local scalars (K4 without
         // the mu update)
-        float* gp_rows = m->gp ? m->gp : m->gq + (size_t)m->cap * m->D;
         int par = 0;
-        if ((rc = tile_step_launch(m, du, di, dr, B, nullptr, d_store_ids, next_ids, gp_rows, &par, &nblk))) return rc;
+        if ((rc = tile_step_launch(m, du, di, dr, B, nullptr, d_store_ids, next_ids, &par, &nblk))) return rc;
         f.nblk = nblk;
-        TileDenseLaunch L;
-        memset(&L, 0, sizeof(L));
-        TileDenseArgs d;
-        memset(&d, 0, sizeof(d));
-        d.err = m->d_err; d.D = m->D; d.ntiles = (int32_t)((B + CSORT_TILE - 1) / CSORT_TILE);
-        L.a[0] = d;
-        L.a[0].tab = par ? m->offs_i : m->hist_i; L.a[0].nbins = 1 << m->bits_i; L.a[0].rows = m->I;
-        L.a[0].grad_rows = m->gq; L.a[0].grad_bias = m->gbq; L.a[0].out_rows = gQ; L.a[0].out_bias = gbi;
-        L.a[1] = d;
-        L.a[1].tab = par ? m->offs_u : m->hist_u; L.a[1].nbins = 1 << m->bits_u; L.a[1].rows = m->U;
-        L.a[1].grad_rows = gp_rows; L.a[1].grad_bias = m->gbp; L.a[1].out_rows = gP; L.a[1].out_bias = gbu;
-        L.f = f;
+        TileDenseLaunch L = tile_dense(m, B, par, f);
+        L.a[0].out_rows = gQ; L.a[0].out_bias = gbi;
+        L.a[1].out_rows = gP; L.a[1].out_bias = gbu;
         {
             Prof p(m, TFR_K_APPLY);
             launch_dense_tiles(L, true, true, m->G, m->VEC, s);
@@ -2718,20 +2733,10 @@ int tfr_dp_local_grads(tfr_model* m, const int32_t* du, const int32_t* di, const
         fin_done = true;
     } else if (B > 0) {
         if ((rc = front_and_sort(m, du, di, dr, B, nullptr, d_store_ids, f, nblk, fin_done))) return rc;
-        RedArgs r;
-        memset(&r, 0, sizeof(r));
-        r.g = m->d_g; r.err = m->d_err; r.B = B; r.D = m->D;
-        r.item_abs = o.item_abs; r.reg_bias = o.reg_bias; r.lam = o.reg;
-        RedPair pr;
-        pr.a[0] = r;                   // whole runs go straight to their row of the flat buffer
-        pr.a[0].side = 1; pr.a[0].ks = m->ks_i; pr.a[0].ps = m->ps_i; pr.a[0].other = du;
-        pr.a[0].own = m->w[TFR_Q]; pr.a[0].partner = m->w[TFR_P]; pr.a[0].own_bias = m->w[TFR_BI];
-        pr.a[0].grad_rows = m->gq; pr.a[0].grad_bias = m->gbq;
+        RedPair pr;                    // whole runs go straight to their row of the flat buffer
+        pr.a[0] = rating_side(m, TFR_Q, m->ks_i, m->ps_i, du, B);
         pr.a[0].dense_rows = gQ; pr.a[0].dense_bias = gbi;
-        pr.a[1] = r;
-        pr.a[1].side = 0; pr.a[1].ks = m->ks_u; pr.a[1].ps = m->ps_u; pr.a[1].other = di;
-        pr.a[1].own = m->w[TFR_P]; pr.a[1].partner = m->w[TFR_Q]; pr.a[1].own_bias = m->w[TFR_BU];
-        pr.a[1].grad_rows = m->gp ? m->gp : m->gq + (size_t)m->cap * m->D; pr.a[1].grad_bias = m->gbp;
+        pr.a[1] = rating_side(m, TFR_P, m->ks_u, m->ps_u, di, B);
         pr.a[1].dense_rows = gP; pr.a[1].dense_bias = gbu;
         {
             Prof p(m, TFR_K_REDUCE_ITEM);
@@ -2740,15 +2745,13 @@ int tfr_dp_local_grads(tfr_model* m, const int32_t* du, const int32_t* di, const
         HIPCHK(hipGetLastError());
         ApplyPair app;                 // runs split over several reduce blocks: add their pieces, emit the row
         memset(&app, 0, sizeof(app));
-        app.a[0].err = m->d_err; app.a[0].B = B; app.a[0].D = m->D; app.a[0].only_split = 1;
-        app.a[0].ks = m->ks_i; app.a[0].grad_rows = m->gq; app.a[0].grad_bias = m->gbq;
+        app.a[0] = apply_split(m, TFR_Q, m->ks_i, B);
         app.a[0].w = gQ; app.a[0].bias_w = gbi;
-        app.a[1] = app.a[0];
-        app.a[1].ks = m->ks_u; app.a[1].grad_rows = pr.a[1].grad_rows; app.a[1].grad_bias = m->gbp;
+        app.a[1] = apply_split(m, TFR_P, m->ks_u, B);
         app.a[1].w = gP; app.a[1].bias_w = gbu;
         {
             Prof p(m, TFR_K_APPLY);
-            launch_apply_rows(app, 2, 2, m->G, m->VEC, s);
+            launch_apply_rows(app, 2, APPLY_EMIT_ROWS, m->G, m->VEC, s);
         }
         HIPCHK(hipGetLastError());
     }
@@ -2774,15 +2777,9 @@ int tfr_dp_apply(tfr_model* m, float* d_flat) {
     float* tail = gbi + m->I;
     DensePair dp;
     memset(&dp, 0, sizeof(dp));
-    DenseArgs d;
-    memset(&d, 0, sizeof(d));
-    d.err = m->d_err; d.D = m->D; d.opt = k.adam ? 0 : 1;
-    set_hyper(d, k);
-    dp.a[0] = d;
-    bind_side(dp.a[0], m, TFR_P);
+    dp.a[0] = dense_side(m, k, TFR_P);
     dp.a[0].dense_grad = gP; dp.a[0].dense_gbias = gbu;
-    dp.a[1] = d;
-    bind_side(dp.a[1], m, TFR_Q);
+    dp.a[1] = dense_side(m, k, TFR_Q);
     dp.a[1].dense_grad = gQ; dp.a[1].dense_gbias = gbi;
     FinArgs f = mu_fin(m, k, !((m->frozen >> TFR_MU) & 1), nullptr);   // bias_global from the all-reduced {loss, reg, sum g}
     f.partials = tail; f.nblk = 1;                                       // rides in the sweep
@@ -2902,28 +2899,22 @@ static int fm_train_core(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_in
         }
         RedPair pr;
         RedArgs& r = pr.a[0];
-        memset(&r, 0, sizeof(r));
-        r.err = m->d_err; r.B = nnz; r.D = m->D; r.side = 0; r.reg_bias = 1; r.lam = o.reg;
-        set_hyper(r, k);
-        bind_side(r, m, TFR_P);          // V and W: the wrapped model's user side (its frozen mask stays 0)
-        r.ks = m->ks_u; r.ps = m->ps_u; r.ent = f->ent;
-        r.own = m->w[TFR_P]; r.partner = f->s_rows; r.own_bias = m->w[TFR_BU];
-        r.grad_rows = m->gq + (size_t)m->cap * m->D; r.grad_bias = m->gbp;
+        r = reduce_side(m, TFR_P, m->ks_u, m->ps_u, nnz);   // V and W: the wrapped model's user side (its frozen mask stays 0)
+        r.reg_bias = 1; r.lam = o.reg;
+        set_hyper(r, k); bind_side(r, m, TFR_P);
+        r.ent = f->ent; r.partner = f->s_rows;
         {
             Prof p(m, TFR_K_REDUCE_USER);
-            launch_seg_reduce(pr, 1, adam ? RMODE_ADAM : RMODE_SGD, m->G, m->VEC, s);
+            launch_seg_reduce(pr, 1, reduce_mode(k), m->G, m->VEC, s);
         }
         HIPCHK(hipGetLastError());
         ApplyPair app;
         ApplyArgs& ap = app.a[0];
-        memset(&ap, 0, sizeof(ap));
-        ap.err = m->d_err; ap.B = nnz; ap.D = m->D; ap.only_split = 1;
-        set_hyper(ap, k);
-        bind_side(ap, m, TFR_P);
-        ap.ks = m->ks_u; ap.grad_rows = r.grad_rows; ap.grad_bias = m->gbp;
+        ap = apply_split(m, TFR_P, m->ks_u, nnz);
+        set_hyper(ap, k); bind_side(ap, m, TFR_P);
         {
             Prof p(m, TFR_K_APPLY);
-            launch_apply_rows(app, 1, adam ? 0 : 1, m->G, m->VEC, s);
+            launch_apply_rows(app, 1, apply_mode(k), m->G, m->VEC, s);
         }
         HIPCHK(hipGetLastError());
     }
