@@ -13,12 +13,14 @@ import pytest
 import tfrecomm_amd as T
 from tfrecomm_amd import _lib as L
 from tests import bpr_ref as R
+from tests import widths as W
 
 pytestmark = pytest.mark.gpu
 
 # k_bpr_users / k_bpr_items are templated on NJ = ceil(D / 64) registers per lane, f = lane + 64 j guarded by f < D
-# (csrc/bpr.hip bpr_nj): one width per (NJ, last register full or partial), and D = 1.
-WIDTHS = (1, 33, 64, 100, 128, 132, 192, 252, 256)
+# (csrc/bpr.hip bpr_nj): one width per (NJ, last register full or partial), and D = 1 - widths.BPR, which
+# tests/test_width_coverage.py holds against that rule.
+WIDTHS = W.BPR
 
 
 def registers(D):

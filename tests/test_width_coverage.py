@@ -26,9 +26,17 @@ def geometry(D):
     return g, vec
 
 
+def shard_class(D):
+    """(G, VEC, full width): k_gather_packed<G, VEC> takes unguarded non-temporal 16-byte loads where D == G * VEC and
+    guarded ones elsewhere (csrc/shard.hip); the sharded reduce takes its three-round load form at full width (csrc/api.hip
+    launch_seg_reduce)"""
+    g, vec = geometry(D)
+    return g, vec, D == g * vec
+
+
 def registers(D):
     """(NJ, last register full): NJ = ceil(D / 64) features per lane, f = lane + 64 j guarded by f < D
-    (csrc/svdpp.hip pp_nj, csrc/finetune.hip launch_finetune)"""
+    (csrc/svdpp.hip pp_nj, csrc/finetune.hip launch_finetune, csrc/bpr.hip bpr_nj)"""
     return -(-D // 64), D % 64 == 0
 
 
@@ -65,12 +73,32 @@ def test_there_are_ten_row_geometries():
     assert len({tile(D) for D in SUPPORTED}) == 10
 
 
-@pytest.mark.parametrize("name", ["SVD_SMALL", "SVD_BIG", "FM"])
+@pytest.mark.parametrize("name", ["SVD_SMALL", "SVD_BIG", "FM", "DP"])
 def test_every_row_geometry(name):
     _check(name, geometry, getattr(W, name), {geometry(D) for D in SUPPORTED})
 
 
-@pytest.mark.parametrize("name", ["SVDPP", "FINETUNE"])
+def test_sharded_stages_reach_every_geometry_at_full_and_partial_width():
+    reachable = {shard_class(D) for D in SUPPORTED}
+    assert len(reachable) == 15 and not any(full for _, vec, full in reachable if vec == 1)
+    _check("SHARD", shard_class, W.SHARD, reachable)
+
+
+def test_the_gpu_tests_take_their_widths_from_these_lists():
+    """a width list only guards what runs at it: the BPR, sharded and data-parallel GPU tests parametrise over these"""
+    import ast
+    import os
+    here = os.path.dirname(os.path.abspath(__file__))
+    for fname, name in (("test_gpu_bpr.py", "BPR"), ("shard_cases.py", "SHARD"), ("shard_cases.py", "DP")):
+        tree = ast.parse(open(os.path.join(here, fname)).read())
+        used = {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == "W"}
+        assert name in used, "%s does not read widths.%s" % (fname, name)
+    from tests import test_gpu_bpr
+    assert test_gpu_bpr.WIDTHS is W.BPR, "test_gpu_bpr.py keeps a private WIDTHS list"
+    assert set(W.BPR) >= {1, 33, 64, 100, 128, 132, 192, 252, 256}, "BPR: the widths the BPR tests ran at must not shrink"
+
+
+@pytest.mark.parametrize("name", ["SVDPP", "FINETUNE", "BPR"])
 def test_every_register_count_full_and_partial(name):
     _check(name, registers, getattr(W, name), {registers(D) for D in SUPPORTED})
 

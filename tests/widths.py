@@ -10,9 +10,17 @@ SVD_SMALL = (2, 5, 15, 16, 25, 28, 61, 64, 128, 200)       # small tables: k_til
 SVD_BIG = (3, 7, 9, 12, 31, 32, 33, 36, 100, 252)          # a side above CSORT_MAX_BINS rows: radix sort, k_seg_reduce, ...
 FM = (2, 6, 13, 8, 25, 28, 61, 44, 100, 200)
 
+# the row-sharded step's stages (tests/test_gpu_shard_stages.py): (G, VEC) crossed with full width D == G * VEC, which picks
+# k_gather_packed's unguarded non-temporal loads and the reduce's three-round load form.  A VEC = 1 row is never full width
+# (D == G would be a multiple of four), so there are fifteen classes
+SHARD = (12, 16, 28, 32, 36, 64, 100, 128, 252, 256, 3, 7, 13, 31, 61)
+# the data-parallel stages (tests/test_gpu_dp_stages.py), on the tile path and on the sort path: one width per (G, VEC)
+DP = (8, 24, 48, 96, 200, 2, 6, 11, 25, 50)
+
 # SVD++ kernels and batched fine-tuning: NJ = ceil(D / 64) registers per lane, the last one full or partial
 SVDPP = (33, 64, 100, 128, 132, 192, 252, 256)
 FINETUNE = (20, 64, 68, 128, 132, 192, 252, 256)
+BPR = (1, 33, 64, 100, 128, 132, 192, 252, 256)            # k_bpr_users / k_bpr_items (csrc/bpr.hip bpr_nj), and D = 1
 FINETUNE_STREAMED = (20, 100, 132, 252)                    # one call stages some users and streams others, each NJ
 
 # top-K and rank: V4 = (D % 4 == 0) crossed with where mfma_tile_dot's last group of four float4s ends

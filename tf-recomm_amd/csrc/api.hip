@@ -2472,6 +2472,10 @@ static int shard_forward_reduce_part(tfr_model* m, const float* d_item_rows, flo
         // anything is updated - every rank then skips the same step and reports it at its next sync
         launch_adopt_peer_err(d_item_rows, (int64_t)(nI / R.world) * DS, R.world, m->D, m->d_err, s);
         HIPCHK(hipGetLastError());
+        // the reduce writes the features and the bias of the slots in use and nothing else: the rest of the buffer goes to the
+        // owners as zeros (they skip slots they were not asked for, but the wire carries no stale or uninitialised rows)
+        launch_clear_grad_slots(d_item_grad, R.counts + 2, R.world, (int32_t)(nI / R.world), m->D, DS, s);
+        HIPCHK(hipGetLastError());
         // K1 runs inside the item-side reduce, on the rows it has in registers anyway (as in the single-GPU big-table step);
         // a separate k_forward launch cost 68 us of the 464 (world-1 rehearsal)
         if (R.sorted_fwd) {             // tfr_shard_presort made the sorted orders ahead of time

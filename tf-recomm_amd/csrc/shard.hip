@@ -312,6 +312,27 @@ void launch_adopt_peer_err(const float* rows, int64_t chunk_floats, int32_t worl
     hipLaunchKernelGGL(k_adopt_peer_err, dim3(1), dim3(64), 0, s, rows, chunk_floats, world, D, err);
 }
 
+// requester side: the words of the gradient exchange buffer that the item-side reduce never writes.  Chunk w holds used[w]
+// slots in use at its front: the rows behind them, and the words behind the bias of every row, go out as zeros and not as
+// whatever the buffer held (an earlier step's gradient of a slot no longer in use, or uninitialised memory).
+__global__ __launch_bounds__(256) void k_clear_grad_slots(float* grad, const int32_t* used, int32_t cap, int32_t D, int32_t stride) {
+    const int w = blockIdx.y;
+    int n = used[w];
+    n = n < 0 ? 0 : (n > cap ? cap : n);                 // a step that overflowed the capacity is void; stay inside the chunk
+    float* chunk = grad + (size_t)w * cap * stride;
+    const int64_t t0 = (int64_t)blockIdx.x * 256 + threadIdx.x, dt = (int64_t)gridDim.x * 256;
+    const int pad = stride - D - 1;
+    for (int64_t k = t0; k < (int64_t)n * pad; k += dt) chunk[(size_t)(k / pad) * stride + D + 1 + (k % pad)] = 0.f;
+    for (int64_t k = (int64_t)n * stride + t0; k < (int64_t)cap * stride; k += dt) chunk[k] = 0.f;
+}
+
+void launch_clear_grad_slots(float* grad, const int32_t* used, int32_t world, int32_t cap, int32_t D, int32_t stride, hipStream_t s) {
+    int64_t nb = ((int64_t)cap * stride / 4 + 255) / 256;        // four words per thread where a whole chunk is unused
+    if (nb > 1024) nb = 1024;
+    if (nb < 1) nb = 1;
+    hipLaunchKernelGGL(k_clear_grad_slots, dim3((int)nb, world), dim3(256), 0, s, grad, used, cap, D, stride);
+}
+
 void launch_gather_packed(const GatherPackedArgs& a, int G, int VEC, hipStream_t s) {
     const int gpb = 4 * (256 / G);                       // UN requests per lane group and round
     int64_t nb = (a.n + gpb - 1) / gpb;

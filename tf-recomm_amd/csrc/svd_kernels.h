@@ -314,6 +314,9 @@ struct GatherPackedArgs {
 void launch_gather_packed(const GatherPackedArgs& a, int G, int VEC, hipStream_t s);
 // the error flags the owners packed beside their rows (float D + 1 of a row; one chunk of `chunk_floats` per owner) -> err |= 8
 void launch_adopt_peer_err(const float* rows, int64_t chunk_floats, int32_t world, int32_t D, int32_t* err, hipStream_t s);
+// zeroes what the item-side reduce leaves unwritten in the gradient exchange buffer [world][cap] x stride: the rows behind the
+// used[w] slots in use of chunk w, and the words behind the bias of every row
+void launch_clear_grad_slots(float* grad, const int32_t* used, int32_t world, int32_t cap, int32_t D, int32_t stride, hipStream_t s);
 // pads (-1) of a received request list -> `pad_key` (one past the last row, sorts last); counts the real ones
 void launch_pad_keys(const int32_t* ids_in, int32_t* keys_out, int64_t n, int32_t pad_key, int32_t* count, hipStream_t s);
 

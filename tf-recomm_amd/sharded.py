@@ -159,10 +159,10 @@ class HipShard(object):
         if cur is not None:
             cur.wait_stream(self._mstream)
 
-    def _get(self, name, shape, dtype):
+    def _get(self, name, shape, dtype, zero=False):
         t = self._buf.get(name)
         if t is None or tuple(t.shape) != tuple(shape):
-            t = torch.empty(shape, dtype=dtype, device=self.device)
+            t = (torch.zeros if zero else torch.empty)(shape, dtype=dtype, device=self.device)
             self._buf[name] = t
         return t
 
@@ -246,7 +246,7 @@ class HipShard(object):
         cap, _ = self._routed
         grad = self._get("grad", tuple(item_rows.shape), torch.float32)
         logits = self._get("logits", (cap,), torch.float32)
-        scal = self._get("scal", (4,), torch.float32)
+        scal = self._get("scal", (4,), torch.float32, zero=True)     # the kernels write {loss, reg, sum g}; the fourth word stays 0
         self._sync_in()
         self.model.shard_forward_reduce(item_rows.data_ptr(), logits.data_ptr(), grad.data_ptr(), scal.data_ptr())
         self._sync_out()
@@ -257,7 +257,7 @@ class HipShard(object):
         cap, _ = self._routed
         grad = self._get("grad", tuple(item_rows.shape), torch.float32)
         logits = self._get("logits", (cap,), torch.float32)
-        scal = self._get("scal", (4,), torch.float32)
+        scal = self._get("scal", (4,), torch.float32, zero=True)     # the kernels write {loss, reg, sum g}; the fourth word stays 0
         self._sync_in()
         self.model.shard_forward_items(item_rows.data_ptr(), logits.data_ptr(), grad.data_ptr(), scal.data_ptr())
         self._sync_out()
