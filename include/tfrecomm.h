@@ -305,6 +305,10 @@ int tfr_fm_destroy(tfr_fm* m);
 int tfr_fm_set(tfr_fm* m, float mu, const float* W, const float* V);          /* host pointers */
 int tfr_fm_get(tfr_fm* m, float* mu, float* W, float* V);                      /* any may be NULL */
 int tfr_fm_init(tfr_fm* m, uint64_t seed, float stddev);                       /* random W, V on device */
+/* One table or Adam slot of the FM model: which = TFR_MU, TFR_BU (= W) or TFR_P (= V), optionally or-ed with TFR_SLOT_M /
+ * TFR_SLOT_V; n = its element count.  TFR_BI / TFR_Q: TFR_ERR_ARG.  tfr_fm_get_step: as tfr_get_step. */
+int tfr_fm_get_table(tfr_fm* m, int32_t which, float* host, int64_t n);
+int tfr_fm_get_step(tfr_fm* m, int64_t* step, float* beta1_power, float* beta2_power);
 int tfr_fm_forward(tfr_fm* m, const int64_t* indptr, const int32_t* indices, const float* data,
                    int64_t n_rows, float* out);                                /* host CSR, synchronous */
 int tfr_fm_forward_dev(tfr_fm* m, const int64_t* d_indptr, const int32_t* d_indices,

@@ -215,52 +215,58 @@ def check_step(before, after, u, i, r, *, opt, mode, loss, item_abs, reg_bias, l
     alpha = alpha_f32(lr, *powers) if adam else 0.0
     for name in NAMES:
         G, E, n = ref[name]
-        b, a = before[name], after[name]
-        if name == "mu":                                  # the scalar as a table of one row
-            G, E, n = (np.reshape(x, (1,)) for x in (G, E, n))
-            b, a = ({k: np.reshape(np.asarray(x, np.float32), (1,)) for k, x in d.items()} for d in (b, a))
-            f32[name] = np.reshape(f32[name], (1,))
-        if frozen >> TID[name] & 1:
-            for slot in b:
-                if not same_bits(b[slot], a[slot]):
-                    bad.append("%s.%s: a frozen table changed" % (name, slot))
-            continue
-        touched = np.broadcast_to(np.asarray(n) > 0, np.shape(G))
-        # -- gradient
-        if adam:
-            g, extra = grad_from_fresh_adam(a["m"]) if fresh else grad_from_adam(a["m"], b["m"])
-        else:
-            g, extra = grad_from_sgd(b["w"], a["w"], lr)
-        if not tf1 and name != "mu":
-            extra = np.where(touched, extra, 0.0)        # lazy Adam, SGD: an untouched row is held to identical bits below
-        srows = rows.get(name) if rows else None
-        c_ref = ratio(f32[name], G, E, n, srows)
-        lim = limit_from(c_ref)
-        got = ratio(g, G, E + extra, n)
-        if report is not None:
-            report[name] = dict(c_ref=c_ref, dev=got)
-        for cls in ("short", "long"):
-            if not got[cls] <= lim[cls]:
-                bad.append("%s gradient, %s runs: %.1f x eps32 x E, limit %.1f (float32 oracle %.1f)"
-                           % (name, cls, got[cls], lim[cls], c_ref[cls]))
-        # -- moments and apply, against the device's own numbers
-        if adam:
-            # lazy Adam moves the touched rows only (the others are held to identical bits below); TF1 and bias_global: all
-            act = touched if (not tf1 and name != "mu") else np.ones(np.shape(G), bool)
-            dg = 0.0 if fresh else (EPS32 * extra)[act]
-            ex = moments_excess(b["v"][act], a["v"][act], g[act], dg)
-            if not ex <= 1:
-                bad.append("%s: v does not follow from g and the previous v (%.2f x its allowance)" % (name, ex))
-            ex = apply_excess(b["w"][act], a["w"][act], a["m"][act], a["v"][act], alpha)
-            if not ex <= 1:
-                bad.append("%s: w does not follow from m and v (%.2f x its allowance)" % (name, ex))
-        # -- rows the batch did not touch
-        if name != "mu" and not touched.all():
-            still = ~touched
-            if not tf1 or fresh:                          # TF1 with all-zero moments: the dense sweep moves nothing
-                for slot in b:
-                    if not same_bits(b[slot][still], a[slot][still]):
-                        bad.append("%s.%s: rows outside the batch changed" % (name, slot))
-            elif not same_bits(a["m"][still], (b["m"][still].astype(np.float64) * float(B1F)).astype(np.float32)):
-                bad.append("%s.m: rows outside the batch did not decay by b1" % name)
+        check_table(bad, name, G, E, n, before[name], after[name], f32[name], adam=adam, tf1=tf1, fresh=fresh, lr=lr,
+                    alpha=alpha, frozen=frozen >> TID[name] & 1, srows=rows.get(name) if rows else None, report=report)
     return bad
+
+
+def check_table(bad, name, G, E, n, b, a, f32g, *, adam, tf1, fresh, lr, alpha, frozen=0, srows=None, report=None):
+    """The statements about one table (``check_step``'s loop body; tests/fm_ref.py states the FM tables with it): ``G, E, n``
+    as ``step_grads`` returns them, ``b`` / ``a`` the table's dict(w=, m=, v=) before and after, ``f32g`` the float32
+    oracle's gradient.  "mu" is the scalar, judged as a table of one row.  Appends the violated statements to ``bad``."""
+    if name == "mu":                                  # the scalar as a table of one row
+        G, E, n = (np.reshape(x, (1,)) for x in (G, E, n))
+        b, a = ({k: np.reshape(np.asarray(x, np.float32), (1,)) for k, x in d.items()} for d in (b, a))
+        f32g = np.reshape(f32g, (1,))
+    if frozen:
+        for slot in b:
+            if not same_bits(b[slot], a[slot]):
+                bad.append("%s.%s: a frozen table changed" % (name, slot))
+        return
+    touched = np.broadcast_to(np.asarray(n) > 0, np.shape(G))
+    # -- gradient
+    if adam:
+        g, extra = grad_from_fresh_adam(a["m"]) if fresh else grad_from_adam(a["m"], b["m"])
+    else:
+        g, extra = grad_from_sgd(b["w"], a["w"], lr)
+    if not tf1 and name != "mu":
+        extra = np.where(touched, extra, 0.0)        # lazy Adam, SGD: an untouched row is held to identical bits below
+    c_ref = ratio(f32g, G, E, n, srows)
+    lim = limit_from(c_ref)
+    got = ratio(g, G, E + extra, n)
+    if report is not None:
+        report[name] = dict(c_ref=c_ref, dev=got)
+    for cls in ("short", "long"):
+        if not got[cls] <= lim[cls]:
+            bad.append("%s gradient, %s runs: %.1f x eps32 x E, limit %.1f (float32 oracle %.1f)"
+                       % (name, cls, got[cls], lim[cls], c_ref[cls]))
+    # -- moments and apply, against the device's own numbers
+    if adam:
+        # lazy Adam moves the touched rows only (the others are held to identical bits below); TF1 and bias_global: all
+        act = touched if (not tf1 and name != "mu") else np.ones(np.shape(G), bool)
+        dg = 0.0 if fresh else (EPS32 * extra)[act]
+        ex = moments_excess(b["v"][act], a["v"][act], g[act], dg)
+        if not ex <= 1:
+            bad.append("%s: v does not follow from g and the previous v (%.2f x its allowance)" % (name, ex))
+        ex = apply_excess(b["w"][act], a["w"][act], a["m"][act], a["v"][act], alpha)
+        if not ex <= 1:
+            bad.append("%s: w does not follow from m and v (%.2f x its allowance)" % (name, ex))
+    # -- rows the batch did not touch
+    if name != "mu" and not touched.all():
+        still = ~touched
+        if not tf1 or fresh:                          # TF1 with all-zero moments: the dense sweep moves nothing
+            for slot in b:
+                if not same_bits(b[slot][still], a[slot][still]):
+                    bad.append("%s.%s: rows outside the batch changed" % (name, slot))
+        elif not same_bits(a["m"][still], (b["m"][still].astype(np.float64) * float(B1F)).astype(np.float32)):
+            bad.append("%s.m: rows outside the batch did not decay by b1" % name)

@@ -84,15 +84,30 @@ def test_sharded_stages_reach_every_geometry_at_full_and_partial_width():
     _check("SHARD", shard_class, W.SHARD, reachable)
 
 
+def test_fm_step_reaches_every_geometry_at_full_and_partial_width():
+    """k_fm_forward<G, VEC, ...> branches on D == G * VEC (csrc/fm_kernels.hip `full`), and launch_seg_reduce gives the FM
+    backward its three-round load form at full width only: the classes of ``shard_class``"""
+    reachable = {shard_class(D) for D in SUPPORTED}
+    assert len(reachable) == 15
+    _check("FM_STEP", shard_class, W.FM_STEP, reachable)
+
+
 def test_the_gpu_tests_take_their_widths_from_these_lists():
-    """a width list only guards what runs at it: the BPR, sharded and data-parallel GPU tests parametrise over these"""
+    """a width list only guards what runs at it: the BPR, sharded, data-parallel and FM step GPU tests parametrise over these"""
     import ast
     import os
     here = os.path.dirname(os.path.abspath(__file__))
-    for fname, name in (("test_gpu_bpr.py", "BPR"), ("shard_cases.py", "SHARD"), ("shard_cases.py", "DP")):
+    for fname, name in (("test_gpu_bpr.py", "BPR"), ("shard_cases.py", "SHARD"), ("shard_cases.py", "DP"),
+                        ("fm_cases.py", "FM_STEP"), ("test_gpu_fm.py", "FM_STEP")):
         tree = ast.parse(open(os.path.join(here, fname)).read())
         used = {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == "W"}
         assert name in used, "%s does not read widths.%s" % (fname, name)
+    # test_gpu_fm_step.py runs the case list of fm_cases.py, whole
+    tree = ast.parse(open(os.path.join(here, "test_gpu_fm_step.py")).read())
+    used = {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == "C"}
+    assert "CASES" in used, "test_gpu_fm_step.py does not run fm_cases.CASES"
+    from tests import fm_cases
+    assert {c["D"] for c in fm_cases.CASES if c["kind"] == "edges"} >= set(W.FM_STEP)
     from tests import test_gpu_bpr
     assert test_gpu_bpr.WIDTHS is W.BPR, "test_gpu_bpr.py keeps a private WIDTHS list"
     assert set(W.BPR) >= {1, 33, 64, 100, 128, 132, 192, 252, 256}, "BPR: the widths the BPR tests ran at must not shrink"

@@ -16,6 +16,9 @@ FM = (2, 6, 13, 8, 25, 28, 61, 44, 100, 200)
 SHARD = (12, 16, 28, 32, 36, 64, 100, 128, 252, 256, 3, 7, 13, 31, 61)
 # the data-parallel stages (tests/test_gpu_dp_stages.py), on the tile path and on the sort path: one width per (G, VEC)
 DP = (8, 24, 48, 96, 200, 2, 6, 11, 25, 50)
+# the FM step per row (tests/test_gpu_fm_step.py) and the FM forward's load forms: the same fifteen classes - k_fm_forward
+# takes unguarded loads at full width, and the FM backward the reduce's three-round load form
+FM_STEP = (12, 16, 28, 32, 36, 64, 100, 128, 252, 256, 3, 7, 13, 31, 61)
 
 # SVD++ kernels and batched fine-tuning: NJ = ceil(D / 64) registers per lane, the last one full or partial
 SVDPP = (33, 64, 100, 128, 132, 192, 252, 256)

@@ -117,6 +117,8 @@ SIGNATURES = {
     "tfr_fm_destroy": (C.c_int, [_p]),
     "tfr_fm_set": (C.c_int, [_p, C.c_float, _f32p, _f32p]),
     "tfr_fm_get": (C.c_int, [_p, _f32p, _f32p, _f32p]),
+    "tfr_fm_get_table": (C.c_int, [_p, C.c_int32, _f32p, C.c_int64]),
+    "tfr_fm_get_step": (C.c_int, [_p, _i64p, _f32p, _f32p]),
     "tfr_fm_train_step": (C.c_int, [_p, _i64p, _i32p, _f32p, _f32p, C.c_int64, _f32p, _f32p]),
     "tfr_fm_train_step_dev": (C.c_int, [_p, _p, _p, _p, _p, C.c_int64, C.c_int64, _p]),
     "tfr_fm_init": (C.c_int, [_p, C.c_uint64, C.c_float]),

@@ -2996,6 +2996,19 @@ int tfr_fm_get(tfr_fm* f, float* mu, float* W, float* V) {
     return rc;
 }
 
+// V, W, mu and their Adam slots are the wrapped model's user side; its item side is a one-row stub and not part of the FM model
+int tfr_fm_get_table(tfr_fm* f, int32_t which, float* host, int64_t n) {
+    if (!f) return fail(TFR_ERR_ARG, "null model");
+    const int t = which & 7;
+    if (t != TFR_MU && t != TFR_BU && t != TFR_P) return fail(TFR_ERR_ARG, "bad FM table id %d (TFR_MU, TFR_BU = W, TFR_P = V)", which);
+    return tfr_get_table(f->m, which, host, n);
+}
+
+int tfr_fm_get_step(tfr_fm* f, int64_t* step, float* b1p, float* b2p) {
+    if (!f) return fail(TFR_ERR_ARG, "null model");
+    return tfr_get_step(f->m, step, b1p, b2p);
+}
+
 int tfr_fm_init(tfr_fm* f, uint64_t seed, float stddev) {
     if (!f) return fail(TFR_ERR_ARG, "null model");
     tfr_model* m = f->m;

@@ -59,6 +59,20 @@ class FmModel(object):
         self._check(self._lib.tfr_fm_get(self._h, L.ptr_f32(mu), L.ptr_f32(W), L.ptr_f32(V)))
         return float(mu[0]), W, V.reshape(self.n_features, self.dim)
 
+    def get_table(self, which):
+        """one table or Adam slot: ``which`` = MU, BU (= W) or P (= V) of ``_lib``, optionally | SLOT_M / SLOT_V"""
+        t = which & 7
+        shape = {L.MU: (), L.BU: (self.n_features,), L.P: (self.n_features, self.dim)}.get(t, (0,))
+        out = np.empty(int(np.prod(shape, dtype=np.int64)), np.float32)
+        self._check(self._lib.tfr_fm_get_table(self._h, int(which), L.ptr_f32(out), out.size))
+        return out.reshape(shape)
+
+    def get_step(self):
+        """(steps taken, beta1^t, beta2^t) as the next step will use them"""
+        s, a, b = C.c_int64(), C.c_float(), C.c_float()
+        self._check(self._lib.tfr_fm_get_step(self._h, C.byref(s), C.byref(a), C.byref(b)))
+        return s.value, a.value, b.value
+
     def train_step(self, x, y):
         """One minibatch of SGD / lazy-Adam training on CSR rows ``x`` with targets ``y``.
         Returns (predictions before the update, data loss)."""
