@@ -327,6 +327,36 @@ int tfr_fm_train_step_dev(tfr_fm* m, const int64_t* d_indptr, const int32_t* d_i
 int tfr_fm_sync(tfr_fm* m, float* last_kernel_ms);
 const char* tfr_fm_last_error(void);
 
+/* ---- FM trainer: resident rows, minibatches gathered on the device, metrics (fm.py:113-131 without host data in the loop)
+ *      tfr_fm_upload_rows copies a host CSR (scipy layout) and its targets once into buffers the handle owns; which = 0 is
+ *      the train store, 1 the eval store; a second upload replaces the first.  Checked on the host before any device work:
+ *      indptr starts at 0 and is non-decreasing (TFR_ERR_ARG), feature ids lie in [0, n_features) (TFR_ERR_OOB).  The call
+ *      synchronises.  The handle keeps the row lengths on the host: a step's radix sort and segmented reduce are launched
+ *      with a host-side nnz, which is then a sum over the step's ids and not a read-back. */
+int tfr_fm_upload_rows(tfr_fm* m, int32_t which, const int64_t* indptr, const int32_t* indices, const float* data,
+                       const float* y, int64_t n_rows);
+/* nsteps minibatches of `batch` train-store rows each: step s trains on rows ids[s*batch .. (s+1)*batch) - scipy's X[ids],
+ * y[ids]: rows in id order, duplicates repeated, empty rows empty - gathered on the device into the handle's minibatch
+ * buffers, then the step of tfr_fm_train_step.  Tables, Adam slots, step counter, beta powers and loss_out[s] are bit for bit
+ * those of nsteps tfr_fm_train_step calls on the same rows.  ids are host values, checked against [0, n_rows) before
+ * anything is queued (TFR_ERR_OOB: no work is done, the model is untouched) and uploaded once.  A batch of empty rows
+ * (nnz 0) is a valid step.  loss_out [nsteps] may be NULL: the call then returns with the steps queued (tfr_fm_sync waits).
+ * A failure to queue a step, or (with loss_out) an error the device reports, restores the step counter and the beta powers
+ * of before the call; steps that ran before it have written their rows, so upload the tables again (tfr_fm_set) before
+ * going on.  With loss_out NULL a device error shows at the next synchronising call, which cannot restore this call's
+ * counter.  No train store: TFR_ERR_STATE. */
+int tfr_fm_train_steps_resident(tfr_fm* m, const int64_t* ids, int64_t batch, int32_t nsteps, float* loss_out);
+/* The minibatch tfr_fm_train_steps_resident builds for `ids`, copied to the host: indptr_out [batch + 1], y_out [batch],
+ * indices_out / data_out [nnz_cap].  More entries than nnz_cap: TFR_ERR_ARG before any device work.  Synchronous. */
+int tfr_fm_gather_rows(tfr_fm* m, int32_t which, const int64_t* ids, int64_t batch, int64_t* indptr_out,
+                       int32_t* indices_out, float* data_out, float* y_out, int64_t nnz_cap);
+/* Predictions (forward.py:21-22) of every row of a store into out [n_rows] (host).  Synchronous. */
+int tfr_fm_predict_resident(tfr_fm* m, int32_t which, float* out);
+/* tfr_eval_binary_resident for the FM, over the eval store: the count of round(sigmoid(pred)) == y, the summed sigmoid
+ * cross-entropy, the rank-sum AUC (ties share their mean rank; NaN when a class is empty; targets > 0.5 are positives) and
+ * the row count.  Needs loss = nll (TFR_ERR_STATE otherwise, and without an eval store).  Outputs may be NULL. */
+int tfr_fm_eval_binary_resident(tfr_fm* m, int64_t* n_equal_out, double* nll_sum_out, double* auc_out, int64_t* n_out);
+
 /* ---- ALS baseline (als3.py), float64 like the reference ----------------------
  *      MangakiALS3.fit (als3.py:20-35) = tfr_als_set (init_vars, als3.py:57-65, drawn by the host
  *      from np.random.rand) + tfr_als_load (bias = mean(y); per-user / per-work rating lists,

@@ -2810,14 +2810,18 @@ int tfr_staged_ids_devptr(tfr_model* m, void** ptr, int64_t* n) {
 // The handle wraps a regular model: V = its user_features [F,D], W = its user_bias [F],
 // mu = its bias_global; so the FM backward reuses the radix sort, the segmented reduce (K3) and
 // the fused SGD / lazy-Adam apply unchanged.
+struct FmFit;                                           // fm_fit_api.inc.h
 struct tfr_fm {
     tfr_model* m = nullptr;
+    FmFit* fit = nullptr;                                // the resident row stores and what the steps drawn from them need
     DevBuf<int64_t> d_indptr;
     DevBuf<int32_t> d_indices;
     DevBuf<float> d_data, d_y, d_out, s_rows;
     DevBuf<int4> ent;                                    // per non-zero {row, g x, lam - g x^2, -} of the training step
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
+
+static void fm_fit_release(tfr_fm* f);
 
 static int fm_stage_csr(tfr_fm* f, const int64_t* indptr, const int32_t* indices, const float* data,
                         const float* y, int64_t n_rows, int64_t* nnz_out) {
@@ -2947,6 +2951,7 @@ int tfr_fm_destroy(tfr_fm* f) {
     }
     if (f->ev0) (void)hipEventDestroy(f->ev0);
     if (f->ev1) (void)hipEventDestroy(f->ev1);
+    fm_fit_release(f);
     delete f;                                            // the FM buffers go first, under the wrapped model's device
     return tfr_destroy(m);
 }
@@ -3545,3 +3550,5 @@ int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, cons
 #include "svdpp_api.inc.h"
 // ---- BPR steps (tfr_bpr_*, bpr.hip) on the model's own tables
 #include "bpr_api.inc.h"
+// ---- FM trainer (tfr_fm_*_resident, fm_fit.hip): resident row stores, gathered minibatches, metrics
+#include "fm_fit_api.inc.h"

@@ -50,6 +50,13 @@ __device__ __forceinline__ void warm_args(const T& args) {
     for (int k = 0; k < NL; ++k) asm volatile("" :: "s"(w[k]));
 }
 
+// The binary-outcome formulas every evaluation shares (the SVD forward's evaluation mode, the FM trainer's metrics):
+// ops.py:77-78 infer = round(sigmoid(logit)), half-to-even; ops.py:125-126 sigmoid cross-entropy on the fed logit.
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
+__device__ __forceinline__ float binary_infer(float logit) { return rintf(sigmoidf_(logit)); }
+__device__ __forceinline__ float sigmoid_xent(float logit, float r) {
+    return fmaxf(logit, 0.f) - logit * r + log1pf(__expf(-fabsf(logit)));
+}
 
 // LDS written by some lanes of a wave and read by others of the same wave
 __device__ __forceinline__ void wave_lds_sync() {

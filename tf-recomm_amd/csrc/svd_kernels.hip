@@ -150,8 +150,6 @@ __device__ __forceinline__ float wave_sum(float x) {
     return x;   // valid in lane 0
 }
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
-
 // block-level sum of NV values per thread -> out[NV] written by thread 0.  NW waves per block.
 template <int NV, int NW>
 __device__ __forceinline__ void block_sum_store(float (&val)[NV], float* out) {
@@ -376,12 +374,12 @@ __device__ __forceinline__ void forward_body(const FwdArgs& a, int block, int nb
                 } else {
                     const float r = rr[j];
                     float inf = logit;                 // canonical infer = logits (README.md:33)
-                    if (a.loss != 0) inf = rintf(sigmoidf_(logit));   // ops.py:77-78, half-to-even
+                    if (a.loss != 0) inf = binary_infer(logit);       // ops.py:77-78, half-to-even
                     const float d = inf - r;
                     acc[0] += d * d;
                     acc[1] += (inf == r) ? 1.f : 0.f;
                     // svd_train_val.py:94,170-178: the epoch line's mean NLL (ops.py:125-126 on the fed logits)
-                    if (a.loss != 0) acc[2] += fmaxf(logit, 0.f) - logit * r + log1pf(__expf(-fabsf(logit)));
+                    if (a.loss != 0) acc[2] += sigmoid_xent(logit, r);
                     if (a.logits) a.logits[k[j]] = logit;                // kept for the AUC (rank sum over the sorted logits)
                 }
             }

@@ -1,7 +1,11 @@
-"""Second-order FM prediction on the GPU (reference: forward.py:14-22).
+"""Second-order FM on the GPU: prediction (reference: forward.py:14-22), training, and the five-fold driver of fm.py.
 
 ``FmModel.fma(X)`` is the reference's ``fma(x)``: X is a scipy.sparse CSR design matrix
 (fm.py:61-93), the result ``mu + X.W + 0.5 * (||X V||^2 - (X*X).(V*V).1)`` per row.
+
+``run(...)`` is fm.py:113-181: users split five ways, one model per fold trained on rows that stay on the device
+(``upload_rows`` / ``train_steps_resident``), ACC / AUC / NLL of the held-out users from ``eval_binary_resident``.
+``python -m tfrecomm_amd.fm --dataset NAME --d D --users --items --iter N`` runs it on a prepared data set.
 """
 from __future__ import annotations
 
@@ -17,6 +21,7 @@ class FmModel(object):
         self._lib = L.load()
         self._h = L._p()
         self.n_features, self.dim = int(n_features), int(dim)
+        self._row_lengths = {}                         # "train" / "eval" -> the uploaded store's row lengths (sizes the outputs)
         o = L.TfrOpts()
         self._lib.tfr_default_opts(C.byref(o))
         o.loss, o.optimizer, o.adam_mode = L.LOSS[loss], L.OPTIMIZER[optimizer], L.ADAM_MODE["lazy"]
@@ -91,6 +96,64 @@ class FmModel(object):
 
     def train_step_dev(self, d_indptr, d_indices, d_data, d_y, n_rows, nnz, d_pred=None):
         self._check(self._lib.tfr_fm_train_step_dev(self._h, d_indptr, d_indices, d_data, d_y, n_rows, nnz, d_pred))
+
+    # ---- the trainer: rows resident on the device, minibatches gathered there
+    _WHICH = {"train": 0, "eval": 1}
+
+    def upload_rows(self, x, y, which="train"):
+        """Copy the CSR design rows ``x`` and targets ``y`` to the device once, as the ``train`` or the ``eval`` store
+        (a second upload replaces the first)."""
+        x = x.tocsr()
+        indptr = np.ascontiguousarray(x.indptr, np.int64)
+        indices = np.ascontiguousarray(x.indices, np.int32)
+        data = np.ascontiguousarray(x.data, np.float32)
+        y = L.as_f32(y)
+        n = indptr.size - 1
+        if y.shape != (n,) or x.shape[1] != self.n_features:
+            raise ValueError("x must be [n, %d] and y [n]" % self.n_features)
+        self._check(self._lib.tfr_fm_upload_rows(self._h, self._WHICH[which], L.ptr_i64(indptr), L.ptr_i32(indices),
+                                                 L.ptr_f32(data), L.ptr_f32(y), n))
+        self._row_lengths[which] = np.diff(indptr)
+
+    def gather_rows(self, ids, which="train"):
+        """The minibatch the device builds for store rows ``ids``: scipy's ``(X[ids], y[ids])``."""
+        import scipy.sparse as sp
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        lengths = self._row_lengths.get(which)
+        # (a bad id or a missing store is the library's to refuse: size the outputs for the ids that are in range)
+        ok = ids[(ids >= 0) & (ids < (0 if lengths is None else lengths.size))]
+        cap = int(lengths[ok].sum()) if ok.size else 0
+        indptr, yb = np.empty(ids.size + 1, np.int64), np.empty(ids.size, np.float32)
+        indices, data = np.empty(cap, np.int32), np.empty(cap, np.float32)
+        self._check(self._lib.tfr_fm_gather_rows(self._h, self._WHICH[which], L.ptr_i64(ids), ids.size, L.ptr_i64(indptr),
+                                                 L.ptr_i32(indices), L.ptr_f32(data), L.ptr_f32(yb), cap))
+        return sp.csr_matrix((data, indices, indptr), shape=(ids.size, self.n_features)), yb
+
+    def train_steps_resident(self, ids, batch, want_loss=True):
+        """``len(ids) // batch`` training steps, step ``s`` on train-store rows ``ids[s*batch:(s+1)*batch]``: the same
+        bits as ``train_step(X[ids_s], y[ids_s])`` per step.  Returns the per-step data losses, or (``want_loss=False``)
+        None with the steps queued."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        batch = int(batch)
+        if batch < 1 or ids.size % batch:
+            raise ValueError("ids must hold a whole number of batches of %d" % batch)
+        nsteps = ids.size // batch
+        loss = np.empty(nsteps, np.float32) if want_loss else None
+        self._check(self._lib.tfr_fm_train_steps_resident(self._h, L.ptr_i64(ids), batch, nsteps,
+                                                          L.ptr_f32(loss) if want_loss else None))
+        return loss
+
+    def predict_resident(self, which="eval"):
+        n = self._row_lengths.get(which)
+        out = np.empty(0 if n is None else n.size, np.float32)
+        self._check(self._lib.tfr_fm_predict_resident(self._h, self._WHICH[which], L.ptr_f32(out)))
+        return out
+
+    def eval_binary_resident(self):
+        """Accuracy, mean sigmoid cross-entropy and AUC of the eval store (fm.py:162-166), computed on the device."""
+        neq, n, nll, auc = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+        self._check(self._lib.tfr_fm_eval_binary_resident(self._h, C.byref(neq), C.byref(nll), C.byref(auc), C.byref(n)))
+        return {"acc": neq.value / n.value, "mean_nll": nll.value / n.value, "auc": auc.value, "n": n.value}
 
     def init(self, seed=0, stddev=0.1):
         self._check(self._lib.tfr_fm_init(self._h, int(seed), stddev))
@@ -189,3 +252,120 @@ def df_to_sparse(df, user_num, item_num, active_agents, qmatrix=None, skill_wins
     x = sp.hstack([blocks[a] for a in chosen]).tocsr().astype(np.float32)
     x.data = np.nan_to_num(x.data)                     # fm.py:126,130
     return x
+
+
+def kfold_by_user(users, n_splits=5, seed=0):
+    """fm.py:114-119's split of the users: the unique users in order of first appearance, shuffled by
+    ``np.random.RandomState(seed).permutation`` and cut by ``np.array_split``; fold ``k`` tests on part ``k`` and trains on
+    the rest.  Returns ``[(users_train, users_test)] * n_splits``; every user is in exactly one test part."""
+    users = np.asarray(users)
+    uniq, first = np.unique(users, return_index=True)
+    uniq = uniq[np.argsort(first, kind="stable")]
+    if n_splits < 2 or n_splits > uniq.size:
+        raise ValueError("n_splits must lie in [2, %d users]" % uniq.size)
+    parts = np.array_split(uniq[np.random.RandomState(seed).permutation(uniq.size)], n_splits)
+    return [(np.concatenate(parts[:k] + parts[k + 1:]), parts[k]) for k in range(n_splits)]
+
+
+def plan_steps(row_lengths, ids, batch):
+    """The non-zeros of each step of ``train_steps_resident(ids, batch)``: the sum of the step's rows' lengths - what the
+    library computes on the host to size each step's launches.  Raises IndexError on an id outside the store."""
+    row_lengths = np.asarray(row_lengths, np.int64)
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    if batch < 1 or ids.size % batch:
+        raise ValueError("ids must hold a whole number of batches of %d" % batch)
+    if ids.size and (ids.min() < 0 or ids.max() >= row_lengths.size):
+        raise IndexError("row id out of range [0, %d)" % row_lengths.size)
+    return row_lengths[ids].reshape(-1, batch).sum(axis=1)
+
+
+def run(df, user_num, item_num, active_agents, d, num_iter, batch, lr, reg, optimizer, seed, out_dir=None, qmatrix=None,
+        skill_wins=None, skill_fails=None, experiment_args=None, device=0, log=None):
+    """fm.py:113-181 on the device.  For each of five folds of the users: the rows of the train users and of the test users
+    are uploaded, a ``d``-dimensional model is initialised (``init(seed + fold)``) and trained for ``num_iter`` epochs of
+    ``len(train) // batch`` minibatches drawn with replacement (``np.random.RandomState(seed + fold).randint``, one
+    ``train_steps_resident`` call per epoch), then evaluated on the test rows.  (The epoch is this project's, as its SGD /
+    lazy-Adam step is: the reference trains by MCMC inside libFM.)  With ``out_dir``, ``<out_dir>/<fold>/results.json``
+    gets the reference's keys.  Returns one dict per fold: ``metrics`` {ACC, AUC, NLL}, ``pred`` (the final model's
+    predictions of the test rows), ``y`` (their outcomes), ``test_rows`` and ``loss`` (per step)."""
+    import json
+    import os
+    from . import dataio
+    if d < 1:
+        raise ValueError("d = %d: the reference fits sklearn's LogisticRegression there (fm.py:139-152); this driver "
+                         "trains the factorization machine only, d >= 1" % d)
+    x = df_to_sparse(df, user_num, item_num, active_agents, qmatrix, skill_wins, skill_fails)
+    y = np.asarray(df["outcome"], np.float32)
+    users = np.asarray(df["user"])
+    args = dict(experiment_args) if experiment_args is not None else dict(
+        {a: a in active_agents for a in AGENTS}, d=d, iter=num_iter, batch=batch, lr=lr, reg=reg, optimizer=optimizer,
+        seed=seed)
+    short, full, latex, _ = dataio.get_legend(dict({a: a in active_agents for a in AGENTS}, d=d))
+    folds = []
+    for fold, (_, users_test) in enumerate(kfold_by_user(users, 5, seed)):
+        test = np.isin(users, users_test)
+        i_train, i_test = np.flatnonzero(~test), np.flatnonzero(test)
+        steps = i_train.size // batch
+        if steps < 1:
+            raise ValueError("fold %d trains on %d rows: fewer than one batch of %d" % (fold, i_train.size, batch))
+        with FmModel(x.shape[1], d, device=device, loss="nll", optimizer=optimizer, lr=lr, reg=reg) as model:
+            model.upload_rows(x[i_train], y[i_train], "train")
+            model.upload_rows(x[i_test], y[i_test], "eval")
+            model.init(seed + fold)
+            rs = np.random.RandomState(seed + fold)
+            losses = []
+            for _ in range(num_iter):
+                losses.append(model.train_steps_resident(rs.randint(0, i_train.size, (steps * batch,)), batch))
+            ev = model.eval_binary_resident()
+            pred = model.predict_resident("eval")
+        metrics = {"ACC": ev["acc"], "AUC": ev["auc"], "NLL": ev["mean_nll"]}
+        if log:
+            log("fold %d: %d train rows, %d test rows, ACC %.4f AUC %.4f NLL %.4f"
+                % (fold, i_train.size, i_test.size, metrics["ACC"], metrics["AUC"], metrics["NLL"]))
+        if out_dir is not None:
+            dataio.prepare_folder(os.path.join(out_dir, str(fold)))
+            with open(os.path.join(out_dir, str(fold), "results.json"), "w") as f:
+                f.write(json.dumps({"args": args, "legends": {"short": short, "full": full, "latex": latex},
+                                    "metrics": metrics}, indent=4))
+        folds.append({"metrics": metrics, "pred": pred, "y": y[i_test], "test_rows": i_test,
+                      "loss": np.concatenate(losses) if losses else np.empty(0, np.float32)})
+    return folds
+
+
+def main(argv=None):
+    import argparse
+    import os
+    from . import dataio
+    ap = argparse.ArgumentParser(description="Knowledge Tracing Machines: five-fold FM training on the GPU (fm.py)")
+    ap.add_argument("--dataset", type=str, default="dummy")
+    ap.add_argument("--data_folder", type=str, default="data")
+    ap.add_argument("--d", type=int, required=True)
+    for a in AGENTS:
+        ap.add_argument("--" + a, action="store_true")
+    ap.add_argument("--iter", type=int, default=500)
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--lr", type=float, default=0.01)
+    ap.add_argument("--reg", type=float, default=0.0)
+    ap.add_argument("--optimizer", choices=sorted(L.OPTIMIZER), default="adam")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", type=int, default=0)
+    o = ap.parse_args(argv)
+    if o.d == 0:
+        raise ValueError("--d 0 is the reference's logistic-regression baseline (fm.py:139-152), which this driver does not "
+                         "have: give --d >= 1")
+    import scipy.sparse as sp
+    folder, _, config_file, q_npz, sw_npz, sf_npz = dataio.build_new_paths(o.dataset, o.data_folder)
+    config = dataio.get_config(config_file)
+    df = dataio.get_new_data(o.dataset, o.data_folder)
+    qmatrix = sp.load_npz(q_npz) if os.path.isfile(q_npz) else None
+    both = os.path.isfile(sw_npz) and os.path.isfile(sf_npz)
+    skill_wins, skill_fails = (sp.load_npz(sw_npz), sp.load_npz(sf_npz)) if both else (None, None)
+    args = vars(o)
+    short, _, _, active = dataio.get_legend(args)
+    run(df, config["USER_NUM"], config["ITEM_NUM"], active, o.d, o.iter, o.batch, o.lr, o.reg, o.optimizer, o.seed,
+        out_dir=os.path.join(folder, short), qmatrix=qmatrix, skill_wins=skill_wins, skill_fails=skill_fails,
+        experiment_args=args, device=o.device, log=print)
+
+
+if __name__ == "__main__":
+    main()
