@@ -554,6 +554,54 @@ int tfr_bpr_train_step_dev(tfr_model* m, const int32_t* d_user, const int32_t* d
  * synchronise): data term per step. */
 int tfr_bpr_train_steps_drawn(tfr_model* m, int64_t batch, int32_t nsteps, float* loss_out);
 
+/* ---- nearest neighbours in factor space: "what is like item i", "who is like user u" - DESIGN §17 -----------------------
+ *      One table T [R, dim] gives the query rows and the candidate rows: TFR_NB_ITEMS = item_features (|Q| with item_abs),
+ *      TFR_NB_USERS = user_features; for SVD++ users the effective rows P[u] + z_u that tfr_svdpp_topk scores with; for the
+ *      FM the feature rows V.
+ *          dot(a, b)    = the f32 fmaf chain over f = 0..dim-1 ascending, from +0, of T[a,f] * T[b,f] (the tfr_topk chain,
+ *                         no bias terms)
+ *          ss[r]        = the f32 fmaf chain over f ascending, from +0, of T[r,f]^2;  rn[r] = 1 / sqrtf(ss[r]), 0 if ss[r] == 0
+ *          TFR_NB_DOT:    s(a, b) = dot(a, b)
+ *          TFR_NB_COSINE: s(a, b) = (dot(a, b) * rn[a]) * rn[b], both products f32, in that order; every score of a zero row
+ *                         is +0, so it is orderable and not NaN
+ *      Per query row a = rows[r] the k best candidates b in [lo, hi) (0 <= lo < hi <= R; ids are row ids of T whatever the
+ *      range) by s descending, then b ascending - the tfr_topk key.  Never returned: a itself, the rows of the query's
+ *      exclusion row, candidates whose score is NaN.  Slots past the eligible candidates hold id -1 / score -INFINITY.
+ *      1 <= k <= 256; duplicate queries allowed; n = 0 is a no-op.
+ *      Exclusions: optional CSR (excl_indptr [n+1], excl) aligned with `rows`, each row non-decreasing row ids of T.  The host
+ *      entries check ids and order first (TFR_ERR_OOB for a query or excluded id out of range, TFR_ERR_ARG for an unsorted
+ *      row, a bad k, metric, table or range; outputs untouched); tfr_neighbours_dev checks on the device with the error bits
+ *      of tfr_topk_dev and reports through the next synchronising call.  Reads the tables only; runs on the model's stream;
+ *      the host entries synchronise, tfr_neighbours_dev does not.  scores_out may be NULL.
+ *      The inverse norms live on the device and are rebuilt when the table may have changed since they were made: after any
+ *      training step (the step counter moved) and after tfr_set_table, tfr_init_tables, tfr_set_step, tfr_set_frozen or a
+ *      voided step; once tfr_table_devptr has handed a table out for writing they are rebuilt on every cosine query. */
+enum { TFR_NB_ITEMS = 0, TFR_NB_USERS = 1 };
+enum { TFR_NB_DOT = 0, TFR_NB_COSINE = 1 };
+int tfr_neighbours(tfr_model* m, int32_t which, int32_t metric, const int32_t* rows, int64_t n, int32_t k,
+                   const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl, int64_t lo, int64_t hi,
+                   int32_t* ids_out /* [n,k] */, float* scores_out /* [n,k], may be NULL */);
+int tfr_neighbours_dev(tfr_model* m, int32_t which, int32_t metric, const int32_t* d_rows, int64_t n, int32_t k,
+                       const int64_t* d_excl_indptr, const int32_t* d_excl, int64_t lo, int64_t hi,
+                       int32_t* d_ids_out, float* d_scores_out);
+/* SVD++: items as tfr_neighbours; users on e_u = P[u] + z_u, rebuilt for every user by each call (needs the implicit sets).
+ * Host pointers; synchronises. */
+int tfr_svdpp_neighbours(tfr_svdpp* m, int32_t which, int32_t metric, const int32_t* rows, int64_t n, int32_t k,
+                         const int64_t* excl_indptr, const int32_t* excl, int64_t lo, int64_t hi,
+                         int32_t* ids_out, float* scores_out);
+int tfr_svdpp_neighbours_dev(tfr_svdpp* m, int32_t which, int32_t metric, const int32_t* d_rows, int64_t n, int32_t k,
+                             const int64_t* d_excl_indptr, const int32_t* d_excl, int64_t lo, int64_t hi,
+                             int32_t* d_ids_out, float* d_scores_out);
+/* FM: features against the features [lo, hi) of V - a block of the design matrix, for example the item block */
+int tfr_fm_neighbours(tfr_fm* m, int32_t metric, const int32_t* features, int64_t n, int32_t k,
+                      const int64_t* excl_indptr, const int32_t* excl, int64_t lo, int64_t hi,
+                      int32_t* ids_out, float* scores_out);
+/* host-only, no device: what the launcher will do for n query rows against n_candidates rows - LDS bytes per workgroup
+ * (the larger of the scoring and the merge kernel; k_row_rnorm uses none), query rows per scoring workgroup, candidate
+ * slices, query rows per chunk */
+int tfr_neighbours_plan(int32_t dim, int32_t k, int64_t n, int64_t n_candidates,
+                        int64_t* lds_bytes, int32_t* rows_per_block, int32_t* slices, int64_t* row_chunk);
+
 /* ---- per-kernel timing with HIP events on the model's stream (bench.py roofline) -------- */
 enum {
     TFR_K_FORWARD = 0,        /* gather-dot forward (+ fused loss/grad when training)       */

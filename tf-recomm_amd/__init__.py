@@ -13,8 +13,8 @@ from .fm import FmModel
 from .svdpp import SvdppModel
 from . import svdpp
 from .als import MangakiALS3
-from . import ranking
+from . import ranking, neighbours
 from .ranking import ranking_metrics, evaluate_ranking
 
 __all__ = ["SvdModel", "device_copy_rate", "rated_matrix", "TfrError", "OutOfRangeError", "_lib", "dataio", "graph", "ops", "config", "cats", "adaptive_test", "finetune",
-           "FmModel", "SvdppModel", "svdpp", "MangakiALS3", "ranking", "ranking_metrics", "evaluate_ranking"]
+           "FmModel", "SvdppModel", "svdpp", "MangakiALS3", "ranking", "ranking_metrics", "evaluate_ranking", "neighbours"]

@@ -23,6 +23,8 @@ LOSS = {"mse": 0, "nll": 1}
 OPTIMIZER = {"adam": 0, "sgd": 1}
 ADAM_MODE = {"tf1": 0, "lazy": 1}
 K_FORWARD, K_SORT, K_REDUCE_ITEM, K_REDUCE_USER, K_APPLY, K_FINALIZE, K_GATHER, K_DRAW = range(8)
+NB_ITEMS, NB_USERS = 0, 1                      # tfr_neighbours: which table
+NB_METRIC = {"dot": 0, "cosine": 1}
 KERNEL_NAMES = ["forward", "sort", "reduce_item", "reduce_user", "apply", "finalize", "gather", "draw"]
 
 
@@ -149,6 +151,16 @@ SIGNATURES = {
     "tfr_topk_dev": (C.c_int, [_p, _p, C.c_int64, C.c_int32, _p, _p, _p, _p]),
     "tfr_fm_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
     "tfr_topk_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, _i64p, _i32p, _i32p, _i64p]),
+    "tfr_neighbours": (C.c_int, [_p, C.c_int32, C.c_int32, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, C.c_int64, C.c_int64,
+                                 _i32p, _f32p]),
+    "tfr_neighbours_dev": (C.c_int, [_p, C.c_int32, C.c_int32, _p, C.c_int64, C.c_int32, _p, _p, C.c_int64, C.c_int64, _p, _p]),
+    "tfr_svdpp_neighbours": (C.c_int, [_p, C.c_int32, C.c_int32, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, C.c_int64,
+                                       C.c_int64, _i32p, _f32p]),
+    "tfr_svdpp_neighbours_dev": (C.c_int, [_p, C.c_int32, C.c_int32, _p, C.c_int64, C.c_int32, _p, _p, C.c_int64, C.c_int64,
+                                           _p, _p]),
+    "tfr_fm_neighbours": (C.c_int, [_p, C.c_int32, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, C.c_int64, C.c_int64, _i32p,
+                                    _f32p]),
+    "tfr_neighbours_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, _i64p, _i32p, _i32p, _i64p]),
     "tfr_rank_items": (C.c_int, [_p, _i32p, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
     "tfr_fm_rank_items": (C.c_int, [_p, _i32p, C.c_int64, C.c_int64, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
     "tfr_rank_plan": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, _i64p, _i32p, _i32p, _i32p, _i64p]),

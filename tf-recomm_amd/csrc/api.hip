@@ -17,6 +17,7 @@
 #include "tfrecomm.h"
 #include "svd_kernels.h"
 #include "topk.h"
+#include "neighbours.h"
 #include "rank.h"
 #include "finetune.h"
 #include "devbuf.h"
@@ -162,6 +163,12 @@ struct tfr_model {
     DevBuf<int32_t> tk_items;
     DevBuf<float> tk_scores;
     DevBuf<int32_t> tk_bad;
+    // nearest neighbours (tfr_neighbours*): the inverse row norms of item_features [0] and user_features [1], each with the
+    // step counter and the table generation it was built at.  tab_gen counts what changes a table without a step (set_table,
+    // init, set_step, set_frozen, a voided step); tab_exposed: tfr_table_devptr handed a table out, writes are unseen from then
+    struct RnCache { DevBuf<float> rn; int64_t step = -1; uint64_t gen = 0; bool valid = false; } nb_rn[2];
+    uint64_t tab_gen = 0;
+    bool tab_exposed = false;
     // held-out ranking (tfr_rank_items*): one piece chunk's staged pieces, targets and exclusions, and its per-piece state
     DevBuf<RankPiece> rk_pieces;
     DevBuf<int32_t> rk_tgt, rk_excl, rk_ranks;
@@ -549,6 +556,7 @@ int tfr_set_table(tfr_model* m, int32_t which, const float* host, int64_t n) {
     int rc = table_ptr(m, which, &p, &cnt);
     if (rc) return rc;
     if (!host || n != cnt) return fail(TFR_ERR_ARG, "table %d expects %lld floats, got %lld", which, (long long)cnt, (long long)n);
+    m->tab_gen += 1;
     HIPCHK(hipMemcpyAsync(p, host, (size_t)n * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return TFR_OK;
@@ -572,6 +580,7 @@ int tfr_table_devptr(tfr_model* m, int32_t which, void** ptr, int64_t* n) {
     if (rc) return rc;
     if (ptr) *ptr = p;
     if (n) *n = cnt;
+    m->tab_exposed = true;
     return TFR_OK;
 }
 
@@ -585,6 +594,7 @@ int tfr_set_frozen(tfr_model* m, uint32_t mask) {
     MODEL_ENTER(m);
     if (mask >> 5) return fail(TFR_ERR_ARG, "frozen mask has bits beyond the 5 tables");
     m->frozen = mask;
+    m->tab_gen += 1;
     return TFR_OK;
 }
 
@@ -602,6 +612,7 @@ int tfr_set_step(tfr_model* m, int64_t step, float b1p, float b2p) {
     m->step = step;
     m->b1p = b1p;
     m->b2p = b2p;
+    m->tab_gen += 1;
     return TFR_OK;
 }
 
@@ -1319,6 +1330,7 @@ static void rollback_step(tfr_model* m, int64_t step0, float b1p0, float b2p0) {
     m->step = step0;
     m->b1p = b1p0;
     m->b2p = b2p0;
+    m->tab_gen += 1;                                     // the voided step may have run: the counter no longer tells
 }
 
 // pinned staging for host-fed batches up to 1M ratings (larger ones take the plain copies)
@@ -1673,6 +1685,7 @@ int tfr_init_tables(tfr_model* m, uint64_t seed, float fstd, float bstd) {
     m->step = 0;
     m->b1p = m->o.beta1;
     m->b2p = m->o.beta2;
+    m->tab_gen += 1;
     HIPCHK(hipStreamSynchronize(s));
     return TFR_OK;
 }
@@ -3018,6 +3031,7 @@ int tfr_fm_init(tfr_fm* f, uint64_t seed, float stddev) {
     if (!f) return fail(TFR_ERR_ARG, "null model");
     tfr_model* m = f->m;
     HIPCHK(hipSetDevice(m->device));
+    m->tab_gen += 1;
     launch_init_trunc_normal(m->w[TFR_P], m->n[TFR_P], stddev, seed * 2 + 0, m->stream);
     launch_init_trunc_normal(m->w[TFR_BU], m->n[TFR_BU], stddev, seed * 2 + 1, m->stream);
     HIPCHK(hipGetLastError());
@@ -3552,3 +3566,5 @@ int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, cons
 #include "bpr_api.inc.h"
 // ---- FM trainer (tfr_fm_*_resident, fm_fit.hip): resident row stores, gathered minibatches, metrics
 #include "fm_fit_api.inc.h"
+
+#include "neighbours_api.inc.h"

@@ -1,5 +1,6 @@
-// score_tile.h - the pieces topk.hip and rank.hip share: the 64-bit ordering key of a scored pair, the one-wave bitonic
-// sort of keys in LDS, and the MFMA tile that scores 32 items against 32 user columns.
+// score_tile.h - the pieces topk.hip, rank.hip and neighbours.hip share: the 64-bit ordering key of a scored pair, the one-wave
+// bitonic sort of keys in LDS, the queue compaction built on it, and the MFMA tile that scores 32 items against 32 user
+// columns.
 //
 // key(s, item) = (order-preserving uint32 of s) << 32 | ~item: one 64-bit compare orders by score descending, then item id
 // ascending; every non-NaN score gives a key above 0, so key 0 marks an empty slot.
@@ -42,6 +43,21 @@ __device__ __forceinline__ void wave_sort_desc(uint64_t* q, int lane) {
     }
 }
 
+// sort user u's queue, keep its k best, raise its threshold (one wave; cnt / thr / queue are LDS)
+template <int CAP>
+__device__ __forceinline__ void topk_compact(uint64_t* q, int32_t* cnt, uint64_t* thr, int k, int lane) {
+    const int n = *cnt;
+    for (int t = n + lane; t < CAP; t += 64) q[t] = 0;
+    wave_lds_sync();
+    wave_sort_desc<CAP>(q, lane);
+    const int keep = n < k ? n : k;
+    if (lane == 0) {
+        *cnt = keep;
+        *thr = keep == k ? q[k - 1] : 0;
+    }
+    wave_lds_sync();
+}
+
 // item in the sorted (non-decreasing) x[lo, hi)
 __device__ __forceinline__ bool topk_excluded(const int32_t* x, int64_t lo, int64_t hi, int32_t item) {
     const int64_t end = hi;
@@ -68,7 +84,8 @@ __device__ __forceinline__ float4 topk_load4(const float* row, int t, int D) {
 // item_abs) and B[f][column c] from prow for f = 2s + h of step s, k ascending from a zero accumulator, odd dims zero-padded.
 // On return the lane holds column c against items (r & 3) + 8 (r >> 2) + 4 h, r = 0..15.  Every element of the tile goes
 // through the same instruction sequence, so a pair's dot has the same bits whichever tile, row or column scored it.
-template <bool V4>
+// ABS_B (neighbours.hip: both operands are rows of the one table): item_abs takes |.| of the B rows too.
+template <bool V4, bool ABS_B = false>
 __device__ __forceinline__ f32x16 mfma_tile_dot(const float* qrow, const float* prow, int D, int item_abs, int h) {
     const int DP4 = (D + 3) >> 2;
     f32x16 acc;
@@ -85,7 +102,8 @@ __device__ __forceinline__ f32x16 mfma_tile_dot(const float* qrow, const float* 
                 float4 q = qa[z];
                 if (item_abs) { q.x = fabsf(q.x); q.y = fabsf(q.y); q.z = fabsf(q.z); q.w = fabsf(q.w); }
                 const float a0 = h ? q.y : q.x, a1 = h ? q.w : q.z;
-                const float b0 = h ? pb[z].y : pb[z].x, b1 = h ? pb[z].w : pb[z].z;
+                float b0 = h ? pb[z].y : pb[z].x, b1 = h ? pb[z].w : pb[z].z;
+                if (ABS_B && item_abs) { b0 = fabsf(b0); b1 = fabsf(b1); }
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc, 0, 0, 0);
             }

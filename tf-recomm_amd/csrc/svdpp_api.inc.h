@@ -273,6 +273,7 @@ int tfr_svdpp_set_table(tfr_svdpp* h, int32_t which, const float* host, int64_t 
     int rc = pp_table(h, which, &p, &cnt);
     if (rc) return rc;
     if (!host || n != cnt) return fail(TFR_ERR_ARG, "table %d expects %lld floats, got %lld", which, (long long)cnt, (long long)n);
+    m->tab_gen += 1;
     HIPCHK(hipMemcpyAsync(p, host, (size_t)n * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipStreamSynchronize(m->stream));
     return TFR_OK;

@@ -15,21 +15,6 @@
 
 namespace tfr {
 
-// sort user u's queue, keep its k best, raise its threshold (one wave; cnt / thr / queue are LDS)
-template <int CAP>
-__device__ __forceinline__ void topk_compact(uint64_t* q, int32_t* cnt, uint64_t* thr, int k, int lane) {
-    const int n = *cnt;
-    for (int t = n + lane; t < CAP; t += 64) q[t] = 0;
-    wave_lds_sync();
-    wave_sort_desc<CAP>(q, lane);
-    const int keep = n < k ? n : k;
-    if (lane == 0) {
-        *cnt = keep;
-        *thr = keep == k ? q[k - 1] : 0;
-    }
-    wave_lds_sync();
-}
-
 template <int UPB, int CAP, bool V4>
 __global__ __launch_bounds__(256) void k_topk_score(TopkArgs a) {
     __shared__ uint64_t queue[UPB * CAP];

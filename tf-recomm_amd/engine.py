@@ -355,6 +355,48 @@ class SvdModel:
         cur.wait_stream(mine)                          # (so no record_stream: the tensors' next users on `cur` come after)
         return (items, scores) if return_scores else items
 
+    # -- nearest neighbours in factor space (include/tfrecomm.h tfr_neighbours) --------------------
+    def _similar(self, which, n_rows, rows, k, metric, exclude, lo, hi, return_scores):
+        from . import neighbours as nb
+
+        def call(*args):
+            L.check(self._lib.tfr_neighbours(self._h, which, *args))
+        return nb.query_host(call, rows, n_rows, k, metric, exclude, lo, hi, return_scores)
+
+    def _similar_dev(self, which, n_rows, rows, k, metric, exclude, lo, hi, return_scores):
+        import torch
+        from . import neighbours as nb
+
+        def call(device, *args):
+            mine = torch.cuda.ExternalStream(self.get_stream(), device=device)
+            cur = torch.cuda.current_stream(device)
+            mine.wait_stream(cur)
+            L.check(self._lib.tfr_neighbours_dev(self._h, which, *args))
+            cur.wait_stream(mine)
+        return nb.query_dev(call, rows, n_rows, k, metric, exclude, lo, hi, return_scores)
+
+    def similar_items(self, items, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """The ``k`` items most like each of ``items`` in factor space, best first, equal scores by item id; an item is never
+        its own neighbour.  ``metric``: ``"cosine"`` (``(Q'[a].Q'[b] / |Q'[a]|) / |Q'[b]|``, a zero row scores 0 against
+        everything) or ``"dot"`` (``Q'[a].Q'[b]``); ``Q' = |Q|`` under ``item_abs``.  ``exclude``: None, an (indptr, ids) CSR
+        aligned with ``items`` or a ``scipy.sparse`` ``[item_num, item_num]`` matrix of items never to return;
+        ``lo`` / ``hi`` restrict the candidates to items ``[lo, hi)``.  Returns ``ids`` int32 ``[n, k]`` (-1 past the
+        eligible items) and, if asked, ``scores`` float32 ``[n, k]`` (-inf there)."""
+        return self._similar(L.NB_ITEMS, self.item_num, items, k, metric, exclude, lo, hi, return_scores)
+
+    def similar_users(self, users, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """``similar_items`` over the rows of ``P``: the ``k`` users most like each of ``users``."""
+        return self._similar(L.NB_USERS, self.user_num, users, k, metric, exclude, lo, hi, return_scores)
+
+    def similar_items_dev(self, items, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """``similar_items`` on torch device tensors (``items`` int32; ``exclude`` None or an (indptr int64, ids int32) pair
+        aligned with ``items``), asynchronous as ``recommend_dev``: an id or order error surfaces at the next ``sync()``."""
+        return self._similar_dev(L.NB_ITEMS, self.item_num, items, k, metric, exclude, lo, hi, return_scores)
+
+    def similar_users_dev(self, users, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """``similar_users`` on torch device tensors, asynchronous as ``recommend_dev``."""
+        return self._similar_dev(L.NB_USERS, self.user_num, users, k, metric, exclude, lo, hi, return_scores)
+
     # -- held-out ranking (include/tfrecomm.h tfr_rank_items; tfrecomm_amd.ranking for the metrics) -------------
     def rank_items(self, users, targets, exclude=None):
         """0-based rank of each target item of each of ``users`` among all items not in ``exclude``: the number of eligible

@@ -190,6 +190,18 @@ class FmModel(object):
                                           L.ptr_i32(items), None if scores is None else L.ptr_f32(scores)))
         return (items, scores) if return_scores else items
 
+    def similar_features(self, features, lo=0, hi=None, k=10, metric="cosine", exclude=None, return_scores=True):
+        """The ``k`` features in ``[lo, hi)`` most like each of ``features`` over the rows of ``V``, best first, equal scores
+        by feature id, a feature never its own neighbour (``SvdModel.similar_items``).  The range picks a block of the design
+        matrix: with the reference's layout (user ``u`` at feature ``u``, item ``i`` at ``user_num + i``),
+        ``similar_features([user_num + i], user_num, user_num + item_num)`` asks for the items like item ``i``.  Ids
+        (returned and in ``exclude``) are feature ids, whatever the range."""
+        from . import neighbours as nb
+
+        def call(*args):
+            self._check(self._lib.tfr_fm_neighbours(self._h, *args))
+        return nb.query_host(call, features, self.n_features, k, metric, exclude, lo, hi, return_scores, "feature ids")
+
     def rank_items(self, user_features, item_lo, item_hi, targets, exclude=None):
         """``SvdModel.rank_items`` for the ``topk`` scores: item features ``[item_lo, item_hi)``, ids (in ``targets`` and
         ``exclude``) relative to ``item_lo``; a sparse ``targets`` / ``exclude`` is indexed by user feature."""

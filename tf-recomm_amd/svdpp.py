@@ -268,6 +268,38 @@ class SvdppModel:
             items.data_ptr(), None if scores is None else scores.data_ptr())))
         return (items, scores) if return_scores else items
 
+    # -- nearest neighbours (the SvdModel signatures; users on the effective rows P[u] + z_u) -------------------------
+    def _similar(self, which, n_rows, rows, k, metric, exclude, lo, hi, return_scores):
+        from . import neighbours as nb
+
+        def call(*args):
+            self._check(self._lib.tfr_svdpp_neighbours(self._h, which, *args))
+        return nb.query_host(call, rows, n_rows, k, metric, exclude, lo, hi, return_scores)
+
+    def _similar_dev(self, which, n_rows, rows, k, metric, exclude, lo, hi, return_scores):
+        from . import neighbours as nb
+
+        def call(device, *args):
+            self._on_stream(device, lambda: self._check(self._lib.tfr_svdpp_neighbours_dev(self._h, which, *args)))
+        return nb.query_dev(call, rows, n_rows, k, metric, exclude, lo, hi, return_scores)
+
+    def similar_items(self, items, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """The ``k`` items most like each of ``items`` over the rows of ``Q'``, as ``SvdModel.similar_items``."""
+        return self._similar(L.NB_ITEMS, self.item_num, items, k, metric, exclude, lo, hi, return_scores)
+
+    def similar_users(self, users, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """The ``k`` users most like each of ``users`` over the effective rows ``P[u] + z_u`` that ``recommend`` scores with
+        (rebuilt for every user by each call; needs the implicit sets)."""
+        return self._similar(L.NB_USERS, self.user_num, users, k, metric, exclude, lo, hi, return_scores)
+
+    def similar_items_dev(self, items, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """``similar_items`` on torch device tensors, asynchronous (as ``SvdModel.similar_items_dev``)."""
+        return self._similar_dev(L.NB_ITEMS, self.item_num, items, k, metric, exclude, lo, hi, return_scores)
+
+    def similar_users_dev(self, users, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """``similar_users`` on torch device tensors, asynchronous."""
+        return self._similar_dev(L.NB_USERS, self.user_num, users, k, metric, exclude, lo, hi, return_scores)
+
     def rank_items(self, users, targets, exclude=None):
         """0-based rank of each target among the eligible items, as ``SvdModel.rank_items``: ``rank < k`` exactly when
         ``recommend(users, k, exclude)`` returns the target, at that position."""
