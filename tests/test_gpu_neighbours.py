@@ -264,6 +264,37 @@ def test_device_entries_equal_host_entries():
     m.close()
 
 
+def test_query_chunks_rebase_the_exclusions():
+    """65536 + 33 queries: two chunks of the shared driver (csrc/topk.h TOPK_CHUNK_MAX), the second with its exclusion indptr
+    rebased on the host path and offset on the device path.  Every row is checked, the chunk's edge rows by name."""
+    import torch
+    rs = np.random.RandomState(111)
+    R, D, k, n = 300, 8, 10, 65536 + 33
+    assert T.neighbours.plan(D, k, n, R)["row_chunk"] == 65536
+    Q = with_ties(rs, dyadic_table(rs, R, D))              # dot exact
+    m = svd_model(Q[:4].copy(), Q)
+    q = rs.randint(0, R, n).astype(np.int32)
+    rows = [np.unique(rs.randint(0, R, rs.randint(1, 60))) if r % 10 == 0 else np.zeros(0, np.int64) for r in range(n)]
+    ex = (np.concatenate([[0], np.cumsum([r.size for r in rows])]).astype(np.int64), np.concatenate(rows).astype(np.int32))
+    hi_, hs = m.similar_items(q, k, "dot", exclude=ex)
+    dev = torch.device("cuda", 0)
+    di, ds = m.similar_items_dev(torch.from_numpy(q).to(dev), k, "dot",
+                                 exclude=(torch.from_numpy(ex[0]).to(dev), torch.from_numpy(ex[1]).to(dev)))
+    m.sync()
+    assert np.array_equal(di.cpu().numpy(), hi_) and np.array_equal(bits(ds.cpu().numpy()), bits(hs))
+    S = neighbour_scores(Q, np.arange(R), "dot")           # per table row, shared by the repeats
+    free_i, free_s = neighbours_from_scores(S, np.arange(R), k)
+    wi, ws = free_i[q], free_s[q]
+    with_x = np.arange(0, n, 10)
+    wi[with_x], ws[with_x] = neighbours_from_scores(S[q[with_x]], q[with_x], k, [rows[r] for r in with_x])
+    for r in (0, 65535, 65536, n - 1):
+        ri, rsc = neighbours_ref(Q, q[r:r + 1], k, "dot", excl=[rows[r]])
+        assert np.array_equal(hi_[r], ri[0]) and np.array_equal(bits(hs[r]), bits(rsc[0])), r
+    assert np.array_equal(hi_, wi) and np.array_equal(bits(hs), bits(ws))
+    assert any(not np.array_equal(wi[r], free_i[q[r]]) for r in with_x if r >= 65536)   # the second chunk's exclusions bite
+    m.close()
+
+
 def pow4_implicit(U, I, rs):
     """|N(u)| in {0, 1, 4, 16}: s_u a power of two, so that on dyadic tables e_u = P[u] + z_u is exact"""
     rows = [np.sort(rs.choice(I, (0, 1, 4, 16)[rs.randint(4)], replace=False)) for _ in range(U)]

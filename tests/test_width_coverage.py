@@ -42,7 +42,7 @@ def registers(D):
 
 def tile(D):
     """(V4, where the last group ends): mfma_tile_dot walks DP4 = ceil(D / 4) float4s in groups of four and masks the last
-    group; V4 = (D % 4 == 0) picks the vector loads (csrc/score_tile.h mfma_tile_dot, topk.hip launch_score_v, rank.hip).
+    group; V4 = (D % 4 == 0) picks the vector loads (csrc/score_tile.h mfma_tile_dot, score_tile.h launch_score_kernel, rank.hip).
     The first group alone, or DP4 % 4 once past it.  tfr_topk_plan / tfr_rank_plan pick no template argument from D."""
     dp4 = -(-D // 4)
     return D % 4 == 0, "first group" if dp4 <= 4 else "DP4 %% 4 = %d" % (dp4 % 4)

@@ -3108,7 +3108,7 @@ int tfr_fm_sync(tfr_fm* f, float* last_kernel_ms) {
 
 }  // extern "C"
 
-// ---- top-K recommendation (topk.hip) ----------------------------------------------------------------------------------------
+// ---- the tables top-K (topk.hip) and held-out ranking (rank.hip) score, and the host checks they share with neighbours ----
 struct TopkTables { const float *P, *bu, *Q, *bi, *mu; int64_t U, n_items; int32_t item_abs; };
 
 static TopkTables svd_topk_tables(const tfr_model* m) {
@@ -3152,54 +3152,75 @@ static int check_csr(const char* who, bool targets, const int64_t* ip, const int
     return TFR_OK;
 }
 
-// one chunk of rows, all pointers on the device: scoring (item slices) -> merge into items_out / scores_out
-static int topk_chunk(tfr_model* m, const TopkTables& t, const TopkPlan& p, const int32_t* d_users, int64_t rows, int32_t k,
-                      const int64_t* d_indptr, const int32_t* d_excl, int32_t* d_items, float* d_scores) {
+// ---- the best k rows by a tile score: the driver of top-K (topk.hip) and nearest neighbours (neighbours.hip) ----------------
+// What a family tells the driver: its name in errors, the bound of the exclusion ids, the candidate count, whether item rows
+// the fused big-table step left in q_alt must come back first.  A query derives from it and adds
+// score(common, plan, stream): fill the family's own argument fields and launch its score kernel for one chunk.
+struct SlicedQuery { const char* who; int64_t excl_rows, n_cand; int32_t item_abs; bool settle; };
+
+static int check_k(const char* who, int32_t k) {
+    return k < 1 || k > TOPK_KMAX ? fail(TFR_ERR_ARG, "%s: k must be in [1, %d] (got %d)", who, TOPK_KMAX, k) : TFR_OK;
+}
+
+// the body of tfr_topk_plan and tfr_neighbours_plan; `counts` words the family's range error
+static int sliced_plan_entry(const char* who, const char* counts, int32_t dim, int32_t k, int64_t n, int64_t n_cand,
+                             int64_t* lds_bytes, int32_t* rows_per_block, int32_t* slices, int64_t* row_chunk) {
+    int G, VEC;
+    if (!geometry(dim, &G, &VEC)) return fail(TFR_ERR_ARG, "unsupported dim %d", dim);
+    if (n < 0 || n_cand < 1) return fail(TFR_ERR_ARG, "%s plan: %s", who, counts);
+    if (int rc = check_k(who, k)) return rc;
+    TopkPlan p;
+    topk_plan(k, n, n_cand, &p);                         // cannot refuse: its conditions are the two above
+    if (lds_bytes) *lds_bytes = (int64_t)(p.lds_score > p.lds_merge ? p.lds_score : p.lds_merge);
+    if (rows_per_block) *rows_per_block = p.upb;
+    if (slices) *slices = p.slices;
+    if (row_chunk) *row_chunk = p.chunk;
+    return TFR_OK;
+}
+
+// what every run starts with, after the family's argument checks: the plan and the reset of the bad-exclusions flag
+template <class Query>
+static int sliced_begin(tfr_model* m, const Query& q, int32_t k, int64_t n, TopkPlan* p) {
+    if (!topk_plan(k, n, q.n_cand, p)) return fail(TFR_ERR_ARG, "%s: no plan for k %d", q.who, k);
+    HIPCHK(m->tk_bad.reserve(1, m->stream));
+    HIPCHK(hipMemsetAsync(m->tk_bad, 0, sizeof(int32_t), m->stream));
+    return q.settle ? settle_q(m) : TFR_OK;
+}
+
+// one chunk of rows, all pointers on the device: scoring (candidate slices) -> merge into d_out / d_scores
+template <class Query>
+static int sliced_chunk(tfr_model* m, const Query& q, const TopkPlan& p, const int32_t* d_ids, int64_t rows, int32_t k,
+                        const int64_t* d_indptr, const int32_t* d_excl, int32_t* d_out, float* d_scores) {
     HIPCHK(m->tk_part.reserve(pow2_cap(rows * p.slices * k), m->stream));
-    TopkArgs a;
-    memset(&a, 0, sizeof(a));
-    a.P = t.P; a.bu = t.bu; a.Q = t.Q; a.bi = t.bi; a.mu = t.mu;
-    a.users = d_users; a.indptr = d_indptr; a.excl = d_excl; a.excl_bad = m->tk_bad;
-    a.part = m->tk_part; a.err = m->d_err;
-    a.n_rows = rows; a.U = t.U; a.n_items = t.n_items;
-    a.D = m->D; a.k = k; a.slices = p.slices; a.item_abs = t.item_abs;
-    launch_topk_score(a, p, m->stream);
+    SlicedArgs c = {};
+    c.rows = d_ids; c.indptr = d_indptr; c.excl = d_excl; c.excl_bad = m->tk_bad;
+    c.part = m->tk_part; c.err = m->d_err;
+    c.n_rows = rows; c.D = m->D; c.k = k; c.slices = p.slices; c.item_abs = q.item_abs;
+    q.score(c, p, m->stream);
     HIPCHK(hipGetLastError());
     TopkMergeArgs g;
     memset(&g, 0, sizeof(g));
-    g.part = m->tk_part; g.items_out = d_items; g.scores_out = d_scores; g.n_rows = rows; g.k = k; g.slices = p.slices;
+    g.part = m->tk_part; g.items_out = d_out; g.scores_out = d_scores; g.n_rows = rows; g.k = k; g.slices = p.slices;
     launch_topk_merge(g, m->stream);
     HIPCHK(hipGetLastError());
     return TFR_OK;
 }
 
-static int topk_prepare(tfr_model* m, int32_t k, int64_t n, int64_t n_items, TopkPlan* p) {
-    if (!topk_plan(k, n, n_items, p)) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
-    HIPCHK(m->tk_bad.reserve(1, m->stream));
-    HIPCHK(hipMemsetAsync(m->tk_bad, 0, sizeof(int32_t), m->stream));
-    return settle_q(m);                                  // item rows the fused big-table step left in q_alt come back first
-}
-
-// the host entries: ids and the exclusion CSR are checked here, before any device work; then chunk by chunk staged, scored,
+// the host entries, their ids and exclusion CSR checked by the family before any device work: chunk by chunk staged, scored,
 // merged and copied back.  Outputs are written only when every check passed.
-static int topk_host(tfr_model* m, const TopkTables& t, const int32_t* users, int64_t n, int32_t k, const int64_t* indptr,
-                     const int32_t* excl, int32_t* items_out, float* scores_out) {
-    if (n < 0) return fail(TFR_ERR_ARG, "top-K: negative n_users");
-    if (k < 1 || k > TOPK_KMAX) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
-    if (n == 0) return TFR_OK;
-    if (!users || !items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
-    if (indptr && !excl && indptr[n] > indptr[0]) return fail(TFR_ERR_ARG, "top-K: exclusion indptr without items");
-    int rc = check_ids("top-K", "user id", users, n, t.U);
-    if (rc || (indptr && (rc = check_csr("top-K", false, indptr, excl, n, t.n_items)))) return rc;
+template <class Query>
+static int sliced_host(tfr_model* m, const Query& q, const int32_t* ids, int64_t n, int32_t k, const int64_t* indptr,
+                       const int32_t* excl, int32_t* ids_out, float* scores_out) {
     TopkPlan p;
-    if ((rc = topk_prepare(m, k, n, t.n_items, &p))) return rc;
+    int rc = sliced_begin(m, q, k, n, &p);
+    if (rc) return rc;
     HIPCHK(m->tk_users.reserve(pow2_cap(p.chunk), m->stream));
     HIPCHK(m->tk_items.reserve(pow2_cap(p.chunk * k), m->stream));
     if (scores_out) HIPCHK(m->tk_scores.reserve(pow2_cap(p.chunk * k), m->stream));
     std::vector<int64_t> rebased;
     for (int64_t c0 = 0; c0 < n; c0 += p.chunk) {
         const int64_t rows = n - c0 < p.chunk ? n - c0 : p.chunk;
-        HIPCHK(hipMemcpyAsync(m->tk_users, users + c0, (size_t)rows * 4, hipMemcpyHostToDevice, m->stream));
+        HIPCHK(hipMemcpyAsync(m->tk_users, ids + c0, (size_t)rows * 4, hipMemcpyHostToDevice, m->stream));
         const int64_t* d_ip = nullptr;
         const int32_t* d_ex = nullptr;
         if (indptr) {
@@ -3213,9 +3234,9 @@ static int topk_host(tfr_model* m, const TopkTables& t, const int32_t* users, in
             d_ip = m->tk_indptr;
             d_ex = m->tk_excl;
         }
-        if ((rc = topk_chunk(m, t, p, m->tk_users, rows, k, d_ip, d_ex, m->tk_items, scores_out ? m->tk_scores : nullptr)))
+        if ((rc = sliced_chunk(m, q, p, m->tk_users, rows, k, d_ip, d_ex, m->tk_items, scores_out ? m->tk_scores : nullptr)))
             return rc;
-        HIPCHK(hipMemcpyAsync(items_out + c0 * k, m->tk_items, (size_t)rows * k * 4, hipMemcpyDeviceToHost, m->stream));
+        HIPCHK(hipMemcpyAsync(ids_out + c0 * k, m->tk_items, (size_t)rows * k * 4, hipMemcpyDeviceToHost, m->stream));
         if (scores_out)
             HIPCHK(hipMemcpyAsync(scores_out + c0 * k, m->tk_scores, (size_t)rows * k * 4, hipMemcpyDeviceToHost, m->stream));
         HIPCHK(hipStreamSynchronize(m->stream));         // the staged inputs are rewritten by the next chunk
@@ -3223,44 +3244,67 @@ static int topk_host(tfr_model* m, const TopkTables& t, const int32_t* users, in
     return check_device_error(m);
 }
 
-// the device entry: every pointer on the device, the exclusion CSR checked there; no synchronisation
-static int topk_dev(tfr_model* m, const TopkTables& t, const int32_t* d_users, int64_t n, int32_t k,
-                    const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t* d_items_out, float* d_scores_out) {
-    if (n < 0) return fail(TFR_ERR_ARG, "top-K: negative n_users");
-    if (k < 1 || k > TOPK_KMAX) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
-    if (n == 0) return TFR_OK;
-    if (!d_users || !d_items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
-    if (d_excl_indptr && !d_excl_items) return fail(TFR_ERR_ARG, "top-K: exclusion indptr without items");
+// the device entries: every pointer on the device, the exclusion CSR checked there; no synchronisation
+template <class Query>
+static int sliced_dev(tfr_model* m, const Query& q, const int32_t* d_ids, int64_t n, int32_t k, const int64_t* d_indptr,
+                      const int32_t* d_excl, int32_t* d_ids_out, float* d_scores_out) {
     TopkPlan p;
-    int rc = topk_prepare(m, k, n, t.n_items, &p);
+    int rc = sliced_begin(m, q, k, n, &p);
     if (rc) return rc;
-    if (d_excl_indptr) {
-        launch_topk_check_excl(d_excl_indptr, d_excl_items, n, t.n_items, m->tk_bad, m->d_err, m->stream);
+    if (d_indptr) {
+        launch_topk_check_excl(d_indptr, d_excl, n, q.excl_rows, m->tk_bad, m->d_err, m->stream);
         HIPCHK(hipGetLastError());
     }
     for (int64_t c0 = 0; c0 < n; c0 += p.chunk) {
         const int64_t rows = n - c0 < p.chunk ? n - c0 : p.chunk;
-        if ((rc = topk_chunk(m, t, p, d_users + c0, rows, k, d_excl_indptr ? d_excl_indptr + c0 : nullptr, d_excl_items,
-                             d_items_out + c0 * k, d_scores_out ? d_scores_out + c0 * k : nullptr)))
+        if ((rc = sliced_chunk(m, q, p, d_ids + c0, rows, k, d_indptr ? d_indptr + c0 : nullptr, d_excl, d_ids_out + c0 * k,
+                               d_scores_out ? d_scores_out + c0 * k : nullptr)))
             return rc;
     }
     return TFR_OK;
+}
+
+// ---- top-K recommendation: its query, its argument checks and its entries ---------------------------------------------------
+struct TopkQuery : SlicedQuery {
+    TopkTables t;
+    explicit TopkQuery(const TopkTables& t_) : SlicedQuery{"top-K", t_.n_items, t_.n_items, t_.item_abs, true}, t(t_) {}
+    void score(const SlicedArgs& c, const TopkPlan& p, hipStream_t s) const {
+        TopkArgs a = {};
+        static_cast<SlicedArgs&>(a) = c;
+        a.P = t.P; a.bu = t.bu; a.Q = t.Q; a.bi = t.bi; a.mu = t.mu;
+        a.U = t.U; a.n_items = t.n_items;
+        launch_topk_score(a, p, s);
+    }
+};
+
+static int topk_host(tfr_model* m, const TopkTables& t, const int32_t* users, int64_t n, int32_t k, const int64_t* indptr,
+                     const int32_t* excl, int32_t* items_out, float* scores_out) {
+    if (n < 0) return fail(TFR_ERR_ARG, "top-K: negative n_users");
+    int rc = check_k("top-K", k);
+    if (rc || n == 0) return rc;
+    if (!users || !items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
+    if (indptr && !excl && indptr[n] > indptr[0]) return fail(TFR_ERR_ARG, "top-K: exclusion indptr without items");
+    if ((rc = check_ids("top-K", "user id", users, n, t.U))) return rc;
+    if (indptr && (rc = check_csr("top-K", false, indptr, excl, n, t.n_items))) return rc;
+    return sliced_host(m, TopkQuery(t), users, n, k, indptr, excl, items_out, scores_out);
+}
+
+static int topk_dev(tfr_model* m, const TopkTables& t, const int32_t* d_users, int64_t n, int32_t k,
+                    const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t* d_items_out, float* d_scores_out) {
+    if (n < 0) return fail(TFR_ERR_ARG, "top-K: negative n_users");
+    const int rc = check_k("top-K", k);
+    if (rc || n == 0) return rc;
+    if (!d_users || !d_items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
+    if (d_excl_indptr && !d_excl_items) return fail(TFR_ERR_ARG, "top-K: exclusion indptr without items");
+    return sliced_dev(m, TopkQuery(t), d_users, n, k, d_excl_indptr, d_excl_items, d_items_out, d_scores_out);
 }
 
 extern "C" {
 
 int tfr_topk_plan(int32_t dim, int32_t k, int64_t n_users, int64_t item_num, int64_t* lds_bytes, int32_t* users_per_block,
                   int32_t* item_slices, int64_t* user_chunk) {
-    int G, VEC;
-    if (!geometry(dim, &G, &VEC)) return fail(TFR_ERR_ARG, "unsupported dim %d", dim);
-    if (n_users < 0 || item_num < 1) return fail(TFR_ERR_ARG, "top-K plan: n_users >= 0 and item_num >= 1");
-    TopkPlan p;
-    if (!topk_plan(k, n_users, item_num, &p)) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
-    if (lds_bytes) *lds_bytes = (int64_t)(p.lds_score > p.lds_merge ? p.lds_score : p.lds_merge);
-    if (users_per_block) *users_per_block = p.upb;
-    if (item_slices) *item_slices = p.slices;
-    if (user_chunk) *user_chunk = p.chunk;
-    return TFR_OK;
+    return sliced_plan_entry("top-K", "n_users >= 0 and item_num >= 1", dim, k, n_users, item_num, lds_bytes, users_per_block,
+                             item_slices, user_chunk);
 }
 
 int tfr_topk(tfr_model* m, const int32_t* users, int64_t n_users, int32_t k, const int64_t* excl_indptr,
@@ -3280,10 +3324,10 @@ int tfr_fm_topk(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_
     if (!f) return fail(TFR_ERR_ARG, "null model");
     tfr_model* m = f->m;
     HIPCHK(hipSetDevice(m->device));
-    if (k < 1 || k > TOPK_KMAX) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
     TopkTables t;
-    const int rc = fm_topk_tables(m, "top-K", item_lo, item_hi, &t);
-    return rc ? rc : topk_host(m, t, user_features, n_users, k, excl_indptr, excl_items, items_out, scores_out);
+    int rc = check_k("top-K", k);
+    if (rc || (rc = fm_topk_tables(m, "top-K", item_lo, item_hi, &t))) return rc;
+    return topk_host(m, t, user_features, n_users, k, excl_indptr, excl_items, items_out, scores_out);
 }
 
 }  // extern "C"

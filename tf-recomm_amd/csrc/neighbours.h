@@ -1,5 +1,5 @@
-// neighbours.h - nearest neighbours in factor space (tfr_neighbours*): launch plan, argument blocks and launchers shared by
-// neighbours.hip and api.hip.
+// neighbours.h - nearest neighbours in factor space (tfr_neighbours*): the argument block and launchers shared by
+// neighbours.hip and api.hip; the launch plan is topk.h's.
 //
 // One table T [R, D] gives the query rows and the candidate rows.  dot(a, b) = the f32 fmaf chain over f = 0..D-1 ascending
 // from +0 of T[a,f] * T[b,f] (the chain of topk.h, no bias terms); cosine(a, b) = (dot(a, b) * rn[a]) * rn[b] with
@@ -14,24 +14,15 @@ namespace tfr {
 
 constexpr int NB_RNORM_ROWS = 256;                     // rows per k_row_rnorm block: one lane per row, 64 rows per wave
 
-// The scoring block is the top-K block with the query rows in the users' place and the candidate range in the items':
-// the same queue capacity, rows per block, slices, chunking and LDS sizes.
-typedef TopkPlan NbPlan;
-inline bool nb_plan(int k, int64_t n_rows, int64_t n_cand, NbPlan* p) { return topk_plan(k, n_rows, n_cand, p); }
-
-struct NbArgs {
-    const float* T;                                    // [R, D] query and candidate rows
+// The scoring block is the top-K block (score_tile.h sliced_topk_block) with the query rows in the users' place and the
+// candidate range in the items': TopkPlan / topk_plan give its queue capacity, rows per block, slices, chunking and LDS sizes.
+struct NbArgs : SlicedArgs {
+    const float* T;                                    // [R, D] query and candidate rows; excl holds row ids of T, sorted
     const float* rn;                                   // [R] inverse norms: cosine; NULL: dot
-    const int32_t* rows;                               // [n_rows] this chunk's query rows
-    const int64_t* indptr; const int32_t* excl;        // exclusion CSR rows of this chunk (row ids of T, sorted), may be NULL
-    const int32_t* excl_bad;                           // nonzero: the exclusion CSR failed its check, it is not read
-    uint64_t* part;                                    // out [n_rows, slices, k] keys, descending
-    int32_t* err;
-    int64_t n_rows, R, lo, hi;                         // candidates are rows [lo, hi)
-    int32_t D, k, slices, item_abs;
+    int64_t R, lo, hi;                                 // candidates are rows [lo, hi)
 };
 
-void launch_nb_score(const NbArgs& a, const NbPlan& p, hipStream_t s);
+void launch_nb_score(const NbArgs& a, const TopkPlan& p, hipStream_t s);
 // rn[r] for r in [0, R): |T| and T have the same squares, so item_abs does not enter
 void launch_row_rnorm(const float* T, int64_t R, int32_t D, float* rn, hipStream_t s);
 

@@ -1,5 +1,5 @@
 // neighbours_api.inc.h - the tfr_*neighbours* entry points (include/tfrecomm.h), compiled inside api.hip beside
-// the top-K entries whose staging buffers, exclusion check, error flag and merge they share.
+// the top-K entries whose driver (sliced_host / sliced_dev: plan, staging buffers, exclusion check, error flag, merge) they run.
 //
 // A query on the model's stream:
 //   k_row_rnorm        cosine only, and only when the table's cached rn is stale (nb_rnorm) or its rows are rebuilt per call
@@ -23,7 +23,7 @@ static int nb_svd_table(tfr_model* m, int32_t which, NbTable* t) {
 
 static int nb_check_args(const NbTable& t, int32_t metric, int64_t n, int32_t k, int64_t lo, int64_t hi) {
     if (n < 0) return fail(TFR_ERR_ARG, "%s: negative n", NB_WHO);
-    if (k < 1 || k > TOPK_KMAX) return fail(TFR_ERR_ARG, "%s: k must be in [1, %d] (got %d)", NB_WHO, TOPK_KMAX, k);
+    if (int rc = check_k(NB_WHO, k)) return rc;
     if (metric != TFR_NB_DOT && metric != TFR_NB_COSINE)
         return fail(TFR_ERR_ARG, "%s: metric must be TFR_NB_DOT or TFR_NB_COSINE (got %d)", NB_WHO, metric);
     if (lo < 0 || hi <= lo || hi > t.R)
@@ -50,65 +50,18 @@ static int nb_rnorm(tfr_model* m, const NbTable& t, int32_t metric, const float*
     return TFR_OK;
 }
 
-// one chunk of query rows, all pointers on the device: scoring (candidate slices) -> merge into ids / scores
-static int nb_chunk(tfr_model* m, const NbTable& t, const float* rn, const NbPlan& p, const int32_t* d_rows, int64_t rows,
-                    int32_t k, const int64_t* d_indptr, const int32_t* d_excl, int64_t lo, int64_t hi, int32_t* d_ids,
-                    float* d_scores) {
-    HIPCHK(m->tk_part.reserve(pow2_cap(rows * p.slices * k), m->stream));
-    NbArgs a;
-    memset(&a, 0, sizeof(a));
-    a.T = t.T; a.rn = rn; a.rows = d_rows; a.indptr = d_indptr; a.excl = d_excl; a.excl_bad = m->tk_bad;
-    a.part = m->tk_part; a.err = m->d_err;
-    a.n_rows = rows; a.R = t.R; a.lo = lo; a.hi = hi;
-    a.D = m->D; a.k = k; a.slices = p.slices; a.item_abs = t.item_abs;
-    launch_nb_score(a, p, m->stream);
-    HIPCHK(hipGetLastError());
-    TopkMergeArgs g;
-    memset(&g, 0, sizeof(g));
-    g.part = m->tk_part; g.items_out = d_ids; g.scores_out = d_scores; g.n_rows = rows; g.k = k; g.slices = p.slices;
-    launch_topk_merge(g, m->stream);
-    HIPCHK(hipGetLastError());
-    return TFR_OK;
-}
-
-// the host entries: ids and the exclusion CSR are checked here, before any device work; then chunk by chunk staged, scored,
-// merged and copied back (the staging buffers of topk_host).  Outputs are written only when every check passed.
-static int nb_host(tfr_model* m, const NbTable& t, const float* rn, const int32_t* rows, int64_t n, int32_t k,
-                   const int64_t* indptr, const int32_t* excl, int64_t lo, int64_t hi, int32_t* ids_out, float* scores_out) {
-    int rc;
-    NbPlan p;
-    if (!nb_plan(k, n, hi - lo, &p)) return fail(TFR_ERR_ARG, "%s: no plan for k %d", NB_WHO, k);
-    HIPCHK(m->tk_bad.reserve(1, m->stream));
-    HIPCHK(hipMemsetAsync(m->tk_bad, 0, sizeof(int32_t), m->stream));
-    HIPCHK(m->tk_users.reserve(pow2_cap(p.chunk), m->stream));
-    HIPCHK(m->tk_items.reserve(pow2_cap(p.chunk * k), m->stream));
-    if (scores_out) HIPCHK(m->tk_scores.reserve(pow2_cap(p.chunk * k), m->stream));
-    std::vector<int64_t> rebased;
-    for (int64_t c0 = 0; c0 < n; c0 += p.chunk) {
-        const int64_t nr = n - c0 < p.chunk ? n - c0 : p.chunk;
-        HIPCHK(hipMemcpyAsync(m->tk_users, rows + c0, (size_t)nr * 4, hipMemcpyHostToDevice, m->stream));
-        const int64_t* d_ip = nullptr;
-        const int32_t* d_ex = nullptr;
-        if (indptr) {
-            const int64_t e0 = indptr[c0], nnz = indptr[c0 + nr] - e0;
-            rebased.resize((size_t)nr + 1);
-            for (int64_t r = 0; r <= nr; ++r) rebased[(size_t)r] = indptr[c0 + r] - e0;
-            HIPCHK(m->tk_indptr.reserve(pow2_cap(nr + 1), m->stream));
-            if (nnz > 0) HIPCHK(m->tk_excl.reserve(pow2_cap(nnz), m->stream));
-            HIPCHK(hipMemcpyAsync(m->tk_indptr, rebased.data(), (size_t)(nr + 1) * 8, hipMemcpyHostToDevice, m->stream));
-            if (nnz > 0) HIPCHK(hipMemcpyAsync(m->tk_excl, excl + e0, (size_t)nnz * 4, hipMemcpyHostToDevice, m->stream));
-            d_ip = m->tk_indptr;
-            d_ex = m->tk_excl;
-        }
-        if ((rc = nb_chunk(m, t, rn, p, m->tk_users, nr, k, d_ip, d_ex, lo, hi, m->tk_items, scores_out ? m->tk_scores : nullptr)))
-            return rc;
-        HIPCHK(hipMemcpyAsync(ids_out + c0 * k, m->tk_items, (size_t)nr * k * 4, hipMemcpyDeviceToHost, m->stream));
-        if (scores_out)
-            HIPCHK(hipMemcpyAsync(scores_out + c0 * k, m->tk_scores, (size_t)nr * k * 4, hipMemcpyDeviceToHost, m->stream));
-        HIPCHK(hipStreamSynchronize(m->stream));         // the staged inputs are rewritten by the next chunk
+// a query for the driver: table t, rn of nb_rnorm, candidates [lo, hi).  The callers settle the item rows, before rn is built.
+struct NbQuery : SlicedQuery {
+    NbTable t; const float* rn; int64_t lo, hi;
+    NbQuery(const NbTable& t_, const float* rn_, int64_t lo_, int64_t hi_)
+        : SlicedQuery{NB_WHO, t_.R, hi_ - lo_, t_.item_abs, false}, t(t_), rn(rn_), lo(lo_), hi(hi_) {}
+    void score(const SlicedArgs& c, const TopkPlan& p, hipStream_t s) const {
+        NbArgs a = {};
+        static_cast<SlicedArgs&>(a) = c;
+        a.T = t.T; a.rn = rn; a.R = t.R; a.lo = lo; a.hi = hi;
+        launch_nb_score(a, p, s);
     }
-    return check_device_error(m);
-}
+};
 
 // what the host entries check before any device work
 static int nb_host_checks(const NbTable& t, int32_t metric, const int32_t* rows, int64_t n, int32_t k, const int64_t* indptr,
@@ -119,27 +72,6 @@ static int nb_host_checks(const NbTable& t, int32_t metric, const int32_t* rows,
     if (indptr && !excl && indptr[n] > indptr[0]) return fail(TFR_ERR_ARG, "%s: exclusion indptr without rows", NB_WHO);
     if ((rc = check_ids(NB_WHO, "row id", rows, n, t.R))) return rc;
     return indptr ? check_csr(NB_WHO, false, indptr, excl, n, t.R) : TFR_OK;
-}
-
-// the device entry: every pointer on the device, the exclusion CSR checked there; no synchronisation
-static int nb_dev(tfr_model* m, const NbTable& t, const float* rn, const int32_t* d_rows, int64_t n, int32_t k,
-                  const int64_t* d_indptr, const int32_t* d_excl, int64_t lo, int64_t hi, int32_t* d_ids_out, float* d_scores_out) {
-    int rc;
-    NbPlan p;
-    if (!nb_plan(k, n, hi - lo, &p)) return fail(TFR_ERR_ARG, "%s: no plan for k %d", NB_WHO, k);
-    HIPCHK(m->tk_bad.reserve(1, m->stream));
-    HIPCHK(hipMemsetAsync(m->tk_bad, 0, sizeof(int32_t), m->stream));
-    if (d_indptr) {
-        launch_topk_check_excl(d_indptr, d_excl, n, t.R, m->tk_bad, m->d_err, m->stream);
-        HIPCHK(hipGetLastError());
-    }
-    for (int64_t c0 = 0; c0 < n; c0 += p.chunk) {
-        const int64_t nr = n - c0 < p.chunk ? n - c0 : p.chunk;
-        if ((rc = nb_chunk(m, t, rn, p, d_rows + c0, nr, k, d_indptr ? d_indptr + c0 : nullptr, d_excl, lo, hi,
-                           d_ids_out + c0 * k, d_scores_out ? d_scores_out + c0 * k : nullptr)))
-            return rc;
-    }
-    return TFR_OK;
 }
 
 static int nb_dev_checks(const NbTable& t, int32_t metric, const int32_t* d_rows, int64_t n, int32_t k, const int64_t* d_indptr,
@@ -173,31 +105,36 @@ static int nb_pp_table(tfr_svdpp* h, int32_t which, NbTable* t) {
     return TFR_OK;
 }
 
+// an SVD / SVD++ entry once its table is named: checks -> (SVD++ users: e_u of every user) -> settle -> rn -> the driver.
+// dev: every pointer is on the device.  h is NULL for the SVD model.
+static int nb_run(tfr_model* m, tfr_svdpp* h, const NbTable& t, bool dev, int32_t metric, const int32_t* rows, int64_t n,
+                  int32_t k, const int64_t* indptr, const int32_t* excl, int64_t lo, int64_t hi, int32_t* ids_out,
+                  float* scores_out) {
+    int rc = dev ? nb_dev_checks(t, metric, rows, n, k, indptr, excl, lo, hi, ids_out)
+                 : nb_host_checks(t, metric, rows, n, k, indptr, excl, lo, hi, ids_out);
+    if (rc || n == 0) return rc;
+    if (h && t.fleeting && (rc = pp_peff_all(h))) return rc;
+    const float* rn;
+    if ((rc = settle_q(m)) || (rc = nb_rnorm(m, t, metric, &rn))) return rc;
+    const NbQuery q(t, rn, lo, hi);
+    return dev ? sliced_dev(m, q, rows, n, k, indptr, excl, ids_out, scores_out)
+               : sliced_host(m, q, rows, n, k, indptr, excl, ids_out, scores_out);
+}
+
 extern "C" {
 
 int tfr_neighbours_plan(int32_t dim, int32_t k, int64_t n, int64_t n_candidates, int64_t* lds_bytes, int32_t* rows_per_block,
                         int32_t* slices, int64_t* row_chunk) {
-    int G, VEC;
-    if (!geometry(dim, &G, &VEC)) return fail(TFR_ERR_ARG, "unsupported dim %d", dim);
-    if (n < 0 || n_candidates < 1) return fail(TFR_ERR_ARG, "%s plan: n >= 0 and n_candidates >= 1", NB_WHO);
-    NbPlan p;
-    if (!nb_plan(k, n, n_candidates, &p)) return fail(TFR_ERR_ARG, "%s: k must be in [1, %d] (got %d)", NB_WHO, TOPK_KMAX, k);
-    if (lds_bytes) *lds_bytes = (int64_t)(p.lds_score > p.lds_merge ? p.lds_score : p.lds_merge);
-    if (rows_per_block) *rows_per_block = p.upb;
-    if (slices) *slices = p.slices;
-    if (row_chunk) *row_chunk = p.chunk;
-    return TFR_OK;
+    return sliced_plan_entry(NB_WHO, "n >= 0 and n_candidates >= 1", dim, k, n, n_candidates, lds_bytes, rows_per_block, slices,
+                             row_chunk);
 }
 
 int tfr_neighbours(tfr_model* m, int32_t which, int32_t metric, const int32_t* rows, int64_t n, int32_t k,
                    const int64_t* excl_indptr, const int32_t* excl, int64_t lo, int64_t hi, int32_t* ids_out, float* scores_out) {
     MODEL_ENTER(m);
     NbTable t;
-    int rc = nb_svd_table(m, which, &t);
-    if (rc || (rc = nb_host_checks(t, metric, rows, n, k, excl_indptr, excl, lo, hi, ids_out)) || n == 0) return rc;
-    const float* rn;
-    if ((rc = settle_q(m)) || (rc = nb_rnorm(m, t, metric, &rn))) return rc;
-    return nb_host(m, t, rn, rows, n, k, excl_indptr, excl, lo, hi, ids_out, scores_out);
+    const int rc = nb_svd_table(m, which, &t);
+    return rc ? rc : nb_run(m, nullptr, t, false, metric, rows, n, k, excl_indptr, excl, lo, hi, ids_out, scores_out);
 }
 
 int tfr_neighbours_dev(tfr_model* m, int32_t which, int32_t metric, const int32_t* d_rows, int64_t n, int32_t k,
@@ -205,11 +142,8 @@ int tfr_neighbours_dev(tfr_model* m, int32_t which, int32_t metric, const int32_
                        float* d_scores_out) {
     MODEL_ENTER(m);
     NbTable t;
-    int rc = nb_svd_table(m, which, &t);
-    if (rc || (rc = nb_dev_checks(t, metric, d_rows, n, k, d_excl_indptr, d_excl, lo, hi, d_ids_out)) || n == 0) return rc;
-    const float* rn;
-    if ((rc = settle_q(m)) || (rc = nb_rnorm(m, t, metric, &rn))) return rc;
-    return nb_dev(m, t, rn, d_rows, n, k, d_excl_indptr, d_excl, lo, hi, d_ids_out, d_scores_out);
+    const int rc = nb_svd_table(m, which, &t);
+    return rc ? rc : nb_run(m, nullptr, t, true, metric, d_rows, n, k, d_excl_indptr, d_excl, lo, hi, d_ids_out, d_scores_out);
 }
 
 int tfr_svdpp_neighbours(tfr_svdpp* h, int32_t which, int32_t metric, const int32_t* rows, int64_t n, int32_t k,
@@ -217,12 +151,8 @@ int tfr_svdpp_neighbours(tfr_svdpp* h, int32_t which, int32_t metric, const int3
                          float* scores_out) {
     PP_ENTER(h);
     NbTable t;
-    int rc = nb_pp_table(h, which, &t);
-    if (rc || (rc = nb_host_checks(t, metric, rows, n, k, excl_indptr, excl, lo, hi, ids_out)) || n == 0) return rc;
-    if (which == TFR_NB_USERS && (rc = pp_peff_all(h))) return rc;
-    const float* rn;
-    if ((rc = settle_q(m)) || (rc = nb_rnorm(m, t, metric, &rn))) return rc;
-    return nb_host(m, t, rn, rows, n, k, excl_indptr, excl, lo, hi, ids_out, scores_out);
+    const int rc = nb_pp_table(h, which, &t);
+    return rc ? rc : nb_run(m, h, t, false, metric, rows, n, k, excl_indptr, excl, lo, hi, ids_out, scores_out);
 }
 
 int tfr_svdpp_neighbours_dev(tfr_svdpp* h, int32_t which, int32_t metric, const int32_t* d_rows, int64_t n, int32_t k,
@@ -230,12 +160,8 @@ int tfr_svdpp_neighbours_dev(tfr_svdpp* h, int32_t which, int32_t metric, const 
                              float* d_scores_out) {
     PP_ENTER(h);
     NbTable t;
-    int rc = nb_pp_table(h, which, &t);
-    if (rc || (rc = nb_dev_checks(t, metric, d_rows, n, k, d_excl_indptr, d_excl, lo, hi, d_ids_out)) || n == 0) return rc;
-    if (which == TFR_NB_USERS && (rc = pp_peff_all(h))) return rc;
-    const float* rn;
-    if ((rc = settle_q(m)) || (rc = nb_rnorm(m, t, metric, &rn))) return rc;
-    return nb_dev(m, t, rn, d_rows, n, k, d_excl_indptr, d_excl, lo, hi, d_ids_out, d_scores_out);
+    const int rc = nb_pp_table(h, which, &t);
+    return rc ? rc : nb_run(m, h, t, true, metric, d_rows, n, k, d_excl_indptr, d_excl, lo, hi, d_ids_out, d_scores_out);
 }
 
 int tfr_fm_neighbours(tfr_fm* f, int32_t metric, const int32_t* features, int64_t n, int32_t k, const int64_t* excl_indptr,
@@ -248,7 +174,7 @@ int tfr_fm_neighbours(tfr_fm* f, int32_t metric, const int32_t* features, int64_
     if (rc || n == 0) return rc;
     const float* rn;
     if ((rc = nb_rnorm(m, t, metric, &rn))) return rc;
-    return nb_host(m, t, rn, features, n, k, excl_indptr, excl, lo, hi, ids_out, scores_out);
+    return sliced_host(m, NbQuery(t, rn, lo, hi), features, n, k, excl_indptr, excl, ids_out, scores_out);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // score_tile.h - the pieces topk.hip, rank.hip and neighbours.hip share: the 64-bit ordering key of a scored pair, the one-wave
-// bitonic sort of keys in LDS, the queue compaction built on it, and the MFMA tile that scores 32 items against 32 user
-// columns.
+// bitonic sort of keys in LDS, the queue compaction built on it, the MFMA tile that scores 32 items against 32 user
+// columns, and sliced_topk_block, the whole scoring block of k_topk_score and k_nb_score, which differ only in their scorer
+// (DESIGN §11, §13, §17).
 //
 // key(s, item) = (order-preserving uint32 of s) << 32 | ~item: one 64-bit compare orders by score descending, then item id
 // ascending; every non-NaN score gives a key above 0, so key 0 marks an empty slot.
@@ -8,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "svd_kernels.h"
+#include "topk.h"
 
 namespace tfr {
 
@@ -110,6 +112,97 @@ __device__ __forceinline__ f32x16 mfma_tile_dot(const float* qrow, const float* 
         }
     }
     return acc;
+}
+
+// The scoring block of "the best k candidates by a tile score" (k_topk_score, k_nb_score).  A block owns a tile of UPB query
+// rows (the 32 columns of a 32x32x2 f32 MFMA) and one slice of the candidates [cand_lo, cand_hi).  Every round each of its 4
+// waves scores a 32-candidate sub-tile against the tile's queries and appends the keys that beat its query's running k-th key
+// (and are eligible, not NaN and not excluded, tested in that order) to that query's LDS queue.  Between rounds a queue that
+// could not take another round is sorted (bitonic, one wave), cut to k and its threshold raised.  At the end every queue is
+// sorted and its first k keys go to part[row, slice].  Query ids outside [0, id_rows) set err bit 0 and score nothing.
+// Scorer(a, qid) is built once per lane: ABS_B, brow (the query's B row), arow(cand), eligible(cand), score(dot, cand).
+template <int UPB, int CAP, bool V4, class Scorer, class Args>
+__device__ __forceinline__ void sliced_topk_block(const Args& a, int64_t id_rows, int64_t cand_lo, int64_t cand_hi) {
+    __shared__ uint64_t queue[UPB * CAP];
+    __shared__ uint64_t thr[UPB];
+    __shared__ int32_t cnt[UPB];
+    static_assert(sizeof(queue) + sizeof(thr) + sizeof(cnt) == topk_score_static_lds(UPB, CAP),
+                  "topk_plan reports a different LDS size than the block declares");
+    static_assert(CAP - TOPK_ROUND >= (CAP == 256 ? 128 : TOPK_KMAX), "a queue must hold k plus one round of appends");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = lane >> 5, c = lane & 31;
+    const int j = c & (UPB - 1);                       // query of this lane's accumulator column
+    const bool own_col = c < UPB;                      // UPB 16: columns 16..31 repeat 0..15 and select nothing
+    const int64_t row = (int64_t)blockIdx.x * UPB + j;
+    const int slice = blockIdx.y;
+    const int k = a.k;
+
+    int32_t qid = -1;
+    if (row < a.n_rows) {
+        qid = a.rows[row];
+        if (qid < 0 || (int64_t)qid >= id_rows) {
+            if (own_col && h == 0) atomicOr(a.err, 1);
+            qid = -1;
+        }
+    }
+    const bool live = own_col && qid >= 0;
+    int64_t xlo = 0, xhi = 0;
+    if (live && a.indptr && *a.excl_bad == 0) { xlo = a.indptr[row]; xhi = a.indptr[row + 1]; }
+    const Scorer sc(a, qid);
+    for (int t = threadIdx.x; t < UPB; t += 256) { cnt[t] = 0; thr[t] = 0; }
+    __syncthreads();
+
+    const int64_t n_cand = cand_hi - cand_lo;
+    const int64_t per = ((n_cand + a.slices - 1) / a.slices + TOPK_ROUND - 1) / TOPK_ROUND * TOPK_ROUND;
+    const int64_t s_lo = cand_lo + (int64_t)slice * per;
+    const int64_t s_hi = s_lo + per < cand_hi ? s_lo + per : cand_hi;
+    const int64_t rounds = s_hi > s_lo ? (s_hi - s_lo + TOPK_ROUND - 1) / TOPK_ROUND : 0;
+
+    for (int64_t rd = 0; rd < rounds; ++rd) {
+        const int64_t base = s_lo + rd * TOPK_ROUND + wave * TOPK_SUB;
+        int64_t my_cand = base + c;                    // A row = candidate; past the slice: a row inside it, result dropped
+        if (my_cand >= s_hi) my_cand = s_hi - 1;
+        const f32x16 acc = mfma_tile_dot<V4, Scorer::ABS_B>(sc.arow(my_cand), sc.brow, a.D, a.item_abs, h);
+        // C[candidate row][query column]: this lane holds query j, candidates base + (r&3) + 8(r>>2) + 4h
+        const uint64_t th = thr[j];
+        if (live) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int64_t cand = base + (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (cand < s_hi && sc.eligible(cand)) {
+                    const float s = sc.score(acc[r], cand);
+                    if (!__builtin_isnan(s)) {
+                        const uint64_t key = topk_key(s, cand);
+                        if (key > th && !(xhi > xlo && topk_excluded(a.excl, xlo, xhi, (int32_t)cand))) {
+                            const int pos = atomicAdd(&cnt[j], 1);
+                            queue[j * CAP + pos] = key;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        for (int u = wave; u < UPB; u += TOPK_WAVES)
+            if (cnt[u] > CAP - TOPK_ROUND) topk_compact<CAP>(queue + u * CAP, cnt + u, thr + u, k, lane);
+        __syncthreads();
+    }
+    for (int u = wave; u < UPB; u += TOPK_WAVES) {
+        const int64_t rw = (int64_t)blockIdx.x * UPB + u;
+        if (rw >= a.n_rows) continue;
+        if (cnt[u] > 0) topk_compact<CAP>(queue + u * CAP, cnt + u, thr + u, k, lane);
+        const int n = cnt[u];
+        uint64_t* dst = a.part + ((size_t)rw * a.slices + slice) * k;
+        for (int q = lane; q < k; q += 64) dst[q] = q < n ? queue[u * CAP + q] : 0;
+    }
+}
+
+// launches the instantiation of a score kernel that the plan's queue capacity and the row width pick
+template <class Args>
+static void launch_score_kernel(void (*k32v)(Args), void (*k32)(Args), void (*k16v)(Args), void (*k16)(Args), const Args& a,
+                                const TopkPlan& p, hipStream_t s) {
+    const dim3 g((unsigned)((a.n_rows + p.upb - 1) / p.upb), (unsigned)p.slices);
+    const bool v4 = (a.D & 3) == 0;
+    hipLaunchKernelGGL(p.cap == 256 ? (v4 ? k32v : k32) : (v4 ? k16v : k16), g, dim3(256), 0, s, a);
 }
 
 }  // namespace tfr

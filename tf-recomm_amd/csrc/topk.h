@@ -1,4 +1,5 @@
-// topk.h - top-K recommendation (tfr_topk*): launch plan, argument blocks and launchers shared by topk.hip and api.hip.
+// topk.h - top-K recommendation (tfr_topk*): launch plan, argument blocks and launchers shared by topk.hip and api.hip; the
+// plan and the common argument block also serve neighbours.h, whose scoring block is the same one (score_tile.h).
 //
 // score(u, i) = ((dot + mu) + bu[u]) + bi[i], dot = f32 fmaf chain over f = 0..D-1 ascending from +0 of P[u,f] * Q'[i,f]
 // (Q' = |Q| with item_abs).  Keys: (order-preserving uint32 of the score) << 32 | ~item, so one 64-bit compare orders by score
@@ -64,17 +65,22 @@ inline bool topk_plan(int k, int64_t n_users, int64_t items, TopkPlan* p) {
     return true;
 }
 
-struct TopkArgs {
-    const float* P; const float* bu;                   // user rows [U, D] and biases
-    const float* Q; const float* bi;                   // item rows [n_items, D] and biases (already offset to the item range)
-    const float* mu;
-    const int32_t* users;                              // [n_rows] this chunk's users
+// what every scoring block (score_tile.h sliced_topk_block) is told, whatever it scores: filled once, by api.hip's driver
+struct SlicedArgs {
+    const int32_t* rows;                               // [n_rows] this chunk's query ids: users, or rows of the one table
     const int64_t* indptr; const int32_t* excl;        // exclusion CSR rows of this chunk (absolute offsets into excl), may be NULL
     const int32_t* excl_bad;                           // nonzero: the exclusion CSR failed its check, it is not read
     uint64_t* part;                                    // out [n_rows, slices, k] keys, descending
     int32_t* err;
-    int64_t n_rows, U, n_items;
+    int64_t n_rows;
     int32_t D, k, slices, item_abs;
+};
+
+struct TopkArgs : SlicedArgs {
+    const float* P; const float* bu;                   // user rows [U, D] and biases
+    const float* Q; const float* bi;                   // item rows [n_items, D] and biases (already offset to the item range)
+    const float* mu;
+    int64_t U, n_items;
 };
 
 struct TopkMergeArgs {
