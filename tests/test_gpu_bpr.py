@@ -18,7 +18,7 @@ from tests import widths as W
 pytestmark = pytest.mark.gpu
 
 # k_bpr_users / k_bpr_items are templated on NJ = ceil(D / 64) registers per lane, f = lane + 64 j guarded by f < D
-# (csrc/bpr.hip bpr_nj): one width per (NJ, last register full or partial), and D = 1 - widths.BPR, which
+# (csrc/wave_rows.h with_nj): one width per (NJ, last register full or partial), and D = 1 - widths.BPR, which
 # tests/test_width_coverage.py holds against that rule.
 WIDTHS = W.BPR
 

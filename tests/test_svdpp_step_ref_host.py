@@ -79,7 +79,7 @@ def _butterfly(v):
 
 
 def _dot(a, b):
-    """pp_sum of a per-lane fmaf chain over j"""
+    """wave_sum_all (csrc/wave_rows.h) of a per-lane fmaf chain over j"""
     A, B = _lanes(a), _lanes(b)
     acc = np.zeros(A.shape[:-2] + (64,), F4)
     for j in range(A.shape[-2]):

@@ -36,7 +36,7 @@ def shard_class(D):
 
 def registers(D):
     """(NJ, last register full): NJ = ceil(D / 64) features per lane, f = lane + 64 j guarded by f < D
-    (csrc/svdpp.hip pp_nj, csrc/finetune.hip launch_finetune, csrc/bpr.hip bpr_nj)"""
+    (csrc/wave_rows.h with_nj: the one dispatcher of svdpp.hip, finetune.hip and bpr.hip)"""
     return -(-D // 64), D % 64 == 0
 
 

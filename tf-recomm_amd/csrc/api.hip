@@ -905,6 +905,18 @@ static int radix_sort_columns(tfr_model* m, int ncols, const int32_t* const* key
     return TFR_OK;
 }
 
+// the radix sort of n keys of du (and, with di, of di) by the model's own key widths into ks_u/ps_u (ks_i/ps_i);
+// checked: ids outside (U, I) void the step
+static int sort_model_columns(tfr_model* m, const int32_t* du, const int32_t* di, int64_t n, bool checked,
+                              const int64_t* store_ids = nullptr) {
+    const int32_t* keys[2] = {du, di};
+    const int bits[2] = {m->bits_u, m->bits_i};
+    int32_t* ks[2] = {m->ks_u, m->ks_i};
+    int32_t* ps[2] = {m->ps_u, m->ps_i};
+    const int64_t limits[2] = {m->U, m->I};
+    return radix_sort_columns(m, di ? 2 : 1, keys, bits, ks, ps, n, checked ? limits : nullptr, store_ids);
+}
+
 // stable sort of batch positions by user id and by item id
 static int sort_columns(tfr_model* m, const int32_t* du, const int32_t* di, int64_t B,
                         const FinArgs* fin = nullptr, bool* fin_done = nullptr, bool validate = false,
@@ -926,12 +938,7 @@ static int sort_columns(tfr_model* m, const int32_t* du, const int32_t* di, int6
         HIPCHK(hipGetLastError());
         return TFR_OK;
     }
-    const int32_t* keys[2] = {du, di};
-    const int bits[2] = {m->bits_u, m->bits_i};
-    int32_t* ks[2] = {m->ks_u, m->ks_i};
-    int32_t* ps[2] = {m->ps_u, m->ps_i};
-    const int64_t limits[2] = {m->U, m->I};
-    return radix_sort_columns(m, 2, keys, bits, ks, ps, B, validate ? limits : nullptr, store_ids);
+    return sort_model_columns(m, du, di, B, validate, store_ids);
 }
 
 // big tables with a touched-rows optimiser: the forward is computed inside the item-side reduce,
@@ -1326,10 +1333,14 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
     return TFR_OK;
 }
 
-static void rollback_step(tfr_model* m, int64_t step0, float b1p0, float b2p0) {
-    m->step = step0;
-    m->b1p = b1p0;
-    m->b2p = b2p0;
+// the step counter and the beta powers as an entry point found them: what a voided step is rolled back to
+struct StepMark { int64_t step; float b1p, b2p; };
+static StepMark mark_step(const tfr_model* m) { return {m->step, m->b1p, m->b2p}; }
+
+static void rollback_step(tfr_model* m, const StepMark& k) {
+    m->step = k.step;
+    m->b1p = k.b1p;
+    m->b2p = k.b2p;
     m->tab_gen += 1;                                     // the voided step may have run: the counter no longer tells
 }
 
@@ -1524,8 +1535,7 @@ int tfr_train_step(tfr_model* m, const int32_t* u, const int32_t* i, const float
     if (rc) return rc;
     if (B > 0 && !r) return fail(TFR_ERR_ARG, "null rate pointer");
     if ((rc = ensure_capacity(m, B > 0 ? B : 1))) return rc;
-    const int64_t step0 = m->step;
-    const float b1p0 = m->b1p, b2p0 = m->b2p;
+    const StepMark mark = mark_step(m);
     float sc[4] = {0.f, 0.f, 0.f, 0.f};
     m->last_r = nullptr;
     if (B > 0 && B <= STAGE_MAX) {
@@ -1543,7 +1553,7 @@ int tfr_train_step(tfr_model* m, const int32_t* u, const int32_t* i, const float
         HIPCHK(hipStreamSynchronize(m->stream));
         const int32_t e = (int32_t)m->h_out[nl + 3];
         if (e) {                                         // a bad batch never advances the step
-            rollback_step(m, step0, b1p0, b2p0);
+            rollback_step(m, mark);
             return device_error(m, e);
         }
         if (logits_out) memcpy(logits_out, m->h_out, (size_t)B * 4);
@@ -1561,7 +1571,7 @@ int tfr_train_step(tfr_model* m, const int32_t* u, const int32_t* i, const float
         HIPCHK(hipMemcpyAsync(sc, m->scalars, 16, hipMemcpyDeviceToHost, m->stream));
         // synchronous entry point: always validate so a bad batch never advances the step
         if ((rc = check_device_error(m))) {
-            rollback_step(m, step0, b1p0, b2p0);
+            rollback_step(m, mark);
             return rc;
         }
     }
@@ -1580,8 +1590,7 @@ int tfr_train_steps_repeat(tfr_model* m, const int32_t* u, const int32_t* i, con
     if (nsteps == 0) return TFR_OK;
     if ((rc = ensure_capacity(m, B))) return rc;
     if (loss_out) HIPCHK(m->step_out.reserve((int64_t)nsteps * 4, m->stream));
-    const int64_t step0 = m->step;
-    const float b1p0 = m->b1p, b2p0 = m->b2p;
+    const StepMark mark = mark_step(m);
     m->last_r = nullptr;
     HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
@@ -1591,7 +1600,7 @@ int tfr_train_steps_repeat(tfr_model* m, const int32_t* u, const int32_t* i, con
         if ((rc = run_train_step(m, m->d_u, m->d_i, m->d_r, B, (last && logits_out) ? m->d_logits : nullptr,
                                  loss_out ? m->step_out + (size_t)s * 4 : nullptr))) {
             (void)hipStreamSynchronize(m->stream);
-            rollback_step(m, step0, b1p0, b2p0);
+            rollback_step(m, mark);
             return rc;
         }
     }
@@ -1602,7 +1611,7 @@ int tfr_train_steps_repeat(tfr_model* m, const int32_t* u, const int32_t* i, con
     }
     if (logits_out) HIPCHK(hipMemcpyAsync(logits_out, m->d_logits, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
     if ((rc = check_device_error(m))) {                    // a bad id voids every step of the call
-        rollback_step(m, step0, b1p0, b2p0);
+        rollback_step(m, mark);
         return rc;
     }
     for (int32_t s = 0; loss_out && s < nsteps; ++s) loss_out[s] = tmp[(size_t)s * 4];
@@ -1915,8 +1924,7 @@ static int staged_steps(tfr_model* m, int64_t first_step, int64_t B, int32_t nst
     int rc;
     if ((rc = ensure_capacity(m, B))) return rc;
     if (loss_out) HIPCHK(m->step_out.reserve((int64_t)nsteps * 4, m->stream));
-    const int64_t step0 = m->step;
-    const float b1p0 = m->b1p, b2p0 = m->b2p;
+    const StepMark mark = mark_step(m);
     static int no_ahead = -1;                              // TFR_NO_LOOKAHEAD=1: A/B switch
     if (no_ahead < 0) { const char* e = getenv("TFR_NO_LOOKAHEAD"); no_ahead = (e && e[0] == '1') ? 1 : 0; }
     if (nsteps > 1 && fwd_in_reduce(m, B) && !m->prof && !no_ahead) {
@@ -1943,7 +1951,7 @@ static int staged_steps(tfr_model* m, int64_t first_step, int64_t B, int32_t nst
         std::vector<float> tmp((size_t)nsteps * 4);
         HIPCHK(hipMemcpyAsync(tmp.data(), m->step_out, tmp.size() * 4, hipMemcpyDeviceToHost, m->stream));
         if ((rc = check_device_error(m))) {
-            rollback_step(m, step0, b1p0, b2p0);
+            rollback_step(m, mark);
             m->pf_valid = false;
             return rc;
         }
@@ -2910,13 +2918,9 @@ static int fm_train_core(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_in
     }
     HIPCHK(hipGetLastError());
     if (nnz > 0) {
-        const int32_t* keys[2] = {d_indices, nullptr};
-        const int bits[2] = {m->bits_u, 0};
-        int32_t* ks[2] = {m->ks_u, nullptr};
-        int32_t* ps[2] = {m->ps_u, nullptr};
         {
             Prof p(m, TFR_K_SORT);
-            if ((rc = radix_sort_columns(m, 1, keys, bits, ks, ps, nnz))) return rc;
+            if ((rc = sort_model_columns(m, d_indices, nullptr, nnz, false))) return rc;
         }
         RedPair pr;
         RedArgs& r = pr.a[0];
@@ -3079,14 +3083,13 @@ int tfr_fm_train_step(tfr_fm* f, const int64_t* indptr, const int32_t* indices, 
     int64_t nnz = 0;
     int rc = fm_stage_csr(f, indptr, indices, data, y, n_rows, &nnz);
     if (rc) return rc;
-    const int64_t step0 = m->step;
-    const float b1p0 = m->b1p, b2p0 = m->b2p;
+    const StepMark mark = mark_step(m);
     if ((rc = fm_train_core(f, f->d_indptr, f->d_indices, f->d_data, f->d_y, n_rows, nnz, f->d_out, nullptr))) return rc;
     float sc[4] = {0.f, 0.f, 0.f, 0.f};
     if (pred_out) HIPCHK(hipMemcpyAsync(pred_out, f->d_out, (size_t)n_rows * 4, hipMemcpyDeviceToHost, m->stream));
     HIPCHK(hipMemcpyAsync(sc, m->scalars, 16, hipMemcpyDeviceToHost, m->stream));
     if ((rc = check_device_error(m))) {
-        rollback_step(m, step0, b1p0, b2p0);
+        rollback_step(m, mark);
         return rc;
     }
     if (loss_out) *loss_out = sc[0];

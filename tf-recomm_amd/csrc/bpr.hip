@@ -10,40 +10,15 @@
 // it was before the user runs wrote it.  Both sides therefore see the tables as they were before the step.
 #include <hip/hip_runtime.h>
 #include "bpr.h"
+#include "wave_rows.h"
 
 namespace tfr {
 
-__device__ __forceinline__ float bpr_sum(float x) {            // butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
+static_assert(BPR_WAVES == ROW_WAVES, "wave_slot and wave_grid count ROW_WAVES waves per block");
 
-__device__ __forceinline__ int64_t bpr_wave_id() { return (int64_t)blockIdx.x * BPR_WAVES + (threadIdx.x >> 6); }
-
-// first sorted position past the run of key at p (ks sorted: the equal keys are a prefix of every 64-entry window)
-__device__ __forceinline__ int64_t bpr_run_end(const int32_t* ks, int64_t p, int64_t n, int lane) {
-    const int32_t key = ks[p];
-    int64_t q = p + 1;
-    for (;;) {
-        const int64_t e = q + lane;
-        const unsigned long long same = __ballot(e < n && ks[e] == key);
-        if (same == ~0ull) { q += 64; continue; }
-        return q + (__ffsll((long long)~same) - 1);
-    }
-}
-
-// lazy Adam (touched rows) in the SVD step's operation order (svd_kernels.hip adam_sparse), or SGD, on one value
+// lazy Adam (touched rows) in the SVD step's operation order (adam_sparse), or SGD, on one value
 __device__ __forceinline__ void bpr_update(float* w, float* m, float* v, int64_t x, float g, const BprArgs& a) {
-    if (a.opt == 0) {
-        const float mm = fmaf(m[x], a.b1, g * a.omb1);
-        const float vv = fmaf(v[x], a.b2, (g * g) * a.omb2);
-        m[x] = mm;
-        v[x] = vv;
-        w[x] = w[x] - a.alpha * mm / (sqrtf(vv) + a.eps);
-    } else {
-        w[x] -= a.lr * g;
-    }
+    update_at(w, m, v, x, g, a.opt == 0, AdamC{a.alpha, a.b1, a.b2, a.eps, a.omb1, a.omb2}, a.lr);
 }
 
 __global__ void __launch_bounds__(256) k_bpr_sample(BprSampleArgs a) {
@@ -93,7 +68,7 @@ __global__ void __launch_bounds__(256) k_bpr_sample(BprSampleArgs a) {
 
 template <int NJ>
 __global__ void __launch_bounds__(64 * BPR_WAVES) k_bpr_users(BprArgs a) {
-    const int64_t w = bpr_wave_id();
+    const int64_t w = wave_slot();
     const int lane = threadIdx.x & 63, D = a.D;
     if (w >= a.B || *a.err) return;
     const int64_t p = 2 * w, n = 2 * a.B;                          // a run holds whole triples: it starts at an even position
@@ -102,7 +77,7 @@ __global__ void __launch_bounds__(64 * BPR_WAVES) k_bpr_users(BprArgs a) {
         if (lane < 4) a.scal[w * 4 + lane] = 0.f;
         return;
     }
-    const int64_t q = bpr_run_end(a.ks_u, p, n, lane);
+    const int64_t q = sorted_run_end(a.ks_u, p, n, lane);
     const int64_t urow = (int64_t)u * D;
     float pu[NJ], dp[NJ], psq = 0.f;
 #pragma unroll
@@ -113,7 +88,7 @@ __global__ void __launch_bounds__(64 * BPR_WAVES) k_bpr_users(BprArgs a) {
         if (f < D) a.pold[w * D + f] = pu[j];
         psq = fmaf(pu[j], pu[j], psq);
     }
-    psq = bpr_sum(psq);
+    psq = wave_sum_all(psq);
     const float lam = a.lam;
     float loss = 0.f, reg = 0.f;
     int32_t cnt = 0;
@@ -124,25 +99,20 @@ __global__ void __launch_bounds__(64 * BPR_WAVES) k_bpr_users(BprArgs a) {
         if (jn < 0) continue;                                      // skipped: absent from the batch
         const int32_t ip = a.pos[b];
         const int64_t irow = (int64_t)ip * D, jrow = (int64_t)jn * D;
-        float qi[NJ], qj[NJ], di = 0.f, dj = 0.f, qisq = 0.f, qjsq = 0.f;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int f = lane + 64 * j;
-            qi[j] = qj[j] = 0.f;
-            if (f < D) {
-                const float x1 = a.Q[irow + f], x2 = a.Q[jrow + f];
-                qi[j] = a.item_abs ? fabsf(x1) : x1;
-                qj[j] = a.item_abs ? fabsf(x2) : x2;
-                di = fmaf(pu[j], qi[j], di);
-                dj = fmaf(pu[j], qj[j], dj);
-                qisq = fmaf(x1, x1, qisq);
-                qjsq = fmaf(x2, x2, qjsq);
-            }
-        }
-        di = bpr_sum(di);
-        dj = bpr_sum(dj);
-        qisq = bpr_sum(qisq);
-        qjsq = bpr_sum(qjsq);
+        float qi[NJ] = {}, qj[NJ] = {}, di = 0.f, dj = 0.f, qisq = 0.f, qjsq = 0.f;
+        each_feature<NJ>(lane, D, [&](int j, int f) {
+            const float x1 = a.Q[irow + f], x2 = a.Q[jrow + f];
+            qi[j] = a.item_abs ? fabsf(x1) : x1;
+            qj[j] = a.item_abs ? fabsf(x2) : x2;
+            di = fmaf(pu[j], qi[j], di);
+            dj = fmaf(pu[j], qj[j], dj);
+            qisq = fmaf(x1, x1, qisq);
+            qjsq = fmaf(x2, x2, qjsq);
+        });
+        di = wave_sum_all(di);
+        dj = wave_sum_all(dj);
+        qisq = wave_sum_all(qisq);
+        qjsq = wave_sum_all(qjsq);
         const float bii = a.bi[ip], bij = a.bi[jn];
         const float x = (di + bii) - (dj + bij);
         const float g = -1.f / (1.f + expf(x));                   // -sigmoid(-x)
@@ -162,22 +132,18 @@ __global__ void __launch_bounds__(64 * BPR_WAVES) k_bpr_users(BprArgs a) {
         a.scal[w * 4 + 3] = 0.f;
     }
     if (cnt == 0 || ((a.frozen >> 3) & 1)) return;                 // every triple skipped: the row and its slots stay
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int f = lane + 64 * j;
-        if (f < D) bpr_update(a.P, a.Pm, a.Pv, urow + f, dp[j], a);
-    }
+    each_feature<NJ>(lane, D, [&](int j, int f) { bpr_update(a.P, a.Pm, a.Pv, urow + f, dp[j], a); });
 }
 
 template <int NJ>
 __global__ void __launch_bounds__(64 * BPR_WAVES) k_bpr_items(BprArgs a) {
-    const int64_t p = bpr_wave_id();
+    const int64_t p = wave_slot();
     const int lane = threadIdx.x & 63, D = a.D;
     const int64_t n = 2 * a.B;
     if (p >= n || *a.err) return;
     const int32_t it = a.ks_i[p];
     if (p > 0 && a.ks_i[p - 1] == it) return;
-    const int64_t q = bpr_run_end(a.ks_i, p, n, lane);
+    const int64_t q = sorted_run_end(a.ks_i, p, n, lane);
     const int64_t irow = (int64_t)it * D;
     const float lam = a.lam, bi = a.bi[it];
     float qr[NJ], sg[NJ], dq[NJ];
@@ -197,29 +163,16 @@ __global__ void __launch_bounds__(64 * BPR_WAVES) k_bpr_items(BprArgs a) {
         const float gb = a.g[b];
         const float g = (k & 1) ? -gb : gb;
         const float* pr = a.pold + (int64_t)a.head[b] * D;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int f = lane + 64 * j;
-            if (f < D) dq[j] += (g * pr[f]) * sg[j] + lam * qr[j];
-        }
+        each_feature<NJ>(lane, D, [&](int j, int f) { dq[j] += (g * pr[f]) * sg[j] + lam * qr[j]; });
         dbi += a.reg_bias ? g + lam * bi : g;
         ++cnt;
     }
     if (cnt == 0) return;                                          // only skipped triples: no touch
-    if (!((a.frozen >> 4) & 1)) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int f = lane + 64 * j;
-            if (f < D) bpr_update(a.Q, a.Qm, a.Qv, irow + f, dq[j], a);
-        }
-    }
+    if (!((a.frozen >> 4) & 1)) each_feature<NJ>(lane, D, [&](int j, int f) { bpr_update(a.Q, a.Qm, a.Qv, irow + f, dq[j], a); });
     if (!((a.frozen >> 2) & 1) && lane == 0) bpr_update(a.bi, a.bim, a.biv, it, dbi, a);
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------
-static int bpr_nj(int D) { return (D + 63) / 64; }
-static unsigned bpr_blocks(int64_t waves) { return (unsigned)((waves + BPR_WAVES - 1) / BPR_WAVES); }
-
 void launch_bpr_sample(const BprSampleArgs& a, hipStream_t s) {
     if (a.B <= 0) return;
     hipLaunchKernelGGL(k_bpr_sample, dim3((unsigned)((a.B + 255) / 256)), dim3(256), 0, s, a);
@@ -227,24 +180,12 @@ void launch_bpr_sample(const BprSampleArgs& a, hipStream_t s) {
 
 void launch_bpr_users(const BprArgs& a, hipStream_t s) {
     if (a.B <= 0) return;
-    const dim3 g(bpr_blocks(a.B)), b(64 * BPR_WAVES);
-    switch (bpr_nj(a.D)) {
-        case 1: hipLaunchKernelGGL(k_bpr_users<1>, g, b, 0, s, a); break;
-        case 2: hipLaunchKernelGGL(k_bpr_users<2>, g, b, 0, s, a); break;
-        case 3: hipLaunchKernelGGL(k_bpr_users<3>, g, b, 0, s, a); break;
-        default: hipLaunchKernelGGL(k_bpr_users<4>, g, b, 0, s, a); break;
-    }
+    with_nj(a.D, [&](auto nj) { hipLaunchKernelGGL(k_bpr_users<decltype(nj)::value>, wave_grid(a.B), wave_block(), 0, s, a); });
 }
 
 void launch_bpr_items(const BprArgs& a, hipStream_t s) {
     if (a.B <= 0) return;
-    const dim3 g(bpr_blocks(2 * a.B)), b(64 * BPR_WAVES);
-    switch (bpr_nj(a.D)) {
-        case 1: hipLaunchKernelGGL(k_bpr_items<1>, g, b, 0, s, a); break;
-        case 2: hipLaunchKernelGGL(k_bpr_items<2>, g, b, 0, s, a); break;
-        case 3: hipLaunchKernelGGL(k_bpr_items<3>, g, b, 0, s, a); break;
-        default: hipLaunchKernelGGL(k_bpr_items<4>, g, b, 0, s, a); break;
-    }
+    with_nj(a.D, [&](auto nj) { hipLaunchKernelGGL(k_bpr_items<decltype(nj)::value>, wave_grid(2 * a.B), wave_block(), 0, s, a); });
 }
 
 }  // namespace tfr

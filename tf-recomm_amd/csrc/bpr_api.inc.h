@@ -94,14 +94,9 @@ static int bpr_step(tfr_model* m, BprState* h, const int32_t* du, const int32_t*
             launch_bpr_sample(sa, s);
         }
         HIPCHK(hipGetLastError());
-        const int32_t* keys[2] = {h->ou, h->oi};
-        const int bits[2] = {m->bits_u, m->bits_i};
-        int32_t* ks[2] = {m->ks_u, m->ks_i};
-        int32_t* ps[2] = {m->ps_u, m->ps_i};
-        const int64_t limits[2] = {m->U, m->I};
         {
             Prof p(m, TFR_K_SORT);
-            if ((rc = radix_sort_columns(m, 2, keys, bits, ks, ps, 2 * B, limits))) return rc;
+            if ((rc = sort_model_columns(m, h->ou, h->oi, 2 * B, true))) return rc;
         }
         BprArgs a;
         memset(&a, 0, sizeof(a));
@@ -213,8 +208,7 @@ int tfr_bpr_train_step(tfr_model* m, const int32_t* user, const int32_t* pos, co
     BprState* h = m->bpr;
     if ((rc = bpr_ensure_batch(m, h, B))) return rc;
     hipStream_t s = m->stream;
-    const int64_t step0 = m->step;
-    const float b1p0 = m->b1p, b2p0 = m->b2p;
+    const StepMark mark = mark_step(m);
     if (B > 0) {
         HIPCHK(hipMemcpyAsync(m->d_u, user, (size_t)B * 4, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(m->d_i, pos, (size_t)B * 4, hipMemcpyHostToDevice, s));
@@ -232,7 +226,7 @@ int tfr_bpr_train_step(tfr_model* m, const int32_t* user, const int32_t* pos, co
     HIPCHK(hipStreamSynchronize(s));
     const int32_t e = (int32_t)back4[3];
     if (e) {                                             // a bad batch never advances the step
-        rollback_step(m, step0, b1p0, b2p0);
+        rollback_step(m, mark);
         return device_error(m, e);
     }
     int64_t skipped = 0;
@@ -286,8 +280,7 @@ int tfr_bpr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* lo
     }
     HIPCHK(hipEventRecord(h->ev_drawn, m->stream3));
     HIPCHK(hipStreamWaitEvent(s, h->ev_drawn, 0));
-    const int64_t step0 = m->step;
-    const float b1p0 = m->b1p, b2p0 = m->b2p;
+    const StepMark mark = mark_step(m);
     for (int32_t st = 0; st < nsteps; ++st)
         if ((rc = bpr_step(m, h, nullptr, nullptr, nullptr, h->ids + (int64_t)st * B, B, nullptr,
                            loss_out ? h->losses + 4 * (int64_t)st : nullptr)))
@@ -299,7 +292,7 @@ int tfr_bpr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* lo
     for (int32_t st = 0; st < nsteps; ++st) {
         const int32_t e = (int32_t)back[(size_t)st * 4 + 3];
         if (e) {                                         // (drawn ids are in range by construction)
-            rollback_step(m, step0, b1p0, b2p0);
+            rollback_step(m, mark);
             return device_error(m, e);
         }
         loss_out[st] = back[(size_t)st * 4];

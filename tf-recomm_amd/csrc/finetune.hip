@@ -15,10 +15,12 @@
 // Every sum has a fixed order and nothing is shared between waves, so a user's results do not depend on which other users
 // share the launch, or on the order the host gives the users (descending work, so the long chains start first).
 #include <hip/hip_runtime.h>
-#include "svd_kernels.h"
 #include "finetune.h"
+#include "wave_rows.h"
 
 namespace tfr {
+
+static_assert(FT_WAVES == ROW_WAVES, "wave_slot and wave_grid count ROW_WAVES waves per block");
 
 __device__ __forceinline__ float ft_sigmoid(float x) { return 1.f / (1.f + __expf(-x)); }
 
@@ -62,7 +64,7 @@ __device__ void ft_user(const FtArgs& a, float* w, int32_t uix, int lane) {
     float p[NJ], m[NJ], v[NJ];
     const int64_t prow = user * D;
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
+    for (int j = 0; j < NJ; ++j) {                     // (clears the registers past D as it loads: not each_feature's shape)
         const int f = lane + 64 * j;
         p[j] = m[j] = v[j] = 0.f;
         if (f < D) {
@@ -77,15 +79,11 @@ __device__ void ft_user(const FtArgs& a, float* w, int32_t uix, int lane) {
     for (int64_t kr = k0; kr < k1; ++kr) {
         const int64_t L = a.prefix[kr];
         const int32_t ask = a.ask[kr];
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int f = lane + 64 * j;
-            if (f < D) {
-                p_s[f] = p[j];
-                const float q = a.Q[(int64_t)ask * D + f];
-                aq_s[f] = a.item_abs ? fabsf(q) : q;
-            }
-        }
+        each_feature<NJ>(lane, D, [&](int j, int f) {
+            p_s[f] = p[j];
+            const float q = a.Q[(int64_t)ask * D + f];
+            aq_s[f] = a.item_abs ? fabsf(q) : q;
+        });
         wave_lds_sync();
         {
             float s = 0.f;
@@ -138,11 +136,9 @@ __device__ void ft_user(const FtArgs& a, float* w, int32_t uix, int lane) {
                 const int cnt = (int)(L - c0 < 64 ? L - c0 : 64);
                 for (int kk = 0; kk < cnt; ++kk) {
                     const float d = dl_s[kk];
-#pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        const int f = lane + 64 * j;
-                        if (f < D) g[j] += fmaf(d, ft_q<STAGED>(q_s, S, a.Q, it, c0 + kk, f, D, a.item_abs), lp[j]);
-                    }
+                    each_feature<NJ>(lane, D, [&](int j, int f) {
+                        g[j] += fmaf(d, ft_q<STAGED>(q_s, S, a.Q, it, c0 + kk, f, D, a.item_abs), lp[j]);
+                    });
                     gb += a.reg_bias ? d + lbu : d;
                 }
                 if (want_loss)
@@ -150,35 +146,23 @@ __device__ void ft_user(const FtArgs& a, float* w, int32_t uix, int lane) {
                 wave_lds_sync();                               // dl_s / ls_s are rewritten by the next pass
             }
             if (a.adam) {
-                const float alpha = lr * sqrtf(1.f - b2p) / (1.f - b1p);
+                const AdamC c = {lr * sqrtf(1.f - b2p) / (1.f - b1p), a.b1, a.b2, a.eps, omb1, omb2};
                 if (!a.frozen_rows) {
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) {
-                        m[j] = fmaf(m[j], a.b1, g[j] * omb1);
-                        v[j] = fmaf(v[j], a.b2, (g[j] * g[j]) * omb2);
-                        p[j] = p[j] - alpha * m[j] / (sqrtf(v[j]) + a.eps);
-                    }
+                    for (int j = 0; j < NJ; ++j) adam_sparse(p[j], m[j], v[j], g[j], c);
                 }
-                if (!a.frozen_bias) {
-                    bm = fmaf(bm, a.b1, gb * omb1);
-                    bv = fmaf(bv, a.b2, (gb * gb) * omb2);
-                    bu = bu - alpha * bm / (sqrtf(bv) + a.eps);
-                }
+                if (!a.frozen_bias) adam_sparse(bu, bm, bv, gb, c);
                 b1p *= a.b1;
                 b2p *= a.b2;
             } else {
                 if (!a.frozen_rows) {
 #pragma unroll
-                    for (int j = 0; j < NJ; ++j) p[j] = p[j] - lr * g[j];
+                    for (int j = 0; j < NJ; ++j) sgd_step(p[j], g[j], lr);
                 }
-                if (!a.frozen_bias) bu = bu - lr * gb;
+                if (!a.frozen_bias) sgd_step(bu, gb, lr);
             }
             if (want_loss && lane == 0) a.loss_out[kr] = lsum;
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int f = lane + 64 * j;
-                if (f < D) p_s[f] = p[j];
-            }
+            each_feature<NJ>(lane, D, [&](int j, int f) { p_s[f] = p[j]; });
             wave_lds_sync();
         }
     }
@@ -200,7 +184,7 @@ template <int NJ>
 __global__ __launch_bounds__(FT_WAVES * 64) void k_finetune(FtArgs a) {
     extern __shared__ float ft_lds[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t slot = (int64_t)blockIdx.x * FT_WAVES + wave;
+    const int64_t slot = wave_slot();
     if (slot >= a.n_users) return;                     // whole waves only: no block barrier follows
     const int32_t uix = a.order[slot];
     float* w = ft_lds + (size_t)wave * a.wave_floats;
@@ -212,12 +196,7 @@ __global__ __launch_bounds__(FT_WAVES * 64) void k_finetune(FtArgs a) {
 
 void launch_finetune(const FtArgs& a, const FtPlan& p, hipStream_t s) {
     if (a.n_users < 1) return;
-    const dim3 grid((unsigned)((a.n_users + FT_WAVES - 1) / FT_WAVES)), block(FT_WAVES * 64);
-    const int nj = (a.D + 63) / 64;
-    if (nj == 1) hipLaunchKernelGGL(k_finetune<1>, grid, block, p.lds_bytes, s, a);
-    else if (nj == 2) hipLaunchKernelGGL(k_finetune<2>, grid, block, p.lds_bytes, s, a);
-    else if (nj == 3) hipLaunchKernelGGL(k_finetune<3>, grid, block, p.lds_bytes, s, a);
-    else hipLaunchKernelGGL(k_finetune<4>, grid, block, p.lds_bytes, s, a);
+    with_nj(a.D, [&](auto nj) { hipLaunchKernelGGL(k_finetune<decltype(nj)::value>, wave_grid(a.n_users), wave_block(), p.lds_bytes, s, a); });
 }
 
 }  // namespace tfr

@@ -192,14 +192,13 @@ int tfr_fm_train_steps_resident(tfr_fm* f, const int64_t* ids, int64_t batch, in
     HIPCHK(hipMemcpyAsync(h->ids, ids, (size_t)nsteps * batch * 8, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));                     // the caller's ids are free again
     tr.mark("ids uploaded");
-    const int64_t step0 = m->step;
-    const float b1p0 = m->b1p, b2p0 = m->b2p;
+    const StepMark mark = mark_step(m);
     for (int32_t k = 0; k < nsteps; ++k) {
         const int64_t nnz = h->step_nnz[(size_t)k];
         if ((rc = fm_fit_gather(f, *st, h->ids + (size_t)k * batch, batch, nnz)) ||
             (rc = fm_train_core(f, f->d_indptr, f->d_indices, f->d_data, f->d_y, batch, nnz, nullptr, h->losses + (size_t)k * 4))) {
             (void)hipStreamSynchronize(s);               // a launch failed: the call is void (tfr_train_steps_repeat)
-            rollback_step(m, step0, b1p0, b2p0);
+            rollback_step(m, mark);
             return rc;
         }
     }
@@ -208,7 +207,7 @@ int tfr_fm_train_steps_resident(tfr_fm* f, const int64_t* ids, int64_t batch, in
     std::vector<float> l4((size_t)nsteps * 4);
     HIPCHK(hipMemcpyAsync(l4.data(), h->losses, l4.size() * 4, hipMemcpyDeviceToHost, s));
     if ((rc = check_device_error(m))) {
-        rollback_step(m, step0, b1p0, b2p0);
+        rollback_step(m, mark);
         return rc;
     }
     for (int32_t k = 0; k < nsteps; ++k) loss_out[k] = l4[(size_t)k * 4];

@@ -65,6 +65,18 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// Optimiser arithmetic, written in the operation order of the TF kernels they restate: used by the SVD step
+// (svd_kernels.hip) and by the wave-per-run kernels (wave_rows.h: BPR, fine-tuning).
+struct AdamC { float alpha, b1, b2, eps, omb1, omb2; };
+
+// AdamOptimizer._apply_sparse_shared [TF1-lib]: m*b1 + g*(1-b1); v*b2 + g*g*(1-b2);
+// var - alpha*m/(sqrt(v)+eps)
+__device__ __forceinline__ void adam_sparse(float& w, float& m, float& v, float g, const AdamC& c) {
+    m = fmaf(m, c.b1, g * c.omb1);                       // which product is fused is pinned here: left to the compiler it
+    v = fmaf(v, c.b2, (g * g) * c.omb2);                 // differed between instantiations of the same kernel
+    w = w - c.alpha * m / (sqrtf(v) + c.eps);
+}
+
 struct RedArgs {
     const int32_t* ks; const int32_t* ps; const int32_t* other; const float* g;
     const float* own; const float* partner; const float* own_bias;

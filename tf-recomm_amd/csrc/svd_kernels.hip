@@ -979,17 +979,7 @@ __global__ __launch_bounds__(256) void k_pack_triples(const int32_t* u, const in
         store[k] = make_int4(u[k], it[k], __float_as_int(r[k]), 0);
 }
 
-// ------------------------------------------------------------------------------------
-// Optimiser arithmetic, written in the operation order of the TF kernels they restate.
-struct AdamC { float alpha, b1, b2, eps, omb1, omb2; };
-
-// AdamOptimizer._apply_sparse_shared [TF1-lib]: m*b1 + g*(1-b1); v*b2 + g*g*(1-b2);
-// var - alpha*m/(sqrt(v)+eps)
-__device__ __forceinline__ void adam_sparse(float& w, float& m, float& v, float g, const AdamC& c) {
-    m = fmaf(m, c.b1, g * c.omb1);                       // which product is fused is pinned here: left to the compiler it
-    v = fmaf(v, c.b2, (g * g) * c.omb2);                 // differed between instantiations of the same kernel
-    w = w - c.alpha * m / (sqrtf(v) + c.eps);
-}
+// (the optimiser arithmetic, AdamC and adam_sparse, is in svd_kernels.h: the wave-per-run kernels share it)
 
 // ------------------------------------------------------------------------------------
 // K3  deterministic segmented reduce over a table's rows (backward of embedding_lookup:

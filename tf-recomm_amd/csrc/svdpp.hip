@@ -13,28 +13,11 @@
 // Phase handoffs (peff / W / g -> item and Y kernels, partials -> their owners) are kernel boundaries on the stream.
 #include <hip/hip_runtime.h>
 #include "svdpp.h"
+#include "wave_rows.h"
 
 namespace tfr {
 
-__device__ __forceinline__ float pp_sum(float x) {             // butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-__device__ __forceinline__ int64_t pp_wave_id() { return (int64_t)blockIdx.x * PP_WAVES + (threadIdx.x >> 6); }
-
-// first sorted position past the run of key at p (ks sorted: the equal keys are a prefix of every 64-entry window)
-__device__ __forceinline__ int64_t pp_run_end(const int32_t* ks, int64_t p, int64_t n, int lane) {
-    const int32_t key = ks[p];
-    int64_t q = p + 1;
-    for (;;) {
-        const int64_t e = q + lane;
-        const unsigned long long same = __ballot(e < n && ks[e] == key);
-        if (same == ~0ull) { q += 64; continue; }
-        return q + (__ffsll((long long)~same) - 1);
-    }
-}
+static_assert(PP_WAVES == ROW_WAVES, "wave_slot and wave_grid count ROW_WAVES waves per block");
 
 __device__ __forceinline__ void pp_piece_range(const PpCsr& c, int64_t w, int32_t row, int64_t* lo, int64_t* hi) {
     const int64_t l = c.ip[row] + (w - c.pbeg[row]) * (int64_t)PP_PIECE;
@@ -43,7 +26,8 @@ __device__ __forceinline__ void pp_piece_range(const PpCsr& c, int64_t w, int32_
     *hi = l + PP_PIECE < end ? l + PP_PIECE : end;
 }
 
-// lazy Adam (touched rows) or SGD on one value
+// lazy Adam (touched rows) or SGD on one value.  The one form left unpinned: which product the compiler fuses is its choice
+// here, unlike adam_sparse (svd_kernels.h).  Pinning it changes bits, so it waits for a pull request of its own.
 __device__ __forceinline__ void pp_update(float* w, float* m, float* v, int64_t x, float g, const PpArgs& a) {
     if (a.opt == 0) {
         const float mm = m[x] * a.b1 + g * (1.f - a.b1);
@@ -68,45 +52,35 @@ __global__ void __launch_bounds__(256) k_pp_mark(PpActive a, const int32_t* err)
 
 template <int NJ>
 __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_ypart(PpArgs a) {
-    const int64_t w = pp_wave_id();
+    const int64_t w = wave_slot();
     const int lane = threadIdx.x & 63, D = a.D;
     if (w >= a.N.n_pieces || *a.err) return;
     const int32_t u = a.N.prow[w];
     if (a.act.stamp[u] != a.act.cur) return;
     int64_t lo, hi;
     pp_piece_range(a.N, w, u, &lo, &hi);
-    float acc[NJ], sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = 0.f;
+    float acc[NJ] = {}, sq = 0.f;
     const int32_t jl = lo + lane < hi ? a.N.idx[lo + lane] : 0;    // a piece is at most 64 x 2 entries: two id loads
     const int32_t jl2 = lo + 64 + lane < hi ? a.N.idx[lo + 64 + lane] : 0;
     const int n = (int)(hi - lo);
     for (int t = 0; t < n; ++t) {
         const int32_t item = t < 64 ? __shfl(jl, t, 64) : __shfl(jl2, t - 64, 64);
         const float* y = a.Y + (int64_t)item * D;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int f = lane + 64 * j;
-            if (f < D) {
-                const float x = y[f];
-                acc[j] += x;
-                sq = fmaf(x, x, sq);
-            }
-        }
+        each_feature<NJ>(lane, D, [&](int j, int f) {
+            const float x = y[f];
+            acc[j] += x;
+            sq = fmaf(x, x, sq);
+        });
     }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int f = lane + 64 * j;
-        if (f < D) a.part[w * D + f] = acc[j];
-    }
-    sq = pp_sum(sq);
+    each_feature<NJ>(lane, D, [&](int j, int f) { a.part[w * D + f] = acc[j]; });
+    sq = wave_sum_all(sq);
     if (lane == 0) a.part_sq[w] = sq;
 }
 static_assert(PP_PIECE <= 128, "k_pp_ypart stages a piece's ids in two loads per lane");
 
 template <int NJ, int MODE>
 __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_users(PpArgs a) {
-    const int64_t p = pp_wave_id();
+    const int64_t p = wave_slot();
     const int lane = threadIdx.x & 63, D = a.D;
     const int64_t n = a.act.n;
     if (p >= n || *a.err) return;
@@ -115,65 +89,47 @@ __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_users(PpArgs a) {
         if (MODE == PP_USERS_TRAIN && lane < 4) a.scal[p * 4 + lane] = 0.f;
         return;
     }
-    const int64_t q = pp_run_end(a.act.ks, p, n, lane);
+    const int64_t q = sorted_run_end(a.act.ks, p, n, lane);
     const int64_t nu = a.N.ip[u + 1] - a.N.ip[u];
     const float s = nu > 0 ? 1.f / sqrtf((float)nu) : 0.f;
-    float z[NJ], pe[NJ], pu[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) z[j] = 0.f;
+    float z[NJ] = {}, pe[NJ] = {}, pu[NJ] = {};
     float ysq = 0.f;
     for (int32_t pc = a.N.pbeg[u]; pc < a.N.pbeg[u + 1]; ++pc) {
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int f = lane + 64 * j;
-            if (f < D) z[j] += a.part[(int64_t)pc * D + f];
-        }
+        each_feature<NJ>(lane, D, [&](int j, int f) { z[j] += a.part[(int64_t)pc * D + f]; });
         ysq += a.part_sq[pc];
     }
     const int64_t urow = (int64_t)u * D;
     float psq = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int f = lane + 64 * j;
-        pu[j] = pe[j] = 0.f;
-        if (f < D) {
-            pu[j] = a.P[urow + f];
-            pe[j] = pu[j] + s * z[j];
-            a.peff[urow + f] = pe[j];
-            psq = fmaf(pu[j], pu[j], psq);
-        }
-    }
+    each_feature<NJ>(lane, D, [&](int j, int f) {
+        pu[j] = a.P[urow + f];
+        pe[j] = pu[j] + s * z[j];
+        a.peff[urow + f] = pe[j];
+        psq = fmaf(pu[j], pu[j], psq);
+    });
     if (MODE == PP_USERS_PEFF) return;
-    psq = pp_sum(psq);
+    psq = wave_sum_all(psq);
     const float mu = a.mu[0], bu = a.bu[u], lam = a.lam;
-    float wacc[NJ], dp[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) wacc[j] = dp[j] = 0.f;
+    float wacc[NJ] = {}, dp[NJ] = {};
     float loss = 0.f, reg = 0.f, sumg = 0.f, dbu = 0.f;
     for (int64_t e = p; e < q; ++e) {
         const int32_t k = a.act.ps[e];
         const int32_t i = a.it[k];
         const int64_t irow = (int64_t)i * D;
-        float qt[NJ], dot = 0.f, qsq = 0.f;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int f = lane + 64 * j;
-            qt[j] = 0.f;
-            if (f < D) {
-                const float qq = a.Q[irow + f];
-                qt[j] = a.item_abs ? fabsf(qq) : qq;
-                dot = fmaf(pe[j], qt[j], dot);
-                qsq = fmaf(qq, qq, qsq);
-            }
-        }
-        dot = pp_sum(dot);
+        float qt[NJ] = {}, dot = 0.f, qsq = 0.f;
+        each_feature<NJ>(lane, D, [&](int j, int f) {
+            const float qq = a.Q[irow + f];
+            qt[j] = a.item_abs ? fabsf(qq) : qq;
+            dot = fmaf(pe[j], qt[j], dot);
+            qsq = fmaf(qq, qq, qsq);
+        });
+        dot = wave_sum_all(dot);
         const float bi = a.bi[i];
         const float x = ((dot + mu) + bu) + bi;
         if (MODE == PP_USERS_FORWARD) {
             if (lane == 0) a.logits[k] = x;
             continue;
         }
-        qsq = pp_sum(qsq);
+        qsq = wave_sum_all(qsq);
         const float rt = a.r[k];
         float g;
         if (a.loss == 0) {
@@ -204,11 +160,7 @@ __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_users(PpArgs a) {
         sumg += g;
     }
     if (MODE == PP_USERS_FORWARD) return;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int f = lane + 64 * j;
-        if (f < D) a.W[p * D + f] = s * wacc[j];
-    }
+    each_feature<NJ>(lane, D, [&](int j, int f) { a.W[p * D + f] = s * wacc[j]; });
     if (lane == 0) {
         a.cnt[p] = (int32_t)(q - p);
         a.scal[p * 4 + 0] = loss;
@@ -218,7 +170,7 @@ __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_users(PpArgs a) {
     }
     if (!((a.frozen >> 3) & 1)) {
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
+        for (int j = 0; j < NJ; ++j) {                               // (pp_update sites keep the plain loop: see pp_update)
             const int f = lane + 64 * j;
             if (f < D) pp_update(a.P, a.Pm, a.Pv, urow + f, dp[j], a);
         }
@@ -228,12 +180,12 @@ __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_users(PpArgs a) {
 
 template <int NJ>
 __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_items(PpArgs a) {
-    const int64_t p = pp_wave_id();
+    const int64_t p = wave_slot();
     const int lane = threadIdx.x & 63, D = a.D;
     if (p >= a.B || *a.err) return;
     const int32_t i = a.ks_i[p];
     if (p > 0 && a.ks_i[p - 1] == i) return;
-    const int64_t q = pp_run_end(a.ks_i, p, a.B, lane);
+    const int64_t q = sorted_run_end(a.ks_i, p, a.B, lane);
     const int64_t irow = (int64_t)i * D;
     const float lam = a.lam, bi = a.bi[i];
     float qr[NJ], sg[NJ], dq[NJ];
@@ -249,16 +201,12 @@ __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_items(PpArgs a) {
         const int32_t k = a.ps_i[e];
         const float g = a.g[k];
         const int64_t urow = (int64_t)a.u[k] * D;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int f = lane + 64 * j;
-            if (f < D) dq[j] += (g * a.peff[urow + f]) * sg[j] + lam * qr[j];
-        }
+        each_feature<NJ>(lane, D, [&](int j, int f) { dq[j] += (g * a.peff[urow + f]) * sg[j] + lam * qr[j]; });
         dbi += a.reg_bias ? g + lam * bi : g;
     }
     if (!((a.frozen >> 4) & 1)) {
 #pragma unroll
-        for (int j = 0; j < NJ; ++j) {
+        for (int j = 0; j < NJ; ++j) {                               // (pp_update sites keep the plain loop: see pp_update)
             const int f = lane + 64 * j;
             if (f < D) pp_update(a.Q, a.Qm, a.Qv, irow + f, dq[j], a);
         }
@@ -268,20 +216,15 @@ __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_items(PpArgs a) {
 
 template <int NJ>
 __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_ygrad(PpArgs a) {
-    const int64_t w = pp_wave_id();
+    const int64_t w = wave_slot();
     const int lane = threadIdx.x & 63, D = a.D;
     if (w >= a.NT.n_pieces || *a.err) return;
     const int32_t item = a.NT.prow[w];
     int64_t lo, hi;
     pp_piece_range(a.NT, w, item, &lo, &hi);
     const int64_t yrow = (int64_t)item * D;
-    float y[NJ], acc[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int f = lane + 64 * j;
-        y[j] = f < D ? a.Y[yrow + f] : 0.f;
-        acc[j] = 0.f;
-    }
+    float y[NJ] = {}, acc[NJ] = {};
+    each_feature<NJ>(lane, D, [&](int j, int f) { y[j] = a.Y[yrow + f]; });
     int32_t c = 0;
     for (int64_t base = lo; base < hi; base += 64) {
         const int64_t e = base + lane;
@@ -297,54 +240,37 @@ __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_ygrad(PpArgs a) {
             const int32_t r = __shfl(run, b, 64);
             const int32_t cr = a.cnt[r];
             const float lc = a.lam * (float)cr;
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) {
-                const int f = lane + 64 * j;
-                if (f < D) acc[j] += a.W[(int64_t)r * D + f] + lc * y[j];
-            }
+            each_feature<NJ>(lane, D, [&](int j, int f) { acc[j] += a.W[(int64_t)r * D + f] + lc * y[j]; });
             c += cr;
         }
     }
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) {
-        const int f = lane + 64 * j;
-        if (f < D) a.gpart[w * D + f] = acc[j];
-    }
+    each_feature<NJ>(lane, D, [&](int j, int f) { a.gpart[w * D + f] = acc[j]; });
     if (lane == 0) a.gcnt[w] = c;
 }
 
 template <int NJ>
 __global__ void __launch_bounds__(64 * PP_WAVES) k_pp_yapply(PpArgs a) {
-    const int64_t j0 = pp_wave_id();
+    const int64_t j0 = wave_slot();
     const int lane = threadIdx.x & 63, D = a.D;
     if (j0 >= a.I || *a.err) return;
-    float gy[NJ];
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) gy[j] = 0.f;
+    float gy[NJ] = {};
     int32_t c = 0;
     for (int32_t pc = a.NT.pbeg[j0]; pc < a.NT.pbeg[j0 + 1]; ++pc) {
         const int32_t cc = a.gcnt[pc];
         if (cc == 0) continue;
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-            const int f = lane + 64 * j;
-            if (f < D) gy[j] += a.gpart[(int64_t)pc * D + f];
-        }
+        each_feature<NJ>(lane, D, [&](int j, int f) { gy[j] += a.gpart[(int64_t)pc * D + f]; });
         c += cc;
     }
     if (c == 0) return;                                             // untouched row: lazy Adam leaves its slots alone
     const int64_t yrow = j0 * D;
 #pragma unroll
-    for (int j = 0; j < NJ; ++j) {
+    for (int j = 0; j < NJ; ++j) {                               // (pp_update sites keep the plain loop: see pp_update)
         const int f = lane + 64 * j;
         if (f < D) pp_update(a.Y, a.Ym, a.Yv, yrow + f, gy[j], a);
     }
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------
-static int pp_nj(int D) { return (D + 63) / 64; }
-static unsigned pp_blocks(int64_t waves) { return (unsigned)((waves + PP_WAVES - 1) / PP_WAVES); }
-
 void launch_pp_mark(const PpActive& a, const int32_t* err, hipStream_t s) {
     if (a.n <= 0) return;
     hipLaunchKernelGGL(k_pp_mark, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a, err);
@@ -352,24 +278,12 @@ void launch_pp_mark(const PpActive& a, const int32_t* err, hipStream_t s) {
 
 void launch_pp_ypart(const PpArgs& a, hipStream_t s) {
     if (a.N.n_pieces <= 0) return;
-    const dim3 g(pp_blocks(a.N.n_pieces)), b(64 * PP_WAVES);
-    switch (pp_nj(a.D)) {
-        case 1: hipLaunchKernelGGL(k_pp_ypart<1>, g, b, 0, s, a); break;
-        case 2: hipLaunchKernelGGL(k_pp_ypart<2>, g, b, 0, s, a); break;
-        case 3: hipLaunchKernelGGL(k_pp_ypart<3>, g, b, 0, s, a); break;
-        default: hipLaunchKernelGGL(k_pp_ypart<4>, g, b, 0, s, a); break;
-    }
+    with_nj(a.D, [&](auto nj) { hipLaunchKernelGGL(k_pp_ypart<decltype(nj)::value>, wave_grid(a.N.n_pieces), wave_block(), 0, s, a); });
 }
 
 template <int MODE>
 static void launch_users_mode(const PpArgs& a, hipStream_t s) {
-    const dim3 g(pp_blocks(a.act.n)), b(64 * PP_WAVES);
-    switch (pp_nj(a.D)) {
-        case 1: hipLaunchKernelGGL((k_pp_users<1, MODE>), g, b, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((k_pp_users<2, MODE>), g, b, 0, s, a); break;
-        case 3: hipLaunchKernelGGL((k_pp_users<3, MODE>), g, b, 0, s, a); break;
-        default: hipLaunchKernelGGL((k_pp_users<4, MODE>), g, b, 0, s, a); break;
-    }
+    with_nj(a.D, [&](auto nj) { hipLaunchKernelGGL((k_pp_users<decltype(nj)::value, MODE>), wave_grid(a.act.n), wave_block(), 0, s, a); });
 }
 
 void launch_pp_users(const PpArgs& a, int mode, hipStream_t s) {
@@ -381,36 +295,15 @@ void launch_pp_users(const PpArgs& a, int mode, hipStream_t s) {
 
 void launch_pp_items(const PpArgs& a, hipStream_t s) {
     if (a.B <= 0) return;
-    const dim3 g(pp_blocks(a.B)), b(64 * PP_WAVES);
-    switch (pp_nj(a.D)) {
-        case 1: hipLaunchKernelGGL(k_pp_items<1>, g, b, 0, s, a); break;
-        case 2: hipLaunchKernelGGL(k_pp_items<2>, g, b, 0, s, a); break;
-        case 3: hipLaunchKernelGGL(k_pp_items<3>, g, b, 0, s, a); break;
-        default: hipLaunchKernelGGL(k_pp_items<4>, g, b, 0, s, a); break;
-    }
+    with_nj(a.D, [&](auto nj) { hipLaunchKernelGGL(k_pp_items<decltype(nj)::value>, wave_grid(a.B), wave_block(), 0, s, a); });
 }
 
 void launch_pp_y(const PpArgs& a, hipStream_t s) {
-    if ((a.frozen >> 5) & 1) return;                            // Y frozen: neither its gradient nor its update
-    const dim3 b(64 * PP_WAVES);
-    if (a.NT.n_pieces > 0) {
-        const dim3 g(pp_blocks(a.NT.n_pieces));
-        switch (pp_nj(a.D)) {
-            case 1: hipLaunchKernelGGL(k_pp_ygrad<1>, g, b, 0, s, a); break;
-            case 2: hipLaunchKernelGGL(k_pp_ygrad<2>, g, b, 0, s, a); break;
-            case 3: hipLaunchKernelGGL(k_pp_ygrad<3>, g, b, 0, s, a); break;
-            default: hipLaunchKernelGGL(k_pp_ygrad<4>, g, b, 0, s, a); break;
-        }
-    }
-    if (a.I > 0 && a.NT.n_pieces > 0) {
-        const dim3 g(pp_blocks(a.I));
-        switch (pp_nj(a.D)) {
-            case 1: hipLaunchKernelGGL(k_pp_yapply<1>, g, b, 0, s, a); break;
-            case 2: hipLaunchKernelGGL(k_pp_yapply<2>, g, b, 0, s, a); break;
-            case 3: hipLaunchKernelGGL(k_pp_yapply<3>, g, b, 0, s, a); break;
-            default: hipLaunchKernelGGL(k_pp_yapply<4>, g, b, 0, s, a); break;
-        }
-    }
+    if (((a.frozen >> 5) & 1) || a.NT.n_pieces <= 0) return;   // Y frozen: neither its gradient nor its update
+    with_nj(a.D, [&](auto nj) {
+        hipLaunchKernelGGL(k_pp_ygrad<decltype(nj)::value>, wave_grid(a.NT.n_pieces), wave_block(), 0, s, a);
+        if (a.I > 0) hipLaunchKernelGGL(k_pp_yapply<decltype(nj)::value>, wave_grid(a.I), wave_block(), 0, s, a);
+    });
 }
 
 }  // namespace tfr

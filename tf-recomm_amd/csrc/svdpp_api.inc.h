@@ -88,15 +88,10 @@ static PpArgs pp_args(tfr_svdpp* h) {
 // sort n ids by user (and, with di, by item; both columns checked against the tables) and stamp the user runs
 static int pp_activate(tfr_svdpp* h, PpArgs& a, const int32_t* du, const int32_t* di, int64_t n) {
     tfr_model* m = h->m;
-    const int32_t* keys[2] = {du, di};
-    const int bits[2] = {m->bits_u, m->bits_i};
-    int32_t* ks[2] = {m->ks_u, m->ks_i};
-    int32_t* ps[2] = {m->ps_u, m->ps_i};
-    const int64_t limits[2] = {m->U, m->I};
     int rc;
     {
         Prof p(m, TFR_K_SORT);
-        if ((rc = radix_sort_columns(m, di ? 2 : 1, keys, bits, ks, ps, n, limits))) return rc;
+        if ((rc = sort_model_columns(m, du, di, n, true))) return rc;
     }
     if (h->cur == 0x7fffffff) {                          // the numbers wrap: start the stamps afresh
         HIPCHK(hipMemsetAsync(h->stamp, 0, (size_t)m->U * 4, m->stream));
@@ -438,8 +433,7 @@ int tfr_svdpp_train_step(tfr_svdpp* h, const int32_t* u, const int32_t* i, const
     if (rc) return rc;
     if (B > 0 && !r) return fail(TFR_ERR_ARG, "null rate pointer");
     if ((rc = pp_ensure_batch(h, B))) return rc;
-    const int64_t step0 = m->step;
-    const float b1p0 = m->b1p, b2p0 = m->b2p;
+    const StepMark mark = mark_step(m);
     if (B > 0) {
         HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
         HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
@@ -452,7 +446,7 @@ int tfr_svdpp_train_step(tfr_svdpp* h, const int32_t* u, const int32_t* i, const
     HIPCHK(hipStreamSynchronize(m->stream));
     const int32_t e = (int32_t)back[(size_t)B + 3];
     if (e) {                                             // a bad batch never advances the step
-        rollback_step(m, step0, b1p0, b2p0);
+        rollback_step(m, mark);
         return device_error(m, e);
     }
     if (logits_out && B > 0) memcpy(logits_out, back.data(), (size_t)B * 4);
@@ -465,7 +459,7 @@ int tfr_svdpp_topk(tfr_svdpp* h, const int32_t* users, int64_t n, int32_t k, con
                    const int32_t* excl_items, int32_t* items_out, float* scores_out) {
     PP_ENTER(h);
     if (n < 0) return fail(TFR_ERR_ARG, "top-K: negative n_users");
-    if (k < 1 || k > TOPK_KMAX) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
+    if (int rc = check_k("top-K", k)) return rc;
     if (n == 0) return pp_need_n(h);
     if (!users || !items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
     if (excl_indptr && !excl_items && excl_indptr[n] > excl_indptr[0]) return fail(TFR_ERR_ARG, "top-K: exclusion indptr without items");
@@ -479,8 +473,9 @@ int tfr_svdpp_topk_dev(tfr_svdpp* h, const int32_t* d_users, int64_t n, int32_t 
                        const int32_t* d_excl_items, int32_t* d_items_out, float* d_scores_out) {
     PP_ENTER(h);
     if (n < 0) return fail(TFR_ERR_ARG, "top-K: negative n_users");
-    if (k < 1 || k > TOPK_KMAX) return fail(TFR_ERR_ARG, "top-K: k must be in [1, %d] (got %d)", TOPK_KMAX, k);
-    int rc = pp_need_n(h);
+    int rc = check_k("top-K", k);
+    if (rc) return rc;
+    rc = pp_need_n(h);
     if (rc || n == 0) return rc;
     if (!d_users || !d_items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
     if ((rc = pp_ensure_batch(h, n))) return rc;
