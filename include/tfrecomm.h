@@ -626,6 +626,13 @@ int tfr_profile_read(tfr_model* m, int32_t kernel, double* total_ms, int64_t* la
 int tfr_lds_bytes(int32_t kernel, int32_t dim, int64_t batch, int64_t user_num, int64_t item_num,
                   int64_t* static_bytes, int64_t* dynamic_bytes);
 
+/* Residency guard of the small-table sweep (k_dense_tiles as a training step launches it for this shape): workgroups
+ * of it that fit one CU and its scratch bytes per lane, as the runtime reports them for the loaded code, and the
+ * workgroups of the launch.  The step's timing rests on the whole grid being resident at once and on no spills.
+ * Needs a device. */
+int tfr_sweep_residency(int32_t dim, int64_t batch, int64_t user_num, int64_t item_num,
+                        int32_t* blocks_per_cu, int64_t* scratch_bytes, int64_t* grid_blocks);
+
 /* ---- misc ------------------------------------------------------------------------------ */
 int tfr_sync(tfr_model* m);            /* drains the stream; reports deferred TFR_ERR_OOB   */
 const char* tfr_last_error(void);

@@ -147,6 +147,7 @@ SIGNATURES = {
     "tfr_profile": (C.c_int, [_p, C.c_int32]),
     "tfr_profile_read": (C.c_int, [_p, C.c_int32, C.POINTER(C.c_double), _i64p]),
     "tfr_lds_bytes": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _i64p, _i64p]),
+    "tfr_sweep_residency": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, _i32p, _i64p, _i64p]),
     "tfr_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
     "tfr_topk_dev": (C.c_int, [_p, _p, C.c_int64, C.c_int32, _p, _p, _p, _p]),
     "tfr_fm_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),

@@ -2286,6 +2286,29 @@ int tfr_lds_bytes(int32_t kernel, int32_t dim, int64_t batch, int64_t user_num, 
     return TFR_OK;
 }
 
+// what keeps the small-table sweep one shift of workgroups: its step instantiation's resident workgroups per CU and
+// scratch bytes per lane as the runtime reports them for the loaded code object, and the grid the shape launches
+int tfr_sweep_residency(int32_t dim, int64_t batch, int64_t user_num, int64_t item_num,
+                        int32_t* blocks_per_cu, int64_t* scratch_bytes, int64_t* grid_blocks) {
+    int G, VEC;
+    if (!geometry(dim, &G, &VEC)) return fail(TFR_ERR_ARG, "unsupported dim %d", dim);
+    if (batch < 1 || user_num < 1 || item_num < 1) return fail(TFR_ERR_ARG, "sweep_residency: batch and row counts must be >= 1");
+    const int bu = bits_for(user_num), bi = bits_for(item_num);
+    const int64_t ntiles = (batch + CSORT_TILE - 1) / CSORT_TILE;
+    if ((1 << (bu > bi ? bu : bi)) > CSORT_MAX_BINS || !csort_eligible(batch, bu, bi) || ntiles > 16)
+        return fail(TFR_ERR_ARG, "shape does not take k_dense_tiles");
+    const void* k = dense_tiles_kernel(false, G, VEC, (int)ntiles);
+    if (!k) return fail(TFR_ERR_ARG, "no k_dense_tiles instantiation for dim %d", dim);
+    int nblk = 0;
+    hipFuncAttributes attr;
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nblk, k, 256, 0));
+    HIPCHK(hipFuncGetAttributes(&attr, k));
+    if (blocks_per_cu) *blocks_per_cu = nblk;
+    if (scratch_bytes) *scratch_bytes = (int64_t)attr.localSizeBytes;
+    if (grid_blocks) *grid_blocks = 2 * ((int64_t)dense_tiles_grid(user_num > item_num ? user_num : item_num, G) + 1);
+    return TFR_OK;
+}
+
 static int ensure_ring(tfr_model* m, int64_t B) {
     if (B <= m->ring_cap) return TFR_OK;
     const int64_t cap = pow2_cap(B);

@@ -168,6 +168,7 @@ enum : int32_t {
 };
 constexpr int32_t TFR_WT_DEFAULT = TFR_WT_ROWS | TFR_WT_MOMENTS | TFR_WT_BIAS | TFR_WT_PIECES | TFR_WT_PUBLISH;
 int tile_step_wt();
+int sweep_rounds();                                 // TFR_SWEEP_ROUNDS=0: k_dense_tiles takes its general form everywhere (A/B, bit-identical)
 
 // small-table sweep over per-tile partial gradients (k_dense_tiles)
 struct TileDenseArgs {
@@ -180,8 +181,13 @@ struct TileDenseArgs {
     int32_t D, nbins, ntiles, frozen_rows, frozen_bias, opt, skip_untouched;
     float alpha, b1, b2, eps, lr;
 };
-struct TileDenseLaunch { TileDenseArgs a[2]; FinArgs f; int32_t with_fin; int32_t wt; };
+struct TileDenseLaunch { TileDenseArgs a[2]; FinArgs f; int32_t with_fin; int32_t wt; int32_t rounds; };   // rounds: the full-width three-round form (set by the launcher)
 void launch_dense_tiles(const TileDenseLaunch& L, bool write, bool with_fin, int G, int VEC, hipStream_t s);
+// the instantiation launch_dense_tiles takes for this geometry and tile count (nullptr: none), its grid's block columns,
+// and whether a launch of `rows` rows of width D takes the three-round form
+const void* dense_tiles_kernel(bool write, int G, int VEC, int ntiles);
+int dense_tiles_grid(int64_t rows, int G);
+bool dense_tiles_rounds_taken(int64_t rows, int D, int G, int VEC);
 
 // one-pass stable counting sort of both id columns (small tables: all bins fit in LDS)
 struct CSortArgs {

@@ -118,6 +118,26 @@ __device__ __forceinline__ void store_word_p(void* base, size_t idx, uint32_t x,
     else reinterpret_cast<uint32_t*>(base)[idx] = x;
 }
 
+// loads through the same kind of resource (k_dense_tiles' full-width form): one VGPR of byte offset per address, and a load
+// predicated without a branch - an offset past the resource's 2^31 - 1 bytes is answered with zeros and goes to no
+// cache (unlike a dummy address, which would be one hot L2 line), so a row of loads is one basic block
+constexpr int BUF_NONE = (int)0x80000000u;
+__device__ __forceinline__ uint32_t buf_load_word(__amdgpu_buffer_rsrc_t r, int byte_off) {
+    return __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0);
+}
+template <int VEC>
+__device__ __forceinline__ Frag<VEC> buf_load_frag(__amdgpu_buffer_rsrc_t r, int byte_off) {
+    Frag<VEC> f;
+    if constexpr (VEC == 4) {
+        typedef unsigned uintx4 __attribute__((ext_vector_type(4)));
+        const uintx4 t = __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0);
+        f.v[0] = __uint_as_float(t.x); f.v[1] = __uint_as_float(t.y); f.v[2] = __uint_as_float(t.z); f.v[3] = __uint_as_float(t.w);
+    } else {
+        f.v[0] = __uint_as_float(buf_load_word(r, byte_off));
+    }
+    return f;
+}
+
 template <int G>
 __device__ __forceinline__ float group_sum(float x) {
     // butterfly over the G lanes of a group (G is a power of two <= 64); every lane of the
@@ -1653,12 +1673,181 @@ __global__ __launch_bounds__(256) void k_adam_dense(DensePair pr) {
 //      tables, so the loads are independent) and then either applies the optimiser (TF1 Adam: every
 //      row; lazy Adam / SGD: touched rows) or - data parallel - writes the row into the dense
 //      gradient buffer.  blockIdx.y == 2 runs the step's finalize (K4).
+//
+//      Full-width rows (D == G * VEC) with one lane group per row in the grid take dense_tiles_rounds: the same sums in
+//      the same order in three load rounds.  Round 1: the NT table entries, the error word, then w, m, v and the bias
+//      words; only the entries and the error word are waited for.  Round 2: every head piece and the first two k = 1
+//      continuation pieces of the row (their addresses follow from the entries alone), all in flight together.
+//      Round 3: the stores.  A row with more than two k = 1 continuations or a deeper one (a run over three pieces)
+//      goes through the round-major loop from k = 1 as in the general form.  Absent pieces are loads past the
+//      resource's end (zeros, no memory access) and are added as +0.0f: the sums start at +0.0f and never become
+//      -0.0f, so that changes no bit.
 template <int G, int VEC, bool WRITE, int NT>
-__global__ __launch_bounds__(256) void k_dense_tiles(TileDenseLaunch L) {
+__device__ __forceinline__ void dense_tiles_rounds(const TileDenseLaunch& L) {
+    const TileDenseArgs& a = L.a[blockIdx.y];
+    constexpr int GPB = 256 / G;
+    constexpr int EPB = 1024 / G;
+    constexpr int D = G * VEC;
+    constexpr int NB = (NT > 12) ? 8 : NT;               // NT = 16: the heads in two batches of eight
+    const int gl = threadIdx.x % G;
+    const int d0 = gl * VEC;
+    const int row = (int)blockIdx.x * GPB + threadIdx.x / G;
+    if (row >= a.rows) return;
+    // ---- round 1
+    const __amdgpu_buffer_rsrc_t rtab =                  // ends with the last tile's table: entries of tiles past it read as 0
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(a.tab), 0, a.ntiles * a.nbins * 4, 0x00020000);
+    int32_t ent[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) ent[t] = (int32_t)buf_load_word(rtab, (t * a.nbins + row) * 4);
+    int32_t err = (int32_t)buf_load_word(wt_rsrc(a.err), 0);
+    __builtin_amdgcn_sched_barrier(0);
+    const int roff = (row * D + d0) * 4;
+    Frag<VEC> w, mrow, vrow;
+    float bw = 0.f, mb = 0.f, vb = 0.f;
+    if constexpr (!WRITE) {
+        const int ow = a.frozen_rows ? BUF_NONE : roff;
+        const int om = (a.frozen_rows || a.opt != 0) ? BUF_NONE : roff;
+        w = buf_load_frag<VEC>(wt_rsrc(a.w), ow);
+        mrow = buf_load_frag<VEC>(wt_rsrc(a.m), om);
+        vrow = buf_load_frag<VEC>(wt_rsrc(a.v), om);
+        const int ob = (gl == 0 && !a.frozen_bias) ? row * 4 : BUF_NONE;
+        const int obm = (gl == 0 && !a.frozen_bias && a.opt == 0) ? row * 4 : BUF_NONE;
+        bw = __uint_as_float(buf_load_word(wt_rsrc(a.bias_w), ob));
+        mb = __uint_as_float(buf_load_word(wt_rsrc(a.bias_m), obm));
+        vb = __uint_as_float(buf_load_word(wt_rsrc(a.bias_v), obm));
+    }
+    __builtin_amdgcn_sched_barrier(0);                   // everything above is issued before the error word is looked at
+    asm volatile("" : "+v"(err) : : "memory");
+    if (err) return;                                     // a voided step: the tables' contents are not to be trusted as addresses
+    // ---- round 2: addresses from the entries alone
+    int s0 = -1, s1 = -1, nk1 = 0;                       // the first two k = 1 continuation pieces (entry index), how many there are
+    bool deep = false, touched = false;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        const int32_t e = ent[t];
+        const int off = e & 0xffff;
+        const int pp = t * 1024 + (off / EPB + 1) * EPB;
+        const int end = t * 1024 + off + (e >> 16);
+        const bool has1 = pp < end;
+        deep = deep || pp + EPB < end;
+        s1 = (has1 && nk1 == 1) ? pp : s1;
+        s0 = (has1 && nk1 == 0) ? pp : s0;
+        nk1 += has1 ? 1 : 0;
+        touched = touched || (e >> 16);
+    }
+    const __amdgpu_buffer_rsrc_t rg = wt_rsrc(a.grad_rows), rgb = wt_rsrc(a.grad_bias);
+    Frag<VEC> tot, c0, c1;
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) tot.v[q] = 0.f;
+    float gb = 0.f, cb0 = 0.f, cb1 = 0.f;
+#pragma unroll
+    for (int t0 = 0; t0 < NT; t0 += NB) {
+        Frag<VEC> x[NB];
+        float xb[NB];
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {
+            const int32_t e = ent[t0 + t];
+            const int j = (t0 + t) * 1024 + (e & 0xffff);
+            x[t] = buf_load_frag<VEC>(rg, (e >> 16) ? (j * D + d0) * 4 : BUF_NONE);
+            xb[t] = __uint_as_float(buf_load_word(rgb, ((e >> 16) && gl == 0) ? j * 4 : BUF_NONE));
+        }
+        if (t0 == 0) {
+            c0 = buf_load_frag<VEC>(rg, s0 >= 0 ? (s0 * D + d0) * 4 : BUF_NONE);
+            cb0 = __uint_as_float(buf_load_word(rgb, (s0 >= 0 && gl == 0) ? s0 * 4 : BUF_NONE));
+            c1 = buf_load_frag<VEC>(rg, s1 >= 0 ? (s1 * D + d0) * 4 : BUF_NONE);
+            cb1 = __uint_as_float(buf_load_word(rgb, (s1 >= 0 && gl == 0) ? s1 * 4 : BUF_NONE));
+        }
+        __builtin_amdgcn_sched_barrier(0);               // the batch is in flight before its first piece is added
+#pragma unroll
+        for (int t = 0; t < NB; ++t) {                   // head pieces, added in tile order
+#pragma unroll
+            for (int q = 0; q < VEC; ++q) tot.v[q] += x[t].v[q];
+            gb += xb[t];
+        }
+    }
+    if (nk1 <= 2 && !deep) {                             // round k = 1 by tile, and there is no round k = 2
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) tot.v[q] += c0.v[q];
+        gb += cb0;
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) tot.v[q] += c1.v[q];
+        gb += cb1;
+    } else {                                             // hot rows: round-major, tile-minor from k = 1 (see the general form)
+        for (int k = 1;; ++k) {
+            bool more = false;
+#pragma unroll
+            for (int t0 = 0; t0 < NT; t0 += NB) {
+                Frag<VEC> y[NB];
+                float yb[NB];
+#pragma unroll
+                for (int t = 0; t < NB; ++t) {
+                    const int32_t e = ent[t0 + t];
+                    const int j = (t0 + t) * 1024 + (e & 0xffff);
+                    const int pp = (j / EPB + k) * EPB;
+                    const bool has = pp < j + (e >> 16);
+                    y[t] = buf_load_frag<VEC>(rg, has ? (pp * D + d0) * 4 : BUF_NONE);
+                    yb[t] = __uint_as_float(buf_load_word(rgb, (has && gl == 0) ? pp * 4 : BUF_NONE));
+                    more = more || has;
+                }
+#pragma unroll
+                for (int t = 0; t < NB; ++t) {
+#pragma unroll
+                    for (int q = 0; q < VEC; ++q) tot.v[q] += y[t].v[q];
+                    gb += yb[t];
+                }
+            }
+            if (!more) break;
+        }
+    }
+    // ---- round 3
+    const size_t rfl = (size_t)row * D;
+    if constexpr (WRITE) {
+        if (touched) {
+            store_frag<VEC>(a.out_rows + rfl, d0, D, tot);
+            if (gl == 0) a.out_bias[row] = gb;
+        }
+    } else {
+        if (!touched && a.skip_untouched) return;
+        const AdamC c = {a.alpha, a.b1, a.b2, a.eps, 1.f - a.b1, 1.f - a.b2};
+        const int wt = L.wt;
+        if (!a.frozen_rows) {
+            if (a.opt == 0) {
+#pragma unroll
+                for (int q = 0; q < VEC; ++q) adam_sparse(w.v[q], mrow.v[q], vrow.v[q], tot.v[q], c);
+                store_frag_p<VEC>(a.m, rfl, d0, D, mrow, wt & TFR_WT_MOMENTS);
+                store_frag_p<VEC>(a.v, rfl, d0, D, vrow, wt & TFR_WT_MOMENTS);
+            } else {                                     // spelled as the general form is compiled (one fused multiply-add per
+#pragma unroll                                           // element; the bias below a product and a difference): bit-identical
+                for (int q = 0; q < VEC; ++q) w.v[q] = __builtin_fmaf(-a.lr, tot.v[q], w.v[q]);
+            }
+            store_frag_p<VEC>(a.w, rfl, d0, D, w, wt & TFR_WT_ROWS);
+        }
+        if (gl == 0 && !a.frozen_bias) {
+            const bool wb = wt & TFR_WT_BIAS;
+            if (a.opt == 0) {
+                adam_sparse(bw, mb, vb, gb, c);
+                store_word_p(a.bias_m, (size_t)row, __float_as_uint(mb), wb);
+                store_word_p(a.bias_v, (size_t)row, __float_as_uint(vb), wb);
+            } else {
+                bw = bw - __fmul_rn(a.lr, gb);
+            }
+            store_word_p(a.bias_w, (size_t)row, __float_as_uint(bw), wb);
+        }
+    }
+}
+
+template <int G, int VEC, bool WRITE, int NT>
+__global__ __launch_bounds__(256, (NT > 12 && VEC == 4 && !WRITE) ? 2 : 3) void k_dense_tiles(TileDenseLaunch L) {   // (the register budget)
     warm_args(L.a[blockIdx.y]);
     if (blockIdx.x == gridDim.x - 1) {                   // the extra block column: K4 (optional), nothing else
         if (blockIdx.y == 0 && L.with_fin) finalize_body(L.f);
         return;
+    }
+    if constexpr (VEC == 4) {                            // (VEC == 1 rows are never full width: D % 4 != 0 there)
+        if (L.rounds) {                                  // block-uniform: full-width rows, one lane group per row (launch_dense_tiles)
+            dense_tiles_rounds<G, VEC, WRITE, NT>(L);
+            return;
+        }
     }
     const TileDenseArgs& a = L.a[blockIdx.y];
     const int32_t err = *a.err;                          // looked at behind the first round of loads (they need no lookup table):
@@ -2079,36 +2268,64 @@ void launch_apply_rows(const ApplyPair& p, int n, int opt, int G, int VEC, hipSt
 #undef TFR_APP_CASE
 }
 
-void launch_dense_tiles(const TileDenseLaunch& L, bool write, bool with_fin, int G, int VEC, hipStream_t s) {
+int sweep_rounds() {                                     // TFR_SWEEP_ROUNDS=0: A/B switch, the general form of k_dense_tiles everywhere
+    static int on = -1;
+    if (on < 0) { const char* e = getenv("TFR_SWEEP_ROUNDS"); on = (e && e[0] == '0') ? 0 : 1; }
+    return on;
+}
+
+int dense_tiles_grid(int64_t rows, int G) {              // block columns that hold rows (the launch adds one for K4)
     const int gpb = 256 / G;
-    int64_t rows = L.a[0].rows > L.a[1].rows ? L.a[0].rows : L.a[1].rows;
     int64_t nb = (rows + gpb - 1) / gpb;
     if (nb > 4096) nb = 4096;
     if (nb < 1) nb = 1;
-    const dim3 grid((int)nb + 1, 2);                     // + one block column for K4
+    return (int)nb;
+}
+
+// the three-round form has no row loop and no width guards: full-width rows, one lane group per row in the grid
+bool dense_tiles_rounds_taken(int64_t rows, int D, int G, int VEC) {
+    return sweep_rounds() && VEC == 4 && D == G * VEC && rows <= (int64_t)dense_tiles_grid(rows, G) * (256 / G);
+}
+
+#define TFR_DT_PICK(g, v, wr, nt) TFR_DT_DO((k_dense_tiles<g, v, wr, nt>))
+#define TFR_DT_CASE(g, v)                                                                         \
+    if (G == g && VEC == v) {                                                                     \
+        if (write) {                                                                              \
+            if (nt <= 4) TFR_DT_PICK(g, v, true, 4); else if (nt <= 8) TFR_DT_PICK(g, v, true, 8);          \
+            else if (nt <= 10) TFR_DT_PICK(g, v, true, 10);                                                 \
+            else if (nt <= 12) TFR_DT_PICK(g, v, true, 12); else TFR_DT_PICK(g, v, true, 16);               \
+        } else {                                                                                  \
+            if (nt <= 4) TFR_DT_PICK(g, v, false, 4); else if (nt <= 8) TFR_DT_PICK(g, v, false, 8);        \
+            else if (nt <= 10) TFR_DT_PICK(g, v, false, 10);                                                \
+            else if (nt <= 12) TFR_DT_PICK(g, v, false, 12); else TFR_DT_PICK(g, v, false, 16);             \
+        }                                                                                         \
+    }
+#define TFR_DT_ALL                                                                                \
+    TFR_DT_CASE(4, 4) TFR_DT_CASE(8, 4) TFR_DT_CASE(16, 4) TFR_DT_CASE(32, 4) TFR_DT_CASE(64, 4)  \
+    TFR_DT_CASE(4, 1) TFR_DT_CASE(8, 1) TFR_DT_CASE(16, 1) TFR_DT_CASE(32, 1) TFR_DT_CASE(64, 1)
+
+const void* dense_tiles_kernel(bool write, int G, int VEC, int nt) {
+#define TFR_DT_DO(k) return reinterpret_cast<const void*>(&k)
+    TFR_DT_ALL
+#undef TFR_DT_DO
+    return nullptr;
+}
+
+void launch_dense_tiles(const TileDenseLaunch& L, bool write, bool with_fin, int G, int VEC, hipStream_t s) {
+    const int64_t rows = L.a[0].rows > L.a[1].rows ? L.a[0].rows : L.a[1].rows;
+    const dim3 grid(dense_tiles_grid(rows, G) + 1, 2);   // + one block column for K4
     TileDenseLaunch LL = L;
     LL.with_fin = with_fin ? 1 : 0;
     LL.wt = tile_step_wt() & (TFR_WT_ROWS | TFR_WT_MOMENTS | TFR_WT_BIAS);
-#define TFR_DT_LAUNCH(g, v, wr, nt) hipLaunchKernelGGL((k_dense_tiles<g, v, wr, nt>), grid, dim3(256), 0, s, LL)
-#define TFR_DT_CASE(g, v)                                                                         \
-    if (G == g && VEC == v) {                                                                     \
-        const int nt = L.a[0].ntiles;                                                             \
-        if (write) {                                                                              \
-            if (nt <= 4) TFR_DT_LAUNCH(g, v, true, 4); else if (nt <= 8) TFR_DT_LAUNCH(g, v, true, 8);      \
-            else if (nt <= 10) TFR_DT_LAUNCH(g, v, true, 10);                                               \
-            else if (nt <= 12) TFR_DT_LAUNCH(g, v, true, 12); else TFR_DT_LAUNCH(g, v, true, 16);           \
-        } else {                                                                                  \
-            if (nt <= 4) TFR_DT_LAUNCH(g, v, false, 4); else if (nt <= 8) TFR_DT_LAUNCH(g, v, false, 8);    \
-            else if (nt <= 10) TFR_DT_LAUNCH(g, v, false, 10);                                              \
-            else if (nt <= 12) TFR_DT_LAUNCH(g, v, false, 12); else TFR_DT_LAUNCH(g, v, false, 16);         \
-        }                                                                                         \
-        return;                                                                                   \
-    }
-    TFR_DT_CASE(4, 4) TFR_DT_CASE(8, 4) TFR_DT_CASE(16, 4) TFR_DT_CASE(32, 4) TFR_DT_CASE(64, 4)
-    TFR_DT_CASE(4, 1) TFR_DT_CASE(8, 1) TFR_DT_CASE(16, 1) TFR_DT_CASE(32, 1) TFR_DT_CASE(64, 1)
-#undef TFR_DT_LAUNCH
-#undef TFR_DT_CASE
+    LL.rounds = (L.a[0].D == L.a[1].D && dense_tiles_rounds_taken(rows, L.a[0].D, G, VEC)) ? 1 : 0;
+    const int nt = L.a[0].ntiles;
+#define TFR_DT_DO(k) do { hipLaunchKernelGGL(k, grid, dim3(256), 0, s, LL); return; } while (0)
+    TFR_DT_ALL
+#undef TFR_DT_DO
 }
+#undef TFR_DT_ALL
+#undef TFR_DT_CASE
+#undef TFR_DT_PICK
 
 void launch_adam_dense(DensePair& p, int n, int G, int VEC, hipStream_t s, const FinArgs* fin) {
     if (fin) { p.f = *fin; n = 3; }
