@@ -146,3 +146,27 @@ def test_als_reaches_both_ends_of_the_one_wave_cholesky():
         assert all(1 <= d <= ALS_MAXD for d in listed), (name, listed)
     assert {1, ALS_MAXD} <= set(W.ALS), "ALS: d = 1 and d = %d not both listed" % ALS_MAXD
     assert ALS_MAXD in W.ALS_CHUNKED, "ALS_CHUNKED: no chunked long list at d = %d" % ALS_MAXD
+
+
+def als_step_class(d):
+    """(live A-entry slots, last slot exactly full, one staging pass, end of the range): k_als_fit and k_als_partial keep
+    entry t = tid + 256 q of A in acc[q], so ceil(d * d / 256) slots are live and the last is full where d * d is a multiple
+    of 256; als_accumulate stages a 32-rating tile with `for (t = tid; t < nk * d; t += 256)`, one pass while 32 d <= 256
+    (csrc/als_kernels.hip).  A range of widths with the same slots and passes is run at its lowest and its highest d."""
+    key = lambda x: (-(-x * x // 256), -(-32 * x // 256) == 1)
+    first = d == 1 or key(d - 1) != key(d)
+    last = d == ALS_MAXD or key(d + 1) != key(d)
+    return key(d)[0], d * d % 256 == 0, key(d)[1], "lowest d" if first else "highest d" if last else "inside"
+
+
+def test_als_step_reaches_both_ends_of_every_slot_count_and_staging_form():
+    assert all(1 <= d <= ALS_MAXD for d in W.ALS_STEP), W.ALS_STEP
+    reachable = {als_step_class(d) for d in range(1, ALS_MAXD + 1)}
+    assert {c[0] for c in reachable} == {1, 2, 3, 4} and {c[:2] for c in reachable if c[1]} == {(1, True), (4, True)}
+    wanted = {c for c in reachable if c[3] != "inside"}
+    assert len(wanted) == 10
+    covered = {als_step_class(d) for d in W.ALS_STEP}
+    missing = sorted(wanted - covered)
+    assert not missing, "ALS_STEP: no width reaches %s (widths %s)" % (", ".join(map(str, missing)), list(W.ALS_STEP))
+    from tests import als_cases
+    assert {c["d"] for c in als_cases.CASES if c["id"].startswith("tile_edges")} >= set(W.ALS_STEP)

@@ -36,3 +36,6 @@ FM_TOPK = (25, 200)                                        # FM get_ranking / ra
 # ALS: one-wave Cholesky, lane r owns row r, 1 <= d <= ALS_MAXD
 ALS = (1, 32)
 ALS_CHUNKED = (32,)
+# the ALS half-sweep per entity (tests/test_gpu_als_step.py): both ends of each count of live A-entry slots ceil(d*d / 256)
+# (the last slot exactly full at d = 16 and d = 32), and both sides of the one-pass LDS staging of a 32-rating tile (d <= 8)
+ALS_STEP = (1, 8, 9, 16, 17, 22, 23, 27, 28, 32)
