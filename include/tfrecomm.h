@@ -375,6 +375,35 @@ int tfr_als_sweep(tfr_als* m, int32_t n_iterations, float* elapsed_ms /* may be 
 int tfr_als_predict(tfr_als* m, const int64_t* user_ids, const int64_t* work_ids, int64_t n, double* out);
 const char* tfr_als_last_error(void);
 
+/* ---- implicit-feedback ALS (Hu, Koren, Volinsky: weighted matrix factorisation), float64, 1 <= d <= 64 ----------------
+ *      Data: a user x item CSR R of strictly positive values, each row strictly increasing in item id.  Preference
+ *      p_ui = 1 on stored pairs, 0 elsewhere; confidence c_ui = 1 + alpha r_ui on stored pairs, 1 elsewhere.  Minimises
+ *          L(X, Y) = sum_{u,i} c_ui (p_ui - x_u . y_i)^2 + lambda (||X||_F^2 + ||Y||_F^2)       over all U x I pairs.
+ *      A half-sweep of side 0 solves, for every user, (G + sum_{i in N(u)} (c_ui - 1) y_i y_i^T + lambda I) x_u =
+ *      sum_{i in N(u)} c_ui y_i with G = Y^T Y (Cholesky); a user without pairs gets exactly 0.  Side 1 is the same for the
+ *      items over the transposed lists (users ascending), which tfr_ials_load builds.  tfr_ials_sweep runs n x (side 0,
+ *      side 1).  Every sum has a fixed order (32-row tiles, chunks of `chunk` entries for longer lists, Gram slices set by
+ *      the table's row count alone): results are bit-identical from run to run.
+ *      tfr_ials_gram(side) returns T^T T of side's table: what the next half-sweep of the OTHER side uses.
+ *      tfr_ials_loss evaluates L without the dense matrix: sum_u [x_u^T G x_u + sum_{N(u)} (c (1 - s)^2 - s^2)] +
+ *      lambda (||X||^2 + trace G), s = x_u . y_i, G = Y^T Y.
+ *      Host pointers; every call synchronises.  Checked before any device work (the model is left as it was):
+ *      TFR_ERR_ARG for d outside [1, 64], lambda_ <= 0, alpha < 0, a value that is not positive and finite, a row that is
+ *      not strictly increasing, a chunk that is not a positive multiple of 32 (0 = 512); TFR_ERR_OOB for an item id out
+ *      of range; TFR_ERR_STATE for half, sweep or loss before a load.  A second load replaces the first. */
+typedef struct tfr_ials tfr_ials;
+int tfr_ials_create(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t d, double lambda_, double alpha, int32_t device);
+int tfr_ials_destroy(tfr_ials* m);
+int tfr_ials_set(tfr_ials* m, const double* X, const double* Y);          /* either may be NULL */
+int tfr_ials_get(tfr_ials* m, double* X, double* Y);                      /* either may be NULL */
+int tfr_ials_load(tfr_ials* m, const int64_t* indptr /* [n_users+1] */, const int32_t* items, const double* vals,
+                  int32_t chunk /* 0 = 512 */);
+int tfr_ials_half(tfr_ials* m, int32_t side /* 0 users, 1 items */, float* elapsed_ms /* may be NULL */);
+int tfr_ials_sweep(tfr_ials* m, int32_t n_iterations, float* elapsed_ms /* may be NULL */);
+int tfr_ials_gram(tfr_ials* m, int32_t side, double* G_out /* [d*d] */);
+int tfr_ials_loss(tfr_ials* m, double* loss_out);
+const char* tfr_ials_last_error(void);
+
 /* ---- top-K recommendation: forward.py:47-61 get_ranking(), als3.py:110-113 (rank the dense U.V^T + biases) ----------------
  *      score(u, i) = ((dot + mu) + bu[u]) + bi[i] (the forward's order), dot = the f32 fmaf chain over f = 0..dim-1 ascending,
  *      from +0, of P[u,f] * Q'[i,f] (Q' = |Q| with item_abs); the logit under the NLL head.  Per requested user the k best

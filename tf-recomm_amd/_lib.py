@@ -142,6 +142,16 @@ SIGNATURES = {
     "tfr_als_sweep": (C.c_int, [_p, C.c_int32, _f32p]),
     "tfr_als_predict": (C.c_int, [_p, _i64p, _i64p, C.c_int64, _f64p]),
     "tfr_als_last_error": (C.c_char_p, []),
+    "tfr_ials_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32]),
+    "tfr_ials_destroy": (C.c_int, [_p]),
+    "tfr_ials_set": (C.c_int, [_p, _f64p, _f64p]),
+    "tfr_ials_get": (C.c_int, [_p, _f64p, _f64p]),
+    "tfr_ials_load": (C.c_int, [_p, _i64p, _i32p, _f64p, C.c_int32]),
+    "tfr_ials_half": (C.c_int, [_p, C.c_int32, _f32p]),
+    "tfr_ials_sweep": (C.c_int, [_p, C.c_int32, _f32p]),
+    "tfr_ials_gram": (C.c_int, [_p, C.c_int32, _f64p]),
+    "tfr_ials_loss": (C.c_int, [_p, _f64p]),
+    "tfr_ials_last_error": (C.c_char_p, []),
     "tfr_sort_segments": (C.c_int, [_p, C.c_int32, _i32p, C.c_int64, _i32p, _i32p]),
     "tfr_kernel_plan": (C.c_int, [_p, C.c_int64, C.c_char_p, C.c_int64]),
     "tfr_profile": (C.c_int, [_p, C.c_int32]),

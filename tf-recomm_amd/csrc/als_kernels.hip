@@ -19,6 +19,7 @@
 #include <algorithm>
 #include "tfrecomm.h"
 #include "devbuf.h"
+#include "als_common.h"
 
 using tfr::DevBuf;
 
@@ -128,39 +129,8 @@ __global__ __launch_bounds__(256) void k_als_fit(AlsFitArgs a) {
         }
         if (tid < d) bvec[tid] = accb;
         __syncthreads();
-        // Cholesky A = L L^T (in place, lower triangle) and the two triangular solves, by ONE wave: lane r owns row r, a column
-        // step is j LDS reads of row j (broadcast) and of the lane's own row - no block barrier (a wave's LDS accesses are made
-        // in program order; volatile keeps the compiler from moving a read of another lane's element over the write it follows).
-        // The block-wide version (thread 0 alone on the diagonal and in the substitutions, a barrier pair per column) cost
-        // ~50 us per entity, most of the sweep.  Same operations in the same order per element.
-        if (tid < 64) {
-            const int r = tid;
-            volatile double (*L)[ALS_MAXD + 1] = A;
-            for (int j = 0; j < d; ++j) {
-                double s = 0.0;
-                if (r >= j && r < d) {
-                    s = L[r][j];
-                    for (int k = 0; k < j; ++k) s -= L[r][k] * L[j][k];
-                }
-                const double piv = sqrt(__shfl(s, j, 64));
-                if (r == j) L[j][j] = piv;
-                else if (r > j && r < d) L[r][j] = s / piv;
-            }
-            // L y = b, column by column: lane i finishes y_i, the lanes below take it off their right-hand sides
-            double y = (r < d) ? bvec[r] : 0.0;
-            for (int i = 0; i < d; ++i) {
-                const double yi = __shfl(y / ((r == i) ? L[i][i] : 1.0), i, 64);
-                if (r == i) y = yi;
-                else if (r > i && r < d) y -= L[r][i] * yi;
-            }
-            // L^T x = y, from the last column up: column i of L^T is row i of L
-            for (int i = d - 1; i >= 0; --i) {
-                const double xi = __shfl(y / ((r == i) ? L[i][i] : 1.0), i, 64);
-                if (r == i) y = xi;
-                else if (r < i) y -= L[i][r] * xi;
-            }
-            if (r < d) xvec[r] = y;
-        }
+        // Cholesky and the two triangular solves by one wave (als_common.h)
+        if (tid < 64) tfr::chol_wave_solve<ALS_MAXD + 1>(A, bvec, xvec, d);
         __syncthreads();
         if (tid < d) a.own[(size_t)idx * d + tid] = xvec[tid];
         // W_own = mean(R - x.V[J] - W_other[J]) / (1 + lambda) - bias
@@ -222,9 +192,7 @@ struct tfr_als {
     DevBuf<int32_t> ids_u, ids_w, users, works;
     DevBuf<double> val_u, val_w;
     // chunk tables for long rating lists, per side (0 = users, 1 = works)
-    DevBuf<int32_t> cfirst[2], ccount[2], chunk_ent[2];
-    DevBuf<int64_t> chunk_lo[2], chunk_hi[2];
-    int64_t n_chunks[2] = {0, 0};
+    tfr::DevChunks chunks[2];
     DevBuf<double> partial;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
@@ -360,39 +328,15 @@ int tfr_als_load(tfr_als* m, const int64_t* user_ids, const int64_t* work_ids, c
     if (!lu.empty()) ALSCHK(hipMemcpy(m->users, lu.data(), lu.size() * 4, hipMemcpyHostToDevice));
     if (!lw.empty()) ALSCHK(hipMemcpy(m->works, lw.data(), lw.size() * 4, hipMemcpyHostToDevice));
     m->n = n; m->n_users = (int64_t)lu.size(); m->n_works = (int64_t)lw.size();
-    // long lists (a blockbuster item can hold a few per cent of all ratings) would leave one block working
-    // long after the rest of the sweep has finished: cut them into chunks of CH ratings
+    // long lists are cut into chunks of CH ratings (als_common.h)
     int64_t CH = 512;                                     // A/B in one call: 2048 1.33 ms per iteration, 1024 1.18, 512 1.12, 256 1.16, 128 1.38
     if (const char* e = getenv("TFR_ALS_CHUNK")) { const long v = atol(e); if (v >= ALS_TILE) CH = (v / ALS_TILE) * ALS_TILE; }
     size_t max_chunks = 0;
     for (int z = 0; z < 2; ++z) {
-        const std::vector<int64_t>& ptr = z == 0 ? pu : pw;
         const int64_t rows = z == 0 ? m->nu : m->nw;
-        std::vector<int32_t> cf((size_t)rows, -1), cc((size_t)rows, 0), ce;
-        std::vector<int64_t> cl, chh;
-        for (int64_t r = 0; r < rows; ++r) {
-            const int64_t lo = ptr[(size_t)r], hi = ptr[(size_t)r + 1];
-            if (hi - lo <= CH) continue;
-            cf[(size_t)r] = (int32_t)ce.size();
-            for (int64_t s0 = lo; s0 < hi; s0 += CH) {
-                ce.push_back((int32_t)r); cl.push_back(s0); chh.push_back(std::min(hi, s0 + CH));
-                cc[(size_t)r]++;
-            }
-        }
-        m->n_chunks[z] = (int64_t)ce.size();
-        ALSCHK(m->cfirst[z].reserve(rows, m->stream));
-        ALSCHK(m->ccount[z].reserve(rows, m->stream));
-        ALSCHK(hipMemcpy(m->cfirst[z], cf.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
-        ALSCHK(hipMemcpy(m->ccount[z], cc.data(), (size_t)rows * 4, hipMemcpyHostToDevice));
-        if (!ce.empty()) {
-            ALSCHK(m->chunk_ent[z].reserve((int64_t)ce.size(), m->stream));
-            ALSCHK(m->chunk_lo[z].reserve((int64_t)ce.size(), m->stream));
-            ALSCHK(m->chunk_hi[z].reserve((int64_t)ce.size(), m->stream));
-            ALSCHK(hipMemcpy(m->chunk_ent[z], ce.data(), ce.size() * 4, hipMemcpyHostToDevice));
-            ALSCHK(hipMemcpy(m->chunk_lo[z], cl.data(), ce.size() * 8, hipMemcpyHostToDevice));
-            ALSCHK(hipMemcpy(m->chunk_hi[z], chh.data(), ce.size() * 8, hipMemcpyHostToDevice));
-        }
-        max_chunks = std::max(max_chunks, ce.size());
+        const tfr::ChunkPlan plan = tfr::plan_chunks(z == 0 ? pu : pw, rows, CH);
+        ALSCHK(m->chunks[z].upload(plan, rows, m->stream));
+        max_chunks = std::max(max_chunks, plan.ent.size());
     }
     ALSCHK(m->partial.reserve((int64_t)max_chunks * (m->d * m->d + m->d), m->stream));
     return TFR_OK;
@@ -415,14 +359,14 @@ int tfr_als_sweep(tfr_als* m, int32_t n_iterations, float* elapsed_ms) {
         a.bias = m->bias; a.lambda = m->lambda; a.d = m->d;
         a.list = m->users; a.n_list = m->n_users; a.ptr = m->ptr_u; a.ids = m->ids_u; a.vals = m->val_u;
         a.own = m->U; a.w_own = m->Wu; a.other = m->V; a.w_other = m->Ww;
-        a.cfirst = m->cfirst[0]; a.ccount = m->ccount[0]; a.chunk_ent = m->chunk_ent[0]; a.chunk_lo = m->chunk_lo[0];
-        a.chunk_hi = m->chunk_hi[0]; a.n_chunks = m->n_chunks[0]; a.partial = m->partial;
+        a.cfirst = m->chunks[0].cfirst; a.ccount = m->chunks[0].ccount; a.chunk_ent = m->chunks[0].ent; a.chunk_lo = m->chunks[0].lo;
+        a.chunk_hi = m->chunks[0].hi; a.n_chunks = m->chunks[0].n; a.partial = m->partial;
         if (a.n_list && a.n_chunks) hipLaunchKernelGGL(k_als_partial, dim3((unsigned)std::min<int64_t>(a.n_chunks, 65535)), dim3(256), 0, m->stream, a);
         if (a.n_list) hipLaunchKernelGGL(k_als_fit, dim3((unsigned)std::min<int64_t>(a.n_list, 65535)), dim3(256), 0, m->stream, a);
         a.list = m->works; a.n_list = m->n_works; a.ptr = m->ptr_w; a.ids = m->ids_w; a.vals = m->val_w;
         a.own = m->V; a.w_own = m->Ww; a.other = m->U; a.w_other = m->Wu;
-        a.cfirst = m->cfirst[1]; a.ccount = m->ccount[1]; a.chunk_ent = m->chunk_ent[1]; a.chunk_lo = m->chunk_lo[1];
-        a.chunk_hi = m->chunk_hi[1]; a.n_chunks = m->n_chunks[1]; a.partial = m->partial;
+        a.cfirst = m->chunks[1].cfirst; a.ccount = m->chunks[1].ccount; a.chunk_ent = m->chunks[1].ent; a.chunk_lo = m->chunks[1].lo;
+        a.chunk_hi = m->chunks[1].hi; a.n_chunks = m->chunks[1].n; a.partial = m->partial;
         if (a.n_list && a.n_chunks) hipLaunchKernelGGL(k_als_partial, dim3((unsigned)std::min<int64_t>(a.n_chunks, 65535)), dim3(256), 0, m->stream, a);
         if (a.n_list) hipLaunchKernelGGL(k_als_fit, dim3((unsigned)std::min<int64_t>(a.n_list, 65535)), dim3(256), 0, m->stream, a);
     }

@@ -1,0 +1,504 @@
+// ials.hip - implicit-feedback ALS (Hu, Koren, Volinsky: weighted matrix factorisation) on the GPU, float64, 1 <= d <= 64.
+//   R: user x item CSR of strictly positive values.  p_ui = 1 on stored pairs, 0 elsewhere; c_ui = 1 + alpha r_ui on
+//   stored pairs, 1 elsewhere.  One half-sweep, for every entity u with list N(u) in CSR order and partner table Y:
+//       G   = Y^T Y                                         (k_ials_gram + k_ials_gram_sum, once per half-sweep)
+//       A_u = G + sum_{i in N(u)} w_ui y_i y_i^T + lambda I   w_ui = alpha r_ui = c_ui - 1
+//       b_u = sum_{i in N(u)} c_ui y_i                        c_ui = 1 + w_ui
+//       x_u = A_u^{-1} b_u                                    (one-wave Cholesky, als_common.h); an empty list gives exactly 0
+//   One 256-thread block per entity builds the sums from 32-row tiles of partner rows staged in LDS: thread tid keeps the
+//   A entries t = tid + 256 q (row t / d, column t % d) in registers, up to 16 of them, and thread tid < d the b entry tid.
+//   Lists longer than the chunk size are cut into chunks: k_ials_partial builds each chunk's sums in its own block, the
+//   entity's block adds them in list order.  The Gram is cut into row slices whose size depends on n only; each slice's
+//   d x d partial is built by one block and the partials are added in ascending slice order.  No atomics anywhere: every
+//   sum has a fixed order and the results are bit-identical from run to run, whatever the grid.
+//   Loss: L = sum_u [ x_u^T G x_u + sum_{i in N(u)} (c_ui (1 - s_ui)^2 - s_ui^2) ] + lambda (||X||^2 + trace(G)),
+//   s_ui = x_u . y_i, G = Y^T Y - the dense U x I matrix is never formed.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdarg.h>
+#include <stdio.h>
+#include <string.h>
+#include <new>
+#include <vector>
+#include <algorithm>
+#include "tfrecomm.h"
+#include "devbuf.h"
+#include "als_common.h"
+
+using tfr::DevBuf;
+
+namespace {
+
+constexpr int IALS_MAXD = 64;
+constexpr int IALS_TILE = 32;            // partner rows staged per LDS tile
+constexpr int IALS_LD = IALS_MAXD + 1;   // LDS row stride: lane r of the Cholesky walks row r, the odd stride spreads the banks
+constexpr int IALS_SLOTS = IALS_MAXD * IALS_MAXD / 256;   // A entries per thread at d = 64
+constexpr int64_t IALS_GRAM_ROWS = 128;  // smallest Gram slice
+constexpr int64_t IALS_GRAM_SLICES = 1024;   // most Gram slices: bounds the partial buffer at 1024 d^2 doubles
+
+// rows per Gram slice: a function of n alone, a multiple of the tile
+__host__ __device__ inline int64_t gram_slice_rows(int64_t n) {
+    const int64_t per = (n + IALS_GRAM_SLICES - 1) / IALS_GRAM_SLICES;
+    const int64_t rows = (per + IALS_TILE - 1) / IALS_TILE * IALS_TILE;
+    return rows < IALS_GRAM_ROWS ? IALS_GRAM_ROWS : rows;
+}
+
+struct IalsArgs {
+    int64_t n;                                                     // entities of this side, empty ones included
+    const int64_t* ptr; const int32_t* ids; const double* vals;    // their lists: partner ids, values
+    double* own; const double* other; const double* G;             // G = other^T other
+    double lambda, alpha;
+    int32_t d;
+    const int32_t* cfirst; const int32_t* ccount;
+    const int32_t* chunk_ent; const int64_t* chunk_lo; const int64_t* chunk_hi; int64_t n_chunks;
+    double* partial;                                               // [n_chunks][d*d + d]
+};
+
+// Sums over the list entries [lo, hi): acc[q] += sum_k (w_k y_k[r]) y_k[c] for the A entries t = tid + 256 q = r d + c,
+// accb += sum_k c_k y_k[tid]; 32-row tiles staged in LDS, k ascending.  WEIGHTED = false is the Gram's form: the rows
+// lo .. hi - 1 of T themselves, acc[q] += sum_k y_k[r] y_k[c], no b.
+template <bool WEIGHTED>
+__device__ __forceinline__ void ials_accumulate(const double* T, const int32_t* ids, const double* vals, double alpha, int d,
+                                                int64_t lo, int64_t hi, double (&acc)[IALS_SLOTS], double& accb,
+                                                double (*rows)[IALS_LD], double* wk, double* ck) {
+    const int tid = threadIdx.x, dd = d * d;
+    int rc[IALS_SLOTS];                                            // r << 8 | c of each live slot
+#pragma unroll
+    for (int q = 0; q < IALS_SLOTS; ++q) {
+        const int t = tid + 256 * q;
+        rc[q] = (t < dd) ? ((t / d) << 8 | (t % d)) : -1;
+    }
+    for (int64_t s = lo; s < hi; s += IALS_TILE) {
+        const int nk = (int)((hi - s < IALS_TILE) ? hi - s : IALS_TILE);
+        for (int t = tid; t < nk * d; t += 256) {
+            const int k = t / d, c = t % d;
+            const int64_t row = WEIGHTED ? (int64_t)ids[s + k] : s + k;
+            rows[k][c] = T[(size_t)row * d + c];
+        }
+        if (WEIGHTED && tid < nk) {
+            const double w = alpha * vals[s + tid];
+            wk[tid] = w;
+            ck[tid] = 1.0 + w;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < IALS_SLOTS; ++q) {
+            if (rc[q] >= 0) {
+                const int r = rc[q] >> 8, c = rc[q] & 255;
+                double sacc = acc[q];
+                if (WEIGHTED) for (int k = 0; k < nk; ++k) sacc += (wk[k] * rows[k][r]) * rows[k][c];
+                else for (int k = 0; k < nk; ++k) sacc += rows[k][r] * rows[k][c];
+                acc[q] = sacc;
+            }
+        }
+        if (WEIGHTED && tid < d) {
+            double sb = accb;
+            for (int k = 0; k < nk; ++k) sb += ck[k] * rows[k][tid];
+            accb = sb;
+        }
+        __syncthreads();
+    }
+}
+
+// one Gram slice: partial[slice][t] = sum over the slice's rows, ascending
+__global__ __launch_bounds__(256) void k_ials_gram(const double* T, int64_t n, int d, int64_t slice_rows, int64_t n_slices, double* partial) {
+    __shared__ double rows[IALS_TILE][IALS_LD];
+    const int tid = threadIdx.x, dd = d * d;
+    for (int64_t sl = blockIdx.x; sl < n_slices; sl += gridDim.x) {
+        const int64_t lo = sl * slice_rows, hi = (lo + slice_rows < n) ? lo + slice_rows : n;
+        double acc[IALS_SLOTS];
+#pragma unroll
+        for (int q = 0; q < IALS_SLOTS; ++q) acc[q] = 0.0;
+        double accb = 0.0;
+        __syncthreads();
+        ials_accumulate<false>(T, nullptr, nullptr, 0.0, d, lo, hi, acc, accb, rows, nullptr, nullptr);
+        double* pp = partial + (size_t)sl * dd;
+#pragma unroll
+        for (int q = 0; q < IALS_SLOTS; ++q) { const int t = tid + 256 * q; if (t < dd) pp[t] = acc[q]; }
+    }
+}
+
+// G[t] = the slices' partials added in ascending slice order
+__global__ __launch_bounds__(256) void k_ials_gram_sum(const double* partial, int64_t n_slices, int d, double* G) {
+    const int dd = d * d;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= dd) return;
+    double s = 0.0;
+    for (int64_t sl = 0; sl < n_slices; ++sl) s += partial[(size_t)sl * dd + t];
+    G[t] = s;
+}
+
+// partial sums of one chunk of a long list
+__global__ __launch_bounds__(256) void k_ials_partial(IalsArgs a) {
+    __shared__ double rows[IALS_TILE][IALS_LD];
+    __shared__ double wk[IALS_TILE], ck[IALS_TILE];
+    const int tid = threadIdx.x, d = a.d, dd = d * d;
+    for (int64_t c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
+        double acc[IALS_SLOTS];
+#pragma unroll
+        for (int q = 0; q < IALS_SLOTS; ++q) acc[q] = 0.0;
+        double accb = 0.0;
+        __syncthreads();
+        ials_accumulate<true>(a.other, a.ids, a.vals, a.alpha, d, a.chunk_lo[c], a.chunk_hi[c], acc, accb, rows, wk, ck);
+        double* pp = a.partial + (size_t)c * (dd + d);
+#pragma unroll
+        for (int q = 0; q < IALS_SLOTS; ++q) { const int t = tid + 256 * q; if (t < dd) pp[t] = acc[q]; }
+        if (tid < d) pp[dd + tid] = accb;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_ials_fit(IalsArgs a) {
+    __shared__ double A[IALS_MAXD][IALS_LD];
+    __shared__ double rows[IALS_TILE][IALS_LD];
+    __shared__ double wk[IALS_TILE], ck[IALS_TILE];
+    __shared__ double bvec[IALS_MAXD], xvec[IALS_MAXD];
+    const int tid = threadIdx.x, d = a.d, dd = d * d;
+    for (int64_t e = blockIdx.x; e < a.n; e += gridDim.x) {
+        const int64_t lo = a.ptr[e], hi = a.ptr[e + 1];
+        if (lo == hi) {                                            // b = 0: the minimiser is 0
+            if (tid < d) a.own[(size_t)e * d + tid] = 0.0;
+            continue;
+        }
+        double acc[IALS_SLOTS];
+#pragma unroll
+        for (int q = 0; q < IALS_SLOTS; ++q) acc[q] = 0.0;
+        double accb = 0.0;
+        __syncthreads();
+        const int32_t nch = a.ccount[e];
+        if (nch > 0) {                                             // a long list: add the chunks' partial sums, in list order
+            const int32_t c0 = a.cfirst[e];
+            for (int32_t ch = 0; ch < nch; ++ch) {
+                const double* pp = a.partial + (size_t)(c0 + ch) * (dd + d);
+#pragma unroll
+                for (int q = 0; q < IALS_SLOTS; ++q) { const int t = tid + 256 * q; if (t < dd) acc[q] += pp[t]; }
+                if (tid < d) accb += pp[dd + tid];
+            }
+        } else {
+            ials_accumulate<true>(a.other, a.ids, a.vals, a.alpha, d, lo, hi, acc, accb, rows, wk, ck);
+        }
+#pragma unroll
+        for (int q = 0; q < IALS_SLOTS; ++q) {
+            const int t = tid + 256 * q;
+            if (t < dd) {
+                const int r = t / d, c = t % d;
+                A[r][c] = (a.G[t] + acc[q]) + ((r == c) ? a.lambda : 0.0);
+            }
+        }
+        if (tid < d) bvec[tid] = accb;
+        __syncthreads();
+        if (tid < 64) tfr::chol_wave_solve<IALS_LD>(A, bvec, xvec, d);
+        __syncthreads();
+        if (tid < d) a.own[(size_t)e * d + tid] = xvec[tid];
+    }
+}
+
+// per-user part of the loss: x^T G x + lambda |x|^2 + sum_{i in N(u)} (c (1 - s)^2 - s^2); G = Y^T Y.
+// Thread tid < d holds x_tid ((G x)_tid + lambda x_tid), thread tid the list entries lo + tid + 256 j; both go into
+// red[tid], summed by a halving tree.
+__global__ __launch_bounds__(256) void k_ials_loss_users(IalsArgs a, double* per_user) {
+    __shared__ double x[IALS_MAXD];
+    __shared__ double red[256];
+    const int tid = threadIdx.x, d = a.d;
+    for (int64_t e = blockIdx.x; e < a.n; e += gridDim.x) {
+        __syncthreads();
+        if (tid < d) x[tid] = a.own[(size_t)e * d + tid];
+        __syncthreads();
+        double part = 0.0;
+        if (tid < d) {
+            double gx = 0.0;
+            for (int c = 0; c < d; ++c) gx += a.G[tid * d + c] * x[c];
+            part = x[tid] * (gx + a.lambda * x[tid]);
+        }
+        const int64_t lo = a.ptr[e], hi = a.ptr[e + 1];
+        for (int64_t k = lo + tid; k < hi; k += 256) {
+            const double* y = a.other + (size_t)a.ids[k] * d;
+            double s = 0.0;
+            for (int c = 0; c < d; ++c) s += x[c] * y[c];
+            const double cc = 1.0 + a.alpha * a.vals[k];
+            const double om = 1.0 - s;
+            part += cc * (om * om) - s * s;
+        }
+        red[tid] = part;
+        __syncthreads();
+        for (int o = 128; o >= 1; o >>= 1) {
+            if (tid < o) red[tid] += red[tid + o];
+            __syncthreads();
+        }
+        if (tid == 0) per_user[e] = red[0];
+    }
+}
+
+// loss = (sum of per_user: 256 strided sums, then a halving tree) + lambda trace(G); one block
+__global__ __launch_bounds__(256) void k_ials_loss_reduce(const double* per_user, int64_t n, const double* G, int d, double lambda, double* out) {
+    __shared__ double red[256];
+    const int tid = threadIdx.x;
+    double part = 0.0;
+    for (int64_t k = tid; k < n; k += 256) part += per_user[k];
+    red[tid] = part;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if (tid < o) red[tid] += red[tid + o];
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double tr = 0.0;
+        for (int c = 0; c < d; ++c) tr += G[c * d + c];
+        out[0] = red[0] + lambda * tr;
+    }
+}
+
+thread_local char g_ials_err[512] = "";
+int ials_fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_ials_err, sizeof(g_ials_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+#define IALSCHK(expr)                                                                                  \
+    do {                                                                                               \
+        hipError_t e_ = (expr);                                                                        \
+        if (e_ != hipSuccess) return ials_fail(e_ == hipErrorOutOfMemory ? TFR_ERR_NOMEM : TFR_ERR_HIP, \
+                                               "%s: %s", #expr, hipGetErrorString(e_));                \
+    } while (0)
+
+}  // namespace
+
+struct tfr_ials {
+    int64_t n[2] = {0, 0};                               // users, items
+    int32_t d = 0;
+    double lambda = 0.0, alpha = 0.0;
+    int device = 0;
+    bool loaded = false;
+    hipStream_t stream = nullptr;
+    DevBuf<double> tab[2];                               // X [n_users, d], Y [n_items, d]
+    // side z: the lists of its entities (side 0: the CSR as given; side 1: its transpose, each list by ascending user)
+    DevBuf<int64_t> ptr[2];
+    DevBuf<int32_t> ids[2];
+    DevBuf<double> vals[2];
+    tfr::DevChunks chunks[2];
+    DevBuf<double> partial, G, gram_partial, per_user, loss;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+namespace {
+
+// G = tab[side]^T tab[side], queued on the model's stream
+hipError_t queue_gram(tfr_ials* m, int side) {
+    const int64_t n = m->n[side], rows = gram_slice_rows(n), ns = (n + rows - 1) / rows;
+    hipLaunchKernelGGL(k_ials_gram, dim3((unsigned)ns), dim3(256), 0, m->stream, m->tab[side].get(), n, m->d, rows, ns, m->gram_partial.get());
+    hipLaunchKernelGGL(k_ials_gram_sum, dim3((unsigned)((m->d * m->d + 255) / 256)), dim3(256), 0, m->stream, m->gram_partial.get(), ns,
+                       m->d, m->G.get());
+    return hipGetLastError();
+}
+
+IalsArgs side_args(tfr_ials* m, int side) {
+    IalsArgs a;
+    a.n = m->n[side]; a.ptr = m->ptr[side]; a.ids = m->ids[side]; a.vals = m->vals[side];
+    a.own = m->tab[side]; a.other = m->tab[1 - side]; a.G = m->G;
+    a.lambda = m->lambda; a.alpha = m->alpha; a.d = m->d;
+    a.cfirst = m->chunks[side].cfirst; a.ccount = m->chunks[side].ccount; a.chunk_ent = m->chunks[side].ent;
+    a.chunk_lo = m->chunks[side].lo; a.chunk_hi = m->chunks[side].hi; a.n_chunks = m->chunks[side].n;
+    a.partial = m->partial;
+    return a;
+}
+
+// one half-sweep of `side`, queued: the partner table's Gram, the long lists' chunks, every entity
+hipError_t queue_half(tfr_ials* m, int side) {
+    hipError_t e = queue_gram(m, 1 - side);
+    if (e != hipSuccess) return e;
+    const IalsArgs a = side_args(m, side);
+    if (a.n_chunks) hipLaunchKernelGGL(k_ials_partial, dim3((unsigned)std::min<int64_t>(a.n_chunks, 65535)), dim3(256), 0, m->stream, a);
+    hipLaunchKernelGGL(k_ials_fit, dim3((unsigned)std::min<int64_t>(a.n, 65535)), dim3(256), 0, m->stream, a);
+    return hipGetLastError();
+}
+
+int finish_timed(tfr_ials* m, float* elapsed_ms) {
+    (void)hipEventRecord(m->ev1, m->stream);
+    IALSCHK(hipStreamSynchronize(m->stream));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, m->ev0, m->ev1) != hipSuccess) ms = 0.f;
+        *elapsed_ms = ms;
+    }
+    return TFR_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* tfr_ials_last_error(void) { return g_ials_err; }
+
+int tfr_ials_destroy(tfr_ials* m) {
+    if (!m) return TFR_OK;
+    (void)hipSetDevice(m->device);                       // the buffers are freed with the model's device current
+    if (m->stream) (void)hipStreamSynchronize(m->stream);
+    if (m->ev0) (void)hipEventDestroy(m->ev0);
+    if (m->ev1) (void)hipEventDestroy(m->ev1);
+    if (m->stream) (void)hipStreamDestroy(m->stream);
+    delete m;
+    return TFR_OK;
+}
+
+int tfr_ials_create(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t d, double lambda_, double alpha, int32_t device) {
+    if (!out) return ials_fail(TFR_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (n_users < 1 || n_items < 1 || n_users > 0x7fffffffLL || n_items > 0x7fffffffLL || d < 1 || d > IALS_MAXD)
+        return ials_fail(TFR_ERR_ARG, "need 1 <= d <= %d and positive int32 table sizes", IALS_MAXD);
+    if (!(lambda_ > 0.0) || !std::isfinite(lambda_)) return ials_fail(TFR_ERR_ARG, "lambda must be positive and finite");
+    if (!(alpha >= 0.0) || !std::isfinite(alpha)) return ials_fail(TFR_ERR_ARG, "alpha must be non-negative and finite");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+        return ials_fail(TFR_ERR_HIP, "no HIP device available - this library has no CPU path");
+    if (device < 0 || device >= ndev) return ials_fail(TFR_ERR_ARG, "device %d not in [0,%d)", device, ndev);
+    IALSCHK(hipSetDevice(device));
+    tfr_ials* m = new (std::nothrow) tfr_ials();
+    if (!m) return ials_fail(TFR_ERR_NOMEM, "host allocation failed");
+    m->n[0] = n_users; m->n[1] = n_items; m->d = d; m->lambda = lambda_; m->alpha = alpha; m->device = device;
+    const int64_t max_slices = std::max((n_users + gram_slice_rows(n_users) - 1) / gram_slice_rows(n_users),
+                                        (n_items + gram_slice_rows(n_items) - 1) / gram_slice_rows(n_items));
+    hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
+    for (int z = 0; z < 2 && e == hipSuccess; ++z) {
+        e = m->tab[z].reserve(m->n[z] * d, m->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(m->tab[z], 0, (size_t)m->n[z] * d * 8, m->stream);
+    }
+    if (e == hipSuccess) e = m->G.reserve((int64_t)d * d, m->stream);
+    if (e == hipSuccess) e = m->gram_partial.reserve(max_slices * d * d, m->stream);
+    if (e == hipSuccess) e = m->per_user.reserve(n_users, m->stream);
+    if (e == hipSuccess) e = m->loss.reserve(1, m->stream);
+    if (e == hipSuccess) e = hipEventCreate(&m->ev0);
+    if (e == hipSuccess) e = hipEventCreate(&m->ev1);
+    if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+    if (e != hipSuccess) {
+        const int code = e == hipErrorOutOfMemory ? TFR_ERR_NOMEM : TFR_ERR_HIP;
+        tfr_ials_destroy(m);
+        return ials_fail(code, "ials_create: %s", hipGetErrorString(e));
+    }
+    *out = m;
+    return TFR_OK;
+}
+
+int tfr_ials_set(tfr_ials* m, const double* X, const double* Y) {
+    if (!m) return ials_fail(TFR_ERR_ARG, "null model");
+    IALSCHK(hipSetDevice(m->device));
+    if (X) IALSCHK(hipMemcpyAsync(m->tab[0], X, (size_t)m->n[0] * m->d * 8, hipMemcpyHostToDevice, m->stream));
+    if (Y) IALSCHK(hipMemcpyAsync(m->tab[1], Y, (size_t)m->n[1] * m->d * 8, hipMemcpyHostToDevice, m->stream));
+    IALSCHK(hipStreamSynchronize(m->stream));
+    return TFR_OK;
+}
+
+int tfr_ials_get(tfr_ials* m, double* X, double* Y) {
+    if (!m) return ials_fail(TFR_ERR_ARG, "null model");
+    IALSCHK(hipSetDevice(m->device));
+    if (X) IALSCHK(hipMemcpyAsync(X, m->tab[0], (size_t)m->n[0] * m->d * 8, hipMemcpyDeviceToHost, m->stream));
+    if (Y) IALSCHK(hipMemcpyAsync(Y, m->tab[1], (size_t)m->n[1] * m->d * 8, hipMemcpyDeviceToHost, m->stream));
+    IALSCHK(hipStreamSynchronize(m->stream));
+    return TFR_OK;
+}
+
+// The user x item CSR.  Everything is checked and both orientations and their chunk tables are built on the host before
+// any device work, so a refused load leaves the model as it was.
+int tfr_ials_load(tfr_ials* m, const int64_t* indptr, const int32_t* items, const double* vals, int32_t chunk) {
+    if (!m || !indptr) return ials_fail(TFR_ERR_ARG, "load: null model or indptr");
+    if (chunk == 0) chunk = 512;
+    if (chunk < IALS_TILE || chunk % IALS_TILE) return ials_fail(TFR_ERR_ARG, "load: chunk must be a positive multiple of %d", IALS_TILE);
+    const int64_t nu = m->n[0], ni = m->n[1];
+    if (indptr[0] != 0) return ials_fail(TFR_ERR_ARG, "load: indptr must start at 0");
+    for (int64_t u = 0; u < nu; ++u)
+        if (indptr[u + 1] < indptr[u]) return ials_fail(TFR_ERR_ARG, "load: indptr decreases at row %lld", (long long)u);
+    const int64_t nnz = indptr[nu];
+    if (nnz > 0 && (!items || !vals)) return ials_fail(TFR_ERR_ARG, "load: null items or values");
+    for (int64_t u = 0; u < nu; ++u)
+        for (int64_t k = indptr[u]; k < indptr[u + 1]; ++k) {
+            if (items[k] < 0 || items[k] >= ni) return ials_fail(TFR_ERR_OOB, "load: row %lld: item %d out of range", (long long)u, items[k]);
+            if (k > indptr[u] && items[k] <= items[k - 1])
+                return ials_fail(TFR_ERR_ARG, "load: row %lld is not strictly increasing", (long long)u);
+            if (!(vals[k] > 0.0) || !std::isfinite(vals[k]))
+                return ials_fail(TFR_ERR_ARG, "load: row %lld: values must be positive and finite", (long long)u);
+        }
+    // the item-major orientation: users ascend inside each item's list because the rows are walked in order
+    std::vector<int64_t> pu(indptr, indptr + nu + 1), pi((size_t)ni + 1, 0);
+    for (int64_t k = 0; k < nnz; ++k) pi[(size_t)items[k] + 1]++;
+    for (int64_t i = 0; i < ni; ++i) pi[(size_t)i + 1] += pi[(size_t)i];
+    std::vector<int64_t> cur(pi.begin(), pi.end() - 1);
+    std::vector<int32_t> iu((size_t)nnz);
+    std::vector<double> vi((size_t)nnz);
+    for (int64_t u = 0; u < nu; ++u)
+        for (int64_t k = indptr[u]; k < indptr[u + 1]; ++k) {
+            const int64_t p = cur[(size_t)items[k]]++;
+            iu[(size_t)p] = (int32_t)u;
+            vi[(size_t)p] = vals[k];
+        }
+    const tfr::ChunkPlan plan[2] = {tfr::plan_chunks(pu, nu, chunk), tfr::plan_chunks(pi, ni, chunk)};
+    const int64_t max_chunks = (int64_t)std::max(plan[0].ent.size(), plan[1].ent.size());
+
+    IALSCHK(hipSetDevice(m->device));
+    IALSCHK(hipStreamSynchronize(m->stream));
+    m->loaded = false;
+    const int64_t cap = std::max<int64_t>(1, nnz);
+    for (int z = 0; z < 2; ++z) {
+        IALSCHK(m->ptr[z].reserve(m->n[z] + 1, m->stream));
+        IALSCHK(m->ids[z].reserve(cap, m->stream));
+        IALSCHK(m->vals[z].reserve(cap, m->stream));
+        IALSCHK(m->chunks[z].upload(plan[z], m->n[z], m->stream));
+    }
+    IALSCHK(m->partial.reserve(std::max<int64_t>(1, max_chunks * (m->d * m->d + m->d)), m->stream));
+    IALSCHK(hipMemcpy(m->ptr[0], pu.data(), pu.size() * 8, hipMemcpyHostToDevice));
+    IALSCHK(hipMemcpy(m->ptr[1], pi.data(), pi.size() * 8, hipMemcpyHostToDevice));
+    if (nnz) {
+        IALSCHK(hipMemcpy(m->ids[0], items, (size_t)nnz * 4, hipMemcpyHostToDevice));
+        IALSCHK(hipMemcpy(m->vals[0], vals, (size_t)nnz * 8, hipMemcpyHostToDevice));
+        IALSCHK(hipMemcpy(m->ids[1], iu.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
+        IALSCHK(hipMemcpy(m->vals[1], vi.data(), (size_t)nnz * 8, hipMemcpyHostToDevice));
+    }
+    m->loaded = true;
+    return TFR_OK;
+}
+
+int tfr_ials_half(tfr_ials* m, int32_t side, float* elapsed_ms) {
+    if (!m || side < 0 || side > 1) return ials_fail(TFR_ERR_ARG, "bad arguments");
+    if (!m->loaded) return ials_fail(TFR_ERR_STATE, "no data: call tfr_ials_load first");
+    IALSCHK(hipSetDevice(m->device));
+    (void)hipEventRecord(m->ev0, m->stream);
+    IALSCHK(queue_half(m, side));
+    return finish_timed(m, elapsed_ms);
+}
+
+int tfr_ials_sweep(tfr_ials* m, int32_t n_iterations, float* elapsed_ms) {
+    if (!m || n_iterations < 0) return ials_fail(TFR_ERR_ARG, "bad arguments");
+    if (!m->loaded) return ials_fail(TFR_ERR_STATE, "no data: call tfr_ials_load first");
+    IALSCHK(hipSetDevice(m->device));
+    (void)hipEventRecord(m->ev0, m->stream);
+    for (int it = 0; it < n_iterations; ++it) {
+        IALSCHK(queue_half(m, 0));
+        IALSCHK(queue_half(m, 1));
+    }
+    return finish_timed(m, elapsed_ms);
+}
+
+int tfr_ials_gram(tfr_ials* m, int32_t side, double* G_out) {
+    if (!m || side < 0 || side > 1 || !G_out) return ials_fail(TFR_ERR_ARG, "bad arguments");
+    IALSCHK(hipSetDevice(m->device));
+    IALSCHK(queue_gram(m, side));
+    IALSCHK(hipMemcpyAsync(G_out, m->G, (size_t)m->d * m->d * 8, hipMemcpyDeviceToHost, m->stream));
+    IALSCHK(hipStreamSynchronize(m->stream));
+    return TFR_OK;
+}
+
+int tfr_ials_loss(tfr_ials* m, double* loss_out) {
+    if (!m || !loss_out) return ials_fail(TFR_ERR_ARG, "bad arguments");
+    if (!m->loaded) return ials_fail(TFR_ERR_STATE, "no data: call tfr_ials_load first");
+    IALSCHK(hipSetDevice(m->device));
+    IALSCHK(queue_gram(m, 1));
+    const IalsArgs a = side_args(m, 0);
+    hipLaunchKernelGGL(k_ials_loss_users, dim3((unsigned)std::min<int64_t>(a.n, 65535)), dim3(256), 0, m->stream, a, m->per_user.get());
+    hipLaunchKernelGGL(k_ials_loss_reduce, dim3(1), dim3(256), 0, m->stream, m->per_user.get(), a.n, m->G.get(), m->d, m->lambda,
+                       m->loss.get());
+    IALSCHK(hipGetLastError());
+    IALSCHK(hipMemcpyAsync(loss_out, m->loss, 8, hipMemcpyDeviceToHost, m->stream));
+    IALSCHK(hipStreamSynchronize(m->stream));
+    return TFR_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,123 @@
+"""Implicit ALS iteration timings: one JSON line per width, every leg on the same pairs in the same process.
+
+    python tools/bench_ials.py [--dims 32,64] [--iters 10] [--out profiles/bench_ials.jsonl]
+
+Data: ML-1M-shaped synthetic pairs (6040 x 3706, 1 M draws, item popularity p(i) ~ 1 / (i + 50), as tools/bench_bpr.py),
+values 1 .. 5.  Legs: ImplicitALS.sweep (device time per iteration from the library's events) and each half on its own
+(tfr_ials_half); MangakiALS3's iteration on the same pairs as ratings, at d = 32 only (its limit); and the NumPy float64
+restatement of one iteration on one core (the CPU baseline; a few hundred users and items timed, scaled to the whole).
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+for _v in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
+    os.environ[_v] = "1"                                   # the NumPy leg is the one-core baseline
+
+import numpy as np  # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+SHAPE = (6040, 3706, 1000209)
+
+
+def pairs(U, I, n, seed=0):
+    rs = np.random.RandomState(seed)
+    w = 1.0 / (np.arange(I) + 50.0)
+    u = rs.randint(0, U, n).astype(np.int32)
+    i = rs.choice(I, n, p=w / w.sum()).astype(np.int32)
+    return u, i, rs.randint(1, 6, n).astype(np.float64)
+
+
+def numpy_half_seconds(other, x, lam, alpha, sample, rs):
+    """one half-sweep in NumPy float64 (G + corrections, LAPACK's Cholesky solve per row): `sample` rows timed, scaled to all"""
+    n = x.shape[0]
+    rows = rs.choice(n, min(sample, n), replace=False)
+    t0 = time.perf_counter()
+    G = other.T @ other + lam * np.eye(other.shape[1])
+    tg = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    for r in rows:
+        j, v = x.indices[x.indptr[r]:x.indptr[r + 1]], x.data[x.indptr[r]:x.indptr[r + 1]]
+        Y = other[j]
+        w = alpha * v
+        A = G + (Y * w[:, None]).T @ Y
+        b = (1.0 + w) @ Y
+        np.linalg.solve(A, b)
+    return tg + (time.perf_counter() - t0) * n / rows.size
+
+
+def run_dim(d, iters, sample):
+    import scipy.sparse as sp
+    import tfrecomm_amd as T
+    from tfrecomm_amd import _lib as L
+    U, I, n = SHAPE
+    u, i, v = pairs(U, I, n)
+    x = sp.csr_matrix((v, (u, i)), shape=(U, I))
+    x.sum_duplicates()
+    x.sort_indices()
+    row = dict(users=U, items=I, pairs=int(x.nnz), d=d, iters=iters, lam=0.01, alpha=40.0, chunk=512)
+    with T.ImplicitALS(U, I, factors=d, regularization=0.01, alpha=40.0) as m:
+        m.load(x)
+        m.init_factors(0)
+        m.sweep(2)                                          # warm-up: code objects, buffers
+        row["ials_iter_ms"] = m.sweep(iters) / iters
+        h = [0.0, 0.0]
+        for _ in range(iters):
+            h[0] += m.half_sweep(0)
+            h[1] += m.half_sweep(1)
+        row["ials_user_half_ms"], row["ials_item_half_ms"] = h[0] / iters, h[1] / iters
+        t0 = time.perf_counter()
+        m.sweep(iters)
+        row["ials_iter_wall_ms"] = (time.perf_counter() - t0) / iters * 1e3
+        row["ials_loss"] = m.loss()
+        X, Y = m.user_factors, m.item_factors
+    if d <= 32:
+        als = T.MangakiALS3(nb_components=d, nb_iterations=1, lambda_=0.1, verbose=False)
+        als.nb_users, als.nb_works = U, I
+        np.random.seed(0)
+        als.init_vars()
+        rowof = np.repeat(np.arange(U, dtype=np.int64), np.diff(x.indptr))
+        uu, ww, yy = np.ascontiguousarray(rowof), np.ascontiguousarray(x.indices, np.int64), np.ascontiguousarray(x.data)
+        als._check(als._lib.tfr_als_load(als._h, L.ptr_i64(uu), L.ptr_i64(ww), als._p64(yy), yy.size))
+        ms = C.c_float()
+        als._check(als._lib.tfr_als_sweep(als._h, 2, C.byref(ms)))
+        als._check(als._lib.tfr_als_sweep(als._h, iters, C.byref(ms)))
+        row["als3_iter_ms"] = ms.value / iters
+        row["ials_over_als3"] = row["ials_iter_ms"] / row["als3_iter_ms"]
+        als.close()
+    rs = np.random.RandomState(1)
+    xt = x.T.tocsr()
+    xt.sort_indices()
+    sec = numpy_half_seconds(Y, x, 0.01, 40.0, sample, rs) + numpy_half_seconds(X, xt, 0.01, 40.0, sample, rs)
+    row["numpy_f64_iter_ms"] = sec * 1e3
+    row["numpy_threads"] = 1
+    row["numpy_rows_timed"] = sample
+    row["numpy_over_ials"] = row["numpy_f64_iter_ms"] / row["ials_iter_ms"]
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dims", default="32,64")
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--numpy-rows", type=int, default=400)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    fh = open(a.out, "a") if a.out else None
+    for d in a.dims.split(","):
+        row = run_dim(int(d), a.iters, a.numpy_rows)
+        line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row.items()})
+        print(line, flush=True)
+        if fh:
+            fh.write(line + "\n")
+            fh.flush()
+    if fh:
+        fh.close()
+
+
+if __name__ == "__main__":
+    main()
