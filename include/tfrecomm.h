@@ -404,6 +404,31 @@ int tfr_ials_gram(tfr_ials* m, int32_t side, double* G_out /* [d*d] */);
 int tfr_ials_loss(tfr_ials* m, double* loss_out);
 const char* tfr_ials_last_error(void);
 
+/* ---- implicit-feedback ALS by conjugate gradient: the model and loss of the block above, float64, 1 <= d <= 256 ----------
+ *      tfr_ials_create_cg makes the same handle type; set, get, load, half, sweep, gram, loss and destroy work on it at any
+ *      d <= 256, and half and sweep run the solver below instead of the Cholesky solve.  No per-row matrix is formed.
+ *      A half-sweep of side 0 uses G = Y^T Y, computed once per half-sweep.  For each user with list N(u) in CSR order,
+ *      w_i = alpha r_ui, c_i = 1 + w_i:
+ *          x  = X[u]                                             warm start: the row as it stands
+ *          r  = sum_{i in N(u)} (c_i - w_i (y_i . x)) y_i - (G x + lambda x)
+ *          p  = r ;  rs = r . r ;  stop = 2^-104 rs
+ *          repeat at most cg_steps times, while rs > stop:
+ *              Ap = G p + lambda p + sum_{i in N(u)} w_i (y_i . p) y_i
+ *              a  = rs / (p . Ap) ;  x += a p ;  r -= a Ap
+ *              rn = r . r ;  p = r + (rn / rs) p ;  rs = rn
+ *          X[u] = x
+ *      A user without pairs gets exactly 0 (the minimiser, and what the Cholesky path writes).  Side 1 is the same over the
+ *      transposed lists.  rs > stop is the only early exit: it is false when r is exactly 0 and once the residual has
+ *      dropped to the rounding level of its start, where a further step would divide rounding noise by rounding noise.
+ *      Every sum has a fixed order that depends on d and the list alone (list entry k and row k of G go to wave k mod 4 of
+ *      the row's block, the four waves' vectors are added in wave order; the Gram's slices as above, its output cut into
+ *      64 x 64 tiles, G bitwise symmetric): results are bit-identical from run to run.  tfr_ials_load checks `chunk` as
+ *      above; this path does not use it.
+ *      TFR_ERR_ARG before any device work (*out stays NULL) for d outside [1, 256], cg_steps outside [1, 1024], lambda_ <= 0
+ *      or alpha < 0. */
+int tfr_ials_create_cg(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t d, double lambda_, double alpha,
+                       int32_t cg_steps, int32_t device);
+
 /* ---- top-K recommendation: forward.py:47-61 get_ranking(), als3.py:110-113 (rank the dense U.V^T + biases) ----------------
  *      score(u, i) = ((dot + mu) + bu[u]) + bi[i] (the forward's order), dot = the f32 fmaf chain over f = 0..dim-1 ascending,
  *      from +0, of P[u,f] * Q'[i,f] (Q' = |Q| with item_abs); the logit under the NLL head.  Per requested user the k best

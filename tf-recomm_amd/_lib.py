@@ -143,6 +143,7 @@ SIGNATURES = {
     "tfr_als_predict": (C.c_int, [_p, _i64p, _i64p, C.c_int64, _f64p]),
     "tfr_als_last_error": (C.c_char_p, []),
     "tfr_ials_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32]),
+    "tfr_ials_create_cg": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32]),
     "tfr_ials_destroy": (C.c_int, [_p]),
     "tfr_ials_set": (C.c_int, [_p, _f64p, _f64p]),
     "tfr_ials_get": (C.c_int, [_p, _f64p, _f64p]),

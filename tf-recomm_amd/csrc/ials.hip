@@ -24,24 +24,16 @@
 #include "tfrecomm.h"
 #include "devbuf.h"
 #include "als_common.h"
+#include "ials_model.h"
 
 using tfr::DevBuf;
 
 namespace {
 
 constexpr int IALS_MAXD = 64;
-constexpr int IALS_TILE = 32;            // partner rows staged per LDS tile
 constexpr int IALS_LD = IALS_MAXD + 1;   // LDS row stride: lane r of the Cholesky walks row r, the odd stride spreads the banks
 constexpr int IALS_SLOTS = IALS_MAXD * IALS_MAXD / 256;   // A entries per thread at d = 64
-constexpr int64_t IALS_GRAM_ROWS = 128;  // smallest Gram slice
-constexpr int64_t IALS_GRAM_SLICES = 1024;   // most Gram slices: bounds the partial buffer at 1024 d^2 doubles
-
-// rows per Gram slice: a function of n alone, a multiple of the tile
-__host__ __device__ inline int64_t gram_slice_rows(int64_t n) {
-    const int64_t per = (n + IALS_GRAM_SLICES - 1) / IALS_GRAM_SLICES;
-    const int64_t rows = (per + IALS_TILE - 1) / IALS_TILE * IALS_TILE;
-    return rows < IALS_GRAM_ROWS ? IALS_GRAM_ROWS : rows;
-}
+// IALS_TILE, the Gram slice rule and the handle itself: ials_model.h, shared with the conjugate-gradient path (ials_cg.hip)
 
 struct IalsArgs {
     int64_t n;                                                     // entities of this side, empty ones included
@@ -264,27 +256,11 @@ int ials_fail(int code, const char* fmt, ...) {
 
 }  // namespace
 
-struct tfr_ials {
-    int64_t n[2] = {0, 0};                               // users, items
-    int32_t d = 0;
-    double lambda = 0.0, alpha = 0.0;
-    int device = 0;
-    bool loaded = false;
-    hipStream_t stream = nullptr;
-    DevBuf<double> tab[2];                               // X [n_users, d], Y [n_items, d]
-    // side z: the lists of its entities (side 0: the CSR as given; side 1: its transpose, each list by ascending user)
-    DevBuf<int64_t> ptr[2];
-    DevBuf<int32_t> ids[2];
-    DevBuf<double> vals[2];
-    tfr::DevChunks chunks[2];
-    DevBuf<double> partial, G, gram_partial, per_user, loss;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-};
-
 namespace {
 
 // G = tab[side]^T tab[side], queued on the model's stream
 hipError_t queue_gram(tfr_ials* m, int side) {
+    if (m->cg_steps) return tfr::ials_cg_queue_gram(m, side);
     const int64_t n = m->n[side], rows = gram_slice_rows(n), ns = (n + rows - 1) / rows;
     hipLaunchKernelGGL(k_ials_gram, dim3((unsigned)ns), dim3(256), 0, m->stream, m->tab[side].get(), n, m->d, rows, ns, m->gram_partial.get());
     hipLaunchKernelGGL(k_ials_gram_sum, dim3((unsigned)((m->d * m->d + 255) / 256)), dim3(256), 0, m->stream, m->gram_partial.get(), ns,
@@ -307,6 +283,7 @@ IalsArgs side_args(tfr_ials* m, int side) {
 hipError_t queue_half(tfr_ials* m, int side) {
     hipError_t e = queue_gram(m, 1 - side);
     if (e != hipSuccess) return e;
+    if (m->cg_steps) return tfr::ials_cg_queue_fit(m, side);
     const IalsArgs a = side_args(m, side);
     if (a.n_chunks) hipLaunchKernelGGL(k_ials_partial, dim3((unsigned)std::min<int64_t>(a.n_chunks, 65535)), dim3(256), 0, m->stream, a);
     hipLaunchKernelGGL(k_ials_fit, dim3((unsigned)std::min<int64_t>(a.n, 65535)), dim3(256), 0, m->stream, a);
@@ -341,11 +318,12 @@ int tfr_ials_destroy(tfr_ials* m) {
     return TFR_OK;
 }
 
-int tfr_ials_create(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t d, double lambda_, double alpha, int32_t device) {
-    if (!out) return ials_fail(TFR_ERR_ARG, "out is null");
-    *out = nullptr;
-    if (n_users < 1 || n_items < 1 || n_users > 0x7fffffffLL || n_items > 0x7fffffffLL || d < 1 || d > IALS_MAXD)
-        return ials_fail(TFR_ERR_ARG, "need 1 <= d <= %d and positive int32 table sizes", IALS_MAXD);
+// both creators: cg_steps = 0 is the Cholesky path (d <= 64), cg_steps > 0 the conjugate-gradient path (d <= 256)
+static int ials_create(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t d, double lambda_, double alpha, int32_t cg_steps,
+                       int32_t device) {
+    const int maxd = cg_steps ? IALS_CG_MAXD : IALS_MAXD;
+    if (n_users < 1 || n_items < 1 || n_users > 0x7fffffffLL || n_items > 0x7fffffffLL || d < 1 || d > maxd)
+        return ials_fail(TFR_ERR_ARG, "need 1 <= d <= %d and positive int32 table sizes", maxd);
     if (!(lambda_ > 0.0) || !std::isfinite(lambda_)) return ials_fail(TFR_ERR_ARG, "lambda must be positive and finite");
     if (!(alpha >= 0.0) || !std::isfinite(alpha)) return ials_fail(TFR_ERR_ARG, "alpha must be non-negative and finite");
     int ndev = 0;
@@ -356,6 +334,7 @@ int tfr_ials_create(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t d,
     tfr_ials* m = new (std::nothrow) tfr_ials();
     if (!m) return ials_fail(TFR_ERR_NOMEM, "host allocation failed");
     m->n[0] = n_users; m->n[1] = n_items; m->d = d; m->lambda = lambda_; m->alpha = alpha; m->device = device;
+    m->cg_steps = cg_steps;
     const int64_t max_slices = std::max((n_users + gram_slice_rows(n_users) - 1) / gram_slice_rows(n_users),
                                         (n_items + gram_slice_rows(n_items) - 1) / gram_slice_rows(n_items));
     hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
@@ -377,6 +356,20 @@ int tfr_ials_create(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t d,
     }
     *out = m;
     return TFR_OK;
+}
+
+int tfr_ials_create(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t d, double lambda_, double alpha, int32_t device) {
+    if (!out) return ials_fail(TFR_ERR_ARG, "out is null");
+    *out = nullptr;
+    return ials_create(out, n_users, n_items, d, lambda_, alpha, 0, device);
+}
+
+int tfr_ials_create_cg(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t d, double lambda_, double alpha, int32_t cg_steps,
+                       int32_t device) {
+    if (!out) return ials_fail(TFR_ERR_ARG, "out is null");
+    *out = nullptr;
+    if (cg_steps < 1 || cg_steps > 1024) return ials_fail(TFR_ERR_ARG, "need 1 <= cg_steps <= 1024");
+    return ials_create(out, n_users, n_items, d, lambda_, alpha, cg_steps, device);
 }
 
 int tfr_ials_set(tfr_ials* m, const double* X, const double* Y) {
@@ -443,7 +436,8 @@ int tfr_ials_load(tfr_ials* m, const int64_t* indptr, const int32_t* items, cons
         IALSCHK(m->vals[z].reserve(cap, m->stream));
         IALSCHK(m->chunks[z].upload(plan[z], m->n[z], m->stream));
     }
-    IALSCHK(m->partial.reserve(std::max<int64_t>(1, max_chunks * (m->d * m->d + m->d)), m->stream));
+    // the chunks' partial sums: the conjugate-gradient path forms no per-row matrix and reads no chunk table
+    IALSCHK(m->partial.reserve(m->cg_steps ? 1 : std::max<int64_t>(1, max_chunks * (m->d * m->d + m->d)), m->stream));
     IALSCHK(hipMemcpy(m->ptr[0], pu.data(), pu.size() * 8, hipMemcpyHostToDevice));
     IALSCHK(hipMemcpy(m->ptr[1], pi.data(), pi.size() * 8, hipMemcpyHostToDevice));
     if (nnz) {
@@ -492,7 +486,8 @@ int tfr_ials_loss(tfr_ials* m, double* loss_out) {
     IALSCHK(hipSetDevice(m->device));
     IALSCHK(queue_gram(m, 1));
     const IalsArgs a = side_args(m, 0);
-    hipLaunchKernelGGL(k_ials_loss_users, dim3((unsigned)std::min<int64_t>(a.n, 65535)), dim3(256), 0, m->stream, a, m->per_user.get());
+    if (m->cg_steps) IALSCHK(tfr::ials_cg_queue_loss_users(m));
+    else hipLaunchKernelGGL(k_ials_loss_users, dim3((unsigned)std::min<int64_t>(a.n, 65535)), dim3(256), 0, m->stream, a, m->per_user.get());
     hipLaunchKernelGGL(k_ials_loss_reduce, dim3(1), dim3(256), 0, m->stream, m->per_user.get(), a.n, m->G.get(), m->d, m->lambda,
                        m->loss.get());
     IALSCHK(hipGetLastError());

@@ -1,0 +1,46 @@
+// ials_model.h - the implicit-ALS handle, shared by the Cholesky path (ials.hip) and the conjugate-gradient path
+// (ials_cg.hip).  ials.hip owns the C-ABI entries; a handle with cg_steps > 0 was made by tfr_ials_create_cg and its Gram,
+// half-sweeps and loss go through the three queue_* functions below.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "tfrecomm.h"
+#include "devbuf.h"
+#include "als_common.h"
+
+constexpr int IALS_TILE = 32;                // partner rows staged per LDS tile
+constexpr int IALS_CG_MAXD = 256;            // widest table of the conjugate-gradient path
+constexpr int64_t IALS_GRAM_ROWS = 128;      // smallest Gram slice
+constexpr int64_t IALS_GRAM_SLICES = 1024;   // most Gram slices: bounds the partial buffer at 1024 d^2 doubles
+
+// rows per Gram slice: a function of n alone, a multiple of the tile
+__host__ __device__ inline int64_t gram_slice_rows(int64_t n) {
+    const int64_t per = (n + IALS_GRAM_SLICES - 1) / IALS_GRAM_SLICES;
+    const int64_t rows = (per + IALS_TILE - 1) / IALS_TILE * IALS_TILE;
+    return rows < IALS_GRAM_ROWS ? IALS_GRAM_ROWS : rows;
+}
+
+struct tfr_ials {
+    int64_t n[2] = {0, 0};                               // users, items
+    int32_t d = 0;
+    int32_t cg_steps = 0;                                // 0: the Cholesky path; > 0: that many CG steps per row
+    double lambda = 0.0, alpha = 0.0;
+    int device = 0;
+    bool loaded = false;
+    hipStream_t stream = nullptr;
+    tfr::DevBuf<double> tab[2];                          // X [n_users, d], Y [n_items, d]
+    // side z: the lists of its entities (side 0: the CSR as given; side 1: its transpose, each list by ascending user)
+    tfr::DevBuf<int64_t> ptr[2];
+    tfr::DevBuf<int32_t> ids[2];
+    tfr::DevBuf<double> vals[2];
+    tfr::DevChunks chunks[2];
+    tfr::DevBuf<double> partial, G, gram_partial, per_user, loss;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+};
+
+namespace tfr {
+// queued on the model's stream; each returns hipGetLastError() after its launches
+hipError_t ials_cg_queue_gram(tfr_ials* m, int side);          // m->G = tab[side]^T tab[side], any d <= 256
+hipError_t ials_cg_queue_fit(tfr_ials* m, int side);           // cg_steps steps for every entity of `side`, from m->G
+hipError_t ials_cg_queue_loss_users(tfr_ials* m);              // m->per_user, from m->G = Y^T Y
+}  // namespace tfr

@@ -5,6 +5,11 @@
     svd = m.to_svd_model()                  # P = X, Q = Y as float32, mu = 0, biases = 0
     svd.recommend(users, 10, exclude=user_items)
 
+    ImplicitALS(user_num, item_num, factors=128, solver="cg", cg_steps=3)      # conjugate gradient: factors up to 256
+
+``solver="cholesky"`` (the default, factors up to 64) solves every row's normal equations exactly; ``solver="cg"`` takes
+``cg_steps`` conjugate-gradient steps per row from the row as it stands and never forms a per-row matrix
+(csrc/ials_cg.hip; the header states the solver).
 Preference 1 on stored pairs and 0 elsewhere, confidence ``1 + alpha * value`` on stored pairs and 1 elsewhere; the fit
 minimises ``sum_{u,i} c_ui (p_ui - x_u . y_i)^2 + regularization (|X|^2 + |Y|^2)`` over all pairs (include/tfrecomm.h).
 Serving goes through ``to_svd_model``: ``recommend``, ``rank_items``, ``similar_items`` and ``evaluate_ranking`` take the
@@ -20,15 +25,23 @@ from . import _lib as L
 
 
 class ImplicitALS(object):
-    def __init__(self, user_num, item_num, factors=32, regularization=0.01, alpha=40.0, iterations=15, device=0, chunk=512):
+    def __init__(self, user_num, item_num, factors=32, regularization=0.01, alpha=40.0, iterations=15, device=0, chunk=512,
+                 solver="cholesky", cg_steps=3):
         self.user_num, self.item_num, self.factors = int(user_num), int(item_num), int(factors)
         self.regularization, self.alpha, self.iterations = float(regularization), float(alpha), int(iterations)
         self.device, self.chunk = int(device), int(chunk)
+        if solver not in ("cholesky", "cg"):
+            raise ValueError("solver must be 'cholesky' or 'cg', got %r" % (solver,))
+        self.solver, self.cg_steps = solver, int(cg_steps)
         self.sweep_ms = 0.0
         self._lib = L.load()
         self._h = L._p()
-        self._check(self._lib.tfr_ials_create(C.byref(self._h), self.user_num, self.item_num, self.factors, self.regularization,
-                                              self.alpha, self.device))
+        if solver == "cg":
+            self._check(self._lib.tfr_ials_create_cg(C.byref(self._h), self.user_num, self.item_num, self.factors,
+                                                     self.regularization, self.alpha, self.cg_steps, self.device))
+        else:
+            self._check(self._lib.tfr_ials_create(C.byref(self._h), self.user_num, self.item_num, self.factors, self.regularization,
+                                                  self.alpha, self.device))
 
     def _check(self, rc):
         if rc != L.OK:

@@ -1,11 +1,17 @@
 """Implicit ALS iteration timings: one JSON line per width, every leg on the same pairs in the same process.
 
     python tools/bench_ials.py [--dims 32,64] [--iters 10] [--out profiles/bench_ials.jsonl]
+    python tools/bench_ials.py --solver cg --cg-steps 3 --dims 32,64,128,256 --also-cholesky 32,64 --cap 1024,256 \
+        --out profiles/bench_ials_cg.jsonl                                      
 
 Data: ML-1M-shaped synthetic pairs (6040 x 3706, 1 M draws, item popularity p(i) ~ 1 / (i + 50), as tools/bench_bpr.py),
 values 1 .. 5.  Legs: ImplicitALS.sweep (device time per iteration from the library's events) and each half on its own
 (tfr_ials_half); MangakiALS3's iteration on the same pairs as ratings, at d = 32 only (its limit); and the NumPy float64
 restatement of one iteration on one core (the CPU baseline; a few hundred users and items timed, scaled to the whole).
+With --solver cg the rows are the conjugate-gradient path's (dims up to 256; no MangakiALS3 and no NumPy leg): the iteration,
+each half, and the loss after 15 iterations from the library's initialisation.  --also-cholesky adds the Cholesky path's rows
+at those dims in the same process; --cap N[,M] adds a further row per width and length on the same pairs with every item's list cut to its
+first N users (popularity capped), which takes the longest lists (one block each) out of the halves.
 """
 import argparse
 import ctypes as C
@@ -48,6 +54,51 @@ def numpy_half_seconds(other, x, lam, alpha, sample, rs):
         b = (1.0 + w) @ Y
         np.linalg.solve(A, b)
     return tg + (time.perf_counter() - t0) * n / rows.size
+
+
+def capped(x, cap):
+    """the CSR with every item's list (column) cut to its first `cap` users: popularity capped, the users' lists barely change"""
+    t = x.T.tocsr()
+    t.sort_indices()
+    keep = np.arange(t.nnz) - np.repeat(t.indptr[:-1], np.diff(t.indptr)) < cap
+    t.data[~keep] = 0.0
+    t.eliminate_zeros()
+    x = t.T.tocsr()
+    x.sort_indices()
+    return x
+
+
+def run_solver(d, iters, solver, cg_steps, cap=0):
+    """one row of the --solver cg form: either solver, device times only"""
+    import scipy.sparse as sp
+    import tfrecomm_amd as T
+    U, I, n = SHAPE
+    u, i, v = pairs(U, I, n)
+    x = sp.csr_matrix((v, (u, i)), shape=(U, I))
+    x.sum_duplicates()
+    x.sort_indices()
+    if cap:
+        x = capped(x, cap)
+    xt = x.T.tocsr()
+    row = dict(users=U, items=I, pairs=int(x.nnz), d=d, iters=iters, lam=0.01, alpha=40.0, solver=solver, cap=cap,
+               longest_user_list=int(np.diff(x.indptr).max()), longest_item_list=int(np.diff(xt.indptr).max()))
+    kw = dict(solver="cg", cg_steps=cg_steps) if solver == "cg" else {}
+    if solver == "cg":
+        row["cg_steps"] = cg_steps
+    with T.ImplicitALS(U, I, factors=d, regularization=0.01, alpha=40.0, **kw) as m:
+        m.load(x)
+        m.init_factors(0)
+        m.sweep(2)                                          # warm-up: code objects, buffers
+        row["ials_iter_ms"] = m.sweep(iters) / iters
+        h = [0.0, 0.0]
+        for _ in range(iters):
+            h[0] += m.half_sweep(0)
+            h[1] += m.half_sweep(1)
+        row["ials_user_half_ms"], row["ials_item_half_ms"] = h[0] / iters, h[1] / iters
+        m.init_factors(0)
+        m.sweep(15)
+        row["ials_loss_after_15"] = m.loss()
+    return row
 
 
 def run_dim(d, iters, sample):
@@ -105,11 +156,20 @@ def main():
     ap.add_argument("--dims", default="32,64")
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--numpy-rows", type=int, default=400)
+    ap.add_argument("--solver", choices=("cholesky", "cg"))
+    ap.add_argument("--cg-steps", type=int, default=3)
+    ap.add_argument("--also-cholesky", default="", help="with --solver cg: dims at which the Cholesky path runs too")
+    ap.add_argument("--cap", default="", help="with --solver: a further row per width and per listed length, every item's list cut to it")
     ap.add_argument("--out")
     a = ap.parse_args()
     fh = open(a.out, "a") if a.out else None
-    for d in a.dims.split(","):
-        row = run_dim(int(d), a.iters, a.numpy_rows)
+    if a.solver is None:
+        jobs = [lambda d=int(d): run_dim(d, a.iters, a.numpy_rows) for d in a.dims.split(",")]
+    else:
+        legs = [(a.solver, int(d)) for d in a.dims.split(",")] + [("cholesky", int(d)) for d in a.also_cholesky.split(",") if d]
+        jobs = [lambda s=s, d=d, cap=cap: run_solver(d, a.iters, s, a.cg_steps, cap) for s, d in legs for cap in [0] + [int(c) for c in a.cap.split(",") if c]]
+    for job in jobs:
+        row = job()
         line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row.items()})
         print(line, flush=True)
         if fh:
