@@ -18,8 +18,10 @@ WIDTHS = (1, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256)
 LENGTHS = (0, 1, 2, 3, 4, 5, 7, 8, 9, 12, 13, 16, 17, 31, 32, 33, 63, 64, 65)
 LONG_LENGTHS = C.LONG_LENGTHS + (1100,)                    # 1100: every partner, the longest sum of the suite
 LONG_WIDTHS = (1, 65, 256)
-# the wide Gram: both ends of every count of 64-wide output tiles per side, 1 .. 4, and the widths around them
-GRAM_WIDTHS = (1, 63, 64, 65, 127, 128, 129, 192, 193, 255, 256)
+# the Gram of both solvers: both ends of every count of 64-wide output tiles per side, 1 .. 4, and the widths around them; a
+# thread's 4 x 4 block partly or wholly past d and a partly filled single tile (17, 33); both sides of the width below which
+# the narrow kernel takes over (23, 24), and small widths of that kernel (1 slot: 3, 4, 5; 2: 17; 3: 23)
+GRAM_WIDTHS = (1, 3, 4, 5, 17, 23, 24, 33, 63, 64, 65, 127, 128, 129, 192, 193, 255, 256)
 GRAM_NS = (1, 127, 128, 129, 5 * 128 + 3)                  # 131 073 rows (slices of 160) run at d = 65 only
 LAMBDAS = (0.1, 1e-3, 1e-6)
 ALPHAS = (1.0, 40.0)

@@ -10,7 +10,7 @@ Per entity with list N, w = alpha r, c = 1 + w, G = Y^T Y and the row x0 as it s
     cg_half_f64    float64 in the kernels' order: wave w takes the list entries and the rows of G with index = w mod 4, a
                    lane the components l + 64 j, a dot is the lane's products (j ascending) then the butterfly, the four
                    waves' vectors are added in wave order
-    gram_f64       k_ials_gram_wide + k_ials_gram_sum_wide: rows ascending inside a slice, slices ascending
+    gram_f64       ials_ref.gram_f64 itself: both solvers share one Gram (k_ials_gram_tiled + k_ials_gram_sum)
     loss_f64       k_ials_loss_users_wide + k_ials_loss_reduce
 
 Bounds (eps = 2^-52; cond2(A) of A = G + sum_N w y y^T + lam I), per entity and for the loss:
@@ -33,7 +33,7 @@ import numpy as np
 from tests.als_step_ref import EPS, LD
 from tests import ials_ref as R
 
-WAVES, LANES, TILE_OUT, MAXD, THREADS = 4, 64, 64, 256, 256
+WAVES, LANES, MAXD, THREADS = 4, 64, 256, 256
 STOP = 2.0 ** -104
 
 MEASURED_RHO_CG = 75.513          # cg-long-d1-normal, item half, 1 step: cond = 1, the rounding of 1100-term sums
@@ -49,9 +49,7 @@ def lane_components(d):
     return -(-d // LANES)
 
 
-def gram_tiles(d):
-    """64-wide output tiles per side of k_ials_gram_wide"""
-    return -(-d // TILE_OUT)
+gram_tiles, gram_f64 = R.gram_tiles, R.gram_f64              # the Gram is not restated here
 
 
 # ----------------------------------------------------------------------------- longdouble reference
@@ -157,22 +155,8 @@ def _by_wave(rows, fault=None):
     return ((part[0] + part[1]) + part[2]) + part[3]
 
 
-def gram_f64(T, fault=None):
-    """slices of ials_ref.gram_slice_rows(n) rows, row after row inside a slice, the partials added in ascending order.
-    ``fault`` = drop_last_tile: the last 64 x 64 output tile is never written."""
-    n, d = T.shape
-    rows = R.gram_slice_rows(n)
-    G = np.zeros((d, d))
-    for lo in range(0, n, rows):
-        t = T[lo:min(n, lo + rows)]
-        G = G + R._seq(np.zeros((d, d)), t[:, :, None] * t[:, None, :])
-    if fault == "drop_last_tile":
-        G[(gram_tiles(d) - 1) * TILE_OUT:, (gram_tiles(d) - 1) * TILE_OUT:] = 0.0
-    return G
-
-
 def cg_half_f64(own, other, lst, lam, alpha, steps, G=None, fault=None):
-    """x [n, d] in float64 in the order of k_ials_gram_wide / k_ials_cg_fit.  ``fault`` plants one error: no_ridge_in_Ap
+    """x [n, d] in float64 in the order of k_ials_gram_tiled / k_ials_cg_fit.  ``fault`` plants one error: no_ridge_in_Ap
     (lam p dropped from Ap), c_for_w (c used for w in Ap), no_beta ((rn / rs) forced to 0: seen from step 2), cold_start
     (x0 = 0), drop_last_wave (the entries k = 3 mod 4 of every list dropped), drop_last_tile (of the Gram)."""
     ptr, ids, vals, _ = lst

@@ -6,6 +6,7 @@ A case (tests/ials_cases.py) holds the user x item CSR (indptr, items, vals), d,
     dense_half   the definition: per entity the full confidence vector over ALL partners,
                  (Y^T diag(c) Y + lambda I) x = Y^T diag(c) p, in np.longdouble
     half         the decomposed form, A = G + sum_N w y y^T + lambda I, b = sum_N c y, in longdouble; takes a given G
+    gram_f64     the one Gram of both solvers (k_ials_gram_tiled + k_ials_gram_sum), float64 in the kernels' order
     half_f64     float64 in the kernels' order: Gram slices, 32-row tiles, chunks, (w y_r) y_c, (G + acc) + lambda
     loss_dense / loss / loss_f64   the loss by its definition, by the formula that never forms the dense matrix, and that
                  formula in float64 in the kernels' order
@@ -28,6 +29,8 @@ import numpy as np
 from tests.als_step_ref import EPS, LD, chol_solve
 
 TILE, CHUNK, THREADS = 32, 512, 256
+GRAM_TILE = 64                                             # csrc/ials.hip GRAM_T: the edge of a block's output tile
+GRAM_NARROW = 23                                           # csrc/ials.hip GRAM_NARROW_D: up to here one block keeps a whole slice
 GRAM_ROWS, GRAM_SLICES = 128, 1024                         # csrc/ials.hip IALS_GRAM_ROWS, IALS_GRAM_SLICES
 MAXD = 64
 MEASURED_RHO_X, MEASURED_RHO_LOSS = 8.357, 0.544
@@ -194,20 +197,25 @@ def _seq(acc, terms):
     return np.cumsum(np.concatenate((acc[None], terms)), axis=0)[-1]
 
 
+def gram_tiles(d):
+    """64-wide output tiles per side of k_ials_gram_tiled"""
+    return -(-d // GRAM_TILE)
+
+
 def gram_f64(T, fault=None):
-    """k_ials_gram + k_ials_gram_sum: slices of gram_slice_rows(n) rows, inside a slice 32-row tiles row after row, the
-    slices' partials added in ascending order"""
+    """k_ials_gram_tiled (k_ials_gram_narrow below 24 columns: the same order) + k_ials_gram_sum, any d <= 256: slices of
+    gram_slice_rows(n) rows, row after row inside a slice, the slices' partials added in ascending order.  ``fault`` = drop_last_slice: the last of several slices is left out of
+    the sum; drop_last_tile: the last 64 x 64 output tile is never written."""
     n, d = T.shape
     rows = gram_slice_rows(n)
     G = np.zeros((d, d))
     for lo in range(0, n, rows):
-        part = np.zeros((d, d))
-        for s in range(lo, min(n, lo + rows), TILE):
-            t = T[s:min(n, lo + rows, s + TILE)]
-            part = _seq(part, t[:, :, None] * t[:, None, :])
         if fault == "drop_last_slice" and lo + rows >= n and lo > 0:
             break
-        G = G + part
+        t = T[lo:min(n, lo + rows)]
+        G = G + _seq(np.zeros((d, d)), t[:, :, None] * t[:, None, :])
+    if fault == "drop_last_tile":
+        G[(gram_tiles(d) - 1) * GRAM_TILE:, (gram_tiles(d) - 1) * GRAM_TILE:] = 0.0
     return G
 
 
@@ -225,7 +233,7 @@ def _accumulate(rows, w, acc, accb, fault):
 
 
 def half_f64(other, lst, lam, alpha, ch=CHUNK, G=None, fault=None):
-    """x [n, d] in float64 in the order of k_ials_gram / k_ials_partial / k_ials_fit.  ``fault`` plants one error:
+    """x [n, d] in float64 in the order of k_ials_gram_tiled / k_ials_partial / k_ials_fit.  ``fault`` plants one error:
     drop_partial_tile, skip_slot15 (A entries 3840.. never accumulated), drop_last_chunk, drop_last_slice, unit_confidence
     (b summed with c = 1), no_ridge."""
     ptr, ids, vals, _ = lst

@@ -28,6 +28,7 @@ def test_the_widths_reach_both_ends_of_every_lane_and_tile_count():
         for k in range(1, 5):
             ends = {min(d for d in range(1, G.MAXD + 1) if count(d) == k), max(d for d in range(1, G.MAXD + 1) if count(d) == k)}
             assert ends <= set(widths), (k, ends)
+    assert {1, R.GRAM_NARROW, R.GRAM_NARROW + 1} <= set(C.GRAM_WIDTHS)       # both Gram kernels at their ends
     assert {c["d"] for c in C.CASES if c["id"].startswith("cg-widths")} == set(C.WIDTHS)
     assert {c["d"] for c in C.CASES if c["id"].startswith("cg-long")} == set(C.LONG_WIDTHS)
     assert {0, 1, 2, 3, 4, 5, 7, 8, 9, 31, 32, 33, 63, 64, 65} <= set(C.LENGTHS)
@@ -132,6 +133,7 @@ def test_no_beta_is_invisible_at_one_step():
 
 
 def test_the_wide_gram_restatement_is_symmetric_and_within_its_bound():
+    assert G.gram_f64 is R.gram_f64                        # nothing else restates the Gram
     rs = np.random.RandomState(3)
     for n, d in ((129, 65), (300, 129), (5, 256)):
         T = rs.uniform(-1.0, 1.0, (n, d))

@@ -1,5 +1,6 @@
-// als_common.h - what the two ALS solvers share (als_kernels.hip: explicit ALS, d <= 32; ials.hip: implicit ALS, d <= 64):
-// the one-wave Cholesky solve of a d x d SPD system held in LDS, and the host's chunk tables for long lists.
+// als_common.h - what the two Cholesky ALS solvers share (als_kernels.hip: explicit ALS, d <= 32; ials.hip: implicit ALS,
+// d <= 64): the one-wave Cholesky solve of a d x d SPD system held in LDS, the chunk tables for long lists with the kernel
+// argument that carries them, and the bookkeeping of a thread's slots of the normal equations.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -70,11 +71,21 @@ inline ChunkPlan plan_chunks(const std::vector<int64_t>& ptr, int64_t rows, int6
     return p;
 }
 
+// what a kernel sees of one side's chunk tables, and where the chunks' partial sums go
+struct ChunkArgs {
+    const int32_t* cfirst; const int32_t* ccount;                  // per entity
+    const int32_t* ent; const int64_t* lo; const int64_t* hi;      // per chunk
+    int64_t n;                                                     // chunks
+    double* partial;                                               // [n][d*d + d]: a chunk's A entries, then its b
+};
+
 // one side's chunk tables on the device
 struct DevChunks {
     DevBuf<int32_t> cfirst, ccount, ent;
     DevBuf<int64_t> lo, hi;
     int64_t n = 0;
+
+    ChunkArgs args(double* partial) const { return ChunkArgs{cfirst.get(), ccount.get(), ent.get(), lo.get(), hi.get(), n, partial}; }
 
     hipError_t upload(const ChunkPlan& p, int64_t rows, hipStream_t s) {
         n = 0;
@@ -95,5 +106,51 @@ struct DevChunks {
         return e;
     }
 };
+
+// A 256-thread block keeps the normal equations of one entity in registers: thread tid the A entries t = tid + 256 q,
+// q < SLOTS (row t / d, column t % d), and thread tid < d the b entry tid.  SLOTS = 4 serves d <= 32, 16 serves d <= 64.
+template <int SLOTS>
+__device__ __forceinline__ void zero_slots(double (&acc)[SLOTS], double& accb) {
+#pragma unroll
+    for (int q = 0; q < SLOTS; ++q) acc[q] = 0.0;
+    accb = 0.0;
+}
+
+// a long list: adds the partial sums of entity e's nch = ccount[e] > 0 chunks, in list order
+template <int SLOTS>
+__device__ __forceinline__ void add_chunk_partials(const ChunkArgs& ch, int64_t e, int32_t nch, int d, double (&acc)[SLOTS], double& accb) {
+    const int tid = threadIdx.x, dd = d * d;
+    const int32_t c0 = ch.cfirst[e];
+    for (int32_t k = 0; k < nch; ++k) {
+        const double* pp = ch.partial + (size_t)(c0 + k) * (dd + d);
+#pragma unroll
+        for (int q = 0; q < SLOTS; ++q) { const int t = tid + 256 * q; if (t < dd) acc[q] += pp[t]; }
+        if (tid < d) accb += pp[dd + tid];
+    }
+}
+
+template <int SLOTS>
+__device__ __forceinline__ void store_chunk_partial(const ChunkArgs& ch, int64_t c, int d, const double (&acc)[SLOTS], double accb) {
+    const int tid = threadIdx.x, dd = d * d;
+    double* pp = ch.partial + (size_t)c * (dd + d);
+#pragma unroll
+    for (int q = 0; q < SLOTS; ++q) { const int t = tid + 256 * q; if (t < dd) pp[t] = acc[q]; }
+    if (tid < d) pp[dd + tid] = accb;
+}
+
+// A[r][c] = entry(t, acc[q], r == c) for every slot t = r d + c: the caller adds its diagonal term (and whatever else
+// belongs to entry t) to the sum it is handed
+template <int SLOTS, int LD, class Entry>
+__device__ __forceinline__ void slots_to_matrix(const double (&acc)[SLOTS], int d, double (*A)[LD], Entry entry) {
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int q = 0; q < SLOTS; ++q) {
+        const int t = tid + 256 * q;
+        if (t < d * d) {
+            const int r = t / d, c = t % d;
+            A[r][c] = entry(t, acc[q], r == c);
+        }
+    }
+}
 
 }  // namespace tfr

@@ -34,16 +34,12 @@ struct AlsFitArgs {
     double* own; double* w_own; const double* other; const double* w_other;
     double bias, lambda;
     int32_t d;
-    // long rating lists are cut into chunks whose partial normal equations are built by other blocks first
-    // (k_als_partial): cfirst[entity] = its first chunk or -1, ccount[entity] chunks, in list order
-    const int32_t* cfirst; const int32_t* ccount;
-    const int32_t* chunk_ent; const int64_t* chunk_lo; const int64_t* chunk_hi; int64_t n_chunks;
-    double* partial;                                   // [n_chunks][d*d + d]
 };
+constexpr int ALS_SLOTS = ALS_MAXD * ALS_MAXD / 256;  // A entries per thread at d = 32
 
 // normal-equation sums over the ratings [lo, hi) of one entity: acc[q] += sum_k rows[k][r] rows[k][c] for the
 // A entries t = tid + 256 q, accb += sum_k coef[k] rows[k][tid]; 32-row tiles staged in LDS; 256 threads
-__device__ __forceinline__ void als_accumulate(const AlsFitArgs& a, int64_t lo, int64_t hi, double b0, double (&acc)[4], double& accb,
+__device__ __forceinline__ void als_accumulate(const AlsFitArgs& a, int64_t lo, int64_t hi, double b0, double (&acc)[ALS_SLOTS], double& accb,
                                                double (*rows)[ALS_MAXD + 1], double* coef) {
     const int tid = threadIdx.x, d = a.d;
     for (int64_t s = lo; s < hi; s += ALS_TILE) {
@@ -55,7 +51,7 @@ __device__ __forceinline__ void als_accumulate(const AlsFitArgs& a, int64_t lo, 
         if (tid < nk) coef[tid] = a.vals[s + tid] - a.w_other[a.ids[s + tid]] - b0;
         __syncthreads();
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
+        for (int q = 0; q < ALS_SLOTS; ++q) {
             const int t = tid + 256 * q;
             if (t < d * d) {
                 const int r = t / d, c = t % d;
@@ -73,26 +69,22 @@ __device__ __forceinline__ void als_accumulate(const AlsFitArgs& a, int64_t lo, 
     }
 }
 
-// partial normal equations of one chunk of a long rating list
-__global__ __launch_bounds__(256) void k_als_partial(AlsFitArgs a) {
+// partial normal equations of one chunk of a long rating list (the chunk tables: als_common.h)
+__global__ __launch_bounds__(256) void k_als_partial(AlsFitArgs a, tfr::ChunkArgs ch) {
     __shared__ double rows[ALS_TILE][ALS_MAXD + 1];
     __shared__ double coef[ALS_TILE];
-    const int tid = threadIdx.x, d = a.d;
-    for (int64_t c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
-        const int32_t idx = a.chunk_ent[c];
+    for (int64_t c = blockIdx.x; c < ch.n; c += gridDim.x) {
+        const int32_t idx = ch.ent[c];
         const double b0 = a.w_own[idx] + a.bias;
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};
-        double accb = 0.0;
+        double acc[ALS_SLOTS], accb;
+        tfr::zero_slots(acc, accb);
         __syncthreads();
-        als_accumulate(a, a.chunk_lo[c], a.chunk_hi[c], b0, acc, accb, rows, coef);
-        double* pp = a.partial + (size_t)c * (d * d + d);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const int t = tid + 256 * q; if (t < d * d) pp[t] = acc[q]; }
-        if (tid < d) pp[d * d + tid] = accb;
+        als_accumulate(a, ch.lo[c], ch.hi[c], b0, acc, accb, rows, coef);
+        tfr::store_chunk_partial(ch, c, a.d, acc, accb);
     }
 }
 
-__global__ __launch_bounds__(256) void k_als_fit(AlsFitArgs a) {
+__global__ __launch_bounds__(256) void k_als_fit(AlsFitArgs a, tfr::ChunkArgs ch) {
     __shared__ double A[ALS_MAXD][ALS_MAXD + 1];
     __shared__ double rows[ALS_TILE][ALS_MAXD + 1];
     __shared__ double coef[ALS_TILE];
@@ -104,29 +96,14 @@ __global__ __launch_bounds__(256) void k_als_fit(AlsFitArgs a) {
         const int64_t lo = a.ptr[idx], hi = a.ptr[idx + 1];
         const int64_t N = hi - lo;
         const double b0 = a.w_own[idx] + a.bias;
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};           // A entries t = tid + 256*q  (d*d <= 1024)
-        double accb = 0.0;                               // b entry tid (< d)
+        double acc[ALS_SLOTS], accb;                     // A entries t = tid + 256*q (d*d <= 1024), b entry tid (< d)
+        tfr::zero_slots(acc, accb);
         __syncthreads();
-        const int32_t nch = a.ccount ? a.ccount[idx] : 0;
-        if (nch > 0) {                                   // a long list: add the chunks' partial sums, in list order
-            const int32_t c0 = a.cfirst[idx];
-            for (int32_t ch = 0; ch < nch; ++ch) {
-                const double* pp = a.partial + (size_t)(c0 + ch) * (d * d + d);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { const int t = tid + 256 * q; if (t < d * d) acc[q] += pp[t]; }
-                if (tid < d) accb += pp[d * d + tid];
-            }
-        } else {
-            als_accumulate(a, lo, hi, b0, acc, accb, rows, coef);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int t = tid + 256 * q;
-            if (t < d * d) {
-                const int r = t / d, c = t % d;
-                A[r][c] = acc[q] + ((r == c) ? a.lambda * (double)N : 0.0);
-            }
-        }
+        const int32_t nch = ch.ccount ? ch.ccount[idx] : 0;   // without chunk tables every list is summed here
+        if (nch > 0) tfr::add_chunk_partials(ch, idx, nch, d, acc, accb);
+        else als_accumulate(a, lo, hi, b0, acc, accb, rows, coef);
+        const double ridge = a.lambda * (double)N;
+        tfr::slots_to_matrix(acc, d, A, [&](int, double s, bool diag) { return s + (diag ? ridge : 0.0); });
         if (tid < d) bvec[tid] = accb;
         __syncthreads();
         // Cholesky and the two triangular solves by one wave (als_common.h)
@@ -196,6 +173,14 @@ struct tfr_als {
     DevBuf<double> partial;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
+
+// one half-sweep, queued: the long lists' chunks, then every entity of the list
+static void queue_half(tfr_als* m, const AlsFitArgs& a, int side) {
+    if (!a.n_list) return;
+    const tfr::ChunkArgs ch = m->chunks[side].args(m->partial);
+    if (ch.n) hipLaunchKernelGGL(k_als_partial, dim3((unsigned)std::min<int64_t>(ch.n, 65535)), dim3(256), 0, m->stream, a, ch);
+    hipLaunchKernelGGL(k_als_fit, dim3((unsigned)std::min<int64_t>(a.n_list, 65535)), dim3(256), 0, m->stream, a, ch);
+}
 
 extern "C" {
 
@@ -280,12 +265,9 @@ int tfr_als_load(tfr_als* m, const int64_t* user_ids, const int64_t* work_ids, c
     for (int64_t k = 0; k < n; ++k)
         if (user_ids[k] < 0 || user_ids[k] >= m->nu || work_ids[k] < 0 || work_ids[k] >= m->nw)
             return als_fail(TFR_ERR_OOB, "rating %lld: id out of range", (long long)k);
-    double sum = 0.0;
-    for (int64_t k = 0; k < n; ++k) sum += y[k];
     // numpy's mean uses pairwise summation; reproduce its value exactly enough by summing in long double
     long double ls = 0.0L;
     for (int64_t k = 0; k < n; ++k) ls += (long double)y[k];
-    (void)sum;
     m->bias = (double)(ls / (long double)n);
     auto build = [&](const int64_t* key, const int64_t* oth, int64_t rows, std::vector<int64_t>& ptr,
                      std::vector<int32_t>& ids, std::vector<double>& vals, std::vector<int32_t>& list) {
@@ -359,16 +341,10 @@ int tfr_als_sweep(tfr_als* m, int32_t n_iterations, float* elapsed_ms) {
         a.bias = m->bias; a.lambda = m->lambda; a.d = m->d;
         a.list = m->users; a.n_list = m->n_users; a.ptr = m->ptr_u; a.ids = m->ids_u; a.vals = m->val_u;
         a.own = m->U; a.w_own = m->Wu; a.other = m->V; a.w_other = m->Ww;
-        a.cfirst = m->chunks[0].cfirst; a.ccount = m->chunks[0].ccount; a.chunk_ent = m->chunks[0].ent; a.chunk_lo = m->chunks[0].lo;
-        a.chunk_hi = m->chunks[0].hi; a.n_chunks = m->chunks[0].n; a.partial = m->partial;
-        if (a.n_list && a.n_chunks) hipLaunchKernelGGL(k_als_partial, dim3((unsigned)std::min<int64_t>(a.n_chunks, 65535)), dim3(256), 0, m->stream, a);
-        if (a.n_list) hipLaunchKernelGGL(k_als_fit, dim3((unsigned)std::min<int64_t>(a.n_list, 65535)), dim3(256), 0, m->stream, a);
+        queue_half(m, a, 0);
         a.list = m->works; a.n_list = m->n_works; a.ptr = m->ptr_w; a.ids = m->ids_w; a.vals = m->val_w;
         a.own = m->V; a.w_own = m->Ww; a.other = m->U; a.w_other = m->Wu;
-        a.cfirst = m->chunks[1].cfirst; a.ccount = m->chunks[1].ccount; a.chunk_ent = m->chunks[1].ent; a.chunk_lo = m->chunks[1].lo;
-        a.chunk_hi = m->chunks[1].hi; a.n_chunks = m->chunks[1].n; a.partial = m->partial;
-        if (a.n_list && a.n_chunks) hipLaunchKernelGGL(k_als_partial, dim3((unsigned)std::min<int64_t>(a.n_chunks, 65535)), dim3(256), 0, m->stream, a);
-        if (a.n_list) hipLaunchKernelGGL(k_als_fit, dim3((unsigned)std::min<int64_t>(a.n_list, 65535)), dim3(256), 0, m->stream, a);
+        queue_half(m, a, 1);
     }
     (void)hipEventRecord(m->ev1, m->stream);
     ALSCHK(hipGetLastError());

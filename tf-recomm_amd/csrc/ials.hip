@@ -1,16 +1,21 @@
 // ials.hip - implicit-feedback ALS (Hu, Koren, Volinsky: weighted matrix factorisation) on the GPU, float64, 1 <= d <= 64.
 //   R: user x item CSR of strictly positive values.  p_ui = 1 on stored pairs, 0 elsewhere; c_ui = 1 + alpha r_ui on
 //   stored pairs, 1 elsewhere.  One half-sweep, for every entity u with list N(u) in CSR order and partner table Y:
-//       G   = Y^T Y                                         (k_ials_gram + k_ials_gram_sum, once per half-sweep)
+//       G   = Y^T Y                                         (k_ials_gram_tiled + k_ials_gram_sum, once per half-sweep)
 //       A_u = G + sum_{i in N(u)} w_ui y_i y_i^T + lambda I   w_ui = alpha r_ui = c_ui - 1
 //       b_u = sum_{i in N(u)} c_ui y_i                        c_ui = 1 + w_ui
 //       x_u = A_u^{-1} b_u                                    (one-wave Cholesky, als_common.h); an empty list gives exactly 0
 //   One 256-thread block per entity builds the sums from 32-row tiles of partner rows staged in LDS: thread tid keeps the
 //   A entries t = tid + 256 q (row t / d, column t % d) in registers, up to 16 of them, and thread tid < d the b entry tid.
 //   Lists longer than the chunk size are cut into chunks: k_ials_partial builds each chunk's sums in its own block, the
-//   entity's block adds them in list order.  The Gram is cut into row slices whose size depends on n only; each slice's
-//   d x d partial is built by one block and the partials are added in ascending slice order.  No atomics anywhere: every
-//   sum has a fixed order and the results are bit-identical from run to run, whatever the grid.
+//   entity's block adds them in list order.  No atomics anywhere: every sum has a fixed order and the results are
+//   bit-identical from run to run, whatever the grid.
+//   The Gram, for both this path and the conjugate-gradient one (ials_cg.hip), any d <= 256: cut into row slices whose size
+//   depends on n only; one block per (slice, 64 x 64 output tile), thread (tr, tc) = (tid / 16, tid % 16) keeps the 4 x 4
+//   entries at rows 4 tr.., columns 4 tc.. of the tile; the slice's rows ascend, 32 at a time through LDS; the slices'
+//   partials are added in ascending slice order.  Entries (r, c) and (c, r) add the same products in the same order: G is
+//   bitwise symmetric.  Below 24 columns a tile is mostly padding and one block per slice keeps the whole d x d partial
+//   (k_ials_gram_narrow): the same sums in the same order, so the same bits; the width alone chooses.
 //   Loss: L = sum_u [ x_u^T G x_u + sum_{i in N(u)} (c_ui (1 - s_ui)^2 - s_ui^2) ] + lambda (||X||^2 + trace(G)),
 //   s_ui = x_u . y_i, G = Y^T Y - the dense U x I matrix is never formed.
 #include <hip/hip_runtime.h>
@@ -33,27 +38,17 @@ namespace {
 constexpr int IALS_MAXD = 64;
 constexpr int IALS_LD = IALS_MAXD + 1;   // LDS row stride: lane r of the Cholesky walks row r, the odd stride spreads the banks
 constexpr int IALS_SLOTS = IALS_MAXD * IALS_MAXD / 256;   // A entries per thread at d = 64
-// IALS_TILE, the Gram slice rule and the handle itself: ials_model.h, shared with the conjugate-gradient path (ials_cg.hip)
-
-struct IalsArgs {
-    int64_t n;                                                     // entities of this side, empty ones included
-    const int64_t* ptr; const int32_t* ids; const double* vals;    // their lists: partner ids, values
-    double* own; const double* other; const double* G;             // G = other^T other
-    double lambda, alpha;
-    int32_t d;
-    const int32_t* cfirst; const int32_t* ccount;
-    const int32_t* chunk_ent; const int64_t* chunk_lo; const int64_t* chunk_hi; int64_t n_chunks;
-    double* partial;                                               // [n_chunks][d*d + d]
-};
+constexpr int GRAM_T = 64;               // output tile edge of the Gram
+constexpr int GRAM_LD = GRAM_T + 4;      // LDS row stride of a staged tile: 16-byte aligned rows, shifted banks
+constexpr int GRAM_NARROW_D = 23;        // widest table of the narrow Gram: measured faster than a mostly empty tile below 24
+constexpr int GRAM_NARROW_SLOTS = (GRAM_NARROW_D * GRAM_NARROW_D + 255) / 256;
+// IALS_TILE, the Gram slice rule, the handle and IalsArgs: ials_model.h, shared with the conjugate-gradient path (ials_cg.hip)
 
 // Sums over the list entries [lo, hi): acc[q] += sum_k (w_k y_k[r]) y_k[c] for the A entries t = tid + 256 q = r d + c,
-// accb += sum_k c_k y_k[tid]; 32-row tiles staged in LDS, k ascending.  WEIGHTED = false is the Gram's form: the rows
-// lo .. hi - 1 of T themselves, acc[q] += sum_k y_k[r] y_k[c], no b.
-template <bool WEIGHTED>
-__device__ __forceinline__ void ials_accumulate(const double* T, const int32_t* ids, const double* vals, double alpha, int d,
-                                                int64_t lo, int64_t hi, double (&acc)[IALS_SLOTS], double& accb,
+// accb += sum_k c_k y_k[tid]; 32-row tiles staged in LDS, k ascending.
+__device__ __forceinline__ void ials_accumulate(const IalsArgs& a, int64_t lo, int64_t hi, double (&acc)[IALS_SLOTS], double& accb,
                                                 double (*rows)[IALS_LD], double* wk, double* ck) {
-    const int tid = threadIdx.x, dd = d * d;
+    const int tid = threadIdx.x, d = a.d, dd = d * d;
     int rc[IALS_SLOTS];                                            // r << 8 | c of each live slot
 #pragma unroll
     for (int q = 0; q < IALS_SLOTS; ++q) {
@@ -64,11 +59,10 @@ __device__ __forceinline__ void ials_accumulate(const double* T, const int32_t* 
         const int nk = (int)((hi - s < IALS_TILE) ? hi - s : IALS_TILE);
         for (int t = tid; t < nk * d; t += 256) {
             const int k = t / d, c = t % d;
-            const int64_t row = WEIGHTED ? (int64_t)ids[s + k] : s + k;
-            rows[k][c] = T[(size_t)row * d + c];
+            rows[k][c] = a.other[(size_t)a.ids[s + k] * d + c];
         }
-        if (WEIGHTED && tid < nk) {
-            const double w = alpha * vals[s + tid];
+        if (tid < nk) {
+            const double w = a.alpha * a.vals[s + tid];
             wk[tid] = w;
             ck[tid] = 1.0 + w;
         }
@@ -78,12 +72,11 @@ __device__ __forceinline__ void ials_accumulate(const double* T, const int32_t* 
             if (rc[q] >= 0) {
                 const int r = rc[q] >> 8, c = rc[q] & 255;
                 double sacc = acc[q];
-                if (WEIGHTED) for (int k = 0; k < nk; ++k) sacc += (wk[k] * rows[k][r]) * rows[k][c];
-                else for (int k = 0; k < nk; ++k) sacc += rows[k][r] * rows[k][c];
+                for (int k = 0; k < nk; ++k) sacc += (wk[k] * rows[k][r]) * rows[k][c];
                 acc[q] = sacc;
             }
         }
-        if (WEIGHTED && tid < d) {
+        if (tid < d) {
             double sb = accb;
             for (int k = 0; k < nk; ++k) sb += ck[k] * rows[k][tid];
             accb = sb;
@@ -92,22 +85,76 @@ __device__ __forceinline__ void ials_accumulate(const double* T, const int32_t* 
     }
 }
 
-// one Gram slice: partial[slice][t] = sum over the slice's rows, ascending
-__global__ __launch_bounds__(256) void k_ials_gram(const double* T, int64_t n, int d, int64_t slice_rows, int64_t n_slices, double* partial) {
-    __shared__ double rows[IALS_TILE][IALS_LD];
-    const int tid = threadIdx.x, dd = d * d;
-    for (int64_t sl = blockIdx.x; sl < n_slices; sl += gridDim.x) {
-        const int64_t lo = sl * slice_rows, hi = (lo + slice_rows < n) ? lo + slice_rows : n;
-        double acc[IALS_SLOTS];
+// one (slice, row tile, column tile): partial[slice][r d + c] for r, c of the tile
+__global__ __launch_bounds__(256) void k_ials_gram_tiled(const double* T, int64_t n, int d, int64_t slice_rows, int nt, double* partial) {
+    __shared__ double ra[IALS_TILE][GRAM_LD];
+    __shared__ double rb[IALS_TILE][GRAM_LD];
+    const int tid = threadIdx.x, tr = tid >> 4, tc = tid & 15;
+    const int64_t sl = blockIdx.x / (nt * nt);
+    const int tile = (int)(blockIdx.x % (nt * nt)), r0 = (tile / nt) * GRAM_T, c0 = (tile % nt) * GRAM_T;
+    const int64_t lo = sl * slice_rows, hi = (lo + slice_rows < n) ? lo + slice_rows : n;
+    double acc[4][4];
 #pragma unroll
-        for (int q = 0; q < IALS_SLOTS; ++q) acc[q] = 0.0;
-        double accb = 0.0;
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
+    for (int64_t s = lo; s < hi; s += IALS_TILE) {
+        const int nk = (int)((hi - s < IALS_TILE) ? hi - s : IALS_TILE);
+        for (int t = tid; t < nk * GRAM_T; t += 256) {       // columns past d are staged as 0 and never written out
+            const int k = t / GRAM_T, c = t % GRAM_T;
+            const double* row = T + (size_t)(s + k) * d;
+            ra[k][c] = (r0 + c < d) ? row[r0 + c] : 0.0;
+            rb[k][c] = (c0 + c < d) ? row[c0 + c] : 0.0;
+        }
         __syncthreads();
-        ials_accumulate<false>(T, nullptr, nullptr, 0.0, d, lo, hi, acc, accb, rows, nullptr, nullptr);
-        double* pp = partial + (size_t)sl * dd;
+        for (int k = 0; k < nk; ++k) {
+            double a[4], b[4];
 #pragma unroll
-        for (int q = 0; q < IALS_SLOTS; ++q) { const int t = tid + 256 * q; if (t < dd) pp[t] = acc[q]; }
+            for (int i = 0; i < 4; ++i) { a[i] = ra[k][4 * tr + i]; b[i] = rb[k][4 * tc + i]; }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] += a[i] * b[j];
+        }
+        __syncthreads();
     }
+    double* pp = partial + (size_t)sl * d * d;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int r = r0 + 4 * tr + i, c = c0 + 4 * tc + j;
+            if (r < d && c < d) pp[(size_t)r * d + c] = acc[i][j];
+        }
+}
+
+// one slice of a table of at most GRAM_NARROW_D columns, where a 64 x 64 tile would be mostly padding: thread tid keeps
+// the entries t = tid + 256 q = r d + c of the slice's partial; the same products in the same order as the tiled kernel
+__global__ __launch_bounds__(256) void k_ials_gram_narrow(const double* T, int64_t n, int d, int64_t slice_rows, double* partial) {
+    __shared__ double rows[IALS_TILE][GRAM_NARROW_D + 1];
+    const int tid = threadIdx.x, dd = d * d;
+    const int64_t sl = blockIdx.x, lo = sl * slice_rows, hi = (lo + slice_rows < n) ? lo + slice_rows : n;
+    double acc[GRAM_NARROW_SLOTS];
+#pragma unroll
+    for (int q = 0; q < GRAM_NARROW_SLOTS; ++q) acc[q] = 0.0;
+    for (int64_t s = lo; s < hi; s += IALS_TILE) {
+        const int nk = (int)((hi - s < IALS_TILE) ? hi - s : IALS_TILE);
+        for (int t = tid; t < nk * d; t += 256) rows[t / d][t % d] = T[(size_t)s * d + t];
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < GRAM_NARROW_SLOTS; ++q) {
+            const int t = tid + 256 * q;
+            if (t < dd) {
+                const int r = t / d, c = t % d;
+                double sacc = acc[q];
+                for (int k = 0; k < nk; ++k) sacc += rows[k][r] * rows[k][c];
+                acc[q] = sacc;
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < GRAM_NARROW_SLOTS; ++q) { const int t = tid + 256 * q; if (t < dd) partial[(size_t)sl * dd + t] = acc[q]; }
 }
 
 // G[t] = the slices' partials added in ascending slice order
@@ -121,61 +168,37 @@ __global__ __launch_bounds__(256) void k_ials_gram_sum(const double* partial, in
 }
 
 // partial sums of one chunk of a long list
-__global__ __launch_bounds__(256) void k_ials_partial(IalsArgs a) {
+__global__ __launch_bounds__(256) void k_ials_partial(IalsArgs a, tfr::ChunkArgs ch) {
     __shared__ double rows[IALS_TILE][IALS_LD];
     __shared__ double wk[IALS_TILE], ck[IALS_TILE];
-    const int tid = threadIdx.x, d = a.d, dd = d * d;
-    for (int64_t c = blockIdx.x; c < a.n_chunks; c += gridDim.x) {
-        double acc[IALS_SLOTS];
-#pragma unroll
-        for (int q = 0; q < IALS_SLOTS; ++q) acc[q] = 0.0;
-        double accb = 0.0;
+    for (int64_t c = blockIdx.x; c < ch.n; c += gridDim.x) {
+        double acc[IALS_SLOTS], accb;
+        tfr::zero_slots(acc, accb);
         __syncthreads();
-        ials_accumulate<true>(a.other, a.ids, a.vals, a.alpha, d, a.chunk_lo[c], a.chunk_hi[c], acc, accb, rows, wk, ck);
-        double* pp = a.partial + (size_t)c * (dd + d);
-#pragma unroll
-        for (int q = 0; q < IALS_SLOTS; ++q) { const int t = tid + 256 * q; if (t < dd) pp[t] = acc[q]; }
-        if (tid < d) pp[dd + tid] = accb;
+        ials_accumulate(a, ch.lo[c], ch.hi[c], acc, accb, rows, wk, ck);
+        tfr::store_chunk_partial(ch, c, a.d, acc, accb);
     }
 }
 
-__global__ __launch_bounds__(256) void k_ials_fit(IalsArgs a) {
+__global__ __launch_bounds__(256) void k_ials_fit(IalsArgs a, tfr::ChunkArgs ch) {
     __shared__ double A[IALS_MAXD][IALS_LD];
     __shared__ double rows[IALS_TILE][IALS_LD];
     __shared__ double wk[IALS_TILE], ck[IALS_TILE];
     __shared__ double bvec[IALS_MAXD], xvec[IALS_MAXD];
-    const int tid = threadIdx.x, d = a.d, dd = d * d;
+    const int tid = threadIdx.x, d = a.d;
     for (int64_t e = blockIdx.x; e < a.n; e += gridDim.x) {
         const int64_t lo = a.ptr[e], hi = a.ptr[e + 1];
         if (lo == hi) {                                            // b = 0: the minimiser is 0
             if (tid < d) a.own[(size_t)e * d + tid] = 0.0;
             continue;
         }
-        double acc[IALS_SLOTS];
-#pragma unroll
-        for (int q = 0; q < IALS_SLOTS; ++q) acc[q] = 0.0;
-        double accb = 0.0;
+        double acc[IALS_SLOTS], accb;
+        tfr::zero_slots(acc, accb);
         __syncthreads();
-        const int32_t nch = a.ccount[e];
-        if (nch > 0) {                                             // a long list: add the chunks' partial sums, in list order
-            const int32_t c0 = a.cfirst[e];
-            for (int32_t ch = 0; ch < nch; ++ch) {
-                const double* pp = a.partial + (size_t)(c0 + ch) * (dd + d);
-#pragma unroll
-                for (int q = 0; q < IALS_SLOTS; ++q) { const int t = tid + 256 * q; if (t < dd) acc[q] += pp[t]; }
-                if (tid < d) accb += pp[dd + tid];
-            }
-        } else {
-            ials_accumulate<true>(a.other, a.ids, a.vals, a.alpha, d, lo, hi, acc, accb, rows, wk, ck);
-        }
-#pragma unroll
-        for (int q = 0; q < IALS_SLOTS; ++q) {
-            const int t = tid + 256 * q;
-            if (t < dd) {
-                const int r = t / d, c = t % d;
-                A[r][c] = (a.G[t] + acc[q]) + ((r == c) ? a.lambda : 0.0);
-            }
-        }
+        const int32_t nch = ch.ccount[e];
+        if (nch > 0) tfr::add_chunk_partials(ch, e, nch, d, acc, accb);
+        else ials_accumulate(a, lo, hi, acc, accb, rows, wk, ck);
+        tfr::slots_to_matrix(acc, d, A, [&](int t, double s, bool diag) { return (a.G[t] + s) + (diag ? a.lambda : 0.0); });
         if (tid < d) bvec[tid] = accb;
         __syncthreads();
         if (tid < 64) tfr::chol_wave_solve<IALS_LD>(A, bvec, xvec, d);
@@ -254,29 +277,18 @@ int ials_fail(int code, const char* fmt, ...) {
                                                "%s: %s", #expr, hipGetErrorString(e_));                \
     } while (0)
 
-}  // namespace
-
-namespace {
-
-// G = tab[side]^T tab[side], queued on the model's stream
+// G = tab[side]^T tab[side] for any d <= 256, queued on the model's stream
 hipError_t queue_gram(tfr_ials* m, int side) {
-    if (m->cg_steps) return tfr::ials_cg_queue_gram(m, side);
     const int64_t n = m->n[side], rows = gram_slice_rows(n), ns = (n + rows - 1) / rows;
-    hipLaunchKernelGGL(k_ials_gram, dim3((unsigned)ns), dim3(256), 0, m->stream, m->tab[side].get(), n, m->d, rows, ns, m->gram_partial.get());
-    hipLaunchKernelGGL(k_ials_gram_sum, dim3((unsigned)((m->d * m->d + 255) / 256)), dim3(256), 0, m->stream, m->gram_partial.get(), ns,
-                       m->d, m->G.get());
+    const int d = m->d, nt = (d + GRAM_T - 1) / GRAM_T;
+    if (d <= GRAM_NARROW_D)
+        hipLaunchKernelGGL(k_ials_gram_narrow, dim3((unsigned)ns), dim3(256), 0, m->stream, m->tab[side].get(), n, d, rows, m->gram_partial.get());
+    else
+        hipLaunchKernelGGL(k_ials_gram_tiled, dim3((unsigned)(ns * nt * nt)), dim3(256), 0, m->stream, m->tab[side].get(), n, d, rows, nt,
+                           m->gram_partial.get());
+    hipLaunchKernelGGL(k_ials_gram_sum, dim3((unsigned)((d * d + 255) / 256)), dim3(256), 0, m->stream, m->gram_partial.get(), ns, d,
+                       m->G.get());
     return hipGetLastError();
-}
-
-IalsArgs side_args(tfr_ials* m, int side) {
-    IalsArgs a;
-    a.n = m->n[side]; a.ptr = m->ptr[side]; a.ids = m->ids[side]; a.vals = m->vals[side];
-    a.own = m->tab[side]; a.other = m->tab[1 - side]; a.G = m->G;
-    a.lambda = m->lambda; a.alpha = m->alpha; a.d = m->d;
-    a.cfirst = m->chunks[side].cfirst; a.ccount = m->chunks[side].ccount; a.chunk_ent = m->chunks[side].ent;
-    a.chunk_lo = m->chunks[side].lo; a.chunk_hi = m->chunks[side].hi; a.n_chunks = m->chunks[side].n;
-    a.partial = m->partial;
-    return a;
 }
 
 // one half-sweep of `side`, queued: the partner table's Gram, the long lists' chunks, every entity
@@ -284,9 +296,10 @@ hipError_t queue_half(tfr_ials* m, int side) {
     hipError_t e = queue_gram(m, 1 - side);
     if (e != hipSuccess) return e;
     if (m->cg_steps) return tfr::ials_cg_queue_fit(m, side);
-    const IalsArgs a = side_args(m, side);
-    if (a.n_chunks) hipLaunchKernelGGL(k_ials_partial, dim3((unsigned)std::min<int64_t>(a.n_chunks, 65535)), dim3(256), 0, m->stream, a);
-    hipLaunchKernelGGL(k_ials_fit, dim3((unsigned)std::min<int64_t>(a.n, 65535)), dim3(256), 0, m->stream, a);
+    const IalsArgs a = tfr::ials_side_args(m, side);
+    const tfr::ChunkArgs ch = m->chunks[side].args(m->partial);
+    if (ch.n) hipLaunchKernelGGL(k_ials_partial, dim3((unsigned)std::min<int64_t>(ch.n, 65535)), dim3(256), 0, m->stream, a, ch);
+    hipLaunchKernelGGL(k_ials_fit, dim3((unsigned)std::min<int64_t>(a.n, 65535)), dim3(256), 0, m->stream, a, ch);
     return hipGetLastError();
 }
 
@@ -485,7 +498,7 @@ int tfr_ials_loss(tfr_ials* m, double* loss_out) {
     if (!m->loaded) return ials_fail(TFR_ERR_STATE, "no data: call tfr_ials_load first");
     IALSCHK(hipSetDevice(m->device));
     IALSCHK(queue_gram(m, 1));
-    const IalsArgs a = side_args(m, 0);
+    const IalsArgs a = tfr::ials_side_args(m, 0);
     if (m->cg_steps) IALSCHK(tfr::ials_cg_queue_loss_users(m));
     else hipLaunchKernelGGL(k_ials_loss_users, dim3((unsigned)std::min<int64_t>(a.n, 65535)), dim3(256), 0, m->stream, a, m->per_user.get());
     hipLaunchKernelGGL(k_ials_loss_reduce, dim3(1), dim3(256), 0, m->stream, m->per_user.get(), a.n, m->G.get(), m->d, m->lambda,

@@ -1,10 +1,6 @@
 // ials_cg.hip - the conjugate-gradient half-sweep of the implicit ALS (include/tfrecomm.h states the solver), float64,
 // 1 <= d <= 256.  No per-row matrix is formed: per row and per step the solver multiplies by G = Y^T Y and walks the row's
-// list once.
-//   k_ials_gram_wide + k_ials_gram_sum_wide   G for any d <= 256: one block per (Gram slice, 64 x 64 output tile), thread
-//       (tr, tc) = (tid / 16, tid % 16) keeps the 4 x 4 entries at rows 4 tr.., columns 4 tc.. of the tile; the slice's rows
-//       ascend, 32 at a time through LDS; the slices' partials are added in ascending slice order.  Entries (r, c) and
-//       (c, r) add the same products in the same order: G is bitwise symmetric.
+// list once.  G comes from the one Gram of both paths (ials.hip) and is bitwise symmetric.
 //   k_ials_cg_fit<NC>   one 256-thread block per entity, grid-stride, empty entities included (they get exactly 0).
 //       x, r, p, Ap live in LDS.  A pass over a vector v (x for the first residual, p in a step) gives every wave the list
 //       entries k = wave, wave + 4, ... and the rows c' = wave, wave + 4, ... of G: lane l holds the components l + 64 j,
@@ -19,74 +15,12 @@
 // list length.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <type_traits>
 #include "ials_model.h"
 
 namespace {
 
-constexpr int CG_T = 64;                     // output tile edge of the wide Gram
 constexpr int CG_AHEAD = 4;                  // list entries a wave gathers ahead in the fit kernel's pass
-constexpr int CG_LD = CG_T + 4;              // LDS row stride of a staged tile: 16-byte aligned rows, shifted banks
-
-// one (slice, row tile, column tile): partial[slice][r d + c] for r, c of the tile
-__global__ __launch_bounds__(256) void k_ials_gram_wide(const double* T, int64_t n, int d, int64_t slice_rows, int nt, double* partial) {
-    __shared__ double ra[IALS_TILE][CG_LD];
-    __shared__ double rb[IALS_TILE][CG_LD];
-    const int tid = threadIdx.x, tr = tid >> 4, tc = tid & 15;
-    const int64_t sl = blockIdx.x / (nt * nt);
-    const int tile = (int)(blockIdx.x % (nt * nt)), r0 = (tile / nt) * CG_T, c0 = (tile % nt) * CG_T;
-    const int64_t lo = sl * slice_rows, hi = (lo + slice_rows < n) ? lo + slice_rows : n;
-    double acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = 0.0;
-    for (int64_t s = lo; s < hi; s += IALS_TILE) {
-        const int nk = (int)((hi - s < IALS_TILE) ? hi - s : IALS_TILE);
-        for (int t = tid; t < nk * CG_T; t += 256) {       // columns past d are staged as 0 and never written out
-            const int k = t / CG_T, c = t % CG_T;
-            const double* row = T + (size_t)(s + k) * d;
-            ra[k][c] = (r0 + c < d) ? row[r0 + c] : 0.0;
-            rb[k][c] = (c0 + c < d) ? row[c0 + c] : 0.0;
-        }
-        __syncthreads();
-        for (int k = 0; k < nk; ++k) {
-            double a[4], b[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { a[i] = ra[k][4 * tr + i]; b[i] = rb[k][4 * tc + i]; }
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) acc[i][j] += a[i] * b[j];
-        }
-        __syncthreads();
-    }
-    double* pp = partial + (size_t)sl * d * d;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int r = r0 + 4 * tr + i, c = c0 + 4 * tc + j;
-            if (r < d && c < d) pp[(size_t)r * d + c] = acc[i][j];
-        }
-}
-
-// G[t] = the slices' partials added in ascending slice order
-__global__ __launch_bounds__(256) void k_ials_gram_sum_wide(const double* partial, int64_t n_slices, int d, double* G) {
-    const int dd = d * d;
-    const int t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= dd) return;
-    double s = 0.0;
-    for (int64_t sl = 0; sl < n_slices; ++sl) s += partial[(size_t)sl * dd + t];
-    G[t] = s;
-}
-
-struct CgArgs {
-    int64_t n;                                                     // entities of this side, empty ones included
-    const int64_t* ptr; const int32_t* ids; const double* vals;    // their lists: partner ids, values
-    double* own; const double* other; const double* G;             // G = other^T other
-    double lambda, alpha;
-    int32_t d, cg_steps;
-};
 
 // the sum over the wave, in every lane: xor 32, 16, 8, 4, 2, 1
 __device__ __forceinline__ double wave_sum(double v) {
@@ -110,7 +44,7 @@ __device__ __forceinline__ double block_dot(const double* a, const double* b, in
 // gv = G v.  Wave w takes k = lo + w, lo + w + 4, ... and the rows c' = w, w + 4, ... of G; its two partial vectors go to
 // pl[w] and pg[w].  The caller's barrier makes them visible.
 template <int NC, bool FIRST>
-__device__ __forceinline__ void cg_pass(const CgArgs& a, int64_t lo, int64_t hi, const double* v, double (*pl)[IALS_CG_MAXD],
+__device__ __forceinline__ void cg_pass(const IalsArgs& a, int64_t lo, int64_t hi, const double* v, double (*pl)[IALS_CG_MAXD],
                                         double (*pg)[IALS_CG_MAXD]) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, d = a.d;
     double vr[NC], al[NC], ag[NC];
@@ -180,7 +114,7 @@ __device__ __forceinline__ void cg_pass(const CgArgs& a, int64_t lo, int64_t hi,
 }
 
 template <int NC>
-__global__ __launch_bounds__(256) void k_ials_cg_fit(CgArgs a) {
+__global__ __launch_bounds__(256) void k_ials_cg_fit(IalsArgs a) {
     __shared__ double xs[IALS_CG_MAXD], rs_[IALS_CG_MAXD], ps[IALS_CG_MAXD], aps[IALS_CG_MAXD];
     __shared__ double pl[4][IALS_CG_MAXD], pg[4][IALS_CG_MAXD];
     __shared__ double wred[4];
@@ -230,7 +164,7 @@ __global__ __launch_bounds__(256) void k_ials_cg_fit(CgArgs a) {
 
 // per-user part of the loss: x^T G x + lambda |x|^2 + sum_{i in N(u)} (c (1 - s)^2 - s^2); G = Y^T Y
 template <int NC>
-__global__ __launch_bounds__(256) void k_ials_loss_users_wide(CgArgs a, double* per_user) {
+__global__ __launch_bounds__(256) void k_ials_loss_users_wide(IalsArgs a, double* per_user) {
     __shared__ double x[IALS_CG_MAXD];
     __shared__ double red[256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, d = a.d;
@@ -271,51 +205,34 @@ __global__ __launch_bounds__(256) void k_ials_loss_users_wide(CgArgs a, double* 
     }
 }
 
-CgArgs cg_args(tfr_ials* m, int side) {
-    CgArgs a;
-    a.n = m->n[side]; a.ptr = m->ptr[side]; a.ids = m->ids[side]; a.vals = m->vals[side];
-    a.own = m->tab[side]; a.other = m->tab[1 - side]; a.G = m->G;
-    a.lambda = m->lambda; a.alpha = m->alpha; a.d = m->d; a.cg_steps = m->cg_steps;
-    return a;
+// calls launch(std::integral_constant<int, NC>) for NC = ceil(d / 64), the components per lane, with the grid of one block
+// per entity
+template <class Launch>
+hipError_t with_nc(const IalsArgs& a, Launch launch) {
+    const dim3 grid((unsigned)std::min<int64_t>(a.n, 65535));
+    switch ((a.d + 63) / 64) {
+        case 1: launch(std::integral_constant<int, 1>(), grid); break;
+        case 2: launch(std::integral_constant<int, 2>(), grid); break;
+        case 3: launch(std::integral_constant<int, 3>(), grid); break;
+        default: launch(std::integral_constant<int, 4>(), grid); break;
+    }
+    return hipGetLastError();
 }
 
 }  // namespace
 
 namespace tfr {
 
-hipError_t ials_cg_queue_gram(tfr_ials* m, int side) {
-    const int64_t n = m->n[side], rows = gram_slice_rows(n), ns = (n + rows - 1) / rows;
-    const int d = m->d, nt = (d + CG_T - 1) / CG_T;
-    hipLaunchKernelGGL(k_ials_gram_wide, dim3((unsigned)(ns * nt * nt)), dim3(256), 0, m->stream, m->tab[side].get(), n, d, rows, nt,
-                       m->gram_partial.get());
-    hipLaunchKernelGGL(k_ials_gram_sum_wide, dim3((unsigned)((d * d + 255) / 256)), dim3(256), 0, m->stream, m->gram_partial.get(), ns, d,
-                       m->G.get());
-    return hipGetLastError();
-}
-
 hipError_t ials_cg_queue_fit(tfr_ials* m, int side) {
-    const CgArgs a = cg_args(m, side);
-    const dim3 grid((unsigned)std::min<int64_t>(a.n, 65535)), block(256);
-    switch ((a.d + 63) / 64) {
-        case 1: hipLaunchKernelGGL(k_ials_cg_fit<1>, grid, block, 0, m->stream, a); break;
-        case 2: hipLaunchKernelGGL(k_ials_cg_fit<2>, grid, block, 0, m->stream, a); break;
-        case 3: hipLaunchKernelGGL(k_ials_cg_fit<3>, grid, block, 0, m->stream, a); break;
-        default: hipLaunchKernelGGL(k_ials_cg_fit<4>, grid, block, 0, m->stream, a); break;
-    }
-    return hipGetLastError();
+    const IalsArgs a = ials_side_args(m, side);
+    return with_nc(a, [&](auto nc, dim3 grid) { hipLaunchKernelGGL(k_ials_cg_fit<decltype(nc)::value>, grid, dim3(256), 0, m->stream, a); });
 }
 
 hipError_t ials_cg_queue_loss_users(tfr_ials* m) {
-    const CgArgs a = cg_args(m, 0);
-    const dim3 grid((unsigned)std::min<int64_t>(a.n, 65535)), block(256);
-    double* out = m->per_user.get();
-    switch ((a.d + 63) / 64) {
-        case 1: hipLaunchKernelGGL(k_ials_loss_users_wide<1>, grid, block, 0, m->stream, a, out); break;
-        case 2: hipLaunchKernelGGL(k_ials_loss_users_wide<2>, grid, block, 0, m->stream, a, out); break;
-        case 3: hipLaunchKernelGGL(k_ials_loss_users_wide<3>, grid, block, 0, m->stream, a, out); break;
-        default: hipLaunchKernelGGL(k_ials_loss_users_wide<4>, grid, block, 0, m->stream, a, out); break;
-    }
-    return hipGetLastError();
+    const IalsArgs a = ials_side_args(m, 0);
+    return with_nc(a, [&](auto nc, dim3 grid) {
+        hipLaunchKernelGGL(k_ials_loss_users_wide<decltype(nc)::value>, grid, dim3(256), 0, m->stream, a, m->per_user.get());
+    });
 }
 
 }  // namespace tfr

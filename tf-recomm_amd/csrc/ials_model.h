@@ -1,6 +1,7 @@
-// ials_model.h - the implicit-ALS handle, shared by the Cholesky path (ials.hip) and the conjugate-gradient path
-// (ials_cg.hip).  ials.hip owns the C-ABI entries; a handle with cg_steps > 0 was made by tfr_ials_create_cg and its Gram,
-// half-sweeps and loss go through the three queue_* functions below.
+// ials_model.h - the implicit-ALS handle and the one argument block of its kernels, shared by the Cholesky path (ials.hip)
+// and the conjugate-gradient path (ials_cg.hip).  ials.hip owns the C-ABI entries, the Gram and the loss's last kernel; a
+// handle with cg_steps > 0 was made by tfr_ials_create_cg and its half-sweeps and per-user loss go through the two queue_*
+// functions below.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,9 +39,21 @@ struct tfr_ials {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
+// what every kernel of both paths sees of one side
+struct IalsArgs {
+    int64_t n;                                                     // entities of this side, empty ones included
+    const int64_t* ptr; const int32_t* ids; const double* vals;    // their lists: partner ids, values
+    double* own; const double* other; const double* G;             // G = other^T other
+    double lambda, alpha;
+    int32_t d, cg_steps;
+};
+
 namespace tfr {
+inline IalsArgs ials_side_args(const tfr_ials* m, int side) {
+    return IalsArgs{m->n[side], m->ptr[side].get(), m->ids[side].get(), m->vals[side].get(), m->tab[side].get(),
+                    m->tab[1 - side].get(), m->G.get(), m->lambda, m->alpha, m->d, m->cg_steps};
+}
 // queued on the model's stream; each returns hipGetLastError() after its launches
-hipError_t ials_cg_queue_gram(tfr_ials* m, int side);          // m->G = tab[side]^T tab[side], any d <= 256
 hipError_t ials_cg_queue_fit(tfr_ials* m, int side);           // cg_steps steps for every entity of `side`, from m->G
 hipError_t ials_cg_queue_loss_users(tfr_ials* m);              // m->per_user, from m->G = Y^T Y
 }  // namespace tfr
