@@ -687,6 +687,32 @@ int tfr_lds_bytes(int32_t kernel, int32_t dim, int64_t batch, int64_t user_num, 
 int tfr_sweep_residency(int32_t dim, int64_t batch, int64_t user_num, int64_t item_num,
                         int32_t* blocks_per_cu, int64_t* scratch_bytes, int64_t* grid_blocks);
 
+/* ---- bf16 snapshot: predict and evaluate at half the row bytes - DESIGN §21 ---------------------------------------------
+ *      A copy of the five tables at a point of the stream's order, private to the model: P and Q as bf16 rows, mu and
+ *      the biases as float32 so that they belong to the same moment.  Training stays float32; later steps,
+ *      tfr_set_table and tfr_init_tables do not change the snapshot, only another tfr_bf16_snapshot does.  tfr_destroy
+ *      frees it.
+ *      Element: the upper 16 bits of the float32, rounded to nearest, ties to even: (bits + 0x7FFF + ((bits >> 16) & 1))
+ *      >> 16; overflow rounds to +-inf, subnormals are not flushed; NaN becomes (bits >> 16) | 0x40 (sign kept, quiet).
+ *      Row: D elements at a stride of DP = 8 * ceil(D / 8) elements (tfr_bf16_row_stride), pads +0.  The layout is the
+ *      library's own; tfr_bf16_get_rows reads it for debugging.
+ *      Scoring widens by a shift and multiplies in float32: the products are exact, and the sum, the bias order
+ *      ((dot + mu) + bu) + bi, item_abs and the evaluation formulas are tfr_forward's / tfr_eval's.
+ *      tfr_bf16_snapshot builds or refreshes the copy on the model's stream and does not synchronise; memory
+ *      (user_num + item_num) * DP * 2 bytes plus the bias copies; TFR_ERR_NOMEM leaves the model without a snapshot.
+ *      tfr_bf16_drop frees it (TFR_OK when there is none).  The forward and eval entries return TFR_ERR_STATE before
+ *      a snapshot; argument checks, batch = 0, device-pointer conventions and TFR_ERR_OOB at the next synchronising
+ *      call are those of tfr_forward, tfr_forward_dev and tfr_eval.  nll_sum_out (may be NULL): the summed sigmoid
+ *      cross-entropy under loss = nll, 0 otherwise.  tfr_bf16_get_rows: which = TFR_P or TFR_Q, n = rows * DP. */
+int tfr_bf16_snapshot(tfr_model* m);
+int tfr_bf16_drop(tfr_model* m);
+int tfr_bf16_forward(tfr_model* m, const int32_t* user, const int32_t* item, int64_t batch, float* logits_out);
+int tfr_bf16_forward_dev(tfr_model* m, const int32_t* d_user, const int32_t* d_item, int64_t batch, float* d_logits);
+int tfr_bf16_eval(tfr_model* m, const int32_t* user, const int32_t* item, const float* rate, int64_t batch,
+                  double* sum_sq_err_out, int64_t* n_equal_out, double* nll_sum_out);
+int tfr_bf16_get_rows(tfr_model* m, int32_t which, uint16_t* host, int64_t n);
+int tfr_bf16_row_stride(int32_t dim);
+
 /* ---- misc ------------------------------------------------------------------------------ */
 int tfr_sync(tfr_model* m);            /* drains the stream; reports deferred TFR_ERR_OOB   */
 const char* tfr_last_error(void);

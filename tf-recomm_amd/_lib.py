@@ -67,6 +67,13 @@ SIGNATURES = {
     "tfr_set_hyper": (C.c_int, [_p, C.c_float, C.c_float]),
     "tfr_forward": (C.c_int, [_p, _i32p, _i32p, C.c_int64, _f32p]),
     "tfr_eval": (C.c_int, [_p, _i32p, _i32p, _f32p, C.c_int64, C.POINTER(C.c_double), _i64p]),
+    "tfr_bf16_snapshot": (C.c_int, [_p]),
+    "tfr_bf16_drop": (C.c_int, [_p]),
+    "tfr_bf16_forward": (C.c_int, [_p, _i32p, _i32p, C.c_int64, _f32p]),
+    "tfr_bf16_forward_dev": (C.c_int, [_p, _p, _p, C.c_int64, _p]),
+    "tfr_bf16_eval": (C.c_int, [_p, _i32p, _i32p, _f32p, C.c_int64, _f64p, _i64p, _f64p]),
+    "tfr_bf16_get_rows": (C.c_int, [_p, C.c_int32, C.POINTER(C.c_uint16), C.c_int64]),
+    "tfr_bf16_row_stride": (C.c_int, [C.c_int32]),
     "tfr_upload_eval_triples": (C.c_int, [_p, _i32p, _i32p, _f32p, C.c_int64]),
     "tfr_eval_resident": (C.c_int, [_p, C.POINTER(C.c_double), _i64p, _i64p]),
     "tfr_eval_binary": (C.c_int, [_p, _i32p, _i32p, _f32p, C.c_int64, _i64p, _f64p, _f64p]),

@@ -20,6 +20,7 @@
 #include "neighbours.h"
 #include "rank.h"
 #include "finetune.h"
+#include "bf16_rows.h"
 #include "devbuf.h"
 
 using namespace tfr;
@@ -176,6 +177,11 @@ struct tfr_model {
     DevBuf<int32_t> rk_order, rk_bins, rk_nr;
     // batched fine-tuning (tfr_finetune_users): one device buffer for a call's schedule and outputs
     DevBuf<char> ft_buf;
+    // bf16 snapshot (tfr_bf16_*): P and Q as padded bf16 rows, mu and the biases as they were at the same moment
+    struct Bf16Snap {
+        DevBuf<uint16_t> p, q; DevBuf<float> bu, bi, mu; bool valid = false;
+        void drop() { p.reset(); q.reset(); bu.reset(); bi.reset(); mu.reset(); valid = false; }
+    } bf;
     // BPR steps (tfr_bpr_*): the positives, the sampler's settings and the step's buffers; created by the first BPR call
     BprState* bpr = nullptr;
     // profiling
@@ -1458,6 +1464,160 @@ int tfr_eval(tfr_model* m, const int32_t* u, const int32_t* i, const float* r, i
     HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(m->d_r, r, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
     return eval_device(m, m->d_u, m->d_i, m->d_r, B, sse_out, neq_out);
+}
+
+// ---- bf16 snapshot (bf16_rows.h) -------------------------------------------------------
+int tfr_bf16_row_stride(int32_t dim) { return dim < 1 ? 0 : bf16_row_stride(dim); }
+
+int tfr_bf16_snapshot(tfr_model* m) {
+    MODEL_ENTER(m);
+    int rc = settle_q(m);                                // item rows may live in the two-table step's second table
+    if (rc) return rc;
+    hipStream_t s = m->stream;
+    const int64_t DP = bf16_row_stride(m->D);
+    tfr_model::Bf16Snap& b = m->bf;
+    b.valid = false;
+    hipError_t e = b.p.reserve(m->U * DP, s);
+    if (e == hipSuccess) e = b.q.reserve(m->I * DP, s);
+    if (e == hipSuccess) e = b.bu.reserve(m->U, s);
+    if (e == hipSuccess) e = b.bi.reserve(m->I, s);
+    if (e == hipSuccess) e = b.mu.reserve(1, s);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(s);                   // a refresh: earlier scoring calls may still read the buffers
+        b.drop();
+        return fail(e == hipErrorOutOfMemory ? TFR_ERR_NOMEM : TFR_ERR_HIP, "tfr_bf16_snapshot: %s", hipGetErrorString(e));
+    }
+    launch_rows_to_bf16(m->w[TFR_P], b.p, m->U, m->D, s);
+    launch_rows_to_bf16(m->w[TFR_Q], b.q, m->I, m->D, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(b.bu, m->w[TFR_BU], (size_t)m->U * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.bi, m->w[TFR_BI], (size_t)m->I * 4, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.mu, m->w[TFR_MU], 4, hipMemcpyDeviceToDevice, s));
+    b.valid = true;
+    return TFR_OK;
+}
+
+int tfr_bf16_drop(tfr_model* m) {
+    MODEL_ENTER(m);
+    if (m->bf.valid) HIPCHK(hipStreamSynchronize(m->stream));
+    m->bf.drop();
+    return TFR_OK;
+}
+
+static int bf16_need_snapshot(const tfr_model* m) {
+    return m->bf.valid ? TFR_OK : fail(TFR_ERR_STATE, "no bf16 snapshot: call tfr_bf16_snapshot first");
+}
+
+// TFR_BF16_PNT=0|1: A/B override of the non-temporal user rows (unset: the float32 forward's rule on the snapshot's bytes).
+// Read at every launch, so that one process can alternate the two (tools/bench_bf16_forward.py --pnt-ab).
+static bool bf16_pnt(const tfr_model* m) {
+    const char* e = getenv("TFR_BF16_PNT");
+    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
+    return (size_t)m->U * bf16_row_stride(m->D) * 2 > ((size_t)256 << 20);
+}
+
+// run_forward on the snapshot: device-resident ids, MODE_INFER or MODE_EVAL
+static int run_forward_bf16(tfr_model* m, int mode, const int32_t* du, const int32_t* di, const float* dr,
+                            int64_t B, float* d_logits, int* nblk_out) {
+    Bf16FwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.P = m->bf.p; a.Q = m->bf.q; a.bu = m->bf.bu; a.bi = m->bf.bi; a.mu = m->bf.mu;
+    a.u = du; a.it = di; a.r = dr;
+    a.logits = d_logits; a.partials = m->partials; a.err = m->d_err;
+    a.B = B; a.U = m->U; a.I = m->I;
+    a.DP = bf16_row_stride(m->D); a.loss = m->o.loss; a.item_abs = m->o.item_abs;
+    const int G = bf16_geometry(m->D);
+    const int grid = bf16_forward_grid(B, G, mode);
+    if (nblk_out) *nblk_out = grid;
+    {
+        Prof p(m, TFR_K_FORWARD);
+        launch_forward_bf16(a, mode, G, grid, bf16_pnt(m), m->stream);
+    }
+    HIPCHK(hipGetLastError());
+    return TFR_OK;
+}
+
+int tfr_bf16_forward_dev(tfr_model* m, const int32_t* du, const int32_t* di, int64_t B, float* d_logits) {
+    MODEL_ENTER(m);
+    int rc = check_batch(du, di, B);
+    if (rc) return rc;
+    if ((rc = bf16_need_snapshot(m))) return rc;
+    if (B == 0) return TFR_OK;
+    if (!d_logits) return fail(TFR_ERR_ARG, "null logits pointer");
+    if ((rc = ensure_capacity(m, 1))) return rc;
+    return run_forward_bf16(m, MODE_INFER, du, di, nullptr, B, d_logits, nullptr);
+}
+
+int tfr_bf16_forward(tfr_model* m, const int32_t* u, const int32_t* i, int64_t B, float* logits_out) {
+    MODEL_ENTER(m);
+    int rc = check_batch(u, i, B);
+    if (rc) return rc;
+    if ((rc = bf16_need_snapshot(m))) return rc;
+    if (B == 0) return TFR_OK;
+    if (!logits_out) return fail(TFR_ERR_ARG, "null logits pointer");
+    if ((rc = ensure_capacity(m, B))) return rc;
+    if (B <= STAGE_MAX) {                                // pinned staging, as tfr_forward
+        if ((rc = ensure_staging(m, B))) return rc;
+        memcpy(m->h_in, u, (size_t)B * 4);
+        memcpy(m->h_in + B, i, (size_t)B * 4);
+        HIPCHK(hipMemcpyAsync(m->d_in, m->h_in, (size_t)2 * B * 4, hipMemcpyHostToDevice, m->stream));
+        if ((rc = run_forward_bf16(m, MODE_INFER, m->d_in, m->d_in + B, nullptr, B, m->d_logits, nullptr))) return rc;
+        HIPCHK(hipMemcpyAsync(m->h_out, m->d_logits, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
+        if ((rc = check_device_error(m))) return rc;
+        memcpy(logits_out, m->h_out, (size_t)B * 4);
+        return TFR_OK;
+    }
+    HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    if ((rc = run_forward_bf16(m, MODE_INFER, m->d_u, m->d_i, nullptr, B, m->d_logits, nullptr))) return rc;
+    HIPCHK(hipMemcpyAsync(logits_out, m->d_logits, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
+    return check_device_error(m);
+}
+
+int tfr_bf16_eval(tfr_model* m, const int32_t* u, const int32_t* i, const float* r, int64_t B,
+                  double* sse_out, int64_t* neq_out, double* nll_out) {
+    MODEL_ENTER(m);
+    int rc = check_batch(u, i, B);
+    if (rc) return rc;
+    if (sse_out) *sse_out = 0.0;
+    if (neq_out) *neq_out = 0;
+    if (nll_out) *nll_out = 0.0;
+    if ((rc = bf16_need_snapshot(m))) return rc;
+    if (B == 0) return TFR_OK;
+    if (!r) return fail(TFR_ERR_ARG, "null rate pointer");
+    if ((rc = ensure_capacity(m, B))) return rc;
+    HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(m->d_r, r, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    int nblk = 0;
+    if ((rc = run_forward_bf16(m, MODE_EVAL, m->d_u, m->d_i, m->d_r, B, nullptr, &nblk))) return rc;
+    // the per-block partials are added as eval_device adds them
+    std::vector<float> part((size_t)nblk * 4);
+    HIPCHK(hipMemcpyAsync(part.data(), m->partials, part.size() * 4, hipMemcpyDeviceToHost, m->stream));
+    if ((rc = check_device_error(m))) return rc;
+    double sse = 0.0, nll = 0.0;
+    int64_t neq = 0;
+    for (int b = 0; b < nblk; ++b) {
+        sse += (double)part[(size_t)b * 4 + 0];
+        neq += (int64_t)llround((double)part[(size_t)b * 4 + 1]);
+        nll += (double)part[(size_t)b * 4 + 2];
+    }
+    if (sse_out) *sse_out = sse;
+    if (neq_out) *neq_out = neq;
+    if (nll_out) *nll_out = nll;
+    return TFR_OK;
+}
+
+int tfr_bf16_get_rows(tfr_model* m, int32_t which, uint16_t* host, int64_t n) {
+    MODEL_ENTER(m);
+    if (which != TFR_P && which != TFR_Q) return fail(TFR_ERR_ARG, "tfr_bf16_get_rows: which must be TFR_P or TFR_Q, got %d", which);
+    int rc = bf16_need_snapshot(m);
+    if (rc) return rc;
+    const int64_t cnt = (which == TFR_P ? m->U : m->I) * bf16_row_stride(m->D);
+    if (!host || n != cnt) return fail(TFR_ERR_ARG, "bf16 rows of table %d hold %lld elements, asked %lld", which, (long long)cnt, (long long)n);
+    HIPCHK(hipMemcpyAsync(host, which == TFR_P ? m->bf.p.get() : m->bf.q.get(), (size_t)n * 2, hipMemcpyDeviceToHost, m->stream));
+    HIPCHK(hipStreamSynchronize(m->stream));
+    return TFR_OK;
 }
 
 int tfr_upload_eval_triples(tfr_model* m, const int32_t* u, const int32_t* i, const float* r, int64_t N) {

@@ -213,6 +213,42 @@ class SvdModel:
                                    C.byref(sse), C.byref(neq)))
         return sse.value, neq.value
 
+    # -- bf16 snapshot: predict and evaluate at half the row bytes (bf16.py) ----
+    def snapshot_bf16(self):
+        """Build or refresh the bf16 copy of the tables the ``*_bf16`` calls score from; training does not move it."""
+        L.check(self._lib.tfr_bf16_snapshot(self._h))
+
+    def drop_bf16(self):
+        L.check(self._lib.tfr_bf16_drop(self._h))
+
+    def forward_bf16(self, users, items):
+        u, i = L.as_i32(users, "user ids"), L.as_i32(items, "item ids")
+        if u.shape != i.shape or u.ndim != 1:
+            raise ValueError("user and item batches must be 1-D and of equal length")
+        out = np.empty(u.size, np.float32)
+        L.check(self._lib.tfr_bf16_forward(self._h, L.ptr_i32(u), L.ptr_i32(i), u.size, L.ptr_f32(out)))
+        return out
+
+    def forward_bf16_dev(self, d_user, d_item, batch, d_logits):
+        L.check(self._lib.tfr_bf16_forward_dev(self._h, d_user, d_item, int(batch), d_logits))
+
+    def eval_bf16(self, users, items, rates):
+        """(sse, n_equal) from the snapshot, or (sse, n_equal, nll_sum) under the NLL head."""
+        u, i, r = L.as_i32(users, "user ids"), L.as_i32(items, "item ids"), L.as_f32(rates)
+        if not (u.shape == i.shape == r.shape) or u.ndim != 1:
+            raise ValueError("batches must be 1-D and of equal length")
+        sse, neq, nll = C.c_double(), C.c_int64(), C.c_double()
+        L.check(self._lib.tfr_bf16_eval(self._h, L.ptr_i32(u), L.ptr_i32(i), L.ptr_f32(r), u.size,
+                                        C.byref(sse), C.byref(neq), C.byref(nll)))
+        return (sse.value, neq.value, nll.value) if self.loss == "nll" else (sse.value, neq.value)
+
+    def bf16_rows(self, which):
+        """The snapshot's rows of ``which`` (P or Q) as the library stores them: uint16 [rows, DP]."""
+        rows = self.user_num if which == L.P else self.item_num
+        out = np.empty((rows, self._lib.tfr_bf16_row_stride(self.dim)), np.uint16)
+        L.check(self._lib.tfr_bf16_get_rows(self._h, int(which), out.ctypes.data_as(C.POINTER(C.c_uint16)), out.size))
+        return out
+
     def upload_eval_triples(self, users, items, rates):
         u, i, r = L.as_i32(users, "user ids"), L.as_i32(items, "item ids"), L.as_f32(rates)
         L.check(self._lib.tfr_upload_eval_triples(self._h, L.ptr_i32(u), L.ptr_i32(i), L.ptr_f32(r), u.size))
