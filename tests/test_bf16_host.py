@@ -111,3 +111,29 @@ def test_eval_case_has_no_logit_at_the_rounding_edge():
     t, u, i, _ = C.eval_case("nll")
     x = make_oracle(U, I, D, C.snapshot_tables(t), loss="nll").forward(u, i)
     assert np.abs(x).min() >= 1e-4, np.abs(x).min()
+
+
+# ---------------------------------------------------------------- the exact case of the GPU tests
+@pytest.mark.parametrize("item_abs", [False, True])
+@pytest.mark.parametrize("D", C.WIDTHS)
+def test_exact_case_is_exact_in_any_order(D, item_abs):
+    t, u, i, r = C.exact_case(D, item_abs)
+    assert len(u) == 3 * C.per_block(D) + 5
+    assert C.exactness_faults(t, u, i, r, item_abs) == []
+    x = C.exact_logits(t, u, i, item_abs)
+    sse, neq = C.exact_eval(t, u, i, r, item_abs)
+    assert 0 < neq < len(u) and sse > 0                            # both counts of the evaluation are at work
+    assert len(np.unique(x)) > 20 and (x != np.rint(x)).any()      # the half-valued biases reach the logits
+    if item_abs:
+        assert not np.array_equal(x, C.exact_logits(t, u, i, False))
+
+
+def test_exactness_guard_fails_on_a_planted_third():
+    D, item_abs = 100, False
+    t, u, i, r = C.exact_case(D, item_abs)
+    k = int(np.flatnonzero(t["Q"][i, 0] != 0)[0])
+    t["P"] = t["P"].copy()
+    t["P"][u[k], 0] = np.float32(1.0 / 3.0)                        # neither an integer nor bf16-exact
+    faults = C.exactness_faults(t, u, i, r, item_abs)
+    assert "rows are bf16-exact integers" in faults
+    assert "float32 logits in two orders equal float64" in faults  # the orders do differ: the guard sees it by evaluation

@@ -73,6 +73,23 @@ def test_forward_matches_oracle_on_round_tripped_tables(D, item_abs):
             assert_close(got, orc.forward(u, i), what="D %d B %d logits" % (D, B))
 
 
+# ---------------------------------------------------------------- 2a. one body, two row types: exact agreement
+@pytest.mark.parametrize("item_abs", [False, True])
+@pytest.mark.parametrize("D", C.WIDTHS)
+def test_float32_and_snapshot_entries_agree_bit_for_bit_on_the_exact_case(D, item_abs):
+    """tests/bf16_cases.py exact_case: every partial sum is exact in float32 in any order (tests/test_bf16_host.py
+    holds the inputs to that), so nothing but the float64 values can come out of either row type"""
+    t, u, i, r, want, want_sse, want_neq = C.exact_reference(D, item_abs)
+    U, I = C.EXACT_TABLES
+    with model_from(U, I, D, t, item_abs=item_abs) as m:
+        m.snapshot_bf16()
+        f32, h = m.forward(u, i), m.forward_bf16(u, i)
+        ev, evh = m.eval(u, i, r), m.eval_bf16(u, i, r)
+    print("D %d: sse %r / %r want %r, neq %d / %d want %d" % (D, ev[0], evh[0], want_sse, ev[1], evh[1], want_neq))
+    assert same_bits(f32, want) and same_bits(h, want)
+    assert ev == (want_sse, want_neq) and evh == (want_sse, want_neq)
+
+
 # ---------------------------------------------------------------- 3. grid stride
 def test_grid_stride_infer_and_eval():
     U, I, D = 300, 200, 128

@@ -846,19 +846,41 @@ static FwdArgs fwd_args(const tfr_model* m, const int32_t* du, const int32_t* di
     return a;
 }
 
-// forward on device-resident ids
+// which rows a forward scores from: the float32 tables, or their bf16 snapshot (bf16_rows.h)
+enum FwdRows { ROWS_F32, ROWS_BF16 };
+
+// TFR_BF16_PNT=0|1: A/B override of the non-temporal user rows (unset: the float32 forward's rule on the snapshot's bytes).
+// Read at every launch, so that one process can alternate the two (tools/bench_bf16_forward.py --pnt-ab).
+static bool bf16_pnt(const tfr_model* m) {
+    const char* e = getenv("TFR_BF16_PNT");
+    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
+    return stream_user_rows(m->U, (size_t)bf16_row_stride(m->D) * 2);
+}
+
+// forward on device-resident ids; from the snapshot: MODE_INFER or MODE_EVAL
 static int run_forward(tfr_model* m, int mode, const int32_t* du, const int32_t* di, const float* dr,
                        int64_t B, float* d_logits, float* d_g, int* nblk_out,
-                       const int64_t* d_store_ids = nullptr) {
-    { const int rcq = settle_q(m); if (rcq) return rcq; }
-    FwdArgs a = fwd_args(m, du, di, dr, B, d_logits, d_g, d_store_ids);
-    if (d_store_ids) { a.u_out = m->d_u; a.it_out = m->d_i; }     // the gathered ids, for the backward
-    { static int lr = -1; if (lr < 0) { const char* e = getenv("TFR_LDS_REDUCE"); lr = (e && e[0] == '1') ? 1 : 0; } a.lds_reduce = lr; }
-    const int grid = forward_grid(B, m->G, mode);
+                       const int64_t* d_store_ids = nullptr, FwdRows rows = ROWS_F32) {
+    if (rows == ROWS_F32) { const int rcq = settle_q(m); if (rcq) return rcq; }
+    const int G = rows == ROWS_F32 ? m->G : bf16_geometry(m->D);
+    const int grid = forward_grid(B, G, mode, rows == ROWS_F32 ? 4 : bf16_unroll(G));
     if (nblk_out) *nblk_out = grid;
-    {
+    if (rows == ROWS_F32) {
+        FwdArgs a = fwd_args(m, du, di, dr, B, d_logits, d_g, d_store_ids);
+        if (d_store_ids) { a.u_out = m->d_u; a.it_out = m->d_i; }     // the gathered ids, for the backward
+        { static int lr = -1; if (lr < 0) { const char* e = getenv("TFR_LDS_REDUCE"); lr = (e && e[0] == '1') ? 1 : 0; } a.lds_reduce = lr; }
         Prof p(m, TFR_K_FORWARD);
-        launch_forward(a, mode, m->G, m->VEC, grid, m->stream);
+        launch_forward(a, mode, G, m->VEC, grid, m->stream);
+    } else {
+        Bf16FwdArgs a;
+        memset(&a, 0, sizeof(a));
+        a.P = m->bf.p; a.Q = m->bf.q; a.bu = m->bf.bu; a.bi = m->bf.bi; a.mu = m->bf.mu;
+        a.u = du; a.it = di; a.r = dr;
+        a.logits = d_logits; a.partials = m->partials; a.err = m->d_err;
+        a.B = B; a.U = m->U; a.I = m->I;
+        a.DP = bf16_row_stride(m->D); a.loss = m->o.loss; a.item_abs = m->o.item_abs;
+        Prof p(m, TFR_K_FORWARD);
+        launch_forward_bf16(a, mode, G, grid, bf16_pnt(m), m->stream);
     }
     HIPCHK(hipGetLastError());
     return TFR_OK;
@@ -1366,23 +1388,34 @@ static int check_batch(const void* u, const void* i, int64_t B) {
     return TFR_OK;
 }
 
-extern "C" {
+// a host batch's three columns into d_u / d_i / d_r (the workspace holds B: ensure_capacity)
+static int upload_triples(tfr_model* m, const int32_t* u, const int32_t* i, const float* r, int64_t B) {
+    HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    HIPCHK(hipMemcpyAsync(m->d_r, r, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    return TFR_OK;
+}
+
+static int bf16_need_snapshot(const tfr_model* m) {
+    return m->bf.valid ? TFR_OK : fail(TFR_ERR_STATE, "no bf16 snapshot: call tfr_bf16_snapshot first");
+}
 
 // ---- forward ---------------------------------------------------------------------------
-int tfr_forward_dev(tfr_model* m, const int32_t* du, const int32_t* di, int64_t B, float* d_logits) {
-    MODEL_ENTER(m);
+// the bodies of tfr_forward_dev / tfr_forward and of their snapshot twins, which differ in `rows` and in the snapshot test
+static int forward_dev(tfr_model* m, FwdRows rows, const int32_t* du, const int32_t* di, int64_t B, float* d_logits) {
     int rc = check_batch(du, di, B);
     if (rc) return rc;
+    if (rows == ROWS_BF16 && (rc = bf16_need_snapshot(m))) return rc;
     if (B == 0) return TFR_OK;
     if (!d_logits) return fail(TFR_ERR_ARG, "null logits pointer");
     if ((rc = ensure_capacity(m, 1))) return rc;
-    return run_forward(m, MODE_INFER, du, di, nullptr, B, d_logits, nullptr, nullptr);
+    return run_forward(m, MODE_INFER, du, di, nullptr, B, d_logits, nullptr, nullptr, nullptr, rows);
 }
 
-int tfr_forward(tfr_model* m, const int32_t* u, const int32_t* i, int64_t B, float* logits_out) {
-    MODEL_ENTER(m);
+static int forward_host(tfr_model* m, FwdRows rows, const int32_t* u, const int32_t* i, int64_t B, float* logits_out) {
     int rc = check_batch(u, i, B);
     if (rc) return rc;
+    if (rows == ROWS_BF16 && (rc = bf16_need_snapshot(m))) return rc;
     if (B == 0) return TFR_OK;
     if (!logits_out) return fail(TFR_ERR_ARG, "null logits pointer");
     if ((rc = ensure_capacity(m, B))) return rc;
@@ -1391,7 +1424,7 @@ int tfr_forward(tfr_model* m, const int32_t* u, const int32_t* i, int64_t B, flo
         memcpy(m->h_in, u, (size_t)B * 4);
         memcpy(m->h_in + B, i, (size_t)B * 4);
         HIPCHK(hipMemcpyAsync(m->d_in, m->h_in, (size_t)2 * B * 4, hipMemcpyHostToDevice, m->stream));
-        if ((rc = run_forward(m, MODE_INFER, m->d_in, m->d_in + B, nullptr, B, m->d_logits, nullptr, nullptr))) return rc;
+        if ((rc = run_forward(m, MODE_INFER, m->d_in, m->d_in + B, nullptr, B, m->d_logits, nullptr, nullptr, nullptr, rows))) return rc;
         HIPCHK(hipMemcpyAsync(m->h_out, m->d_logits, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
         if ((rc = check_device_error(m))) return rc;
         memcpy(logits_out, m->h_out, (size_t)B * 4);
@@ -1399,9 +1432,21 @@ int tfr_forward(tfr_model* m, const int32_t* u, const int32_t* i, int64_t B, flo
     }
     HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    if ((rc = run_forward(m, MODE_INFER, m->d_u, m->d_i, nullptr, B, m->d_logits, nullptr, nullptr))) return rc;
+    if ((rc = run_forward(m, MODE_INFER, m->d_u, m->d_i, nullptr, B, m->d_logits, nullptr, nullptr, nullptr, rows))) return rc;
     HIPCHK(hipMemcpyAsync(logits_out, m->d_logits, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
     return check_device_error(m);
+}
+
+extern "C" {
+
+int tfr_forward_dev(tfr_model* m, const int32_t* du, const int32_t* di, int64_t B, float* d_logits) {
+    MODEL_ENTER(m);
+    return forward_dev(m, ROWS_F32, du, di, B, d_logits);
+}
+
+int tfr_forward(tfr_model* m, const int32_t* u, const int32_t* i, int64_t B, float* logits_out) {
+    MODEL_ENTER(m);
+    return forward_host(m, ROWS_F32, u, i, B, logits_out);
 }
 
 // rank-sum AUC of n device scores against device labels (> 0.5 = positive); NaN when a class is empty
@@ -1428,11 +1473,13 @@ static int auc_device(tfr_model* m, const float* d_score, const float* d_label, 
     return TFR_OK;
 }
 
+// the AUC needs the kept logits, which only the float32 rows' forward writes
 static int eval_device(tfr_model* m, const int32_t* du, const int32_t* di, const float* dr, int64_t B,
-                       double* sse_out, int64_t* neq_out, double* nll_out = nullptr, double* auc_out = nullptr) {
+                       double* sse_out, int64_t* neq_out, double* nll_out = nullptr, double* auc_out = nullptr,
+                       FwdRows rows = ROWS_F32) {
     int nblk = 0, rc;
     if (auc_out && (rc = ensure_capacity(m, B))) return rc;
-    if ((rc = run_forward(m, MODE_EVAL, du, di, dr, B, auc_out ? m->d_logits : nullptr, nullptr, &nblk))) return rc;
+    if ((rc = run_forward(m, MODE_EVAL, du, di, dr, B, auc_out ? m->d_logits : nullptr, nullptr, &nblk, nullptr, rows))) return rc;
     std::vector<float> part((size_t)nblk * 4);
     HIPCHK(hipMemcpyAsync(part.data(), m->partials, part.size() * 4, hipMemcpyDeviceToHost, m->stream));
     if ((rc = check_device_error(m))) return rc;
@@ -1460,9 +1507,7 @@ int tfr_eval(tfr_model* m, const int32_t* u, const int32_t* i, const float* r, i
     if (B == 0) return TFR_OK;
     if (!r) return fail(TFR_ERR_ARG, "null rate pointer");
     if ((rc = ensure_capacity(m, B))) return rc;
-    HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_r, r, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    if ((rc = upload_triples(m, u, i, r, B))) return rc;
     return eval_device(m, m->d_u, m->d_i, m->d_r, B, sse_out, neq_out);
 }
 
@@ -1504,74 +1549,14 @@ int tfr_bf16_drop(tfr_model* m) {
     return TFR_OK;
 }
 
-static int bf16_need_snapshot(const tfr_model* m) {
-    return m->bf.valid ? TFR_OK : fail(TFR_ERR_STATE, "no bf16 snapshot: call tfr_bf16_snapshot first");
-}
-
-// TFR_BF16_PNT=0|1: A/B override of the non-temporal user rows (unset: the float32 forward's rule on the snapshot's bytes).
-// Read at every launch, so that one process can alternate the two (tools/bench_bf16_forward.py --pnt-ab).
-static bool bf16_pnt(const tfr_model* m) {
-    const char* e = getenv("TFR_BF16_PNT");
-    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
-    return (size_t)m->U * bf16_row_stride(m->D) * 2 > ((size_t)256 << 20);
-}
-
-// run_forward on the snapshot: device-resident ids, MODE_INFER or MODE_EVAL
-static int run_forward_bf16(tfr_model* m, int mode, const int32_t* du, const int32_t* di, const float* dr,
-                            int64_t B, float* d_logits, int* nblk_out) {
-    Bf16FwdArgs a;
-    memset(&a, 0, sizeof(a));
-    a.P = m->bf.p; a.Q = m->bf.q; a.bu = m->bf.bu; a.bi = m->bf.bi; a.mu = m->bf.mu;
-    a.u = du; a.it = di; a.r = dr;
-    a.logits = d_logits; a.partials = m->partials; a.err = m->d_err;
-    a.B = B; a.U = m->U; a.I = m->I;
-    a.DP = bf16_row_stride(m->D); a.loss = m->o.loss; a.item_abs = m->o.item_abs;
-    const int G = bf16_geometry(m->D);
-    const int grid = bf16_forward_grid(B, G, mode);
-    if (nblk_out) *nblk_out = grid;
-    {
-        Prof p(m, TFR_K_FORWARD);
-        launch_forward_bf16(a, mode, G, grid, bf16_pnt(m), m->stream);
-    }
-    HIPCHK(hipGetLastError());
-    return TFR_OK;
-}
-
 int tfr_bf16_forward_dev(tfr_model* m, const int32_t* du, const int32_t* di, int64_t B, float* d_logits) {
     MODEL_ENTER(m);
-    int rc = check_batch(du, di, B);
-    if (rc) return rc;
-    if ((rc = bf16_need_snapshot(m))) return rc;
-    if (B == 0) return TFR_OK;
-    if (!d_logits) return fail(TFR_ERR_ARG, "null logits pointer");
-    if ((rc = ensure_capacity(m, 1))) return rc;
-    return run_forward_bf16(m, MODE_INFER, du, di, nullptr, B, d_logits, nullptr);
+    return forward_dev(m, ROWS_BF16, du, di, B, d_logits);
 }
 
 int tfr_bf16_forward(tfr_model* m, const int32_t* u, const int32_t* i, int64_t B, float* logits_out) {
     MODEL_ENTER(m);
-    int rc = check_batch(u, i, B);
-    if (rc) return rc;
-    if ((rc = bf16_need_snapshot(m))) return rc;
-    if (B == 0) return TFR_OK;
-    if (!logits_out) return fail(TFR_ERR_ARG, "null logits pointer");
-    if ((rc = ensure_capacity(m, B))) return rc;
-    if (B <= STAGE_MAX) {                                // pinned staging, as tfr_forward
-        if ((rc = ensure_staging(m, B))) return rc;
-        memcpy(m->h_in, u, (size_t)B * 4);
-        memcpy(m->h_in + B, i, (size_t)B * 4);
-        HIPCHK(hipMemcpyAsync(m->d_in, m->h_in, (size_t)2 * B * 4, hipMemcpyHostToDevice, m->stream));
-        if ((rc = run_forward_bf16(m, MODE_INFER, m->d_in, m->d_in + B, nullptr, B, m->d_logits, nullptr))) return rc;
-        HIPCHK(hipMemcpyAsync(m->h_out, m->d_logits, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
-        if ((rc = check_device_error(m))) return rc;
-        memcpy(logits_out, m->h_out, (size_t)B * 4);
-        return TFR_OK;
-    }
-    HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    if ((rc = run_forward_bf16(m, MODE_INFER, m->d_u, m->d_i, nullptr, B, m->d_logits, nullptr))) return rc;
-    HIPCHK(hipMemcpyAsync(logits_out, m->d_logits, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
-    return check_device_error(m);
+    return forward_host(m, ROWS_BF16, u, i, B, logits_out);
 }
 
 int tfr_bf16_eval(tfr_model* m, const int32_t* u, const int32_t* i, const float* r, int64_t B,
@@ -1586,26 +1571,8 @@ int tfr_bf16_eval(tfr_model* m, const int32_t* u, const int32_t* i, const float*
     if (B == 0) return TFR_OK;
     if (!r) return fail(TFR_ERR_ARG, "null rate pointer");
     if ((rc = ensure_capacity(m, B))) return rc;
-    HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_r, r, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    int nblk = 0;
-    if ((rc = run_forward_bf16(m, MODE_EVAL, m->d_u, m->d_i, m->d_r, B, nullptr, &nblk))) return rc;
-    // the per-block partials are added as eval_device adds them
-    std::vector<float> part((size_t)nblk * 4);
-    HIPCHK(hipMemcpyAsync(part.data(), m->partials, part.size() * 4, hipMemcpyDeviceToHost, m->stream));
-    if ((rc = check_device_error(m))) return rc;
-    double sse = 0.0, nll = 0.0;
-    int64_t neq = 0;
-    for (int b = 0; b < nblk; ++b) {
-        sse += (double)part[(size_t)b * 4 + 0];
-        neq += (int64_t)llround((double)part[(size_t)b * 4 + 1]);
-        nll += (double)part[(size_t)b * 4 + 2];
-    }
-    if (sse_out) *sse_out = sse;
-    if (neq_out) *neq_out = neq;
-    if (nll_out) *nll_out = nll;
-    return TFR_OK;
+    if ((rc = upload_triples(m, u, i, r, B))) return rc;
+    return eval_device(m, m->d_u, m->d_i, m->d_r, B, sse_out, neq_out, nll_out, nullptr, ROWS_BF16);
 }
 
 int tfr_bf16_get_rows(tfr_model* m, int32_t which, uint16_t* host, int64_t n) {
@@ -1648,9 +1615,7 @@ int tfr_eval_binary(tfr_model* m, const int32_t* u, const int32_t* i, const floa
     if (!r) return fail(TFR_ERR_ARG, "null rate pointer");
     if (m->o.loss != TFR_LOSS_NLL) return fail(TFR_ERR_STATE, "eval_binary needs the binary-outcome model (loss = nll)");
     if ((rc = ensure_capacity(m, B))) return rc;
-    HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_r, r, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    if ((rc = upload_triples(m, u, i, r, B))) return rc;
     // (the AUC reuses d_i as key scratch - after the forward, in stream order, has read the ids)
     return eval_device(m, m->d_u, m->d_i, m->d_r, B, nullptr, neq_out, nll_sum_out, auc_out);
 }
@@ -1720,11 +1685,7 @@ int tfr_train_step(tfr_model* m, const int32_t* u, const int32_t* i, const float
         sc[0] = m->h_out[nl]; sc[1] = m->h_out[nl + 1];
         m->last_r = logits_out ? reinterpret_cast<const float*>(m->d_in + 2 * B) : nullptr; m->last_B = B;
     } else {
-        if (B > 0) {
-            HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-            HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-            HIPCHK(hipMemcpyAsync(m->d_r, r, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-        }
+        if (B > 0 && (rc = upload_triples(m, u, i, r, B))) return rc;
         if ((rc = run_train_step(m, m->d_u, m->d_i, m->d_r, B, logits_out ? m->d_logits : nullptr, nullptr))) return rc;
         if (logits_out && B > 0)
             HIPCHK(hipMemcpyAsync(logits_out, m->d_logits, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
@@ -1752,9 +1713,7 @@ int tfr_train_steps_repeat(tfr_model* m, const int32_t* u, const int32_t* i, con
     if (loss_out) HIPCHK(m->step_out.reserve((int64_t)nsteps * 4, m->stream));
     const StepMark mark = mark_step(m);
     m->last_r = nullptr;
-    HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
-    HIPCHK(hipMemcpyAsync(m->d_r, r, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
+    if ((rc = upload_triples(m, u, i, r, B))) return rc;
     for (int32_t s = 0; s < nsteps; ++s) {
         const bool last = s + 1 == nsteps;
         if ((rc = run_train_step(m, m->d_u, m->d_i, m->d_r, B, (last && logits_out) ? m->d_logits : nullptr,

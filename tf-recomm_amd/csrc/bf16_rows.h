@@ -39,9 +39,7 @@ struct Bf16FwdArgs {
     int32_t DP, loss, item_abs;
 };
 
-// forward_grid's rule (svd_kernels.hip) at this geometry's ratings per block: 8192 blocks for INFER, 2048 for EVAL
-int bf16_forward_grid(int64_t B, int G, int mode);
-// mode: MODE_INFER or MODE_EVAL; pnt: user rows by non-temporal loads
+// mode: MODE_INFER or MODE_EVAL; grid: forward_grid at bf16_unroll(G); pnt: user rows by non-temporal loads
 void launch_forward_bf16(const Bf16FwdArgs& a, int mode, int G, int grid, bool pnt, hipStream_t s);
 // float32 [rows, D] -> bf16 [rows, DP], pads included
 void launch_rows_to_bf16(const float* src, uint16_t* dst, int64_t rows, int D, hipStream_t s);

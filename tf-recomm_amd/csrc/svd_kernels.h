@@ -285,7 +285,10 @@ inline bool geometry(int D, int* G, int* VEC) {
     return true;
 }
 
-int forward_grid(int64_t B, int G, int mode);
+// blocks of a forward launch: 8192 for INFER, 2048 otherwise, then grid-stride; unr = ratings in flight per lane group
+int forward_grid(int64_t B, int G, int mode, int unr = 4);
+// INFER / EVAL read the user rows by non-temporal loads when the user table cannot stay in the 256 MB Infinity Cache anyway
+inline bool stream_user_rows(int64_t U, size_t row_bytes) { return (size_t)U * row_bytes > ((size_t)256 << 20); }
 void launch_forward(const FwdArgs& a, int mode, int G, int VEC, int grid, hipStream_t s);
 int front_forward_blocks(int64_t B, int G);
 void launch_front(const FrontArgs& fa, int G, int VEC, hipStream_t s);

@@ -7,41 +7,19 @@
 // 512 B).  D % 4 == 0 -> VEC=4 (global_load_dwordx4); otherwise VEC=1 (rows are then not
 // 16-byte aligned; correctness path for the reference's dim=5/15).
 //
-// Reference semantics restated per kernel; file:line into the reference tree.
+// Reference semantics restated per kernel; file:line into the reference tree.  The row fragment, the group / wave /
+// block sums and K1 itself, the gather-dot forward, are in forward_body.h, which the bf16 snapshot's forward
+// (bf16_rows.hip) shares; k_forward and k_front instantiate it on float32 rows.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <stdint.h>
 #include "svd_kernels.h"
+#include "forward_body.h"
 #include "finalize.inc.h"
 
 namespace tfr {
 
 // ------------------------------------------------------------------------------------
-template <int VEC> struct Frag { float v[VEC]; };
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-// NT: non-temporal (streaming) load - rows that are read once should not displace the
-// small, re-used tables (biases, ids) from L2 / Infinity Cache.
-template <int VEC, bool NT = false>
-__device__ __forceinline__ Frag<VEC> load_frag(const float* __restrict__ row, int d0, int D) {
-    Frag<VEC> f;
-    if constexpr (VEC == 4) {
-        if (d0 < D) {
-            floatx4 t;
-            if constexpr (NT) t = __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(row + d0));
-            else t = *reinterpret_cast<const floatx4*>(row + d0);
-            f.v[0] = t.x; f.v[1] = t.y; f.v[2] = t.z; f.v[3] = t.w;
-        } else {
-            f.v[0] = f.v[1] = f.v[2] = f.v[3] = 0.f;
-        }
-    } else {
-        if constexpr (NT) f.v[0] = (d0 < D) ? __builtin_nontemporal_load(row + d0) : 0.f;
-        else f.v[0] = (d0 < D) ? row[d0] : 0.f;
-    }
-    return f;
-}
-
 template <int VEC>
 __device__ __forceinline__ void store_frag(float* __restrict__ row, int d0, int D, const Frag<VEC>& f) {
     if (d0 < D) {
@@ -138,60 +116,6 @@ __device__ __forceinline__ Frag<VEC> buf_load_frag(__amdgpu_buffer_rsrc_t r, int
     return f;
 }
 
-template <int G>
-__device__ __forceinline__ float group_sum(float x) {
-    // butterfly over the G lanes of a group (G is a power of two <= 64); every lane of the
-    // group ends with the same sum, in a fixed order -> deterministic.
-#pragma unroll
-    for (int o = G / 2; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
-// The same reduction staged through LDS memory instead of the cross-lane network: every lane
-// parks its partial in LDS, the group's first lane reads the G values back as 16-byte vectors and
-// adds them in lane order.  Kept for the A/B recorded in DESIGN.md (the butterfly is the default).
-template <int G>
-__device__ __forceinline__ float group_sum_lds(float x, float* wave_slot /* 64 floats of this wave */, int lane) {
-    wave_slot[lane] = x;
-    __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0): the wave's own LDS writes have landed
-    const int g0 = lane & ~(G - 1);
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < G; q += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(wave_slot + g0 + q);
-        s += (v.x + v.y) + (v.z + v.w);
-    }
-    return s;
-}
-
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x += __shfl_down(x, o, 64);
-    return x;   // valid in lane 0
-}
-
-// block-level sum of NV values per thread -> out[NV] written by thread 0.  NW waves per block.
-template <int NV, int NW>
-__device__ __forceinline__ void block_sum_store(float (&val)[NV], float* out) {
-    __shared__ float red[NW][NV];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int c = 0; c < NV; ++c) {
-        const float s = wave_sum(val[c]);
-        if (lane == 0) red[wave][c] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int c = 0; c < NV; ++c) {
-            float t = 0.f;
-#pragma unroll
-            for (int w = 0; w < NW; w += 4) t += (red[w][c] + red[w + 1][c]) + (red[w + 2][c] + red[w + 3][c]);
-            out[c] = t;
-        }
-    }
-}
-
 // per-piece {loss, reg, sum g} for k_tile_step without a cross-lane reduction in every wave: lane
 // group leaders park the entry's loss and g, every lane its share of the regulariser, in LDS;
 // after the barrier wave (h, c) alone adds piece h's values of kind c in a fixed order.
@@ -226,200 +150,14 @@ __device__ __forceinline__ void block_sum_pieces(const float (&val)[3 * EPG], fl
 }
 
 // ------------------------------------------------------------------------------------
-// K1  gather-dot forward (ops.py:13-14,37-38 embedding_lookup x4; ops.py:44-47 dot + biases)
-//     MODE_INFER: logits only                          (svd_train_val.py:120-122)
-//     MODE_TRAIN: + g = dcost/dlogit, per-block partial {data loss, regulariser, sum g}
-//                 (ops.py:81-89 regulariser over gathered rows; ops.py:124 / 125-126 loss)
-//     MODE_EVAL : per-block partial {sum (infer-rate)^2, count infer==rate}
-//                 (svd_train_val.py:144-149)
-// A lane group owns one rating at a time; UNR ratings are in flight per group so each
-// lane has 2*UNR independent 16-byte loads outstanding.
-// Bias gathers take the SCALAR path where a wave holds few ratings (SPW <= 4, i.e. D >= 64): the ids come
-// out of the lanes by v_readlane and the 4-byte loads go through the scalar cache, so they do not queue
-// behind the row gathers in the vector memory pipeline.  Measured on the north-star shape
-// (tools/probes/fwd_shape.hip): per-group vector loads 45.6 us, scalar 42.9 us per 262144 ratings.  The
-// arrays are read-only for the whole launch (constant address space = s_load).  Narrow rows (SPW >= 8) use
-// one wave-wide vector load per table instead: lane j fetches the bias of the wave's j-th rating.
-typedef const float __attribute__((address_space(4))) * cfloat_p;
-
-template <int G, int VEC, int MODE, int UNR, int NW, bool PNT = false>
-__device__ __forceinline__ void forward_body(const FwdArgs& a, int block, int nblocks) {
-    constexpr int SPW = 64 / G;        // ratings per wave per pass; UNR passes in flight
-    constexpr bool SBIAS = SPW <= 4;
-    constexpr int SPI = SPW * UNR;     // ratings per wave-iteration
-    const int lane = threadIdx.x & 63;
-    const int sub = lane / G;
-    const int gl = lane % G;
-    const int d0 = gl * VEC;
-    const int D = a.D;
-    // batch positions fit 32 bits (the workspace caps a batch at 2^30 ratings)
-    const int Bn = a.dB ? *a.dB : (int)a.B;             // row-sharded step: the local batch size lives on the device
-    const size_t qs = a.qstride ? (size_t)a.qstride : (size_t)a.D;      // item rows may sit in a packed exchange buffer
-    const int bis = a.bistride ? a.bistride : 1;
-    const int wave_id = block * NW + (threadIdx.x >> 6);
-    const int stride = nblocks * NW * SPI;
-    const float mu = *a.mu;
-
-    float acc[3] = {0.f, 0.f, 0.f};    // TRAIN: loss, reg, sum g | EVAL: sse, n_equal, -
-    bool oob = false, oob_store = false;
-
-    // TRAIN (few, fat blocks: k_front, the sharded step): the ids of iteration n+1 are fetched while the rows
-    // of iteration n are in flight, so the only exposed round trip per iteration is the row gather itself.
-    // INFER / EVAL fetch them at the top of the iteration instead: without the second id set the kernel fits
-    // 64 VGPRs = 8 waves per SIMD, and the extra waves hide that round trip better than the prefetch did
-    // (north-star shape, one 262144-rating batch per launch: 51.0 -> 43.4 us together with the scalar-path
-    // bias loads and the non-temporal user rows; holding the kernel to 80 SGPRs for an eighth wave per SIMD
-    // changed nothing - gpurun_out/ns_s80_*.json; tools/probes/fwd_shape.hip).
-    constexpr bool PF = MODE == MODE_TRAIN;
-    int32_t u_n[UNR], it_n[UNR];
-    float rr_n[UNR];
-    auto fetch_ids = [&](int base) {
-        if (a.ids) {
-            // fused ShuffleIterator gather (dataio.py:115-117): id -> (user, item, rate) from the
-            // HBM-resident store
-            int64_t id[UNR];
-#pragma unroll
-            for (int j = 0; j < UNR; ++j) {
-                const int k = base + j * SPW + sub;
-                id[j] = (k < Bn) ? a.ids[k] : 0;
-                if ((uint64_t)id[j] >= (uint64_t)a.N) { oob_store = true; id[j] = 0; }
-            }
-#pragma unroll
-            for (int j = 0; j < UNR; ++j) {
-                const int4 rec = a.store[id[j]];          // one 16-byte record: {user, item, rate bits, -}
-                u_n[j] = rec.x;
-                it_n[j] = rec.y;
-                rr_n[j] = __int_as_float(rec.z);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < UNR; ++j) {
-                const int k = base + j * SPW + sub;
-                const bool ok = k < Bn;
-                u_n[j] = ok ? a.u[k] : 0;
-                it_n[j] = ok ? a.it[k] : 0;
-                rr_n[j] = (MODE != MODE_INFER && ok) ? a.r[k] : 0.f;
-            }
-        }
-    };
-
-    int base = wave_id * SPI;
-    if (PF && base < Bn) fetch_ids(base);
-    for (; base < Bn; base += stride) {
-        if (!PF) fetch_ids(base);
-        int k[UNR];
-        int32_t u[UNR], it[UNR];
-        bool ok[UNR];
-        float rr[UNR];
-#pragma unroll
-        for (int j = 0; j < UNR; ++j) {
-            k[j] = base + j * SPW + sub;
-            ok[j] = k[j] < Bn;
-            u[j] = u_n[j]; it[j] = it_n[j]; rr[j] = rr_n[j];
-            if (a.ids && a.u_out && gl == 0 && ok[j]) { a.u_out[k[j]] = u[j]; a.it_out[k[j]] = it[j]; }   // kept for the backward
-            if ((uint64_t)(int64_t)u[j] >= (uint64_t)a.U) { oob = true; u[j] = 0; }
-            if ((uint64_t)(int64_t)it[j] >= (uint64_t)a.I) { oob = true; it[j] = 0; }
-        }
-        Frag<VEC> p[UNR], q[UNR];
-        float bu_[UNR], bi_[UNR];
-#pragma unroll
-        for (int j = 0; j < UNR; ++j) {
-            p[j] = load_frag<VEC, PNT>(a.P + (size_t)u[j] * D, d0, D);
-            q[j] = load_frag<VEC>(a.Q + (size_t)it[j] * qs, d0, D);
-        }
-        if constexpr (SBIAS) {
-            const cfloat_p cbu = (cfloat_p)(uintptr_t)a.bu;
-            const cfloat_p cbi = (cfloat_p)(uintptr_t)a.bi;
-#pragma unroll
-            for (int j = 0; j < UNR; ++j) {
-                float xs[SPW], ys[SPW];
-#pragma unroll
-                for (int s2 = 0; s2 < SPW; ++s2) {
-                    xs[s2] = cbu[__builtin_amdgcn_readlane(u[j], s2 * G)];
-                    ys[s2] = cbi[(size_t)__builtin_amdgcn_readlane(it[j], s2 * G) * bis];
-                }
-                bu_[j] = xs[0]; bi_[j] = ys[0];
-#pragma unroll
-                for (int s2 = 1; s2 < SPW; ++s2) { if (sub == s2) { bu_[j] = xs[s2]; bi_[j] = ys[s2]; } }
-            }
-        } else {
-            // lane l = j * SPW + s holds rating (j, s) of this iteration (SPI <= 64 ratings): one load per table
-            int32_t mu_ = 0, mi_ = 0;
-#pragma unroll
-            for (int j = 0; j < UNR; ++j) {
-                const int src = ((lane - j * SPW) & (SPW - 1)) * G;
-                const int32_t su = __shfl(u[j], src, 64), si = __shfl(it[j], src, 64);
-                if (lane / SPW == j) { mu_ = su; mi_ = si; }
-            }
-            float wx = 0.f, wy = 0.f;
-            if (lane < SPI) { wx = a.bu[mu_]; wy = a.bi[(size_t)mi_ * bis]; }
-#pragma unroll
-            for (int j = 0; j < UNR; ++j) { bu_[j] = __shfl(wx, j * SPW + sub, 64); bi_[j] = __shfl(wy, j * SPW + sub, 64); }
-        }
-        if (PF && base + stride < Bn) fetch_ids(base + stride);      // next iteration's ids, behind the rows
-#pragma unroll
-        for (int j = 0; j < UNR; ++j) {
-            float s = 0.f, sq = 0.f;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) {
-                const float qv = q[j].v[e];
-                s = fmaf(p[j].v[e], a.item_abs ? fabsf(qv) : qv, s);
-                if constexpr (MODE == MODE_TRAIN) sq = fmaf(p[j].v[e], p[j].v[e], fmaf(qv, qv, sq));
-            }
-            if (a.lds_reduce) {
-                __shared__ float stage[NW][64];
-                s = group_sum_lds<G>(s, stage[threadIdx.x >> 6], lane);
-            } else {
-                s = group_sum<G>(s);
-            }
-            const float logit = ((s + mu) + bu_[j]) + bi_[j];      // ops.py:45-47 order
-            if (gl == 0 && ok[j]) {
-                if constexpr (MODE == MODE_INFER) {
-                    a.logits[k[j]] = logit;
-                } else if constexpr (MODE == MODE_TRAIN) {
-                    if (a.logits) a.logits[k[j]] = logit;
-                    const float r = rr[j];
-                    float g, l;
-                    if (a.loss == 0) {                 // ops.py:124  l2_loss(infer - rate)
-                        g = logit - r;
-                        l = 0.5f * g * g;
-                    } else {                           // ops.py:125-126 sigmoid cross-entropy
-                        g = sigmoidf_(logit) - r;
-                        l = fmaxf(logit, 0.f) - logit * r + log1pf(__expf(-fabsf(logit)));
-                    }
-                    a.g[k[j]] = g;
-                    acc[0] += l;
-                    acc[2] += g;
-                    if (a.reg_bias) sq = fmaf(bu_[j], bu_[j], fmaf(bi_[j], bi_[j], sq));
-                } else {
-                    const float r = rr[j];
-                    float inf = logit;                 // canonical infer = logits (README.md:33)
-                    if (a.loss != 0) inf = binary_infer(logit);       // ops.py:77-78, half-to-even
-                    const float d = inf - r;
-                    acc[0] += d * d;
-                    acc[1] += (inf == r) ? 1.f : 0.f;
-                    // svd_train_val.py:94,170-178: the epoch line's mean NLL (ops.py:125-126 on the fed logits)
-                    if (a.loss != 0) acc[2] += sigmoid_xent(logit, r);
-                    if (a.logits) a.logits[k[j]] = logit;                // kept for the AUC (rank sum over the sorted logits)
-                }
-            }
-            if constexpr (MODE == MODE_TRAIN) {
-                if (ok[j]) acc[1] += 0.5f * sq;        // tf.nn.l2_loss = sum(x^2)/2
-            }
-        }
-    }
-    if (oob) atomicOr(a.err, 1);
-    if (oob_store) atomicOr(a.err, 2);
-    if constexpr (MODE != MODE_INFER) block_sum_store<3, NW>(acc, a.partials + (size_t)block * 4);
-}
-
+// K1 on float32 rows (forward_body.h).
 // PNT: user rows by non-temporal loads - set when the user table cannot stay in the 256 MB Infinity Cache
-// anyway, so that it does not evict the item rows and the bias arrays, which can
+// anyway (stream_user_rows), so that it does not evict the item rows and the bias arrays, which can
 // (tools/probes/fwd_policy.hip: 48.3 -> 46.0 us per 262144 ratings at 10M x 1M rows)
 template <int G, int VEC, int MODE, int UNR, bool PNT>
 __global__ __launch_bounds__(256) void k_forward(FwdArgs a) {
     warm_args(a);
-    forward_body<G, VEC, MODE, UNR, 4, PNT>(a, blockIdx.x, gridDim.x);
+    forward_body<Float32Rows<VEC>, G, MODE, UNR, 4, PNT>(a, blockIdx.x, gridDim.x);
 }
 // In-LDS exclusive scan of a tile's nb bin counts into the packed form (count << 16) | start.
 // Thread t owns bins t, t + 1024, ... (bank-conflict free) and those bins are CONSECUTIVE in the
@@ -456,7 +194,7 @@ template <int G, int VEC>
 __global__ __launch_bounds__(1024) void k_front(FrontArgs fa) {
     warm_args(fa);
     if ((int)blockIdx.x < fa.nfwd) {
-        forward_body<G, VEC, MODE_TRAIN, 2, 16>(fa.f, blockIdx.x, fa.nfwd);
+        forward_body<Float32Rows<VEC>, G, MODE_TRAIN, 2, 16>(fa.f, blockIdx.x, fa.nfwd);
         return;
     }
     extern __shared__ int32_t cnt[];
@@ -2067,7 +1805,7 @@ __global__ void k_init_uniform_scalar(float* p, float lo, float hi, uint64_t see
 // launch helpers
 template <int MODE, int UNR>
 static void launch_forward_mode(const FwdArgs& a, int G, int VEC, int grid, hipStream_t s) {
-    const bool pnt = MODE != MODE_TRAIN && (size_t)a.U * a.D * 4 > ((size_t)256 << 20);
+    const bool pnt = MODE != MODE_TRAIN && stream_user_rows(a.U, (size_t)a.D * 4);
 #define TFR_FWD_CASE(g, v) \
     if (G == g && VEC == v) {                                                                                  \
         if (pnt) hipLaunchKernelGGL((k_forward<g, v, MODE, UNR, true>), dim3(grid), dim3(256), 0, s, a);       \
@@ -2079,8 +1817,8 @@ static void launch_forward_mode(const FwdArgs& a, int G, int VEC, int grid, hipS
 #undef TFR_FWD_CASE
 }
 
-int forward_grid(int64_t B, int G, int mode) {
-    const int64_t per_block = 4 * (64 / G) * 4;   // waves * SPW * UNR
+int forward_grid(int64_t B, int G, int mode, int unr) {
+    const int64_t per_block = 4 * (64 / G) * unr;   // waves * SPW * UNR
     int64_t nb = (B + per_block - 1) / per_block;
     const int64_t cap = (mode == MODE_INFER) ? 8192 : 2048;   // TRAIN/EVAL: fewer partials for K4
     if (nb > cap) nb = cap;                              // then grid-stride
