@@ -673,6 +673,13 @@ int tfr_profile(tfr_model* m, int32_t enable);                 /* enable resets 
  * size, spelled as rocprofv3 prints them (what the slots above time) */
 int tfr_kernel_plan(tfr_model* m, int64_t batch, char* buf, int64_t buflen);
 int tfr_profile_read(tfr_model* m, int32_t kernel, double* total_ms, int64_t* launches);
+/* "k_forward<G, VEC, MODE, 4, PNT>;grid=N" or "k_forward_bf16<G, MODE, UNR, PNT>;grid=N": the gather-dot forward that
+ * tfr_forward / tfr_eval (rows 0: float32) or tfr_bf16_forward / tfr_bf16_eval (rows 1: bf16 snapshot) launch for a model of
+ * this dim and user_num at this batch, spelled as rocprofv3 prints it, and its blocks.  mode: 0 INFER, 1 TRAIN, 2 EVAL.  PNT:
+ * the user rows are read by non-temporal loads (a user table above 256 MB; TFR_BF16_PNT=0|1 overrides it for the snapshot).
+ * Computed on the host by the functions the launch itself uses (no model, no device).  TFR_ERR_ARG: unsupported dim, TRAIN on
+ * snapshot rows, a buffer too short for the text. */
+int tfr_forward_plan(int32_t dim, int64_t user_num, int32_t mode, int32_t rows, int64_t batch, char* buf, int64_t buflen);
 
 /* LDS budget guard: static + dynamic LDS bytes per workgroup that the dispatcher requests for a shape, computed
  * on the host exactly as the launchers compute it (no device needed).  kernel: 0 k_tile_step, 1 k_seg_reduce with

@@ -92,13 +92,59 @@ def test_fm_step_reaches_every_geometry_at_full_and_partial_width():
     _check("FM_STEP", shard_class, W.FM_STEP, reachable)
 
 
+def bf16_class(D):
+    """(lanes per rating G, the group is wider than the row): k_forward_bf16<G, ...> is picked by G = the smallest power of
+    two >= DP / 8, DP = 8 * ceil(D / 8) (csrc/bf16_rows.h bf16_geometry); where G * 8 > DP the lanes past DP / 8 have no
+    fragment and Bf16Rows::load aims them at the row's first one (csrc/bf16_rows.hip)"""
+    from tests import bf16_cases
+    g = bf16_cases.lanes(D)
+    return g, g * 8 > bf16_cases.row_stride(D)
+
+
+def test_forward_pnt_reaches_every_geometry_at_full_and_partial_width():
+    """launch_forward_mode picks k_forward<G, VEC, MODE, 4, PNT> by geometry(D) and forward_pnt (csrc/svd_kernels.hip);
+    load_frag<VEC, true> guards its non-temporal load by d0 < D, which is false for some lane only below full width"""
+    reachable = {shard_class(D) for D in SUPPORTED}
+    assert len(reachable) == 15
+    _check("FORWARD_PNT", shard_class, W.FORWARD_PNT, reachable)
+
+
+def test_bf16_pnt_reaches_every_lane_count_with_and_without_spare_lanes():
+    reachable = {bf16_class(D) for D in SUPPORTED}
+    assert {g for g, _ in reachable} == {1, 2, 4, 8, 16, 32} and len(reachable) == 10
+    assert bf16_class(100) == (16, True)                    # the example of csrc/bf16_rows.hip: lanes 13..15
+    _check("BF16_PNT", bf16_class, W.BF16_PNT, reachable)
+
+
+def test_listed_pnt_widths_take_the_non_temporal_kernels_at_the_tests_table_size(monkeypatch):
+    """tfr_forward_plan answers by the functions the launch calls (csrc/api.hip forward_plan): at the U the GPU tests build,
+    every listed width reports PNT = true for INFER and EVAL, and one row fewer reports false; TRAIN never streams"""
+    from tests import forward_cases as F
+    monkeypatch.delenv("TFR_BF16_PNT", raising=False)         # the snapshot's A/B override would answer instead of the rule
+    seen = set()
+    for rows, listed in ((F.F32, W.FORWARD_PNT), (F.BF16, W.BF16_PNT)):
+        for D in listed:
+            U = F.pnt_rows(D, F.row_bytes(D, rows))
+            for mode in (F.INFER, F.EVAL):
+                name, args, _ = F.plan(D, U, mode, rows)
+                assert args[-1] is True, (D, U, mode, rows, name, args)
+                assert F.plan(D, U - 1, mode, rows)[1] == args[:-1] + (False,), (D, U - 1, mode, rows)
+                seen.add((name, args))
+        if rows == F.F32:
+            assert all(F.plan(D, F.pnt_rows(D, 4 * D), F.TRAIN, rows)[1][-1] is False for D in listed)
+    # every PNT instantiation the library compiles: ten geometries and six lane counts, INFER and EVAL
+    assert len({a for n, a in seen if n == "k_forward"}) == 20 and len({a for n, a in seen if n == "k_forward_bf16"}) == 12
+
+
 def test_the_gpu_tests_take_their_widths_from_these_lists():
     """a width list only guards what runs at it: the BPR, sharded, data-parallel and FM step GPU tests parametrise over these"""
     import ast
     import os
     here = os.path.dirname(os.path.abspath(__file__))
     for fname, name in (("test_gpu_bpr.py", "BPR"), ("shard_cases.py", "SHARD"), ("shard_cases.py", "DP"),
-                        ("fm_cases.py", "FM_STEP"), ("test_gpu_fm.py", "FM_STEP")):
+                        ("fm_cases.py", "FM_STEP"), ("test_gpu_fm.py", "FM_STEP"),
+                        ("test_gpu_forward_paths.py", "FORWARD_PNT"), ("test_gpu_forward_paths.py", "BF16_PNT"),
+                        ("test_forward_paths_host.py", "FORWARD_PNT"), ("test_forward_paths_host.py", "BF16_PNT")):
         tree = ast.parse(open(os.path.join(here, fname)).read())
         used = {n.attr for n in ast.walk(tree) if isinstance(n, ast.Attribute) and isinstance(n.value, ast.Name) and n.value.id == "W"}
         assert name in used, "%s does not read widths.%s" % (fname, name)

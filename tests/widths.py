@@ -19,6 +19,12 @@ DP = (8, 24, 48, 96, 200, 2, 6, 11, 25, 50)
 # the FM step per row (tests/test_gpu_fm_step.py) and the FM forward's load forms: the same fifteen classes - k_fm_forward
 # takes unguarded loads at full width, and the FM backward the reduce's three-round load form
 FM_STEP = (12, 16, 28, 32, 36, 64, 100, 128, 252, 256, 3, 7, 13, 31, 61)
+# the forward's non-temporal user-row loads (tests/test_gpu_forward_paths.py): k_forward<G, VEC, MODE, 4, true> on a user
+# table above 256 MB, the same fifteen classes - load_frag<VEC, true> has lanes with d0 >= D at partial width only.
+# k_forward_bf16<G, MODE, UNR, true>: the lanes per rating of the snapshot crossed with a group wider than the row
+# (G * 8 > DP), whose spare lanes take the redirected load
+FORWARD_PNT = (12, 16, 28, 32, 36, 64, 100, 128, 252, 256, 3, 7, 13, 31, 61)
+BF16_PNT = (5, 13, 17, 31, 33, 61, 100, 128, 132, 256)
 
 # SVD++ kernels and batched fine-tuning: NJ = ceil(D / 64) registers per lane, the last one full or partial
 SVDPP = (33, 64, 100, 128, 132, 192, 252, 256)

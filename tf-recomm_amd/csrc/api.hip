@@ -851,10 +851,22 @@ enum FwdRows { ROWS_F32, ROWS_BF16 };
 
 // TFR_BF16_PNT=0|1: A/B override of the non-temporal user rows (unset: the float32 forward's rule on the snapshot's bytes).
 // Read at every launch, so that one process can alternate the two (tools/bench_bf16_forward.py --pnt-ab).
-static bool bf16_pnt(const tfr_model* m) {
+static bool bf16_pnt(int64_t U, int D) {
     const char* e = getenv("TFR_BF16_PNT");
     if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
-    return stream_user_rows(m->U, (size_t)bf16_row_stride(m->D) * 2);
+    return stream_user_rows(U, (size_t)bf16_row_stride(D) * 2);
+}
+
+// what a forward launches for a shape: lanes per rating, ratings in flight per lane group, blocks, and whether the user
+// rows go by non-temporal loads.  run_forward launches by it and tfr_forward_plan reports it.
+struct FwdPlan { int G, unr, grid; bool pnt; };
+static FwdPlan forward_plan(int D, int G_f32, int64_t U, int mode, FwdRows rows, int64_t B) {
+    FwdPlan p;
+    p.G = rows == ROWS_F32 ? G_f32 : bf16_geometry(D);
+    p.unr = rows == ROWS_F32 ? 4 : bf16_unroll(p.G);
+    p.grid = forward_grid(B, p.G, mode, p.unr);
+    p.pnt = rows == ROWS_F32 ? forward_pnt(mode, U, D) : bf16_pnt(U, D);     // float32: launch_forward asks forward_pnt itself
+    return p;
 }
 
 // forward on device-resident ids; from the snapshot: MODE_INFER or MODE_EVAL
@@ -862,8 +874,8 @@ static int run_forward(tfr_model* m, int mode, const int32_t* du, const int32_t*
                        int64_t B, float* d_logits, float* d_g, int* nblk_out,
                        const int64_t* d_store_ids = nullptr, FwdRows rows = ROWS_F32) {
     if (rows == ROWS_F32) { const int rcq = settle_q(m); if (rcq) return rcq; }
-    const int G = rows == ROWS_F32 ? m->G : bf16_geometry(m->D);
-    const int grid = forward_grid(B, G, mode, rows == ROWS_F32 ? 4 : bf16_unroll(G));
+    const FwdPlan fp = forward_plan(m->D, m->G, m->U, mode, rows, B);
+    const int G = fp.G, grid = fp.grid;
     if (nblk_out) *nblk_out = grid;
     if (rows == ROWS_F32) {
         FwdArgs a = fwd_args(m, du, di, dr, B, d_logits, d_g, d_store_ids);
@@ -880,7 +892,7 @@ static int run_forward(tfr_model* m, int mode, const int32_t* du, const int32_t*
         a.B = B; a.U = m->U; a.I = m->I;
         a.DP = bf16_row_stride(m->D); a.loss = m->o.loss; a.item_abs = m->o.item_abs;
         Prof p(m, TFR_K_FORWARD);
-        launch_forward_bf16(a, mode, G, grid, bf16_pnt(m), m->stream);
+        launch_forward_bf16(a, mode, G, grid, fp.pnt, m->stream);
     }
     HIPCHK(hipGetLastError());
     return TFR_OK;
@@ -2368,6 +2380,25 @@ int tfr_kernel_plan(tfr_model* m, int64_t B, char* buf, int64_t buflen) {
                  G, V, G, V, G, V);
     }
     snprintf(buf, (size_t)buflen, "%s", tmp);
+    return TFR_OK;
+}
+
+// which forward instantiation a shape launches and on how many blocks, by the functions run_forward launches by.
+// Needs no model and no device: tests/test_width_coverage.py and tests/test_forward_paths_host.py read it.
+int tfr_forward_plan(int32_t dim, int64_t user_num, int32_t mode, int32_t rows, int64_t batch, char* buf, int64_t buflen) {
+    int G, VEC;
+    if (!geometry(dim, &G, &VEC)) return fail(TFR_ERR_ARG, "unsupported dim %d", dim);
+    if (user_num < 1 || user_num > 0x7fffffffLL || batch < 0) return fail(TFR_ERR_ARG, "forward_plan: need user_num in [1, 2^31) and batch >= 0");
+    if (mode != MODE_INFER && mode != MODE_TRAIN && mode != MODE_EVAL) return fail(TFR_ERR_ARG, "forward_plan: mode must be 0 (INFER), 1 (TRAIN) or 2 (EVAL)");
+    if (rows != ROWS_F32 && rows != ROWS_BF16) return fail(TFR_ERR_ARG, "forward_plan: rows must be 0 (float32) or 1 (bf16 snapshot)");
+    if (rows == ROWS_BF16 && mode == MODE_TRAIN) return fail(TFR_ERR_ARG, "forward_plan: the snapshot has no TRAIN forward");
+    const FwdPlan p = forward_plan(dim, G, user_num, mode, (FwdRows)rows, batch);
+    char tmp[128];
+    int n;
+    if (rows == ROWS_F32) n = snprintf(tmp, sizeof(tmp), "k_forward<%d, %d, %d, 4, %s>;grid=%d", p.G, VEC, mode, p.pnt ? "true" : "false", p.grid);
+    else n = snprintf(tmp, sizeof(tmp), "k_forward_bf16<%d, %d, %d, %s>;grid=%d", p.G, mode, p.unr, p.pnt ? "true" : "false", p.grid);
+    if (!buf || buflen < (int64_t)n + 1) return fail(TFR_ERR_ARG, "forward_plan: need a buffer of >= %d bytes", n + 1);
+    memcpy(buf, tmp, (size_t)n + 1);
     return TFR_OK;
 }
 

@@ -289,6 +289,8 @@ inline bool geometry(int D, int* G, int* VEC) {
 int forward_grid(int64_t B, int G, int mode, int unr = 4);
 // INFER / EVAL read the user rows by non-temporal loads when the user table cannot stay in the 256 MB Infinity Cache anyway
 inline bool stream_user_rows(int64_t U, size_t row_bytes) { return (size_t)U * row_bytes > ((size_t)256 << 20); }
+// the one place that picks k_forward's PNT (launch_forward_mode, and tfr_forward_plan reports it): INFER and EVAL only
+inline bool forward_pnt(int mode, int64_t U, int D) { return mode != MODE_TRAIN && stream_user_rows(U, (size_t)D * 4); }
 void launch_forward(const FwdArgs& a, int mode, int G, int VEC, int grid, hipStream_t s);
 int front_forward_blocks(int64_t B, int G);
 void launch_front(const FrontArgs& fa, int G, int VEC, hipStream_t s);

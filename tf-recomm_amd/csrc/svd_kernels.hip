@@ -1805,7 +1805,7 @@ __global__ void k_init_uniform_scalar(float* p, float lo, float hi, uint64_t see
 // launch helpers
 template <int MODE, int UNR>
 static void launch_forward_mode(const FwdArgs& a, int G, int VEC, int grid, hipStream_t s) {
-    const bool pnt = MODE != MODE_TRAIN && stream_user_rows(a.U, (size_t)a.D * 4);
+    const bool pnt = forward_pnt(MODE, a.U, a.D);
 #define TFR_FWD_CASE(g, v) \
     if (G == g && VEC == v) {                                                                                  \
         if (pnt) hipLaunchKernelGGL((k_forward<g, v, MODE, UNR, true>), dim3(grid), dim3(256), 0, s, a);       \
