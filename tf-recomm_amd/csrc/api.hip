@@ -2335,7 +2335,15 @@ int tfr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* loss_o
     m->n_ids = total;
     IdsReady ready;
     ready.m = m; ready.B = B; ready.nsteps = nsteps; ready.rng = rng;
-    ready.plan(B >= 65536 ? 1 : (65536 / B < 16 ? 65536 / B : 16), pre);     // a chunk holds at most ~64K ids / 16 steps
+    // How large a chunk may grow.  Every chunk costs the small-table step's stream about 4 us (the wait for its event, the five
+    // launches of its draw beside the steps): at 6 steps per chunk, 0.6 us of a 16.7-us step.  plan()'s
+    // growth rule alone keeps the generator ahead of the steps, so the cap only bounds how many steps wait behind one draw where
+    // the generator is the slower of the two: 256 steps (at most 2^22 ids, one pass of the wide draw: a small-table batch is
+    // <= 16 tiles) on the small-table path, TFR_CHUNK_STEPS=<n> for A/B (6 = the former cap at the headline batch); the
+    // big-table step keeps ~64K ids / 16 steps.
+    static int64_t tile_chunk_steps = -1;
+    if (tile_chunk_steps < 0) { const char* e = getenv("TFR_CHUNK_STEPS"); tile_chunk_steps = e ? atoll(e) : 256; if (tile_chunk_steps < 1) tile_chunk_steps = 256; }
+    ready.plan(tiles_eligible(m, B) ? tile_chunk_steps : B >= 65536 ? 1 : (65536 / B < 16 ? 65536 / B : 16), pre);
     if (rng == 0) {                                        // one-rating store: no draw consumed
         HIPCHK(hipMemsetAsync(m->ids.ids, 0, (size_t)total * 8, m->stream3));
         m->ids.n_recs = 0;
