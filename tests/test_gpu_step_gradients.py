@@ -2,6 +2,7 @@
 tight statement (tests/step_ref.py) instead of "the table is near the oracle's".  Two successive steps on a fresh model;
 P, Q, bu, bi, mu and their m and v are read before, between and after.  The cases (tests/step_cases.py) name the step path
 they were written for, and ``kernel_plan`` is held against it."""
+import ctypes
 import time
 
 import numpy as np
@@ -101,3 +102,28 @@ def test_two_steps_per_row(case):
                 print("RATIO %s %s %s dev short %.2f long %.2f | c_ref short %.2f long %.2f" % (
                     case["id"], step, name, v["dev"]["short"], v["dev"]["long"], v["c_ref"]["short"], v["c_ref"]["long"]))
         print("TIME %s %.1f s" % (case["id"], time.time() - t0))
+
+
+# tfr_kernel_plan's whole string on the four branches it has (csrc/api.hip), as it stood before the launchers took their
+# instantiations from csrc/dispatch.h: bench.py looks the kernels of a step up by these strings, byte for byte.
+PLAN_STRINGS = [
+    (dict(U=500, I=500, D=16, adam_mode="tf1"), 3000,
+     "reduce_item=k_tile_step<4, 4, 1>;apply=k_dense_tiles<4, 4, false, 4>"),
+    (dict(U=500, I=500, D=16, adam_mode="tf1"), 20000,                         # beyond 16 tiles
+     "forward=k_front<4, 4>;sort=k_csort_scan/scatter;reduce_item=k_seg_reduce<4, 4, 0, false, true, false>;apply=k_adam_dense"),
+    (dict(U=40000, I=3000, D=64, adam_mode="lazy"), 4096,                      # one side above CSORT_MAX_BINS rows
+     "sort=k_rsort_rank/scan/scatter x2 passes (the first gathers the batch);reduce_item=k_seg_reduce<16, 4, 1, true, true, true>;"
+     "reduce_user=k_seg_reduce<16, 4, 1, false, true, true>;apply=k_apply_rows<16, 4, 0>"),
+    (dict(U=40000, I=3000, D=25, optimizer="sgd"), 4096,
+     "sort=k_rsort_rank/scan/scatter x2 passes (the first gathers the batch);reduce_item=k_seg_reduce<32, 1, 2, true, true, false>;"
+     "reduce_user=k_seg_reduce<32, 1, 2, false, true, false>;apply=k_apply_rows<32, 1, 1>"),
+]
+
+
+@pytest.mark.parametrize("model,B,want", PLAN_STRINGS, ids=["tiles", "csort", "fused-lazy-adam", "fused-sgd"])
+def test_kernel_plan_strings_are_pinned(model, B, want):
+    kw = {k: v for k, v in model.items() if k not in ("U", "I", "D")}
+    buf = ctypes.create_string_buffer(1024)                # the raw string: SvdModel.kernel_plan hands back a dict of it
+    with T.SvdModel(model["U"], model["I"], model["D"], **kw) as m:
+        L.check(m._lib.tfr_kernel_plan(m._h, B, buf, 1024))
+    assert buf.value.decode() == want

@@ -9,7 +9,7 @@ from tests import widths as W
 
 
 def supported(D):
-    """a row width the models accept: geometry() rejects lanes > 64 (csrc/svd_kernels.h geometry)"""
+    """a row width the models accept: geometry() rejects lanes > 64 (csrc/dispatch.h geometry)"""
     return 1 <= D <= 64 or (D % 4 == 0 and D <= 256)
 
 
@@ -17,7 +17,7 @@ SUPPORTED = [D for D in range(1, 257) if supported(D)]
 
 
 def geometry(D):
-    """(G, VEC) of the SVD step and forward and of the FM kernels (csrc/svd_kernels.h geometry, fm_kernels.hip launch_fm)"""
+    """(G, VEC) of the SVD step and forward and of the FM kernels (csrc/dispatch.h geometry and ROW_GEOMETRIES, fm_kernels.hip launch_fm)"""
     vec = 4 if D % 4 == 0 else 1
     lanes = -(-D // vec)
     g = 4
@@ -28,8 +28,8 @@ def geometry(D):
 
 def shard_class(D):
     """(G, VEC, full width): k_gather_packed<G, VEC> takes unguarded non-temporal 16-byte loads where D == G * VEC and
-    guarded ones elsewhere (csrc/shard.hip); the sharded reduce takes its three-round load form at full width (csrc/api.hip
-    launch_seg_reduce)"""
+    guarded ones elsewhere (csrc/shard.hip); the sharded reduce takes its three-round load form at full width
+    (csrc/svd_kernels.h seg_reduce_pick)"""
     g, vec = geometry(D)
     return g, vec, D == g * vec
 
@@ -85,7 +85,7 @@ def test_sharded_stages_reach_every_geometry_at_full_and_partial_width():
 
 
 def test_fm_step_reaches_every_geometry_at_full_and_partial_width():
-    """k_fm_forward<G, VEC, ...> branches on D == G * VEC (csrc/fm_kernels.hip `full`), and launch_seg_reduce gives the FM
+    """k_fm_forward<G, VEC, ...> branches on D == G * VEC (csrc/fm_kernels.hip `full`), and seg_reduce_pick (csrc/svd_kernels.h) gives the FM
     backward its three-round load form at full width only: the classes of ``shard_class``"""
     reachable = {shard_class(D) for D in SUPPORTED}
     assert len(reachable) == 15
@@ -102,7 +102,7 @@ def bf16_class(D):
 
 
 def test_forward_pnt_reaches_every_geometry_at_full_and_partial_width():
-    """launch_forward_mode picks k_forward<G, VEC, MODE, 4, PNT> by geometry(D) and forward_pnt (csrc/svd_kernels.hip);
+    """launch_forward_mode picks k_forward<G, VEC, MODE, 4, PNT> by with_geometry (csrc/dispatch.h) and forward_pnt (csrc/svd_kernels.hip);
     load_frag<VEC, true> guards its non-temporal load by d0 < D, which is false for some lane only below full width"""
     reachable = {shard_class(D) for D in SUPPORTED}
     assert len(reachable) == 15

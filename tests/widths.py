@@ -29,7 +29,7 @@ BF16_PNT = (5, 13, 17, 31, 33, 61, 100, 128, 132, 256)
 # SVD++ kernels and batched fine-tuning: NJ = ceil(D / 64) registers per lane, the last one full or partial
 SVDPP = (33, 64, 100, 128, 132, 192, 252, 256)
 FINETUNE = (20, 64, 68, 128, 132, 192, 252, 256)
-BPR = (1, 33, 64, 100, 128, 132, 192, 252, 256)            # k_bpr_users / k_bpr_items (csrc/wave_rows.h with_nj), and D = 1
+BPR = (1, 33, 64, 100, 128, 132, 192, 252, 256)            # k_bpr_users / k_bpr_items (csrc/wave_rows.h with_nj, over csrc/dispatch.h with_one_of), and D = 1
 FINETUNE_STREAMED = (20, 100, 132, 252)                    # one call stages some users and streams others, each NJ
 
 # top-K and rank: V4 = (D % 4 == 0) crossed with where mfma_tile_dot's last group of four float4s ends

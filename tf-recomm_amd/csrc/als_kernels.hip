@@ -19,6 +19,7 @@
 #include <algorithm>
 #include "tfrecomm.h"
 #include "devbuf.h"
+#include "env_switch.h"
 #include "als_common.h"
 
 using tfr::DevBuf;
@@ -312,7 +313,7 @@ int tfr_als_load(tfr_als* m, const int64_t* user_ids, const int64_t* work_ids, c
     m->n = n; m->n_users = (int64_t)lu.size(); m->n_works = (int64_t)lw.size();
     // long lists are cut into chunks of CH ratings (als_common.h)
     int64_t CH = 512;                                     // A/B in one call: 2048 1.33 ms per iteration, 1024 1.18, 512 1.12, 256 1.16, 128 1.38
-    if (const char* e = getenv("TFR_ALS_CHUNK")) { const long v = atol(e); if (v >= ALS_TILE) CH = (v / ALS_TILE) * ALS_TILE; }
+    if (const long long v = tfr::env_int("TFR_ALS_CHUNK", 0); v >= ALS_TILE) CH = (v / ALS_TILE) * ALS_TILE;   // read at every bind
     size_t max_chunks = 0;
     for (int z = 0; z < 2; ++z) {
         const int64_t rows = z == 0 ? m->nu : m->nw;

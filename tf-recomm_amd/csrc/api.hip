@@ -339,9 +339,8 @@ static int check_device_error(tfr_model* m) {
 struct CallTrace {
     bool on; std::chrono::steady_clock::time_point t0; const char* name;
     explicit CallTrace(const char* n) : name(n) {
-        static int en = -1;
-        if (en < 0) { const char* e = getenv("TFR_CALL_TRACE"); en = (e && e[0] == '1') ? 1 : 0; }
-        on = en == 1;
+        static const bool en = env_default_off("TFR_CALL_TRACE");
+        on = en;
         if (on) t0 = std::chrono::steady_clock::now();
     }
     void mark(const char* what) const {
@@ -852,8 +851,8 @@ enum FwdRows { ROWS_F32, ROWS_BF16 };
 // TFR_BF16_PNT=0|1: A/B override of the non-temporal user rows (unset: the float32 forward's rule on the snapshot's bytes).
 // Read at every launch, so that one process can alternate the two (tools/bench_bf16_forward.py --pnt-ab).
 static bool bf16_pnt(int64_t U, int D) {
-    const char* e = getenv("TFR_BF16_PNT");
-    if (e && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
+    if (env_default_off("TFR_BF16_PNT")) return true;
+    if (!env_default_on("TFR_BF16_PNT")) return false;
     return stream_user_rows(U, (size_t)bf16_row_stride(D) * 2);
 }
 
@@ -880,7 +879,7 @@ static int run_forward(tfr_model* m, int mode, const int32_t* du, const int32_t*
     if (rows == ROWS_F32) {
         FwdArgs a = fwd_args(m, du, di, dr, B, d_logits, d_g, d_store_ids);
         if (d_store_ids) { a.u_out = m->d_u; a.it_out = m->d_i; }     // the gathered ids, for the backward
-        { static int lr = -1; if (lr < 0) { const char* e = getenv("TFR_LDS_REDUCE"); lr = (e && e[0] == '1') ? 1 : 0; } a.lds_reduce = lr; }
+        { static const bool lr = env_default_off("TFR_LDS_REDUCE"); a.lds_reduce = lr; }
         Prof p(m, TFR_K_FORWARD);
         launch_forward(a, mode, G, m->VEC, grid, m->stream);
     } else {
@@ -936,8 +935,7 @@ static int radix_sort_columns(tfr_model* m, int ncols, const int32_t* const* key
         }
         r.err = (p == 0 && limits) ? m->d_err : nullptr;         // ids outside the tables void the step
         if (limits) for (int c = 0; c < ncols; ++c) r.limit[c] = (int32_t)limits[c];
-        static int wide = -1;                                    // TFR_RSORT_WIDE=0: A/B switch
-        if (wide < 0) { const char* e = getenv("TFR_RSORT_WIDE"); wide = (e && e[0] == '0') ? 0 : 1; }
+        static const bool wide = env_default_on("TFR_RSORT_WIDE");   // TFR_RSORT_WIDE=0: A/B switch
         if (wide && rsortw_eligible(B)) launch_rsortw_pass(r, ncols, m->stream);   // from 65536 keys: 4096-key tiles, LDS-staged scatter
         else launch_rsort_pass(r, ncols, m->stream);
     }
@@ -1004,8 +1002,7 @@ static int front_and_sort(tfr_model* m, const int32_t*& du, const int32_t*& di, 
     int rc;
     if (sort_only) {
         const bool radix = !csort_path(m, B);
-        static int fuse = -1;                            // TFR_FUSE_GATHER=0: A/B switch (separate k_gather_triples launch)
-        if (fuse < 0) { const char* e = getenv("TFR_FUSE_GATHER"); fuse = (e && e[0] == '0') ? 0 : 1; }
+        static const bool fuse = env_default_on("TFR_FUSE_GATHER");   // TFR_FUSE_GATHER=0: A/B switch (separate k_gather_triples launch)
         if (d_store_ids && radix && fuse) {                      // the radix sort's first pass gathers the batch itself (one launch less)
             du = m->d_u; di = m->d_i; dr = m->d_r;
             return sort_columns(m, du, di, B, nullptr, nullptr, true, d_store_ids);
@@ -1072,9 +1069,8 @@ static int front_and_sort(tfr_model* m, const int32_t*& du, const int32_t*& di, 
 // parity (hist_* / offs_* serve as the two tables).  *par_out = which table set k_dense_tiles reads.
 // ---- store records beside the id buffers (IdBuf) ---------------------------------------------------------
 static bool recs_on() {                                  // TFR_RECS=0: A/B switch
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("TFR_RECS"); on = (e && e[0] == '0') ? 0 : 1; }
-    return on == 1;
+    static const bool on = env_default_on("TFR_RECS");
+    return on;
 }
 static void recs_forget(tfr_model* m) { m->ids.n_recs = 0; m->ids_alt.n_recs = 0; }      // the store changed
 // does [p, p + n) overlap the id buffer b?
@@ -1136,8 +1132,7 @@ static int tile_step_launch(tfr_model* m, const int32_t* du, const int32_t* di, 
     ts.lam = o.reg;
     *par_out = par;
     *nblk_out = ts.ntiles * m->G;            // one {loss, reg, sum g} slot per piece
-    static int dbg_on = -1;                  // TFR_TILE_DEBUG=1: per-block start / end stamps of every launch on stderr (synchronises)
-    if (dbg_on < 0) { const char* e = getenv("TFR_TILE_DEBUG"); dbg_on = (e && e[0] == '1') ? 1 : 0; }
+    static const bool dbg_on = env_default_off("TFR_TILE_DEBUG");   // TFR_TILE_DEBUG=1: per-block start / end stamps of every launch on stderr (synchronises)
     if (dbg_on && m->tile_dbg.reserve(2048 * 8, m->stream) != hipSuccess) (void)hipGetLastError();
     unsigned long long* d_dbg = m->tile_dbg;
     if (d_dbg && 2 * (ts.next_ntiles + ts.ntiles * m->G) <= 2048) { (void)hipMemsetAsync(d_dbg, 0, 2048 * 64, m->stream); ts.dbg = d_dbg; }
@@ -1271,7 +1266,7 @@ static int step_big_fused(tfr_model* m, const OptStep& k, const int32_t* du, con
     // big tables: every row of this step is touched once and cannot stay cached - non-temporal loads / stores for the
     // rows, default policy only for reading back the pre-update copies (A/B, TFR_NT=<bits>:
     // 523-548 us/step with 0, 498 with 23; bits in svd_kernels.h RedArgs::nt)
-    { static int nt = -1; if (nt < 0) { const char* e = getenv("TFR_NT"); nt = e ? atoi(e) : 23; } ri.nt = ru.nt = fwd_fused ? nt : 0; }
+    { static const int nt = (int)env_int("TFR_NT", 23); ri.nt = ru.nt = fwd_fused ? nt : 0; }
     if (dual) {
         // the updated item row goes to the table the row is NOT in, so the user side still finds the pre-update row where
         // it was: no copy written (4D per rating) and none read
@@ -1285,7 +1280,7 @@ static int step_big_fused(tfr_model* m, const OptStep& k, const int32_t* du, con
     if (fwd_fused) {           // K1 inside the item side: logits, g, per-block {loss, reg, sum g}
         ri.partner_bias = m->w[TFR_BU]; ri.mu = m->w[TFR_MU]; ri.r = dr; ri.loss = m->o.loss;
         ri.g_out = m->d_g; ri.logits_out = d_logits; ri.partials = m->partials;
-        { static int st = -1; if (st < 0) { const char* e = getenv("TFR_STAGE_SUM"); st = (e && e[0] == '0') ? 0 : 1; } ri.stage_sum = st; }
+        { static const bool st = env_default_on("TFR_STAGE_SUM"); ri.stage_sum = st; }
         const int epb = 1024 / m->G;
         f.nblk = (int)((B + epb - 1) / epb);
     }
@@ -1334,9 +1329,7 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
     bool dual = false, one_launch = false;
     if (B > 0) {
         // two-table form of the fused big-table step (no per-entry copy of the pre-update item rows): TFR_DUALQ=0 restores the copy
-        static int dualq = -1;
-        if (dualq < 0) { const char* e = getenv("TFR_DUALQ"); dualq = (e && e[0] == '0') ? 0 : 1; }
-        dual = fwd_fused && dualq;
+        dual = fwd_fused && switch_dualq();
         if (dual && !(m->q_alt && m->q_sel)) {           // both tables or neither
             hipError_t e = m->q_alt.reserve(m->n[TFR_Q], s);
             if (e == hipSuccess) e = m->q_sel.reserve(m->I, s);
@@ -1348,8 +1341,7 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
             }
         }
         if (!dual && (rc = settle_q(m))) return rc;
-        static int split_tiles = -1;   // TFR_TILE_SPLIT=1: the three-launch form (k_front + k_seg_reduce), kept for A/B
-        if (split_tiles < 0) { const char* e = getenv("TFR_TILE_SPLIT"); split_tiles = (e && e[0] == '1') ? 1 : 0; }
+        static const bool split_tiles = env_default_off("TFR_TILE_SPLIT");   // TFR_TILE_SPLIT=1: the three-launch form (k_front + k_seg_reduce), kept for A/B
         one_launch = tiles && !split_tiles;
         if (!one_launch && !(presorted_big && fwd_fused))     // presorted_big: gathered + sorted ahead, on the second stream
             if ((rc = front_and_sort(m, du, di, dr, B, d_logits, d_store_ids, f, nblk, fin_done, tiles, fwd_fused))) return rc;
@@ -2001,8 +1993,7 @@ static int staged_steps_lookahead(tfr_model* m, int64_t first_step, int64_t B, i
     // the next batch's sort chain starts beside the user-side kernel of this step (after the item-side one, which runs the
     // forward and suffers more from company): three A/B pairs in one gpurun call, 494/519/537 -> 489/512/523 us per step.
     // TFR_SORT_LATE=0: start it beside the item-side kernel (the round-1 order), kept for A/B
-    static int late = -1;
-    if (late < 0) { const char* e = getenv("TFR_SORT_LATE"); late = (e && e[0] == '0') ? 0 : 1; }
+    static const bool late = env_default_on("TFR_SORT_LATE");
     if (late) {
         m->ev_mid_on = true;
         for (int32_t s = 0; s < nsteps && !rc; ++s) {
@@ -2056,8 +2047,7 @@ static int staged_steps(tfr_model* m, int64_t first_step, int64_t B, int32_t nst
     if ((rc = ensure_capacity(m, B))) return rc;
     if (loss_out) HIPCHK(m->step_out.reserve((int64_t)nsteps * 4, m->stream));
     const StepMark mark = mark_step(m);
-    static int no_ahead = -1;                              // TFR_NO_LOOKAHEAD=1: A/B switch
-    if (no_ahead < 0) { const char* e = getenv("TFR_NO_LOOKAHEAD"); no_ahead = (e && e[0] == '1') ? 1 : 0; }
+    static const bool no_ahead = env_default_off("TFR_NO_LOOKAHEAD");   // TFR_NO_LOOKAHEAD=1: A/B switch
     if (nsteps > 1 && fwd_in_reduce(m, B) && !m->prof && !no_ahead) {
         if ((rc = staged_steps_lookahead(m, first_step, B, nsteps, loss_out, ready))) {
             (void)hipStreamSynchronize(m->stream2);
@@ -2119,8 +2109,7 @@ int tfr_train_steps_resident(tfr_model* m, const int64_t* ids, int64_t B, int32_
 static int ensure_rng(tfr_model* m) {
     HIPCHK(reserve_each(625, m->stream, m->d_rng, m->d_rng_snap));
     // scratch of the wide draw; TFR_RNG_WIDE=0 keeps every draw on the one-workgroup kernel (A/B)
-    const char* e = getenv("TFR_RNG_WIDE");
-    if (!(e && e[0] == '0')) {
+    if (env_default_on("TFR_RNG_WIDE")) {
         HIPCHK(m->rng_raw.reserve(MT_WIDE_BLOCKS * 624, m->stream));
         HIPCHK(m->rng_counts.reserve(MT_WIDE_BLOCKS, m->stream));
         HIPCHK(m->rng_hdr.reserve(4, m->stream));
@@ -2198,7 +2187,7 @@ int tfr_draw_ids(tfr_model* m, int64_t high, int64_t count, int64_t* ids_out) {
     HIPCHK(d.reserve(count, m->stream3));
     const uint32_t rng = (uint32_t)(high - 1);
     DevBuf<unsigned long long> dbg;
-    if (getenv("TFR_RNG_DEBUG") && dbg.reserve(2, m->stream3) != hipSuccess) (void)hipGetLastError();   // diagnostic: in-kernel clock of the generator
+    if (env_is_set("TFR_RNG_DEBUG") && dbg.reserve(2, m->stream3) != hipSuccess) (void)hipGetLastError();   // diagnostic: in-kernel clock of the generator
     launch_mt_draw(m->d_rng, d, count, rng, mask_for(rng), m->stream3, dbg, &m->rng_ws);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(ids_out, d, (size_t)count * 8, hipMemcpyDeviceToHost, m->stream3);
@@ -2341,8 +2330,7 @@ int tfr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* loss_o
     // the generator is the slower of the two: 256 steps (at most 2^22 ids, one pass of the wide draw: a small-table batch is
     // <= 16 tiles) on the small-table path, TFR_CHUNK_STEPS=<n> for A/B (6 = the former cap at the headline batch); the
     // big-table step keeps ~64K ids / 16 steps.
-    static int64_t tile_chunk_steps = -1;
-    if (tile_chunk_steps < 0) { const char* e = getenv("TFR_CHUNK_STEPS"); tile_chunk_steps = e ? atoll(e) : 256; if (tile_chunk_steps < 1) tile_chunk_steps = 256; }
+    static const int64_t tile_chunk_steps = [] { const int64_t v = env_int("TFR_CHUNK_STEPS", 256); return v < 1 ? 256 : v; }();
     ready.plan(tiles_eligible(m, B) ? tile_chunk_steps : B >= 65536 ? 1 : (65536 / B < 16 ? 65536 / B : 16), pre);
     if (rng == 0) {                                        // one-rating store: no draw consumed
         HIPCHK(hipMemsetAsync(m->ids.ids, 0, (size_t)total * 8, m->stream3));
@@ -2368,14 +2356,13 @@ int tfr_kernel_plan(tfr_model* m, int64_t B, char* buf, int64_t buflen) {
     const int64_t ntiles = (B + CSORT_TILE - 1) / CSORT_TILE;
     char tmp[1024];
     if (tiles_eligible(m, B)) {
-        const int nt = ntiles <= 4 ? 4 : ntiles <= 8 ? 8 : ntiles <= 10 ? 10 : ntiles <= 12 ? 12 : 16;
         snprintf(tmp, sizeof(tmp), "reduce_item=k_tile_step<%d, %d, %d>;apply=k_dense_tiles<%d, %d, false, %d>", G, V,
-                 tile_step_epg((int)ntiles, G, V), G, V, nt);
+                 tile_step_epg((int)ntiles, G, V), G, V, dense_tiles_nt(ntiles));
     } else if (fwd_in_reduce(m, B)) {
         const int rm = reduce_mode(k);
         // the sixth argument: the three-round load form (launch_seg_reduce picks it for the two-table step on full-width rows)
-        const char* e1 = getenv("TFR_DUALQ"); const char* e2 = getenv("TFR_FAST"); const char* e3 = getenv("TFR_LEAN");
-        const bool fast = !(e1 && e1[0] == '0') && !(e2 && e2[0] == '0') && !(e3 && e3[0] == '0') && m->D == G * V;
+        // (a coarser rule than seg_reduce_pick's, kept: bench.py looks kernels up by this string)
+        const bool fast = switch_dualq() && switch_fast() && switch_lean() && m->D == G * V;
         snprintf(tmp, sizeof(tmp), "sort=%s x%d passes (the first gathers the batch);reduce_item=k_seg_reduce<%d, %d, %d, true, true, %s>;"
                  "reduce_user=k_seg_reduce<%d, %d, %d, false, true, %s>;apply=k_apply_rows<%d, %d, %d>",   // K4 rides in the apply launch
                  rsortw_eligible(B) ? "k_rsortw_hist/k_rsort_scan/k_rsortw_scatter" : "k_rsort_rank/scan/scatter",
@@ -3048,8 +3035,7 @@ static int fm_stage_csr(tfr_fm* f, const int64_t* indptr, const int32_t* indices
 
 // k_fm_forward variant (launch_fm): TFR_FM_VARIANT=<bits> overrides for A/B
 static int fm_variant(const tfr_model* m) {
-    static int ov = -2;
-    if (ov == -2) { const char* e = getenv("TFR_FM_VARIANT"); ov = e ? atoi(e) : -1; }
+    static const int ov = (int)env_int("TFR_FM_VARIANT", -1);
     if (ov >= 0) return ov;
     return ((size_t)m->U * m->D * 4 >= ((size_t)128 << 20)) ? 2 : 0;      // V beyond half the Infinity Cache: stream it
 }

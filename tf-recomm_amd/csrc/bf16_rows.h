@@ -28,7 +28,7 @@ inline int bf16_geometry(int D) {
 
 // ratings in flight per lane group: the forward's 4, held to G so that a wave-iteration's 64 / G * UNR ratings fit the
 // 64 lanes of the wave-wide bias load
-inline int bf16_unroll(int G) { return G < 4 ? G : 4; }
+constexpr int bf16_unroll(int G) { return G < 4 ? G : 4; }
 
 // the forward's argument block without what only training reads; P and Q are snapshot rows of stride DP
 struct Bf16FwdArgs {

@@ -92,14 +92,11 @@ __global__ __launch_bounds__(256) void k_forward_bf16(Bf16FwdArgs a) {
 
 template <int MODE>
 void launch_forward_bf16_mode(const Bf16FwdArgs& a, int G, int grid, bool pnt, hipStream_t s) {
-#define TFR_BF16_CASE(g, unr)                                                                              \
-    if (G == g) {                                                                                          \
-        if (pnt) hipLaunchKernelGGL((k_forward_bf16<g, MODE, unr, true>), dim3(grid), dim3(256), 0, s, a); \
-        else hipLaunchKernelGGL((k_forward_bf16<g, MODE, unr, false>), dim3(grid), dim3(256), 0, s, a);    \
-        return;                                                                                            \
-    }
-    TFR_BF16_CASE(1, 1) TFR_BF16_CASE(2, 2) TFR_BF16_CASE(4, 4) TFR_BF16_CASE(8, 4) TFR_BF16_CASE(16, 4) TFR_BF16_CASE(32, 4)
-#undef TFR_BF16_CASE
+    with_one_of<1, 2, 4, 8, 16, 32>(G, [&](auto g) {
+        with_bool(pnt, [&](auto nt) {
+            hipLaunchKernelGGL((k_forward_bf16<g.value, MODE, bf16_unroll(g.value), nt.value>), dim3(grid), dim3(256), 0, s, a);
+        });
+    });
 }
 
 }  // namespace
@@ -112,10 +109,7 @@ void launch_forward_bf16(const Bf16FwdArgs& a, int mode, int G, int grid, bool p
 void launch_rows_to_bf16(const float* src, uint16_t* dst, int64_t rows, int D, hipStream_t s) {
     const int DP = bf16_row_stride(D);
     const int64_t total = rows * (DP / 8);
-    int64_t nb = (total + 255) / 256;
-    if (nb > 65536) nb = 65536;
-    if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(k_rows_to_bf16, dim3((int)nb), dim3(256), 0, s, src, dst, rows, D, DP);
+    hipLaunchKernelGGL(k_rows_to_bf16, dim3(blocks_for(total, 256, 65536)), dim3(256), 0, s, src, dst, rows, D, DP);
 }
 
 }  // namespace tfr

@@ -146,13 +146,8 @@ void launch_fm_gather(const FmGatherArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_fm_indptr, dim3((unsigned)nchunks), dim3(256), 0, s, a);
     if (a.nnz == 0) return;
     const int G = fm_gather_group(a.B, a.nnz);
-    const int rpb = 256 / G;
-    int64_t nb = (a.B + rpb - 1) / rpb;
-    if (nb > 16384) nb = 16384;
-#define TFR_FM_COPY_CASE(g) \
-    if (G == g) { hipLaunchKernelGGL((k_fm_gather_copy<g>), dim3((unsigned)nb), dim3(256), 0, s, a); return; }
-    TFR_FM_COPY_CASE(4) TFR_FM_COPY_CASE(8) TFR_FM_COPY_CASE(16) TFR_FM_COPY_CASE(32) TFR_FM_COPY_CASE(64)
-#undef TFR_FM_COPY_CASE
+    const dim3 grid(blocks_for(a.B, 256 / G, 16384));    // (nnz > 0: at least one row)
+    with_one_of<4, 8, 16, 32, 64>(G, [&](auto g) { hipLaunchKernelGGL((k_fm_gather_copy<g.value>), grid, dim3(256), 0, s, a); });
 }
 
 // ---- binary metrics of n resident predictions: per block {count of infer == y, summed cross-entropy}, by the formulas of
@@ -182,11 +177,8 @@ __global__ __launch_bounds__(256) void k_fm_binary_metrics(const float* __restri
 }
 
 int fm_metrics_grid(int64_t n) {
-    int64_t nb = (n + 255) / 256;
     // a block's count of equal predictions is summed in float: keep it far below 2^24
-    if (nb > 8192) nb = 8192;
-    if (nb < 1) nb = 1;
-    return (int)nb;
+    return blocks_for(n, 256, 8192);
 }
 
 void launch_fm_binary_metrics(const float* logits, const float* y, int64_t n, float* partials, hipStream_t s) {

@@ -156,27 +156,20 @@ __global__ __launch_bounds__(256) void k_fm_forward(FmArgs a) {
 }
 
 int fm_grid(int64_t n_rows, int G, bool train) {
-    const int gpb = 256 / G;
-    int64_t nb = (n_rows + gpb - 1) / gpb;
     // (training forward, one gpurun call, whole step: 2.10-2.12 ms at 2048 blocks, 2.07 at 4096 and at 8192; with its V rows
     // loaded non-temporally like the inference form's: 2.13-2.15 - the backward reads the same rows again and wants them cached)
-    const int64_t cap = train ? 4096 : 8192;
-    if (nb > cap) nb = cap;
-    if (nb < 1) nb = 1;
-    return (int)nb;
+    return blocks_for(n_rows, 256 / G, train ? 4096 : 8192);
 }
 
+// k_fm_forward's <TRAIN, NTV>: training (V rows cached), inference with non-temporal V rows (variant bit 1), inference
+enum { FM_TRAIN = 0, FM_INFER_NTV = 1, FM_INFER = 2 };
+
 void launch_fm(const FmArgs& a, bool train, int G, int VEC, int grid, hipStream_t s) {
-#define TFR_FM_CASE(g, v)                                                                              \
-    if (G == g && VEC == v) {                                                                          \
-        if (train) hipLaunchKernelGGL((k_fm_forward<g, v, true, false>), dim3(grid), dim3(256), 0, s, a);     \
-        else if (a.variant & 2) hipLaunchKernelGGL((k_fm_forward<g, v, false, true>), dim3(grid), dim3(256), 0, s, a);   \
-        else hipLaunchKernelGGL((k_fm_forward<g, v, false, false>), dim3(grid), dim3(256), 0, s, a);   \
-        return;                                                                                        \
-    }
-    TFR_FM_CASE(4, 4) TFR_FM_CASE(8, 4) TFR_FM_CASE(16, 4) TFR_FM_CASE(32, 4) TFR_FM_CASE(64, 4)
-    TFR_FM_CASE(4, 1) TFR_FM_CASE(8, 1) TFR_FM_CASE(16, 1) TFR_FM_CASE(32, 1) TFR_FM_CASE(64, 1)
-#undef TFR_FM_CASE
+    with_geometry(G, VEC, [&](auto g, auto v) {
+        with_one_of<FM_TRAIN, FM_INFER_NTV, FM_INFER>(train ? FM_TRAIN : (a.variant & 2) ? FM_INFER_NTV : FM_INFER, [&](auto form) {
+            hipLaunchKernelGGL((k_fm_forward<g.value, v.value, form.value == FM_TRAIN, form.value == FM_INFER_NTV>), dim3(grid), dim3(256), 0, s, a);
+        });
+    });
 }
 
 }  // namespace tfr

@@ -343,8 +343,7 @@ void launch_mt_draw(uint32_t* d_state, int64_t* d_out, int64_t need, uint32_t rn
             int64_t nb = (int64_t)(((double)n + 6.0 * sqrt((double)n * (1.0 - p)) + 8.0) / p / 624.0) + 2;
             {   // TFR_RNG_WIDE_TRIM=<percent>: generate only that share of the blocks, so that the stream comes up short and the
                 // k_mt_draw tail has work to do (tests)
-                static int trim = -1;
-                if (trim < 0) { const char* e = getenv("TFR_RNG_WIDE_TRIM"); trim = e ? atoi(e) : 100; }
+                static const int trim = (int)env_int("TFR_RNG_WIDE_TRIM", 100);
                 if (trim > 0 && trim < 100) { nb = nb * trim / 100; if (nb < 1) nb = 1; }
             }
             if (nb + 1 > ws->cap_blocks) {                                   // scratch sized for MT_WIDE_MAX ids at p = 1/2

@@ -327,22 +327,13 @@ __global__ __launch_bounds__(256) void k_clear_grad_slots(float* grad, const int
 }
 
 void launch_clear_grad_slots(float* grad, const int32_t* used, int32_t world, int32_t cap, int32_t D, int32_t stride, hipStream_t s) {
-    int64_t nb = ((int64_t)cap * stride / 4 + 255) / 256;        // four words per thread where a whole chunk is unused
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(k_clear_grad_slots, dim3((int)nb, world), dim3(256), 0, s, grad, used, cap, D, stride);
+    const int nb = blocks_for((int64_t)cap * stride / 4, 256, 1024);   // four words per thread where a whole chunk is unused
+    hipLaunchKernelGGL(k_clear_grad_slots, dim3(nb, world), dim3(256), 0, s, grad, used, cap, D, stride);
 }
 
 void launch_gather_packed(const GatherPackedArgs& a, int G, int VEC, hipStream_t s) {
-    const int gpb = 4 * (256 / G);                       // UN requests per lane group and round
-    int64_t nb = (a.n + gpb - 1) / gpb;
-    if (nb > 8192) nb = 8192;
-    if (nb < 1) nb = 1;
-#define TFR_GP_CASE(g, v) \
-    if (G == g && VEC == v) { hipLaunchKernelGGL((k_gather_packed<g, v>), dim3((int)nb), dim3(256), 0, s, a); return; }
-    TFR_GP_CASE(4, 4) TFR_GP_CASE(8, 4) TFR_GP_CASE(16, 4) TFR_GP_CASE(32, 4) TFR_GP_CASE(64, 4)
-    TFR_GP_CASE(4, 1) TFR_GP_CASE(8, 1) TFR_GP_CASE(16, 1) TFR_GP_CASE(32, 1) TFR_GP_CASE(64, 1)
-#undef TFR_GP_CASE
+    const dim3 grid(blocks_for(a.n, 4 * (256 / G), 8192));   // UN requests per lane group and round
+    with_geometry(G, VEC, [&](auto g, auto v) { hipLaunchKernelGGL((k_gather_packed<g.value, v.value>), grid, dim3(256), 0, s, a); });
 }
 
 __global__ __launch_bounds__(256) void k_pad_keys(const int32_t* in, int32_t* out, int64_t n, int32_t pad_key, int32_t* count) {
@@ -364,10 +355,7 @@ __global__ __launch_bounds__(256) void k_pad_keys(const int32_t* in, int32_t* ou
 
 void launch_pad_keys(const int32_t* ids_in, int32_t* keys_out, int64_t n, int32_t pad_key, int32_t* count, hipStream_t s) {
     (void)hipMemsetAsync(count, 0, 4, s);
-    int64_t nb = (n + 255) / 256;
-    if (nb > 512) nb = 512;
-    if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(k_pad_keys, dim3((int)nb), dim3(256), 0, s, ids_in, keys_out, n, pad_key, count);
+    hipLaunchKernelGGL(k_pad_keys, dim3(blocks_for(n, 256, 512)), dim3(256), 0, s, ids_in, keys_out, n, pad_key, count);
 }
 
 }  // namespace tfr

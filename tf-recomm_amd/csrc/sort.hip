@@ -487,8 +487,8 @@ __global__ __launch_bounds__(1024) void k_rsortw_scatter(RSortArgs a) {
 }
 
 bool rsortw_eligible(int64_t B) {
-    static int64_t lo = -1;                              // TFR_RSORT_WIDE_MIN: smallest key count that takes the wide tiles
-    if (lo < 0) { const char* e = getenv("TFR_RSORT_WIDE_MIN"); lo = e ? atoll(e) : 65536; }   // C3's 262144-key sort: 71 -> 66 us
+    // TFR_RSORT_WIDE_MIN: smallest key count that takes the wide tiles (C3's 262144-key sort: 71 -> 66 us)
+    static const int64_t lo = env_int("TFR_RSORT_WIDE_MIN", 65536);
     return B >= lo;
 }
 

@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "dispatch.h"
+#include "env_switch.h"
 
 namespace tfr {
 
@@ -186,6 +188,8 @@ void launch_dense_tiles(const TileDenseLaunch& L, bool write, bool with_fin, int
 // the instantiation launch_dense_tiles takes for this geometry and tile count (nullptr: none), its grid's block columns,
 // and whether a launch of `rows` rows of width D takes the three-round form
 const void* dense_tiles_kernel(bool write, int G, int VEC, int ntiles);
+// k_dense_tiles' NT, the tiles one instantiation has registers for: the smallest of these that holds ntiles
+constexpr int dense_tiles_nt(int64_t ntiles) { return ntiles <= 4 ? 4 : ntiles <= 8 ? 8 : ntiles <= 10 ? 10 : ntiles <= 12 ? 12 : 16; }
 int dense_tiles_grid(int64_t rows, int G);
 bool dense_tiles_rounds_taken(int64_t rows, int D, int G, int VEC);
 
@@ -273,18 +277,6 @@ int tile_step_epg(int ntiles, int G, int VEC);       // pieces per block of k_ti
 int tile_step_item_epg(int64_t B, int G, int VEC, int nsort);   // pieces per block of its item side
 int tile_step_one_barrier();                         // TFR_ONE_BARRIER=1: the cross-wave piece sums after one barrier
 
-// row geometry for a dim: returns false if unsupported
-inline bool geometry(int D, int* G, int* VEC) {
-    if (D < 1) return false;
-    int vec = (D % 4 == 0) ? 4 : 1;
-    int lanes = (D + vec - 1) / vec;
-    int g = 4;
-    while (g < lanes) g <<= 1;
-    if (g > 64) return false;
-    *G = g; *VEC = vec;
-    return true;
-}
-
 // blocks of a forward launch: 8192 for INFER, 2048 otherwise, then grid-stride; unr = ratings in flight per lane group
 int forward_grid(int64_t B, int G, int mode, int unr = 4);
 // INFER / EVAL read the user rows by non-temporal loads when the user table cannot stay in the 256 MB Infinity Cache anyway
@@ -296,6 +288,32 @@ int front_forward_blocks(int64_t B, int G);
 void launch_front(const FrontArgs& fa, int G, int VEC, hipStream_t s);
 void launch_csort_tail(const CSortArgs& a, const FinArgs* fin, hipStream_t s);   // scan (+K4) and scatter only
 void launch_seg_reduce(const RedPair& p, int n, int rmode, int G, int VEC, hipStream_t s, bool fwd = false);
+// k_seg_reduce's <RMODE, FWD, LEAN, FAST>: the 13 forms compiled per row geometry, and the one a launch takes
+struct RedPick { int rmode; bool fwd, lean, fast; };
+constexpr RedPick RED_PICKS[] = {
+    {RMODE_ADAM, true, true, true},   {RMODE_SCRATCH, true, true, true},   {RMODE_SGD, true, true, true},     // FAST is LEAN, with the forward ...
+    {RMODE_SCRATCH, false, true, true}, {RMODE_ADAM, false, true, true},   {RMODE_SGD, false, true, true},    // ... and without
+    {RMODE_ADAM, true, false, false},                                                                         // the one !LEAN form (TFR_LEAN=0)
+    {RMODE_ADAM, true, true, false},  {RMODE_SCRATCH, true, true, false},  {RMODE_SGD, true, true, false},
+    {RMODE_SCRATCH, false, true, false}, {RMODE_ADAM, false, true, false}, {RMODE_SGD, false, true, false},
+};
+// FAST: full-width rows (D = G * VEC), ids and rows from tables or packed exchange buffers (strides), with or without the
+// two-table item form - the fused big-table step (api.hip run_train_step, `dual`) and the row-sharded step's item / user
+// sides and its owners' apply (pre-reduced rows), the FM backward (16-byte entry records); not the per-position copies of
+// the one-table form or tile mode.
+// Its row loads are non-temporal whatever RedArgs::nt says.
+inline RedPick seg_reduce_pick(const RedArgs& a0, int n, int rmode, bool fwd, int G, int VEC) {
+    const bool lean = switch_lean(), fast_en = switch_fast();
+    const bool fast_own = fast_en && lean && n == 1 && a0.rows_in && a0.bias_in && !fwd && !a0.tile && !a0.sel && !a0.ostride && !a0.obstride &&
+                          a0.D == G * VEC && a0.B > 0 && (rmode == RMODE_SCRATCH || a0.own == a0.own_w);
+    const bool fast = fast_own ||
+                      (fast_en && lean && n == 1 && !a0.rows_in && !a0.partner_by_pos && !a0.own_copy_out && !a0.tile &&
+                      a0.D == G * VEC && a0.B > 0 && (a0.other || a0.ent) && (!a0.ent || (!fwd && !a0.osel_in)) && (!a0.osel_in || a0.partner_alt) && (!a0.sel || (a0.own_alt && a0.own_alt == a0.own_w_alt)) &&
+                      (rmode == RMODE_SCRATCH || (a0.own == a0.own_w && !a0.ostride)) &&
+                      (fwd ? (a0.r && a0.partner_bias && !a0.osel_in) : ((a0.g || a0.ent) && !a0.sel)));
+    const int rm = (rmode == RMODE_SCRATCH || rmode == RMODE_ADAM) ? rmode : RMODE_SGD;
+    return {rm, fwd, fast || !(fwd && rm == RMODE_ADAM && !lean), fast};
+}
 void launch_apply_rows(const ApplyPair& p, int n, int opt, int G, int VEC, hipStream_t s);
 void launch_adam_dense(DensePair& p, int n, int G, int VEC, hipStream_t s, const FinArgs* fin = nullptr);
 void launch_gather(const GatherArgs& a, hipStream_t s);

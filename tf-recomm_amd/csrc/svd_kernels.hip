@@ -11,7 +11,6 @@
 // block sums and K1 itself, the gather-dot forward, are in forward_body.h, which the bf16 snapshot's forward
 // (bf16_rows.hip) shares; k_forward and k_front instantiate it on float32 rows.
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include <stdint.h>
 #include "svd_kernels.h"
 #include "forward_body.h"
@@ -1759,12 +1758,10 @@ __global__ __launch_bounds__(256) void k_auc_ranksum(const int32_t* __restrict__
 }
 
 void launch_auc_keys(const float* score, int32_t* keys, int64_t n, hipStream_t s) {
-    int64_t nb = (n + 255) / 256; if (nb > 2048) nb = 2048; if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(k_auc_keys, dim3((int)nb), dim3(256), 0, s, score, keys, n);
+    hipLaunchKernelGGL(k_auc_keys, dim3(blocks_for(n, 256, 2048)), dim3(256), 0, s, score, keys, n);
 }
 void launch_auc_ranksum(const int32_t* ks, const int32_t* ps, const float* label, int64_t n, unsigned long long* out, hipStream_t s) {
-    int64_t nb = (n + 255) / 256; if (nb > 2048) nb = 2048; if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(k_auc_ranksum, dim3((int)nb), dim3(256), 0, s, ks, ps, label, n, out);
+    hipLaunchKernelGGL(k_auc_ranksum, dim3(blocks_for(n, 256, 2048)), dim3(256), 0, s, ks, ps, label, n, out);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1805,52 +1802,34 @@ __global__ void k_init_uniform_scalar(float* p, float lo, float hi, uint64_t see
 // launch helpers
 template <int MODE, int UNR>
 static void launch_forward_mode(const FwdArgs& a, int G, int VEC, int grid, hipStream_t s) {
-    const bool pnt = forward_pnt(MODE, a.U, a.D);
-#define TFR_FWD_CASE(g, v) \
-    if (G == g && VEC == v) {                                                                                  \
-        if (pnt) hipLaunchKernelGGL((k_forward<g, v, MODE, UNR, true>), dim3(grid), dim3(256), 0, s, a);       \
-        else hipLaunchKernelGGL((k_forward<g, v, MODE, UNR, false>), dim3(grid), dim3(256), 0, s, a);          \
-        return;                                                                                                \
-    }
-    TFR_FWD_CASE(4, 4) TFR_FWD_CASE(8, 4) TFR_FWD_CASE(16, 4) TFR_FWD_CASE(32, 4) TFR_FWD_CASE(64, 4)
-    TFR_FWD_CASE(4, 1) TFR_FWD_CASE(8, 1) TFR_FWD_CASE(16, 1) TFR_FWD_CASE(32, 1) TFR_FWD_CASE(64, 1)
-#undef TFR_FWD_CASE
+    with_geometry(G, VEC, [&](auto g, auto v) {
+        with_bool(forward_pnt(MODE, a.U, a.D), [&](auto pnt) {
+            hipLaunchKernelGGL((k_forward<g.value, v.value, MODE, UNR, pnt.value>), dim3(grid), dim3(256), 0, s, a);
+        });
+    });
 }
 
 int forward_grid(int64_t B, int G, int mode, int unr) {
-    const int64_t per_block = 4 * (64 / G) * unr;   // waves * SPW * UNR
-    int64_t nb = (B + per_block - 1) / per_block;
-    const int64_t cap = (mode == MODE_INFER) ? 8192 : 2048;   // TRAIN/EVAL: fewer partials for K4
-    if (nb > cap) nb = cap;                              // then grid-stride
-    if (nb < 1) nb = 1;
-    return (int)nb;
+    // waves * SPW * UNR ratings per block; TRAIN/EVAL: fewer partials for K4; then grid-stride
+    return blocks_for(B, 4 * (64 / G) * unr, (mode == MODE_INFER) ? 8192 : 2048);
 }
 
 int front_forward_blocks(int64_t B, int G) {
-    const int64_t per_block = 16 * (64 / G) * 2;        // waves * SPW * UNR of k_front's forward part
-    int64_t nb = (B + per_block - 1) / per_block;
-    if (nb > 512) nb = 512;
-    if (nb < 1) nb = 1;
-    return (int)nb;
+    return blocks_for(B, 16 * (64 / G) * 2, 512);        // waves * SPW * UNR of k_front's forward part
 }
 
 void launch_front(const FrontArgs& fa, int G, int VEC, hipStream_t s) {
     const int nbmax = fa.c.nbins[0] > fa.c.nbins[1] ? fa.c.nbins[0] : fa.c.nbins[1];
     const dim3 grid(fa.nfwd + 2 * fa.c.ntiles);
-#define TFR_FRONT_CASE(g, v)                                                                          \
-    if (G == g && VEC == v) {                                                                         \
-        static bool attr = false;                                                                     \
-        if (!attr) {                                                                                  \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_front<g, v>),                   \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, CSORT_MAX_BINS * 4); \
-            attr = true;                                                                              \
-        }                                                                                             \
-        hipLaunchKernelGGL((k_front<g, v>), grid, dim3(1024), (size_t)nbmax * 4, s, fa);              \
-        return;                                                                                       \
-    }
-    TFR_FRONT_CASE(4, 4) TFR_FRONT_CASE(8, 4) TFR_FRONT_CASE(16, 4) TFR_FRONT_CASE(32, 4) TFR_FRONT_CASE(64, 4)
-    TFR_FRONT_CASE(4, 1) TFR_FRONT_CASE(8, 1) TFR_FRONT_CASE(16, 1) TFR_FRONT_CASE(32, 1) TFR_FRONT_CASE(64, 1)
-#undef TFR_FRONT_CASE
+    with_geometry(G, VEC, [&](auto g, auto v) {
+        static bool attr = false;                        // one per instantiation
+        if (!attr) {
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_front<g.value, v.value>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, CSORT_MAX_BINS * 4);
+            attr = true;
+        }
+        hipLaunchKernelGGL((k_front<g.value, v.value>), grid, dim3(1024), (size_t)nbmax * 4, s, fa);
+    });
 }
 
 int tile_step_epg(int ntiles, int G, int VEC) {
@@ -1860,8 +1839,7 @@ int tile_step_epg(int ntiles, int G, int VEC) {
     auto fits = [&](int e) {
         return (size_t)2 * e * 16 * G * VEC * 4 <= (size_t)64 * 1024 && tile_step_static_lds(G, e) + (size_t)64 * 1024 <= LDS_PER_CU;
     };
-    static int forced = -1;                              // TFR_EPG=1|2|4: A/B override
-    if (forced < 0) { const char* e = getenv("TFR_EPG"); forced = e ? atoi(e) : 0; }
+    static const int forced = (int)env_int("TFR_EPG", 0);   // TFR_EPG=1|2|4: A/B override
     if (forced == 1 || ((forced == 2 || forced == 4) && forced <= G && fits(forced))) return forced;
     int epg = 1;
     while (epg < 4 && epg < G && ntiles * (G / epg) * 2 > 256 && fits(2 * epg)) epg *= 2;
@@ -1874,21 +1852,19 @@ int tile_step_epg(int ntiles, int G, int VEC) {
 // than one EPG for both sides: off unless TFR_ITEM_SPLIT=1 (A/B).
 int tile_step_item_epg(int64_t B, int G, int VEC, int nsort) {
     const int epg = tile_step_epg((int)((B + 1023) / 1024), G, VEC);
-    static int split = -1;
-    if (split < 0) { const char* e = getenv("TFR_ITEM_SPLIT"); split = (e && e[0] == '1') ? 1 : 0; }
+    static const bool split = env_default_off("TFR_ITEM_SPLIT");
     if (!split || epg < 2) return epg;
     const int64_t epb = 1024 / G;
     const int64_t nu = (B + epb * epg - 1) / (epb * epg), ni = (B + epb * (epg / 2) - 1) / (epb * (epg / 2));
     return nsort + nu + ni <= 256 ? epg / 2 : epg;
 }
 int tile_step_one_barrier() {                            // TFR_ONE_BARRIER=1: A/B switch, measured slower
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("TFR_ONE_BARRIER"); on = (e && e[0] == '1') ? 1 : 0; }
+    static const bool on = env_default_off("TFR_ONE_BARRIER");
     return on;
 }
 int tile_step_wt() {                                     // TFR_WT=<bits>: A/B switch (TFR_WT_* in svd_kernels.h)
-    static int wt = -1;
-    if (wt < 0) { const char* e = getenv("TFR_WT"); wt = e ? (atoi(e) & 31) : TFR_WT_DEFAULT; }
+    static_assert((TFR_WT_DEFAULT & 31) == TFR_WT_DEFAULT, "five bits");
+    static const int wt = (int)env_int("TFR_WT", TFR_WT_DEFAULT) & 31;
     return wt;
 }
 
@@ -1906,26 +1882,18 @@ void launch_tile_step(const TileStepArgs& a0, int G, int VEC, hipStream_t s) {
     const int64_t epb = 1024 / G;
     const int nblk_u = (int)((a.B + epb * epg - 1) / (epb * epg)), nblk_i = (int)((a.B + epb * a.epg_item - 1) / (epb * a.epg_item));
     const dim3 grid(nsort + nblk_u + nblk_i);
-#define TFR_TS_LAUNCH(g, v, e)                                                                        \
-    {                                                                                                 \
-        static size_t attr = 0;              /* static + dynamic LDS must stay within 160 KB: ask for what is needed */ \
-        if (dyn > attr) {                                                                             \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_step<g, v, e>),              \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess) \
-                return;                      /* leaves the error for the caller's hipGetLastError() */ \
-            attr = dyn;                                                                               \
-        }                                                                                             \
-        hipLaunchKernelGGL((k_tile_step<g, v, e>), grid, dim3(1024), dyn, s, a, nsort, nblk_u);       \
-    }
-#define TFR_TS_CASE(g, v)                                                                             \
-    if (G == g && VEC == v) {                                                                         \
-        if (epg == 1) TFR_TS_LAUNCH(g, v, 1) else if (epg == 2) TFR_TS_LAUNCH(g, v, 2) else TFR_TS_LAUNCH(g, v, 4) \
-        return;                                                                                       \
-    }
-    TFR_TS_CASE(4, 4) TFR_TS_CASE(8, 4) TFR_TS_CASE(16, 4) TFR_TS_CASE(32, 4) TFR_TS_CASE(64, 4)
-    TFR_TS_CASE(4, 1) TFR_TS_CASE(8, 1) TFR_TS_CASE(16, 1) TFR_TS_CASE(32, 1) TFR_TS_CASE(64, 1)
-#undef TFR_TS_CASE
-#undef TFR_TS_LAUNCH
+    with_geometry(G, VEC, [&](auto g, auto v) {
+        with_one_of<1, 2, 4>(epg, [&](auto e) {
+            static size_t attr = 0;                      // one per instantiation; static + dynamic LDS must stay within 160 KB: ask for what is needed
+            if (dyn > attr) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_step<g.value, v.value, e.value>),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn) != hipSuccess)
+                    return;                              // no launch: leaves the error for the caller's hipGetLastError()
+                attr = dyn;
+            }
+            hipLaunchKernelGGL((k_tile_step<g.value, v.value, e.value>), grid, dim3(1024), dyn, s, a, nsort, nblk_u);
+        });
+    });
 }
 
 void launch_forward(const FwdArgs& a, int mode, int G, int VEC, int grid, hipStream_t s) {
@@ -1934,57 +1902,25 @@ void launch_forward(const FwdArgs& a, int mode, int G, int VEC, int grid, hipStr
     else launch_forward_mode<MODE_EVAL, 4>(a, G, VEC, grid, s);
 }
 
-static int entry_grid(int64_t B, int G) {
-    const int gpb = 256 / G;
-    int64_t nb = (B + gpb - 1) / gpb;
-    if (nb < 1) nb = 1;
-    return (int)nb;
+static int entry_grid(int64_t B, int G) { return blocks_for(B, 256 / G); }
+
+template <typename F, size_t... K>
+static bool with_red_pick(const RedPick& p, F&& f, std::index_sequence<K...>) {
+    return (... || ((p.rmode == RED_PICKS[K].rmode && p.fwd == RED_PICKS[K].fwd && p.lean == RED_PICKS[K].lean && p.fast == RED_PICKS[K].fast)
+                        ? (f(int_c<RED_PICKS[K].rmode>{}, bool_c<RED_PICKS[K].fwd>{}, bool_c<RED_PICKS[K].lean>{}, bool_c<RED_PICKS[K].fast>{}), true)
+                        : false));
 }
 
 void launch_seg_reduce(const RedPair& p, int n, int rmode, int G, int VEC, hipStream_t s, bool fwd) {
     int64_t B = p.a[0].B;
     if (n > 1 && p.a[1].B > B) B = p.a[1].B;
-    const int epb = 1024 / G;
-    int64_t nb = (B + epb - 1) / epb;
-    if (nb < 1) nb = 1;
-    const dim3 grid((int)nb, n);
-    static int lean = -1;                                // TFR_LEAN=0: A/B switch (own row kept in registers)
-    if (lean < 0) { const char* e = getenv("TFR_LEAN"); lean = (e && e[0] == '0') ? 0 : 1; }
-    // FAST: full-width rows (D = G * VEC), ids and rows from tables or packed exchange buffers (strides), with or without the
-    // two-table item form - the fused big-table step (api.hip run_train_step, `dual`) and the row-sharded step's item / user
-    // sides and its owners' apply (pre-reduced rows), the FM backward (16-byte entry records); not the per-position copies of
-    // the one-table form or tile mode.
-    // Its row loads are non-temporal whatever RedArgs::nt says.
-    static int fast_en = -1;                             // TFR_FAST=0: A/B switch
-    if (fast_en < 0) { const char* e = getenv("TFR_FAST"); fast_en = (e && e[0] == '0') ? 0 : 1; }
-    const RedArgs& a0 = p.a[0];
-    const bool fast_own = fast_en && lean && n == 1 && a0.rows_in && a0.bias_in && !fwd && !a0.tile && !a0.sel && !a0.ostride && !a0.obstride &&
-                          a0.D == G * VEC && a0.B > 0 && (rmode == RMODE_SCRATCH || a0.own == a0.own_w);
-    const bool fast = fast_own ||
-                      (fast_en && lean && n == 1 && !a0.rows_in && !a0.partner_by_pos && !a0.own_copy_out && !a0.tile &&
-                      a0.D == G * VEC && a0.B > 0 && (a0.other || a0.ent) && (!a0.ent || (!fwd && !a0.osel_in)) && (!a0.osel_in || a0.partner_alt) && (!a0.sel || (a0.own_alt && a0.own_alt == a0.own_w_alt)) &&
-                      (rmode == RMODE_SCRATCH || (a0.own == a0.own_w && !a0.ostride)) &&
-                      (fwd ? (a0.r && a0.partner_bias && !a0.osel_in) : ((a0.g || a0.ent) && !a0.sel)));
-#define TFR_RED_CASE(g, v)                                                                             \
-    if (G == g && VEC == v) {                                                                          \
-        if (fast && fwd && rmode == RMODE_ADAM) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_ADAM, true, true, true>), grid, dim3(1024), 0, s, p); \
-        else if (fast && fwd && rmode == RMODE_SCRATCH) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_SCRATCH, true, true, true>), grid, dim3(1024), 0, s, p); \
-        else if (fast && fwd) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_SGD, true, true, true>), grid, dim3(1024), 0, s, p); \
-        else if (fast && rmode == RMODE_SCRATCH) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_SCRATCH, false, true, true>), grid, dim3(1024), 0, s, p); \
-        else if (fast && rmode == RMODE_ADAM) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_ADAM, false, true, true>), grid, dim3(1024), 0, s, p); \
-        else if (fast) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_SGD, false, true, true>), grid, dim3(1024), 0, s, p); \
-        else if (fwd && rmode == RMODE_ADAM && !lean) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_ADAM, true, false>), grid, dim3(1024), 0, s, p); \
-        else if (fwd && rmode == RMODE_ADAM) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_ADAM, true>), grid, dim3(1024), 0, s, p); \
-        else if (fwd && rmode == RMODE_SCRATCH) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_SCRATCH, true>), grid, dim3(1024), 0, s, p); \
-        else if (fwd) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_SGD, true>), grid, dim3(1024), 0, s, p); \
-        else if (rmode == RMODE_SCRATCH) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_SCRATCH>), grid, dim3(1024), 0, s, p); \
-        else if (rmode == RMODE_ADAM) hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_ADAM>), grid, dim3(1024), 0, s, p);  \
-        else hipLaunchKernelGGL((k_seg_reduce<g, v, RMODE_SGD>), grid, dim3(1024), 0, s, p);           \
-        return;                                                                                        \
-    }
-    TFR_RED_CASE(4, 4) TFR_RED_CASE(8, 4) TFR_RED_CASE(16, 4) TFR_RED_CASE(32, 4) TFR_RED_CASE(64, 4)
-    TFR_RED_CASE(4, 1) TFR_RED_CASE(8, 1) TFR_RED_CASE(16, 1) TFR_RED_CASE(32, 1) TFR_RED_CASE(64, 1)
-#undef TFR_RED_CASE
+    const dim3 grid(blocks_for(B, 1024 / G), n);
+    const RedPick pick = seg_reduce_pick(p.a[0], n, rmode, fwd, G, VEC);
+    with_geometry(G, VEC, [&](auto g, auto v) {
+        with_red_pick(pick, [&](auto rm, auto fw, auto lean, auto fast) {
+            hipLaunchKernelGGL((k_seg_reduce<g.value, v.value, rm.value, fw.value, lean.value, fast.value>), grid, dim3(1024), 0, s, p);
+        }, std::make_index_sequence<sizeof(RED_PICKS) / sizeof(RED_PICKS[0])>{});
+    });
 }
 
 void launch_apply_rows(const ApplyPair& p, int n, int opt, int G, int VEC, hipStream_t s) {
@@ -1994,30 +1930,20 @@ void launch_apply_rows(const ApplyPair& p, int n, int opt, int G, int VEC, hipSt
     if (n > 1 && !p.a[1].only_split) all_split = false;
     if (all_split) B = (B + 1024 / G - 1) / (1024 / G);      // one lane group per piece boundary
     const dim3 grid(entry_grid(B, G) + (p.with_fin ? 1 : 0), n);
-#define TFR_APP_CASE(g, v)                                                                  \
-    if (G == g && VEC == v) {                                                               \
-        if (opt == 0) hipLaunchKernelGGL((k_apply_rows<g, v, 0>), grid, dim3(256), 0, s, p); \
-        else if (opt == 1) hipLaunchKernelGGL((k_apply_rows<g, v, 1>), grid, dim3(256), 0, s, p); \
-        else hipLaunchKernelGGL((k_apply_rows<g, v, 2>), grid, dim3(256), 0, s, p);         \
-        return;                                                                             \
-    }
-    TFR_APP_CASE(4, 4) TFR_APP_CASE(8, 4) TFR_APP_CASE(16, 4) TFR_APP_CASE(32, 4) TFR_APP_CASE(64, 4)
-    TFR_APP_CASE(4, 1) TFR_APP_CASE(8, 1) TFR_APP_CASE(16, 1) TFR_APP_CASE(32, 1) TFR_APP_CASE(64, 1)
-#undef TFR_APP_CASE
+    with_geometry(G, VEC, [&](auto g, auto v) {
+        with_one_of<0, 1, 2>(opt == 0 || opt == 1 ? opt : 2, [&](auto o) {
+            hipLaunchKernelGGL((k_apply_rows<g.value, v.value, o.value>), grid, dim3(256), 0, s, p);
+        });
+    });
 }
 
 int sweep_rounds() {                                     // TFR_SWEEP_ROUNDS=0: A/B switch, the general form of k_dense_tiles everywhere
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("TFR_SWEEP_ROUNDS"); on = (e && e[0] == '0') ? 0 : 1; }
+    static const bool on = env_default_on("TFR_SWEEP_ROUNDS");
     return on;
 }
 
 int dense_tiles_grid(int64_t rows, int G) {              // block columns that hold rows (the launch adds one for K4)
-    const int gpb = 256 / G;
-    int64_t nb = (rows + gpb - 1) / gpb;
-    if (nb > 4096) nb = 4096;
-    if (nb < 1) nb = 1;
-    return (int)nb;
+    return blocks_for(rows, 256 / G, 4096);
 }
 
 // the three-round form has no row loop and no width guards: full-width rows, one lane group per row in the grid
@@ -2025,28 +1951,20 @@ bool dense_tiles_rounds_taken(int64_t rows, int D, int G, int VEC) {
     return sweep_rounds() && VEC == 4 && D == G * VEC && rows <= (int64_t)dense_tiles_grid(rows, G) * (256 / G);
 }
 
-#define TFR_DT_PICK(g, v, wr, nt) TFR_DT_DO((k_dense_tiles<g, v, wr, nt>))
-#define TFR_DT_CASE(g, v)                                                                         \
-    if (G == g && VEC == v) {                                                                     \
-        if (write) {                                                                              \
-            if (nt <= 4) TFR_DT_PICK(g, v, true, 4); else if (nt <= 8) TFR_DT_PICK(g, v, true, 8);          \
-            else if (nt <= 10) TFR_DT_PICK(g, v, true, 10);                                                 \
-            else if (nt <= 12) TFR_DT_PICK(g, v, true, 12); else TFR_DT_PICK(g, v, true, 16);               \
-        } else {                                                                                  \
-            if (nt <= 4) TFR_DT_PICK(g, v, false, 4); else if (nt <= 8) TFR_DT_PICK(g, v, false, 8);        \
-            else if (nt <= 10) TFR_DT_PICK(g, v, false, 10);                                                \
-            else if (nt <= 12) TFR_DT_PICK(g, v, false, 12); else TFR_DT_PICK(g, v, false, 16);             \
-        }                                                                                         \
-    }
-#define TFR_DT_ALL                                                                                \
-    TFR_DT_CASE(4, 4) TFR_DT_CASE(8, 4) TFR_DT_CASE(16, 4) TFR_DT_CASE(32, 4) TFR_DT_CASE(64, 4)  \
-    TFR_DT_CASE(4, 1) TFR_DT_CASE(8, 1) TFR_DT_CASE(16, 1) TFR_DT_CASE(32, 1) TFR_DT_CASE(64, 1)
+// f(the k_dense_tiles instantiation for this geometry, mode and tile count): the launcher and dense_tiles_kernel pick by this
+template <typename F>
+static bool with_dense_tiles(bool write, int G, int VEC, int ntiles, F&& f) {
+    return with_geometry(G, VEC, [&](auto g, auto v) {
+        with_bool(write, [&](auto wr) {
+            with_one_of<4, 8, 10, 12, 16>(dense_tiles_nt(ntiles), [&](auto nt) { f(k_dense_tiles<g.value, v.value, wr.value, nt.value>); });
+        });
+    });
+}
 
-const void* dense_tiles_kernel(bool write, int G, int VEC, int nt) {
-#define TFR_DT_DO(k) return reinterpret_cast<const void*>(&k)
-    TFR_DT_ALL
-#undef TFR_DT_DO
-    return nullptr;
+const void* dense_tiles_kernel(bool write, int G, int VEC, int ntiles) {
+    const void* k = nullptr;
+    with_dense_tiles(write, G, VEC, ntiles, [&](auto* kernel) { k = reinterpret_cast<const void*>(kernel); });
+    return k;
 }
 
 void launch_dense_tiles(const TileDenseLaunch& L, bool write, bool with_fin, int G, int VEC, hipStream_t s) {
@@ -2056,48 +1974,22 @@ void launch_dense_tiles(const TileDenseLaunch& L, bool write, bool with_fin, int
     LL.with_fin = with_fin ? 1 : 0;
     LL.wt = tile_step_wt() & (TFR_WT_ROWS | TFR_WT_MOMENTS | TFR_WT_BIAS);
     LL.rounds = (L.a[0].D == L.a[1].D && dense_tiles_rounds_taken(rows, L.a[0].D, G, VEC)) ? 1 : 0;
-    const int nt = L.a[0].ntiles;
-#define TFR_DT_DO(k) do { hipLaunchKernelGGL(k, grid, dim3(256), 0, s, LL); return; } while (0)
-    TFR_DT_ALL
-#undef TFR_DT_DO
+    with_dense_tiles(write, G, VEC, L.a[0].ntiles, [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, LL); });
 }
-#undef TFR_DT_ALL
-#undef TFR_DT_CASE
-#undef TFR_DT_PICK
 
 void launch_adam_dense(DensePair& p, int n, int G, int VEC, hipStream_t s, const FinArgs* fin) {
     if (fin) { p.f = *fin; n = 3; }
-    const int gpb = 256 / G;
     int64_t rows = p.a[0].rows;
     if (n > 1 && p.a[1].rows > rows) rows = p.a[1].rows;
-    int64_t nb = (rows + gpb - 1) / gpb;
-    if (nb > 4096) nb = 4096;
-    if (nb < 1) nb = 1;
-    const dim3 grid((int)nb, n);
-#define TFR_DEN_CASE(g, v) \
-    if (G == g && VEC == v) { hipLaunchKernelGGL((k_adam_dense<g, v>), grid, dim3(256), 0, s, p); return; }
-    TFR_DEN_CASE(4, 4) TFR_DEN_CASE(8, 4) TFR_DEN_CASE(16, 4) TFR_DEN_CASE(32, 4) TFR_DEN_CASE(64, 4)
-    TFR_DEN_CASE(4, 1) TFR_DEN_CASE(8, 1) TFR_DEN_CASE(16, 1) TFR_DEN_CASE(32, 1) TFR_DEN_CASE(64, 1)
-#undef TFR_DEN_CASE
+    const dim3 grid(blocks_for(rows, 256 / G, 4096), n);
+    with_geometry(G, VEC, [&](auto g, auto v) { hipLaunchKernelGGL((k_adam_dense<g.value, v.value>), grid, dim3(256), 0, s, p); });
 }
 
-static int flat_grid(int64_t n) {
-    int64_t nb = (n + 255) / 256;
-    if (nb > 2048) nb = 2048;
-    if (nb < 1) nb = 1;
-    return (int)nb;
-}
+static int flat_grid(int64_t n) { return blocks_for(n, 256, 2048); }
 
 void launch_gather_rows(const GatherRowsArgs& a, int G, int VEC, hipStream_t s) {
-    const int gpb = 256 / G;
-    int64_t nb = (a.n + gpb - 1) / gpb;
-    if (nb > 8192) nb = 8192;
-    if (nb < 1) nb = 1;
-#define TFR_GR_CASE(g, v) \
-    if (G == g && VEC == v) { hipLaunchKernelGGL((k_gather_rows<g, v>), dim3((int)nb), dim3(256), 0, s, a); return; }
-    TFR_GR_CASE(4, 4) TFR_GR_CASE(8, 4) TFR_GR_CASE(16, 4) TFR_GR_CASE(32, 4) TFR_GR_CASE(64, 4)
-    TFR_GR_CASE(4, 1) TFR_GR_CASE(8, 1) TFR_GR_CASE(16, 1) TFR_GR_CASE(32, 1) TFR_GR_CASE(64, 1)
-#undef TFR_GR_CASE
+    const dim3 grid(blocks_for(a.n, 256 / G, 8192));
+    with_geometry(G, VEC, [&](auto g, auto v) { hipLaunchKernelGGL((k_gather_rows<g.value, v.value>), grid, dim3(256), 0, s, a); });
 }
 
 void launch_gather(const GatherArgs& a, hipStream_t s) {
@@ -2127,10 +2019,7 @@ __global__ __launch_bounds__(256) void k_gather_recs(const int64_t* __restrict__
 }
 
 void launch_gather_recs(const int64_t* ids, const void* store, void* recs, int64_t n, int64_t N, hipStream_t s) {
-    int64_t nb = (n + 255) / 256;
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(k_gather_recs, dim3((unsigned)nb), dim3(256), 0, s, ids, reinterpret_cast<const int4*>(store), reinterpret_cast<int4*>(recs), n, N);
+    hipLaunchKernelGGL(k_gather_recs, dim3(blocks_for(n, 256, 1024)), dim3(256), 0, s, ids, reinterpret_cast<const int4*>(store), reinterpret_cast<int4*>(recs), n, N);
 }
 
 // two-table form of the big-table step: bring every row that currently lives in the alternate table back to the main
@@ -2146,10 +2035,7 @@ __global__ __launch_bounds__(256) void k_settle_alt(float* __restrict__ main_t, 
 }
 
 void launch_settle_alt(float* main_t, const float* alt_t, int32_t* sel, int64_t rows, int D, hipStream_t s) {
-    int64_t nb = (rows + 3) / 4;
-    if (nb > 16384) nb = 16384;
-    if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(k_settle_alt, dim3((int)nb), dim3(256), 0, s, main_t, alt_t, sel, rows, D);
+    hipLaunchKernelGGL(k_settle_alt, dim3(blocks_for(rows, 4, 16384)), dim3(256), 0, s, main_t, alt_t, sel, rows, D);
 }
 
 void launch_finalize(const FinArgs& a, hipStream_t s) {

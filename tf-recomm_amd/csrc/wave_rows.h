@@ -61,14 +61,7 @@ __device__ __forceinline__ void update_at(float* w, float* m, float* v, int64_t 
 // ---- host side -----------------------------------------------------------------------------------------------------------
 // NJ from D, once: f(std::integral_constant<int, NJ>) with NJ = ceil(D / 64) in 1..4 (the entry points hold D <= 256)
 template <typename F>
-inline void with_nj(int D, F&& f) {
-    switch ((D + 63) / 64) {
-        case 1: f(std::integral_constant<int, 1>{}); break;
-        case 2: f(std::integral_constant<int, 2>{}); break;
-        case 3: f(std::integral_constant<int, 3>{}); break;
-        default: f(std::integral_constant<int, 4>{}); break;
-    }
-}
+inline void with_nj(int D, F&& f) { with_one_of<1, 2, 3, 4>(D > 0 && D <= 192 ? (D + 63) / 64 : 4, f); }
 
 inline dim3 wave_grid(int64_t waves) { return dim3((unsigned)((waves + ROW_WAVES - 1) / ROW_WAVES)); }
 inline dim3 wave_block() { return dim3(64 * ROW_WAVES); }
