@@ -13,6 +13,7 @@ from tfrecomm_amd import _lib as L
 from tfrecomm_amd import adaptive_test as AT
 from tfrecomm_amd import finetune as FT
 from tests.finetune_ref import OracleDriverModel, per_user_frame
+from tests.finetune_step_ref import powers_at
 from tests.util import assert_close, rand_tables
 from tests import widths as W
 
@@ -122,14 +123,6 @@ def _sub(s, x):
             prefix[k0:k1], E)
 
 
-def _powers_at(b1p, b2p, b1, b2, n):
-    """the model's float32 beta-power recurrence, n steps on"""
-    b1p, b2p, b1, b2 = np.float32(b1p), np.float32(b2p), np.float32(b1), np.float32(b2)
-    for _ in range(n):
-        b1p, b2p = np.float32(b1p * b1), np.float32(b2p * b2)
-    return float(b1p), float(b2p)
-
-
 @pytest.mark.parametrize("opt,D", [("sgd", 20), ("lazy", 5), ("lazy", 64), ("lazy", 256), ("lazy", 192)])
 def test_a_user_alone_and_among_1000_others_is_bit_identical(opt, D):
     U, I = 1200, 500
@@ -153,7 +146,7 @@ def test_a_user_alone_and_among_1000_others_is_bit_identical(opt, D):
         assert a.get_step() == b.get_step()
         # user x alone, started at the beta powers its first round had inside the big call (position k0 * E)
         st = c.get_step()
-        c.set_step(st[0], *(_powers_at(st[1], st[2], 0.9, 0.999, k0 * s[7]) if opt == "lazy" else st[1:]))
+        c.set_step(st[0], *(powers_at(st[1], st[2], 0.9, 0.999, k0 * s[7]) if opt == "lazy" else st[1:]))
         rc = c.finetune_users(*_sub(s, x))
         assert np.array_equal(rc[0], ra[0][k0:k1]) and np.array_equal(rc[1], ra[1][k0:k1])
         assert np.array_equal(rc[2], ra[2][r0:r1], equal_nan=True)
@@ -168,7 +161,7 @@ def test_a_user_alone_and_among_1000_others_is_bit_identical(opt, D):
             assert np.array_equal(after[w], before[w])
         assert a.step == int(s[4][-1]) * s[7]
         if opt == "lazy":
-            assert a.get_step()[1:] == _powers_at(0.9, 0.999, 0.9, 0.999, a.step)
+            assert a.get_step()[1:] == powers_at(0.9, 0.999, 0.9, 0.999, a.step)
 
 
 @pytest.mark.parametrize("opt", ["sgd", "lazy"])
