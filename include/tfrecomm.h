@@ -719,6 +719,25 @@ int tfr_bf16_eval(tfr_model* m, const int32_t* user, const int32_t* item, const 
                   double* sum_sq_err_out, int64_t* n_equal_out, double* nll_sum_out);
 int tfr_bf16_get_rows(tfr_model* m, int32_t which, uint16_t* host, int64_t n);
 int tfr_bf16_row_stride(int32_t dim);
+/* Top-K from the snapshot - DESIGN §24.  Everything tfr_topk / tfr_topk_dev document holds: 1 <= k <= 256, duplicate users,
+ *      n_users = 0 a no-op, the exclusion CSR and its checks, item -1 / score -INFINITY past the eligible items, NaN scores
+ *      never returned, order by score descending then item id ascending, the deferred TFR_ERR_OOB of the device entry, the
+ *      host entry synchronises and the device entry does not, scores_out may be NULL; the launch plan is tfr_topk_plan's.
+ *      Only the score differs: ((dot + mu) + bu[u]) + bi[i] on the snapshot's tables, dot = the float32 sum of the exact
+ *      products of the snapshot's bf16 elements P[u,f] * Q'[i,f] (Q' = |Q| with item_abs), taken 16 features per matrix
+ *      instruction (v_mfma_f32_32x32x16_bf16) in ascending order from +0.  It is not the fmaf chain of tfr_topk, and not
+ *      bit-equal to tfr_bf16_forward on the same pair; it agrees with both on the snapshot's values to float32 rounding.
+ *      Results are bit-identical from run to run and across batch, chunk and slice composition.  Products or partial sums
+ *      in the float32 subnormal range are unspecified: the instruction may flush them.
+ *      Both return TFR_ERR_STATE (naming tfr_bf16_snapshot) before a snapshot, also for n_users = 0.  They read the
+ *      snapshot only: the float32 tables, training, tfr_set_table and the inverse-norm caches neither see nor move
+ *      anything. */
+int tfr_bf16_topk(tfr_model* m, const int32_t* users, int64_t n_users, int32_t k,
+                  const int64_t* excl_indptr, const int32_t* excl_items,
+                  int32_t* items_out, float* scores_out);
+int tfr_bf16_topk_dev(tfr_model* m, const int32_t* d_users, int64_t n_users, int32_t k,
+                      const int64_t* d_excl_indptr, const int32_t* d_excl_items,
+                      int32_t* d_items_out, float* d_scores_out);
 
 /* ---- misc ------------------------------------------------------------------------------ */
 int tfr_sync(tfr_model* m);            /* drains the stream; reports deferred TFR_ERR_OOB   */

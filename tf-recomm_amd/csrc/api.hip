@@ -3434,10 +3434,11 @@ static int sliced_dev(tfr_model* m, const Query& q, const int32_t* d_ids, int64_
     return TFR_OK;
 }
 
-// ---- top-K recommendation: its query, its argument checks and its entries ---------------------------------------------------
+// ---- top-K recommendation: its queries (float32 tables, bf16 snapshot), their argument checks and the entries --------------
 struct TopkQuery : SlicedQuery {
     TopkTables t;
     explicit TopkQuery(const TopkTables& t_) : SlicedQuery{"top-K", t_.n_items, t_.n_items, t_.item_abs, true}, t(t_) {}
+    int64_t users() const { return t.U; }
     void score(const SlicedArgs& c, const TopkPlan& p, hipStream_t s) const {
         TopkArgs a = {};
         static_cast<SlicedArgs&>(a) = c;
@@ -3447,26 +3448,53 @@ struct TopkQuery : SlicedQuery {
     }
 };
 
+// the same query on the model's bf16 snapshot, which was settled when it was made and is all the kernel reads
+struct Bf16TopkQuery : SlicedQuery {
+    tfr_model* m;
+    explicit Bf16TopkQuery(tfr_model* m_) : SlicedQuery{"bf16 top-K", m_->I, m_->I, m_->o.item_abs, false}, m(m_) {}
+    int64_t users() const { return m->U; }
+    void score(const SlicedArgs& c, const TopkPlan& p, hipStream_t s) const {
+        Bf16TopkArgs a = {};
+        static_cast<SlicedArgs&>(a) = c;
+        a.P = m->bf.p; a.bu = m->bf.bu; a.Q = m->bf.q; a.bi = m->bf.bi; a.mu = m->bf.mu;
+        a.U = m->U; a.n_items = m->I; a.DP = bf16_row_stride(m->D);
+        launch_bf16_topk_score(a, p, s);
+    }
+};
+
+template <class Query>
+static int topk_host(tfr_model* m, const Query& q, const int32_t* users, int64_t n, int32_t k, const int64_t* indptr,
+                     const int32_t* excl, int32_t* items_out, float* scores_out) {
+    if (n < 0) return fail(TFR_ERR_ARG, "%s: negative n_users", q.who);
+    int rc = check_k(q.who, k);
+    if (rc || n == 0) return rc;
+    if (!users || !items_out) return fail(TFR_ERR_ARG, "%s: null users / items_out", q.who);
+    if (indptr && !excl && indptr[n] > indptr[0]) return fail(TFR_ERR_ARG, "%s: exclusion indptr without items", q.who);
+    if ((rc = check_ids(q.who, "user id", users, n, q.users()))) return rc;
+    if (indptr && (rc = check_csr(q.who, false, indptr, excl, n, q.n_cand))) return rc;
+    return sliced_host(m, q, users, n, k, indptr, excl, items_out, scores_out);
+}
+
+template <class Query>
+static int topk_dev(tfr_model* m, const Query& q, const int32_t* d_users, int64_t n, int32_t k,
+                    const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t* d_items_out, float* d_scores_out) {
+    if (n < 0) return fail(TFR_ERR_ARG, "%s: negative n_users", q.who);
+    const int rc = check_k(q.who, k);
+    if (rc || n == 0) return rc;
+    if (!d_users || !d_items_out) return fail(TFR_ERR_ARG, "%s: null users / items_out", q.who);
+    if (d_excl_indptr && !d_excl_items) return fail(TFR_ERR_ARG, "%s: exclusion indptr without items", q.who);
+    return sliced_dev(m, q, d_users, n, k, d_excl_indptr, d_excl_items, d_items_out, d_scores_out);
+}
+
+// the float32 tables' entries (SVD, FM, SVD++) name their tables
 static int topk_host(tfr_model* m, const TopkTables& t, const int32_t* users, int64_t n, int32_t k, const int64_t* indptr,
                      const int32_t* excl, int32_t* items_out, float* scores_out) {
-    if (n < 0) return fail(TFR_ERR_ARG, "top-K: negative n_users");
-    int rc = check_k("top-K", k);
-    if (rc || n == 0) return rc;
-    if (!users || !items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
-    if (indptr && !excl && indptr[n] > indptr[0]) return fail(TFR_ERR_ARG, "top-K: exclusion indptr without items");
-    if ((rc = check_ids("top-K", "user id", users, n, t.U))) return rc;
-    if (indptr && (rc = check_csr("top-K", false, indptr, excl, n, t.n_items))) return rc;
-    return sliced_host(m, TopkQuery(t), users, n, k, indptr, excl, items_out, scores_out);
+    return topk_host(m, TopkQuery(t), users, n, k, indptr, excl, items_out, scores_out);
 }
 
 static int topk_dev(tfr_model* m, const TopkTables& t, const int32_t* d_users, int64_t n, int32_t k,
                     const int64_t* d_excl_indptr, const int32_t* d_excl_items, int32_t* d_items_out, float* d_scores_out) {
-    if (n < 0) return fail(TFR_ERR_ARG, "top-K: negative n_users");
-    const int rc = check_k("top-K", k);
-    if (rc || n == 0) return rc;
-    if (!d_users || !d_items_out) return fail(TFR_ERR_ARG, "top-K: null users / items_out");
-    if (d_excl_indptr && !d_excl_items) return fail(TFR_ERR_ARG, "top-K: exclusion indptr without items");
-    return sliced_dev(m, TopkQuery(t), d_users, n, k, d_excl_indptr, d_excl_items, d_items_out, d_scores_out);
+    return topk_dev(m, TopkQuery(t), d_users, n, k, d_excl_indptr, d_excl_items, d_items_out, d_scores_out);
 }
 
 extern "C" {
@@ -3487,6 +3515,21 @@ int tfr_topk_dev(tfr_model* m, const int32_t* d_users, int64_t n, int32_t k, con
                  const int32_t* d_excl_items, int32_t* d_items_out, float* d_scores_out) {
     MODEL_ENTER(m);
     return topk_dev(m, svd_topk_tables(m), d_users, n, k, d_excl_indptr, d_excl_items, d_items_out, d_scores_out);
+}
+
+// the snapshot test comes before every other check, n_users == 0 included, as in the other tfr_bf16_* entries
+int tfr_bf16_topk(tfr_model* m, const int32_t* users, int64_t n_users, int32_t k, const int64_t* excl_indptr,
+                  const int32_t* excl_items, int32_t* items_out, float* scores_out) {
+    MODEL_ENTER(m);
+    if (int rc = bf16_need_snapshot(m)) return rc;
+    return topk_host(m, Bf16TopkQuery(m), users, n_users, k, excl_indptr, excl_items, items_out, scores_out);
+}
+
+int tfr_bf16_topk_dev(tfr_model* m, const int32_t* d_users, int64_t n, int32_t k, const int64_t* d_excl_indptr,
+                      const int32_t* d_excl_items, int32_t* d_items_out, float* d_scores_out) {
+    MODEL_ENTER(m);
+    if (int rc = bf16_need_snapshot(m)) return rc;
+    return topk_dev(m, Bf16TopkQuery(m), d_users, n, k, d_excl_indptr, d_excl_items, d_items_out, d_scores_out);
 }
 
 int tfr_fm_topk(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_t item_lo, int64_t item_hi, int32_t k,

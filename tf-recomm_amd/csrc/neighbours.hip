@@ -42,6 +42,10 @@ struct NbScorer {
         : a(a_), brow(a_.T + (int64_t)(q < 0 ? 0 : q) * a_.D), qid(q), cosine(a_.rn != nullptr),
           rq(cosine && q >= 0 ? a_.rn[q] : 0.f) {}
     __device__ __forceinline__ const float* arow(int64_t cand) const { return a.T + cand * a.D; }
+    template <bool V4>
+    __device__ __forceinline__ f32x16 tile(int64_t cand, int h) const {
+        return mfma_tile_dot<V4, ABS_B>(arow(cand), brow, a.D, a.item_abs, h);
+    }
     __device__ __forceinline__ bool eligible(int64_t cand) const { return cand != qid; }
     __device__ __forceinline__ float score(float dot, int64_t cand) const { return cosine ? (dot * rq) * a.rn[cand] : dot; }
 };

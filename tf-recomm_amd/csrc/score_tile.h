@@ -1,7 +1,7 @@
 // score_tile.h - the pieces topk.hip, rank.hip and neighbours.hip share: the 64-bit ordering key of a scored pair, the one-wave
 // bitonic sort of keys in LDS, the queue compaction built on it, the MFMA tile that scores 32 items against 32 user
-// columns, and sliced_topk_block, the whole scoring block of k_topk_score and k_nb_score, which differ only in their scorer
-// (DESIGN §11, §13, §17).
+// columns (on float32 rows, and on the bf16 snapshot's), and sliced_topk_block, the whole scoring block of k_topk_score,
+// k_nb_score and k_topk_score_bf16, which differ only in their scorer.
 //
 // key(s, item) = (order-preserving uint32 of s) << 32 | ~item: one 64-bit compare orders by score descending, then item id
 // ascending; every non-NaN score gives a key above 0, so key 0 marks an empty slot.
@@ -114,13 +114,57 @@ __device__ __forceinline__ f32x16 mfma_tile_dot(const float* qrow, const float* 
     return acc;
 }
 
-// The scoring block of "the best k candidates by a tile score" (k_topk_score, k_nb_score).  A block owns a tile of UPB query
-// rows (the 32 columns of a 32x32x2 f32 MFMA) and one slice of the candidates [cand_lo, cand_hi).  Every round each of its 4
-// waves scores a 32-candidate sub-tile against the tile's queries and appends the keys that beat its query's running k-th key
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// The same tile on rows of the bf16 snapshot (bf16_rows.h: uint16_t rows at a stride of DP = 8 * ceil(D / 8), 16-byte aligned,
+// pads +0), with the same return contract.  A row is NF = DP / 8 fragments of 8 elements, each the operand fragment of
+// v_mfma_f32_32x32x16_bf16 as it stands: step s = 0 .. ceil(NF / 2) - 1 gives fragment 2 s + h of the candidate row as A
+// (sign bits cleared with item_abs: the bits of fabsf on the widened value) and of the query row as B, one 16-byte load each,
+// steps ascending from a zero accumulator, loaded in groups of four steps ahead of their MFMAs.  With NF odd the upper
+// half-wave has no fragment in the last step: its loads are aimed at the row's first fragment - a valid address, no load
+// is guarded - and both operands are replaced by zero afterwards; one side alone would leave 0 * inf = NaN from
+// the redirected fragment in every score of the tile.
+__device__ __forceinline__ f32x16 mfma_tile_dot_bf16(const uint16_t* qrow, const uint16_t* prow, int DP, int item_abs, int h) {
+    const int NF = DP >> 3, steps = (NF + 1) >> 1;
+    const u32x4* qf = reinterpret_cast<const u32x4*>(qrow);
+    const u32x4* pf = reinterpret_cast<const u32x4*>(prow);
+    const uint32_t keep = item_abs ? 0x7fff7fffu : 0xffffffffu;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int s0 = 0; s0 < steps; s0 += 4) {
+        u32x4 qa[4], pb[4];
+#pragma unroll
+        for (int z = 0; z < 4; ++z)
+            if (s0 + z < steps) {
+                const int f = 2 * (s0 + z) + h;
+                const int at = f < NF ? f : 0;
+                qa[z] = qf[at];
+                pb[z] = pf[at];
+            }
+#pragma unroll
+        for (int z = 0; z < 4; ++z) {
+            if (s0 + z < steps) {
+                const bool has = 2 * (s0 + z) + h < NF;
+                const u32x4 a = has ? qa[z] & keep : (u32x4)0u;
+                const u32x4 b = has ? pb[z] : (u32x4)0u;
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc,
+                                                              0, 0, 0);
+            }
+        }
+    }
+    return acc;
+}
+
+// The scoring block of "the best k candidates by a tile score" (k_topk_score, k_nb_score, k_topk_score_bf16).  A block owns a
+// tile of UPB query rows (the 32 columns of a 32x32 MFMA tile) and one slice of the candidates [cand_lo, cand_hi).  Every
+// round each of its 4 waves scores a 32-candidate sub-tile against the tile's queries and appends the keys that beat its query's running k-th key
 // (and are eligible, not NaN and not excluded, tested in that order) to that query's LDS queue.  Between rounds a queue that
 // could not take another round is sorted (bitonic, one wave), cut to k and its threshold raised.  At the end every queue is
 // sorted and its first k keys go to part[row, slice].  Query ids outside [0, id_rows) set err bit 0 and score nothing.
-// Scorer(a, qid) is built once per lane: ABS_B, brow (the query's B row), arow(cand), eligible(cand), score(dot, cand).
+// Scorer(a, qid) is built once per lane: tile<V4>(cand, h) (the tile of the lane's candidate row against its query row: the
+// scorer picks the row format and with it the MFMA), eligible(cand), score(dot, cand).
 template <int UPB, int CAP, bool V4, class Scorer, class Args>
 __device__ __forceinline__ void sliced_topk_block(const Args& a, int64_t id_rows, int64_t cand_lo, int64_t cand_hi) {
     __shared__ uint64_t queue[UPB * CAP];
@@ -162,7 +206,7 @@ __device__ __forceinline__ void sliced_topk_block(const Args& a, int64_t id_rows
         const int64_t base = s_lo + rd * TOPK_ROUND + wave * TOPK_SUB;
         int64_t my_cand = base + c;                    // A row = candidate; past the slice: a row inside it, result dropped
         if (my_cand >= s_hi) my_cand = s_hi - 1;
-        const f32x16 acc = mfma_tile_dot<V4, Scorer::ABS_B>(sc.arow(my_cand), sc.brow, a.D, a.item_abs, h);
+        const f32x16 acc = sc.template tile<V4>(my_cand, h);
         // C[candidate row][query column]: this lane holds query j, candidates base + (r&3) + 8(r>>2) + 4h
         const uint64_t th = thr[j];
         if (live) {

@@ -83,6 +83,17 @@ struct TopkArgs : SlicedArgs {
     int64_t U, n_items;
 };
 
+// the same scores from the bf16 snapshot (bf16_rows.h): P and Q are snapshot rows at a stride of DP elements, the biases and
+// mu the snapshot's float32 copies of the same moment.  dot = the f32 sum of the exact products of the bf16 elements, 16
+// features per v_mfma_f32_32x32x16_bf16, ascending from +0 (score_tile.h mfma_tile_dot_bf16).
+struct Bf16TopkArgs : SlicedArgs {
+    const uint16_t* P; const float* bu;
+    const uint16_t* Q; const float* bi;
+    const float* mu;
+    int64_t U, n_items;
+    int32_t DP;
+};
+
 struct TopkMergeArgs {
     const uint64_t* part;
     int32_t* items_out; float* scores_out;             // [n_rows, k]; scores may be NULL
@@ -91,6 +102,7 @@ struct TopkMergeArgs {
 };
 
 void launch_topk_score(const TopkArgs& a, const TopkPlan& p, hipStream_t s);
+void launch_bf16_topk_score(const Bf16TopkArgs& a, const TopkPlan& p, hipStream_t s);   // bf16_topk.hip
 void launch_topk_merge(const TopkMergeArgs& a, hipStream_t s);
 // the device entry's exclusion check: ids in [0, n_items) (else err |= 1) and rows non-decreasing (else err |= 16);
 // either sets *bad, which makes the scoring kernel ignore the exclusions

@@ -21,6 +21,10 @@ struct TopkScorer {
     __device__ __forceinline__ TopkScorer(const TopkArgs& a_, int32_t user)
         : a(a_), brow(a_.P + (int64_t)(user < 0 ? 0 : user) * a_.D), mu(*a_.mu), ub(user >= 0 ? a_.bu[user] : 0.f) {}
     __device__ __forceinline__ const float* arow(int64_t item) const { return a.Q + item * a.D; }
+    template <bool V4>
+    __device__ __forceinline__ f32x16 tile(int64_t item, int h) const {
+        return mfma_tile_dot<V4, ABS_B>(arow(item), brow, a.D, a.item_abs, h);
+    }
     __device__ __forceinline__ bool eligible(int64_t) const { return true; }
     __device__ __forceinline__ float score(float dot, int64_t item) const { return ((dot + mu) + ub) + a.bi[item]; }
 };

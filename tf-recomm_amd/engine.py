@@ -357,19 +357,34 @@ class SvdModel:
         NLL head), best first, equal scores by item id.  ``exclude``: None, an (indptr, indices) CSR aligned with ``users``,
         or a ``scipy.sparse`` ``[user_num, item_num]`` matrix of rated items (``rated_matrix``).  Returns ``items`` int32
         ``[n, k]`` (-1 past the eligible items) and, if asked, ``scores`` float32 ``[n, k]`` (-inf there)."""
-        u = L.as_i32(users, "user ids").reshape(-1)
-        indptr, excl = exclusion_csr(exclude, u)
-        items = np.empty((u.size, int(k)), np.int32)
-        scores = np.empty((u.size, int(k)), np.float32) if return_scores else None
-        L.check(self._lib.tfr_topk(self._h, L.ptr_i32(u), u.size, int(k),
-                                   None if indptr is None else L.ptr_i64(indptr), None if excl is None else L.ptr_i32(excl),
-                                   L.ptr_i32(items), None if scores is None else L.ptr_f32(scores)))
-        return (items, scores) if return_scores else items
+        return self._recommend(self._lib.tfr_topk, users, k, exclude, return_scores)
 
     def recommend_dev(self, users, k=10, exclude=None, return_scores=True):
         """``recommend`` on torch device tensors (``users`` int32; ``exclude`` None or an (indptr int64, items int32) pair
         of device tensors aligned with ``users``), asynchronous: ordered after torch's current stream, and that stream
         after it.  An id or order error in the inputs surfaces at the next ``sync()``."""
+        return self._recommend_dev(self._lib.tfr_topk_dev, users, k, exclude, return_scores)
+
+    def recommend_bf16(self, users, k=10, exclude=None, return_scores=True):
+        """``recommend`` from the bf16 snapshot (``snapshot_bf16``): the same arguments and return values, the scores of the
+        snapshot's tables with the dot taken 16 features per bf16 matrix instruction (include/tfrecomm.h tfr_bf16_topk)."""
+        return self._recommend(self._lib.tfr_bf16_topk, users, k, exclude, return_scores)
+
+    def recommend_bf16_dev(self, users, k=10, exclude=None, return_scores=True):
+        """``recommend_dev`` from the bf16 snapshot: the same arguments, return values and stream ordering."""
+        return self._recommend_dev(self._lib.tfr_bf16_topk_dev, users, k, exclude, return_scores)
+
+    def _recommend(self, entry, users, k, exclude, return_scores):
+        u = L.as_i32(users, "user ids").reshape(-1)
+        indptr, excl = exclusion_csr(exclude, u)
+        items = np.empty((u.size, int(k)), np.int32)
+        scores = np.empty((u.size, int(k)), np.float32) if return_scores else None
+        L.check(entry(self._h, L.ptr_i32(u), u.size, int(k),
+                      None if indptr is None else L.ptr_i64(indptr), None if excl is None else L.ptr_i32(excl),
+                      L.ptr_i32(items), None if scores is None else L.ptr_f32(scores)))
+        return (items, scores) if return_scores else items
+
+    def _recommend_dev(self, entry, users, k, exclude, return_scores):
         import torch
         users = users.contiguous()
         if users.dtype != torch.int32 or users.dim() != 1:
@@ -385,9 +400,9 @@ class SvdModel:
         mine = torch.cuda.ExternalStream(self.get_stream(), device=users.device)
         cur = torch.cuda.current_stream(users.device)
         mine.wait_stream(cur)
-        L.check(self._lib.tfr_topk_dev(self._h, users.data_ptr(), n, k, None if ip is None else ip.data_ptr(),
-                                       None if ex is None else ex.data_ptr(), items.data_ptr(),
-                                       None if scores is None else scores.data_ptr()))
+        L.check(entry(self._h, users.data_ptr(), n, k, None if ip is None else ip.data_ptr(),
+                      None if ex is None else ex.data_ptr(), items.data_ptr(),
+                      None if scores is None else scores.data_ptr()))
         cur.wait_stream(mine)                          # (so no record_stream: the tensors' next users on `cur` come after)
         return (items, scores) if return_scores else items
 
