@@ -19,12 +19,13 @@ FROZEN_USER_SIDE = (1 << BU) | (1 << P)
 _CASES = []
 
 
-def _case(path, U, I, D, B, opt, ids="dup", frozen=0, hyper2=None, sample=None):
+def _case(path, U, I, D, B, opt, ids="dup", frozen=0, hyper2=None, sample=None, item_abs=None, tables="rand"):
     x = len(_CASES)                       # loss form and flags rotate as in test_gpu_parity._rotation
-    c = dict(path=path, U=U, I=I, D=D, B=B, opt=opt[0], mode=opt[1], loss=("mse", "nll")[x % 2], item_abs=bool((x >> 1) & 1),
-             reg_bias=bool((x >> 2) & 1), ids=ids, frozen=frozen, hyper2=hyper2, sample=sample)
-    c["id"] = "%s-U%d-I%d-D%d-B%d-%s_%s-%s%s%s" % (path, U, I, D, B, opt[0], opt[1], ids, "-frozen%d" % frozen if frozen else "",
-                                              "-hyper" if hyper2 else "")
+    c = dict(path=path, U=U, I=I, D=D, B=B, opt=opt[0], mode=opt[1], loss=("mse", "nll")[x % 2],
+             item_abs=bool((x >> 1) & 1) if item_abs is None else item_abs,
+             reg_bias=bool((x >> 2) & 1), ids=ids, frozen=frozen, hyper2=hyper2, sample=sample, tables=tables)
+    c["id"] = "%s-U%d-I%d-D%d-B%d-%s_%s-%s%s%s%s" % (path, U, I, D, B, opt[0], opt[1], ids, "-frozen%d" % frozen if frozen else "",
+                                                "-hyper" if hyper2 else "", "-" + tables if tables != "rand" else "")
     _CASES.append(c)
 
 
@@ -77,6 +78,14 @@ _case("tiles4", 500, 300, 64, 700, ADAM_TF1, hyper2=(1e-3, 0.07))
 _case("tiles4", 500, 300, 64, 700, SGD, hyper2=(2.0 ** -12, 0.07))
 _case("fused_big", 70000, 20000, 16, 1057, ADAM_LAZY, hyper2=(1e-3, 0.07))
 _case("fused_big", 70000, 20000, 16, 1057, SGD, hyper2=(2.0 ** -12, 0.07))
+# exact zeros in Q under item_abs (d|q|/dq = sign(q), sign(0) = 0: svd_kernels.hip k_tile_step, k_seg_reduce), planted by
+# ``tables_of`` in rows both steps touch; the tile path at VEC = 4 and VEC = 1, the three-round and the general load form
+_case("tiles4", 500, 300, 64, 700, ADAM_TF1, item_abs=True, tables="zeros")
+_case("tiles4", 500, 300, 15, 700, SGD, item_abs=True, tables="zeros")
+_case("csort", 6040, 3952, 32, 16385, ADAM_LAZY, item_abs=True, tables="zeros")
+_case("tf1_big", 16384 + 77, 300, 12, 3000, ADAM_TF1, item_abs=True, tables="zeros")
+_case("fused_big", 70000, 20000, 16, 1057, SGD, item_abs=True, tables="zeros")
+_case("fused_big", 40000, 30000, 20, 20000, ADAM_LAZY, ids="hot", item_abs=True, tables="zeros")
 
 CASES = tuple(_CASES)
 assert len({c["id"] for c in CASES}) == len(CASES)
@@ -88,7 +97,53 @@ def seed_of(case):
 
 def tables_of(case):
     D = case["D"]
-    return rand_tables(np.random.RandomState(seed_of(case)), case["U"], case["I"], D, scale=0.3 / np.sqrt(max(D, 16) / 16))
+    t = rand_tables(np.random.RandomState(seed_of(case)), case["U"], case["I"], D, scale=0.3 / np.sqrt(max(D, 16) / 16))
+    if case["tables"] == "zeros":
+        for row, cols, vals in zero_plan(case):
+            t["Q"][row, cols] = vals
+    return t
+
+
+def zero_plan(case):
+    """[(Q row, columns, values)] of the planted zeros: a hot row and a once-seen row carry +0.0 and -0.0 at columns 0
+    and D - 1, one 4-column fragment all zero and one partly zero; a third row is zero altogether.  All three rows occur
+    in both steps' batches (asserted)."""
+    D, I = case["D"], case["I"]
+    assert D >= 12
+    n0, n1 = (np.bincount(batch_of(case, s)[1], minlength=I) for s in range(2))
+    both = np.minimum(n0, n1)
+    hot = int(np.argmax(np.where(both > 0, n0, 0)))                     # the longest first-step run the second step meets again
+    once = np.flatnonzero((n0 == 1) & (n1 >= 1))
+    assert n0[hot] >= 2 and both[hot] >= 1 and once.size, (case["id"], n0[hot], once.size)
+    once = int(once[np.argmin(n1[once])])
+    rest = np.flatnonzero((both > 0) & (np.arange(I) != hot) & (np.arange(I) != once))
+    whole = int(rest[rest.size // 2])
+    pz, nz = np.float32(0.0), np.float32(-0.0)
+    cols = np.array([0, D - 1, 4, 5, 6, 7, 9, 10])
+    alt = np.where(np.arange(D) % 2 == 0, pz, nz).astype(np.float32)
+    return [(hot, cols, np.array([pz, nz, pz, nz, nz, pz, nz, pz], np.float32)),
+            (once, cols, np.array([nz, pz, nz, nz, pz, pz, pz, nz], np.float32)),
+            (whole, np.arange(D), alt)]
+
+
+def assert_zero_edges(case):
+    """what a "zeros" case was built for holds: the planted elements are zeros of both signs, their rows are touched in
+    both steps, and the float64 gradient there is exactly lam * 0"""
+    from tests import step_ref
+    assert case["item_abs"] and case["tables"] == "zeros"
+    t = tables_of(case)
+    u, i, r = batch_of(case, 0)
+    G = step_ref.step_grads(t, u, i, r, case["loss"], True, case["reg_bias"], REG)[0]["Q"][0]
+    touched = [np.bincount(batch_of(case, s)[1], minlength=case["I"]) for s in range(2)]
+    signs = set()
+    for row, cols, vals in zero_plan(case):
+        assert touched[0][row] > 0 and touched[1][row] > 0, (case["id"], row)
+        got = t["Q"][row, cols]
+        assert np.all(got == 0) and np.array_equal(np.signbit(got), np.signbit(vals))
+        signs |= set(np.signbit(got).tolist())
+        assert np.all(G[row, cols] == 0), (case["id"], row, G[row, cols])
+        assert np.any(G[row] != 0) or cols.size == case["D"]           # the rest of the row does move
+    assert signs == {True, False}
 
 
 def batch_of(case, s):

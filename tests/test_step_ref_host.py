@@ -43,6 +43,12 @@ def test_float32_oracle_stays_inside_the_bound(case):
         assert c["short"] <= R.LONG_RUN and c["long"] <= np.max(n), (name, c)
 
 
+@pytest.mark.parametrize("case", [c for c in S.CASES if c["tables"] == "zeros"], ids=lambda c: c["id"])
+def test_zero_cases_hold_what_they_were_built_for(case):
+    """planted zeros of both signs in Q rows both steps touch, the float64 gradient there exactly lam * 0"""
+    S.assert_zero_edges(case)
+
+
 # ----------------------------------------------------------------------------- a float32 restatement with planted faults
 U_, I_, D_, B_ = 300, 200, 20, 4000                 # hot rows hold ~90 (users) and ~140 (items) entries
 LR_, LAM_ = 3e-3, 0.02
@@ -194,6 +200,8 @@ def test_cases_reach_every_branch_under_every_optimiser():
     assert not want - got, sorted(want - got)
     tiles = {c["path"] for c in S.CASES if c["path"].startswith("tiles")}
     assert tiles == {"tiles4", "tiles8", "tiles10", "tiles12", "tiles16"}, tiles            # every k_dense_tiles tile count
+    zeros = {(c["path"].rstrip("0123456789"), c["D"]) for c in S.CASES if c["tables"] == "zeros" and c["item_abs"]}
+    assert {("tiles", 64), ("tiles", 15), ("csort", 32), ("tf1_big", 12), ("fused_big", 16), ("fused_big", 20)} <= zeros, zeros
     frozen = {c["path"].rstrip("0123456789") for c in S.CASES if c["frozen"]}
     assert {"tiles", "csort", "tf1_big", "fused_big"} <= frozen, frozen
     # the restated rule itself at its edges: 16 tiles / 17, 16384 rows / 16385, bins x tiles at 2^20
