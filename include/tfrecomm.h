@@ -738,6 +738,32 @@ int tfr_bf16_topk(tfr_model* m, const int32_t* users, int64_t n_users, int32_t k
 int tfr_bf16_topk_dev(tfr_model* m, const int32_t* d_users, int64_t n_users, int32_t k,
                       const int64_t* d_excl_indptr, const int32_t* d_excl_items,
                       int32_t* d_items_out, float* d_scores_out);
+/* Held-out ranking from the snapshot - DESIGN §26.  Everything tfr_rank_items documents holds: -1 for an excluded or
+ *      NaN-scored target, repeated excluded ids counted once, every check on the host before any device work, ranks_out
+ *      untouched on error, n_users = 0 a no-op, it synchronises, and the ranks are bit-identical across batch, chunk, slice and
+ *      row order; the launch plan is tfr_rank_plan's.  Only the keys differ: they are tfr_bf16_topk's, so for every
+ *      K <= 256, 0 <= rank(t) < K exactly when t is in tfr_bf16_topk(users, K, excl)'s row, and rank(t) is its position there.
+ *      TFR_ERR_STATE (naming tfr_bf16_snapshot) before a snapshot, also for n_users = 0.  It reads the snapshot only. */
+int tfr_bf16_rank_items(tfr_model* m, const int32_t* users, int64_t n_users,
+                        const int64_t* tgt_indptr, const int32_t* tgt_items,
+                        const int64_t* excl_indptr, const int32_t* excl_items, int32_t* ranks_out);
+/* Nearest neighbours from the snapshot - DESIGN §26.  Everything tfr_neighbours / tfr_neighbours_dev document holds (which,
+ *      metric, k, the candidate range [lo, hi), the exclusion CSR and its checks, the query row never its own neighbour, id -1
+ *      / score -INFINITY past the eligible rows, the deferred errors of the device entry, the host entry synchronises and
+ *      the device entry does not) on the rows of the snapshot's Q (TFR_NB_ITEMS, Q' = |Q| with item_abs) or P (TFR_NB_USERS).
+ *      dot(a, b) = the float32 sum of the exact products of the snapshot's bf16 elements, taken 16 features per matrix
+ *      instruction (v_mfma_f32_32x32x16_bf16) in ascending order from +0, as in tfr_bf16_topk.  cosine(a, b) =
+ *      (dot(a, b) * rn[a]) * rn[b], rn[r] = 1 / sqrtf(ss[r]) and 0 where ss[r] == 0, ss[r] = the float32 fmaf chain over f
+ *      ascending from +0 of the widened elements squared (the squares are exact in float32; pads add nothing).
+ *      The inverse norms are built by the first cosine query on a table and kept until the next tfr_bf16_snapshot or
+ *      tfr_bf16_drop; steps, tfr_set_table and the float32 tables' own norm caches neither see nor move anything.
+ *      TFR_ERR_STATE (naming tfr_bf16_snapshot) before a snapshot, also for n = 0. */
+int tfr_bf16_neighbours(tfr_model* m, int32_t which, int32_t metric, const int32_t* rows, int64_t n, int32_t k,
+                        const int64_t* excl_indptr, const int32_t* excl, int64_t lo, int64_t hi,
+                        int32_t* ids_out, float* scores_out);
+int tfr_bf16_neighbours_dev(tfr_model* m, int32_t which, int32_t metric, const int32_t* d_rows, int64_t n, int32_t k,
+                            const int64_t* d_excl_indptr, const int32_t* d_excl, int64_t lo, int64_t hi,
+                            int32_t* d_ids_out, float* d_scores_out);
 
 /* ---- misc ------------------------------------------------------------------------------ */
 int tfr_sync(tfr_model* m);            /* drains the stream; reports deferred TFR_ERR_OOB   */

@@ -76,6 +76,11 @@ SIGNATURES = {
     "tfr_bf16_row_stride": (C.c_int, [C.c_int32]),
     "tfr_bf16_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
     "tfr_bf16_topk_dev": (C.c_int, [_p, _p, C.c_int64, C.c_int32, _p, _p, _p, _p]),
+    "tfr_bf16_rank_items": (C.c_int, [_p, _i32p, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
+    "tfr_bf16_neighbours": (C.c_int, [_p, C.c_int32, C.c_int32, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, C.c_int64,
+                                      C.c_int64, _i32p, _f32p]),
+    "tfr_bf16_neighbours_dev": (C.c_int, [_p, C.c_int32, C.c_int32, _p, C.c_int64, C.c_int32, _p, _p, C.c_int64, C.c_int64,
+                                          _p, _p]),
     "tfr_upload_eval_triples": (C.c_int, [_p, _i32p, _i32p, _f32p, C.c_int64]),
     "tfr_eval_resident": (C.c_int, [_p, C.POINTER(C.c_double), _i64p, _i64p]),
     "tfr_eval_binary": (C.c_int, [_p, _i32p, _i32p, _f32p, C.c_int64, _i64p, _f64p, _f64p]),

@@ -178,9 +178,17 @@ struct tfr_model {
     // batched fine-tuning (tfr_finetune_users): one device buffer for a call's schedule and outputs
     DevBuf<char> ft_buf;
     // bf16 snapshot (tfr_bf16_*): P and Q as padded bf16 rows, mu and the biases as they were at the same moment
+    // gen counts the snapshots made and dropped; rn: the inverse row norms of the snapshot's Q [0] and P [1]
+    // (tfr_bf16_neighbours*), each valid for the snapshot generation it was built at - steps and tfr_set_table do not enter
     struct Bf16Snap {
         DevBuf<uint16_t> p, q; DevBuf<float> bu, bi, mu; bool valid = false;
-        void drop() { p.reset(); q.reset(); bu.reset(); bi.reset(); mu.reset(); valid = false; }
+        uint64_t gen = 0;
+        struct Rn { DevBuf<float> rn; uint64_t gen = 0; bool valid = false; } rn[2];
+        void drop() {
+            p.reset(); q.reset(); bu.reset(); bi.reset(); mu.reset(); valid = false;
+            for (Rn& r : rn) { r.rn.reset(); r.valid = false; }
+            gen += 1;
+        }
     } bf;
     // BPR steps (tfr_bpr_*): the positives, the sampler's settings and the step's buffers; created by the first BPR call
     BprState* bpr = nullptr;
@@ -1526,6 +1534,7 @@ int tfr_bf16_snapshot(tfr_model* m) {
     const int64_t DP = bf16_row_stride(m->D);
     tfr_model::Bf16Snap& b = m->bf;
     b.valid = false;
+    b.gen += 1;                                          // the inverse norms of the earlier snapshot are stale from here
     hipError_t e = b.p.reserve(m->U * DP, s);
     if (e == hipSuccess) e = b.q.reserve(m->I * DP, s);
     if (e == hipSuccess) e = b.bu.reserve(m->U, s);
@@ -3545,20 +3554,51 @@ int tfr_fm_topk(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_
 
 }  // extern "C"
 
-// ---- held-out ranking (rank.hip) --------------------------------------------------------------------------------------------
+// ---- held-out ranking (rank.hip, bf16_rank.hip) -----------------------------------------------------------------------------
+// Which tables a ranking reads and which launcher scores them: what rank_host is generic over, as the sliced driver is over
+// its queries.  who: the name in errors; U / n_items: the id bounds; settle: item rows the fused big-table step left in q_alt
+// must come back first.  A query derives from it and adds launch(common, plan, stream): fill the family's own argument
+// fields and launch one chunk's kernels.
+struct RankFamily { const char* who; int64_t U, n_items; int32_t item_abs; bool settle; };
+
+struct RankQuery : RankFamily {
+    TopkTables t;
+    explicit RankQuery(const TopkTables& t_) : RankFamily{"rank", t_.U, t_.n_items, t_.item_abs, true}, t(t_) {}
+    void launch(const RankCommon& c, const RankPlan& p, hipStream_t s) const {
+        RankArgs a = {};
+        static_cast<RankCommon&>(a) = c;
+        a.P = t.P; a.bu = t.bu; a.Q = t.Q; a.bi = t.bi; a.mu = t.mu;
+        launch_rank(a, p, s);
+    }
+};
+
+// the same on the model's bf16 snapshot, which was settled when it was made and is all the kernels read
+struct Bf16RankQuery : RankFamily {
+    tfr_model* m;
+    explicit Bf16RankQuery(tfr_model* m_) : RankFamily{"bf16 rank", m_->U, m_->I, m_->o.item_abs, false}, m(m_) {}
+    void launch(const RankCommon& c, const RankPlan& p, hipStream_t s) const {
+        Bf16RankArgs a = {};
+        static_cast<RankCommon&>(a) = c;
+        a.P = m->bf.p; a.bu = m->bf.bu; a.Q = m->bf.q; a.bi = m->bf.bi; a.mu = m->bf.mu;
+        a.DP = bf16_row_stride(m->D);
+        launch_bf16_rank(a, p, s);
+    }
+};
+
 // the host entries: ids, the target rows and the exclusion CSR are checked here, before any device work; the rows are cut
 // into pieces of at most RANK_CAP targets and ranked chunk by chunk of pieces.  ranks_out is written only when every check
 // passed.
-static int rank_host(tfr_model* m, const TopkTables& t, const int32_t* users, int64_t n, const int64_t* tip,
+template <class Query>
+static int rank_host(tfr_model* m, const Query& t, const int32_t* users, int64_t n, const int64_t* tip,
                      const int32_t* tit, const int64_t* xip, const int32_t* xit, int32_t* ranks_out) {
-    if (n < 0) return fail(TFR_ERR_ARG, "rank: negative n_users");
+    if (n < 0) return fail(TFR_ERR_ARG, "%s: negative n_users", t.who);
     if (n == 0) return TFR_OK;
-    if (!users || !tip) return fail(TFR_ERR_ARG, "rank: null users / target indptr");
+    if (!users || !tip) return fail(TFR_ERR_ARG, "%s: null users / target indptr", t.who);
     const int64_t n_tgt = tip[n] - tip[0];
-    if (n_tgt > 0 && (!tit || !ranks_out)) return fail(TFR_ERR_ARG, "rank: null target items / ranks_out");
-    if (xip && !xit && xip[n] > xip[0]) return fail(TFR_ERR_ARG, "rank: exclusion indptr without items");
-    int rc = check_ids("rank", "user id", users, n, t.U);
-    if (rc || (rc = check_csr("rank", true, tip, tit, n, t.n_items)) || (xip && (rc = check_csr("rank", false, xip, xit, n, t.n_items))))
+    if (n_tgt > 0 && (!tit || !ranks_out)) return fail(TFR_ERR_ARG, "%s: null target items / ranks_out", t.who);
+    if (xip && !xit && xip[n] > xip[0]) return fail(TFR_ERR_ARG, "%s: exclusion indptr without items", t.who);
+    int rc = check_ids(t.who, "user id", users, n, t.U);
+    if (rc || (rc = check_csr(t.who, true, tip, tit, n, t.n_items)) || (xip && (rc = check_csr(t.who, false, xip, xit, n, t.n_items))))
         return rc;
     if (n_tgt == 0) return TFR_OK;
     // pieces in row order: tlo absolute into tit, xlo / xhi absolute into xit (rebased per chunk below); prow = their rows
@@ -3572,8 +3612,8 @@ static int rank_host(tfr_model* m, const TopkTables& t, const int32_t* users, in
         }
     const int64_t np = (int64_t)pieces.size();
     RankPlan p;
-    if (!rank_plan(np, t.n_items, &p)) return fail(TFR_ERR_ARG, "rank: no plan for %lld pieces", (long long)np);
-    if ((rc = settle_q(m))) return rc;                   // item rows the fused big-table step left in q_alt come back first
+    if (!rank_plan(np, t.n_items, &p)) return fail(TFR_ERR_ARG, "%s: no plan for %lld pieces", t.who, (long long)np);
+    if (t.settle && (rc = settle_q(m))) return rc;       // item rows the fused big-table step left in q_alt come back first
     hipStream_t s = m->stream;
     HIPCHK(m->rk_pieces.reserve(pow2_cap(p.chunk), s));
     HIPCHK(reserve_each(pow2_cap(p.chunk * RANK_CAP), s, m->rk_tgt, m->rk_ranks, m->rk_order, m->rk_bins));
@@ -3594,19 +3634,23 @@ static int rank_host(tfr_model* m, const TopkTables& t, const int32_t* users, in
             HIPCHK(m->rk_excl.reserve(pow2_cap(x1 - x0), s));
             HIPCHK(hipMemcpyAsync(m->rk_excl, xit + x0, (size_t)(x1 - x0) * 4, hipMemcpyHostToDevice, s));
         }
-        RankArgs a;
-        memset(&a, 0, sizeof(a));
-        a.P = t.P; a.bu = t.bu; a.Q = t.Q; a.bi = t.bi; a.mu = t.mu;
+        RankCommon a = {};
         a.pieces = m->rk_pieces; a.tgt = m->rk_tgt; a.excl = m->rk_excl;
         a.keys = m->rk_keys; a.order = m->rk_order; a.nr = m->rk_nr; a.bins = m->rk_bins; a.ranks = m->rk_ranks;
         a.n_pieces = cnt; a.n_items = t.n_items;
         a.D = m->D; a.slices = p.slices; a.item_abs = t.item_abs;
-        launch_rank(a, p, s);
+        t.launch(a, p, s);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(ranks_out + (t0 - tip[0]), m->rk_ranks, (size_t)(t1 - t0) * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));                 // the staged inputs are rewritten by the next chunk
     }
     return check_device_error(m);
+}
+
+// the float32 tables' entries (SVD, FM, SVD++) name their tables
+static int rank_host(tfr_model* m, const TopkTables& t, const int32_t* users, int64_t n, const int64_t* tip,
+                     const int32_t* tit, const int64_t* xip, const int32_t* xit, int32_t* ranks_out) {
+    return rank_host(m, RankQuery(t), users, n, tip, tit, xip, xit, ranks_out);
 }
 
 extern "C" {
@@ -3631,6 +3675,14 @@ int tfr_rank_items(tfr_model* m, const int32_t* users, int64_t n_users, const in
                    const int64_t* excl_indptr, const int32_t* excl_items, int32_t* ranks_out) {
     MODEL_ENTER(m);
     return rank_host(m, svd_topk_tables(m), users, n_users, tgt_indptr, tgt_items, excl_indptr, excl_items, ranks_out);
+}
+
+// the snapshot test comes before every other check, n_users == 0 included, as in the other tfr_bf16_* entries
+int tfr_bf16_rank_items(tfr_model* m, const int32_t* users, int64_t n_users, const int64_t* tgt_indptr,
+                        const int32_t* tgt_items, const int64_t* excl_indptr, const int32_t* excl_items, int32_t* ranks_out) {
+    MODEL_ENTER(m);
+    if (int rc = bf16_need_snapshot(m)) return rc;
+    return rank_host(m, Bf16RankQuery(m), users, n_users, tgt_indptr, tgt_items, excl_indptr, excl_items, ranks_out);
 }
 
 int tfr_fm_rank_items(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_t item_lo, int64_t item_hi,

@@ -1,5 +1,5 @@
 // rank.h - ranking of held-out items over the whole catalogue (tfr_rank_items*): launch plan, argument block and launcher
-// shared by rank.hip and api.hip.
+// shared by rank.hip, bf16_rank.hip and api.hip.
 //
 // rank(t) = #{eligible items i with a non-NaN score and key(u, i) > key(u, t)}, keys as in topk.h.  A row's targets are cut
 // into pieces of at most RANK_CAP; a piece is (user, targets, exclusions) and ranks independently of every other piece.
@@ -63,10 +63,8 @@ struct RankPiece {
     int32_t user, nt;
 };
 
-struct RankArgs {
-    const float* P; const float* bu;                   // user rows [U, D] and biases
-    const float* Q; const float* bi;                   // item rows [n_items, D] and biases (already offset to the item range)
-    const float* mu;
+// what the three kernels are told whichever rows they score: filled once per chunk, by api.hip's rank_host
+struct RankCommon {
     const RankPiece* pieces;                           // [n_pieces]
     const int32_t* tgt; const int32_t* excl;
     uint64_t* keys;                                    // [n_pieces, RANK_CAP] the piece's target keys, descending, 0 = unranked
@@ -78,7 +76,25 @@ struct RankArgs {
     int32_t D, slices, item_abs;
 };
 
+struct RankArgs : RankCommon {
+    const float* P; const float* bu;                   // user rows [U, D] and biases
+    const float* Q; const float* bi;                   // item rows [n_items, D] and biases (already offset to the item range)
+    const float* mu;
+};
+
+// the same ranks from the bf16 snapshot (bf16_rows.h): P and Q are snapshot rows at a stride of DP elements, the biases and
+// mu the snapshot's float32 copies; keys are those of Bf16TopkArgs (topk.h), so rank < K is the position in tfr_bf16_topk
+struct Bf16RankArgs : RankCommon {
+    const uint16_t* P; const float* bu;
+    const uint16_t* Q; const float* bi;
+    const float* mu;
+    int32_t DP;
+};
+
 // k_rank_targets -> k_rank_count -> k_rank_finish on stream s
 void launch_rank(const RankArgs& a, const RankPlan& p, hipStream_t s);
+void launch_bf16_rank(const Bf16RankArgs& a, const RankPlan& p, hipStream_t s);     // bf16_rank.hip
+// the last of the three, which reads bins and writes ranks only: one kernel for both (rank.hip)
+void launch_rank_finish(const RankCommon& a, hipStream_t s);
 
 }  // namespace tfr

@@ -10,172 +10,43 @@
 //   beats the piece's lowest ranked target adds 1 to bin p = #{targets with key >= it} (binary search of the sorted keys in
 //   LDS, LDS integer atomic).  The block adds its bins to the piece's with global integer atomics.
 // k_rank_finish: one wave per piece: rank of sorted target j = bins[0] + ... + bins[j], scattered to the target's position.
+// The bodies of the first two live in rank_body.h, generic over a scorer; here they run with RankScorer on the float32 tables,
+// in bf16_rank.hip on the bf16 snapshot.  k_rank_finish reads bins only and serves both (launch_rank_finish).
 #include <hip/hip_runtime.h>
 #include "svd_kernels.h"
 #include "score_tile.h"
 #include "rank.h"
+#include "rank_body.h"
 
 namespace tfr {
 
-// first j in [0, nr) with q[j] < key, given q[0..nr) descending and q[nr-1] < key: the number of targets whose key is >= key
-__device__ __forceinline__ int rank_bin(const uint64_t* q, int nr, uint64_t key) {
-    int lo = 0, hi = nr - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (q[mid] < key) hi = mid; else lo = mid + 1;
+// score(u, i) = ((dot + mu) + bu[u]) + bi[i] on the float32 tables: the scorer of rank_body.h's blocks
+template <bool V4>
+struct RankScorer {
+    const RankArgs& a;
+    const float* prow;
+    float mu, ub;
+    __device__ __forceinline__ RankScorer(const RankArgs& a_, int32_t user)
+        : a(a_), prow(a_.P + (int64_t)user * a_.D), mu(*a_.mu), ub(a_.bu[user]) {}
+    __device__ __forceinline__ f32x16 tile(int64_t row, int h) const {
+        return mfma_tile_dot<V4>(a.Q + row * a.D, prow, a.D, a.item_abs, h);
     }
-    return lo;
-}
+    __device__ __forceinline__ float score(float dot, int64_t item) const { return ((dot + mu) + ub) + a.bi[item]; }
+};
 
 template <bool V4>
 __global__ __launch_bounds__(256) void k_rank_targets(RankArgs a) {
-    __shared__ uint64_t keys[RANK_WAVES * RANK_CAP];
-    __shared__ int32_t bins[RANK_WAVES * RANK_CAP];
-    __shared__ float sc[RANK_WAVES * RANK_SUB];
-    static_assert(sizeof(keys) + sizeof(bins) + sizeof(sc) == rank_targets_static_lds(),
-                  "tfr_rank_plan reports a different LDS size than k_rank_targets declares");
-    static_assert(RANK_CAP % 64 == 0 && RANK_SUB == 32, "a wave sorts RANK_CAP keys and scores 32 items a tile");
     warm_args(a);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int h = lane >> 5, c = lane & 31;
-    const int64_t pc = (int64_t)blockIdx.x * RANK_WAVES + wave;
-    if (pc >= a.n_pieces) return;                      // the whole wave: no block barrier below
-    const RankPiece p = a.pieces[pc];
-    uint64_t* kq = keys + wave * RANK_CAP;
-    int32_t* bq = bins + wave * RANK_CAP;
-    float* sq = sc + wave * RANK_SUB;
-    const int32_t* tg = a.tgt + p.tlo;
-    const float* prow = a.P + (int64_t)p.user * a.D;
-    const float mu = *a.mu;
-    const float ub = a.bu[p.user];
-    for (int t = lane; t < RANK_CAP; t += 64) { kq[t] = 0; bq[t] = 0; }
-    for (int t = lane; t < p.nt; t += 64) a.ranks[p.tlo + t] = -1;
-    wave_lds_sync();
-
-    for (int t0 = 0; t0 < p.nt; t0 += RANK_SUB) {
-        const int ti = t0 + c < p.nt ? t0 + c : p.nt - 1;    // A row = target; past the piece: one inside it, dropped
-        const f32x16 acc = mfma_tile_dot<V4>(a.Q + (int64_t)tg[ti] * a.D, prow, a.D, a.item_abs, h);
-        if (c == 0) {                                  // every column is the piece's user: column 0 has all 32 rows
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sq[(r & 3) + 8 * (r >> 2) + 4 * h] = acc[r];
-        }
-        wave_lds_sync();
-        if (lane < RANK_SUB && t0 + lane < p.nt) {
-            const int32_t item = tg[t0 + lane];
-            const float s = ((sq[lane] + mu) + ub) + a.bi[item];
-            const bool out = __builtin_isnan(s) || (p.xhi > p.xlo && topk_excluded(a.excl, p.xlo, p.xhi, item));
-            kq[t0 + lane] = out ? 0 : topk_key(s, item);
-        }
-        wave_lds_sync();
-    }
-    wave_sort_desc<RANK_CAP>(kq, lane);
-    int nz = 0;
-    for (int t = lane; t < RANK_CAP; t += 64) nz += kq[t] != 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) nz += __shfl_xor(nz, off);
-    const int nr = nz;                                 // the ranked targets lead the sorted keys
-    uint64_t* gk = a.keys + pc * RANK_CAP;
-    int32_t* go = a.order + pc * RANK_CAP;
-    for (int t = lane; t < RANK_CAP; t += 64) {
-        const uint64_t key = kq[t];
-        gk[t] = key;
-        if (t < nr) {                                  // the target rows are sorted: find the key's item among them
-            const int32_t item = (int32_t)~(uint32_t)key;
-            int lo = 0, hi = p.nt - 1;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (tg[mid] < item) lo = mid + 1; else hi = mid;
-            }
-            go[t] = lo;
-        }
-    }
-    if (lane == 0) a.nr[pc] = nr;
-
-    if (nr > 0) {                                      // take the excluded items off, binned as k_rank_count bins them
-        const uint64_t lowest = kq[nr - 1];
-        for (int64_t e0 = p.xlo; e0 < p.xhi; e0 += RANK_SUB) {
-            const int64_t ei = e0 + c < p.xhi ? e0 + c : p.xhi - 1;
-            const f32x16 acc = mfma_tile_dot<V4>(a.Q + (int64_t)a.excl[ei] * a.D, prow, a.D, a.item_abs, h);
-            if (c == 0) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) sq[(r & 3) + 8 * (r >> 2) + 4 * h] = acc[r];
-            }
-            wave_lds_sync();
-            const int64_t e = e0 + lane;
-            if (lane < RANK_SUB && e < p.xhi) {
-                const int32_t item = a.excl[e];
-                if (e == p.xlo || a.excl[e - 1] != item) {   // a repeated id is one item, taken off once
-                    const float s = ((sq[lane] + mu) + ub) + a.bi[item];
-                    if (!__builtin_isnan(s)) {
-                        const uint64_t key = topk_key(s, item);
-                        if (key > lowest) atomicSub(&bq[rank_bin(kq, nr, key)], 1);
-                    }
-                }
-            }
-            wave_lds_sync();
-        }
-    }
-    int32_t* gb = a.bins + pc * RANK_CAP;
-    for (int t = lane; t < RANK_CAP; t += 64) gb[t] = bq[t];
+    rank_targets_block<RankScorer<V4>>(a);
 }
 
 template <bool V4>
 __global__ __launch_bounds__(256) void k_rank_count(RankArgs a) {
-    __shared__ uint64_t keys[RANK_PPB * RANK_CAP];
-    __shared__ int32_t bins[RANK_PPB * RANK_CAP];
-    static_assert(sizeof(keys) + sizeof(bins) == rank_count_static_lds(),
-                  "tfr_rank_plan reports a different LDS size than k_rank_count declares");
-    static_assert(RANK_PPB == 32, "a block's pieces are the 32 columns of the MFMA");
     warm_args(a);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int h = lane >> 5, c = lane & 31;
-    const int64_t p0 = (int64_t)blockIdx.x * RANK_PPB;
-    const int64_t pc = p0 + c;                         // the piece of this lane's accumulator column
-    int nr = 0;
-    int32_t user = 0;                                  // a column past the chunk scores user 0 and bins nothing
-    if (pc < a.n_pieces) { nr = a.nr[pc]; user = a.pieces[pc].user; }
-    for (int t = threadIdx.x; t < RANK_PPB * RANK_CAP; t += 256) {
-        keys[t] = p0 + t / RANK_CAP < a.n_pieces ? a.keys[p0 * RANK_CAP + t] : 0;
-        bins[t] = 0;
-    }
-    __syncthreads();
-    const uint64_t* kq = keys + c * RANK_CAP;
-    const uint64_t lowest = nr > 0 ? kq[nr - 1] : ~0ull;
-    const float* prow = a.P + (int64_t)user * a.D;
-    const float mu = *a.mu;
-    const float ub = a.bu[user];
-
-    const int64_t per = ((a.n_items + a.slices - 1) / a.slices + RANK_ROUND - 1) / RANK_ROUND * RANK_ROUND;
-    const int64_t s_lo = (int64_t)blockIdx.y * per;
-    const int64_t s_hi = s_lo + per < a.n_items ? s_lo + per : a.n_items;
-    const int64_t rounds = s_hi > s_lo ? (s_hi - s_lo + RANK_ROUND - 1) / RANK_ROUND : 0;
-    for (int64_t rd = 0; rd < rounds; ++rd) {
-        const int64_t base = s_lo + rd * RANK_ROUND + wave * RANK_SUB;
-        int64_t my_item = base + c;                    // A row = item; past the slice: a row inside it, result dropped
-        if (my_item >= s_hi) my_item = s_hi - 1;
-        const f32x16 acc = mfma_tile_dot<V4>(a.Q + my_item * a.D, prow, a.D, a.item_abs, h);
-        if (nr > 0) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int64_t item = base + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (item < s_hi) {
-                    const float s = ((acc[r] + mu) + ub) + a.bi[item];
-                    if (!__builtin_isnan(s)) {
-                        const uint64_t key = topk_key(s, item);
-                        if (key > lowest) atomicAdd(&bins[c * RANK_CAP + rank_bin(kq, nr, key)], 1);
-                    }
-                }
-            }
-        }
-    }
-    __syncthreads();
-    for (int t = threadIdx.x; t < RANK_PPB * RANK_CAP; t += 256) {
-        const int32_t v = bins[t];
-        if (v && p0 + t / RANK_CAP < a.n_pieces) atomicAdd(&a.bins[p0 * RANK_CAP + t], v);   // integer sums: the result does not depend on the order
-    }
+    rank_count_block<RankScorer<V4>>(a);
 }
 
-__global__ __launch_bounds__(256) void k_rank_finish(RankArgs a) {
+__global__ __launch_bounds__(256) void k_rank_finish(RankCommon a) {
     static_assert(RANK_CAP == 128, "a lane scans two bins");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t pc = (int64_t)blockIdx.x * RANK_WAVES + wave;
@@ -203,6 +74,11 @@ static void launch_rank_v(const RankArgs& a, const RankPlan& p, hipStream_t s) {
     hipLaunchKernelGGL((k_rank_targets<V4>), dim3(per_wave), dim3(256), 0, s, a);
     const dim3 g((unsigned)((a.n_pieces + p.ppb - 1) / p.ppb), (unsigned)p.slices);
     hipLaunchKernelGGL((k_rank_count<V4>), g, dim3(256), 0, s, a);
+    launch_rank_finish(a, s);
+}
+
+void launch_rank_finish(const RankCommon& a, hipStream_t s) {
+    const unsigned per_wave = (unsigned)((a.n_pieces + RANK_WAVES - 1) / RANK_WAVES);
     hipLaunchKernelGGL(k_rank_finish, dim3(per_wave), dim3(256), 0, s, a);
 }
 

@@ -1,7 +1,8 @@
 // score_tile.h - the pieces topk.hip, rank.hip and neighbours.hip share: the 64-bit ordering key of a scored pair, the one-wave
 // bitonic sort of keys in LDS, the queue compaction built on it, the MFMA tile that scores 32 items against 32 user
 // columns (on float32 rows, and on the bf16 snapshot's), and sliced_topk_block, the whole scoring block of k_topk_score,
-// k_nb_score and k_topk_score_bf16, which differ only in their scorer.
+// k_nb_score, k_topk_score_bf16 and k_nb_score_bf16, which differ only in their scorer.
+// The rank kernels' bodies, generic over a scorer in the same way, are in rank_body.h.
 //
 // key(s, item) = (order-preserving uint32 of s) << 32 | ~item: one 64-bit compare orders by score descending, then item id
 // ascending; every non-NaN score gives a key above 0, so key 0 marks an empty slot.
@@ -125,6 +126,9 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // half-wave has no fragment in the last step: its loads are aimed at the row's first fragment - a valid address, no load
 // is guarded - and both operands are replaced by zero afterwards; one side alone would leave 0 * inf = NaN from
 // the redirected fragment in every score of the tile.
+// ABS_B (bf16_neighbours.hip: both operands are rows of the one snapshot table): item_abs clears the sign bits of the B
+// fragments too; the zeroing of the missing half-fragment stays on both sides.
+template <bool ABS_B = false>
 __device__ __forceinline__ f32x16 mfma_tile_dot_bf16(const uint16_t* qrow, const uint16_t* prow, int DP, int item_abs, int h) {
     const int NF = DP >> 3, steps = (NF + 1) >> 1;
     const u32x4* qf = reinterpret_cast<const u32x4*>(qrow);
@@ -148,7 +152,7 @@ __device__ __forceinline__ f32x16 mfma_tile_dot_bf16(const uint16_t* qrow, const
             if (s0 + z < steps) {
                 const bool has = 2 * (s0 + z) + h < NF;
                 const u32x4 a = has ? qa[z] & keep : (u32x4)0u;
-                const u32x4 b = has ? pb[z] : (u32x4)0u;
+                const u32x4 b = has ? (ABS_B ? pb[z] & keep : pb[z]) : (u32x4)0u;
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc,
                                                               0, 0, 0);
             }
@@ -157,7 +161,7 @@ __device__ __forceinline__ f32x16 mfma_tile_dot_bf16(const uint16_t* qrow, const
     return acc;
 }
 
-// The scoring block of "the best k candidates by a tile score" (k_topk_score, k_nb_score, k_topk_score_bf16).  A block owns a
+// The scoring block of "the best k candidates by a tile score" (k_topk_score, k_nb_score and their bf16 twins).  A block owns a
 // tile of UPB query rows (the 32 columns of a 32x32 MFMA tile) and one slice of the candidates [cand_lo, cand_hi).  Every
 // round each of its 4 waves scores a 32-candidate sub-tile against the tile's queries and appends the keys that beat its query's running k-th key
 // (and are eligible, not NaN and not excluded, tested in that order) to that query's LDS queue.  Between rounds a queue that

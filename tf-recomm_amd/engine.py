@@ -407,22 +407,24 @@ class SvdModel:
         return (items, scores) if return_scores else items
 
     # -- nearest neighbours in factor space (include/tfrecomm.h tfr_neighbours) --------------------
-    def _similar(self, which, n_rows, rows, k, metric, exclude, lo, hi, return_scores):
+    def _similar(self, which, n_rows, rows, k, metric, exclude, lo, hi, return_scores, entry=None):
         from . import neighbours as nb
+        entry = entry or self._lib.tfr_neighbours
 
         def call(*args):
-            L.check(self._lib.tfr_neighbours(self._h, which, *args))
+            L.check(entry(self._h, which, *args))
         return nb.query_host(call, rows, n_rows, k, metric, exclude, lo, hi, return_scores)
 
-    def _similar_dev(self, which, n_rows, rows, k, metric, exclude, lo, hi, return_scores):
+    def _similar_dev(self, which, n_rows, rows, k, metric, exclude, lo, hi, return_scores, entry=None):
         import torch
         from . import neighbours as nb
+        entry = entry or self._lib.tfr_neighbours_dev
 
         def call(device, *args):
             mine = torch.cuda.ExternalStream(self.get_stream(), device=device)
             cur = torch.cuda.current_stream(device)
             mine.wait_stream(cur)
-            L.check(self._lib.tfr_neighbours_dev(self._h, which, *args))
+            L.check(entry(self._h, which, *args))
             cur.wait_stream(mine)
         return nb.query_dev(call, rows, n_rows, k, metric, exclude, lo, hi, return_scores)
 
@@ -448,6 +450,28 @@ class SvdModel:
         """``similar_users`` on torch device tensors, asynchronous as ``recommend_dev``."""
         return self._similar_dev(L.NB_USERS, self.user_num, users, k, metric, exclude, lo, hi, return_scores)
 
+    def similar_items_bf16(self, items, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """``similar_items`` from the bf16 snapshot (``snapshot_bf16``): the same arguments and return values, on the rows of
+        the snapshot's ``Q`` with the dot taken 16 features per bf16 matrix instruction and the norms of the snapshot's
+        values (include/tfrecomm.h tfr_bf16_neighbours).  The float32 tables are not read."""
+        return self._similar(L.NB_ITEMS, self.item_num, items, k, metric, exclude, lo, hi, return_scores,
+                             self._lib.tfr_bf16_neighbours)
+
+    def similar_users_bf16(self, users, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """``similar_users`` from the bf16 snapshot: ``similar_items_bf16`` over the rows of the snapshot's ``P``."""
+        return self._similar(L.NB_USERS, self.user_num, users, k, metric, exclude, lo, hi, return_scores,
+                             self._lib.tfr_bf16_neighbours)
+
+    def similar_items_bf16_dev(self, items, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """``similar_items_dev`` from the bf16 snapshot: the same arguments, return values and stream ordering."""
+        return self._similar_dev(L.NB_ITEMS, self.item_num, items, k, metric, exclude, lo, hi, return_scores,
+                                 self._lib.tfr_bf16_neighbours_dev)
+
+    def similar_users_bf16_dev(self, users, k=10, metric="cosine", exclude=None, return_scores=True, lo=0, hi=None):
+        """``similar_users_dev`` from the bf16 snapshot: the same arguments, return values and stream ordering."""
+        return self._similar_dev(L.NB_USERS, self.user_num, users, k, metric, exclude, lo, hi, return_scores,
+                                 self._lib.tfr_bf16_neighbours_dev)
+
     # -- held-out ranking (include/tfrecomm.h tfr_rank_items; tfrecomm_amd.ranking for the metrics) -------------
     def rank_items(self, users, targets, exclude=None):
         """0-based rank of each target item of each of ``users`` among all items not in ``exclude``: the number of eligible
@@ -460,6 +484,16 @@ class SvdModel:
 
         def call(ip, it, xp, xi, out):
             L.check(self._lib.tfr_rank_items(self._h, L.ptr_i32(u), u.size, ip, it, xp, xi, out))
+        return rank_call(call, u, targets, exclude)
+
+    def rank_items_bf16(self, users, targets, exclude=None):
+        """``rank_items`` from the bf16 snapshot (``snapshot_bf16``): the same arguments and return values, by the keys of
+        ``recommend_bf16``, so ``rank < k`` exactly when the target is in ``recommend_bf16(users, k, exclude)``, at that
+        position (include/tfrecomm.h tfr_bf16_rank_items).  The float32 tables are not read."""
+        u = L.as_i32(users, "user ids").reshape(-1)
+
+        def call(ip, it, xp, xi, out):
+            L.check(self._lib.tfr_bf16_rank_items(self._h, L.ptr_i32(u), u.size, ip, it, xp, xi, out))
         return rank_call(call, u, targets, exclude)
 
     # -- resident store -----------------------------------------------------------

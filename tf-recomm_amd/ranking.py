@@ -88,14 +88,19 @@ def _means(m):
     return res
 
 
-def evaluate_ranking(model, test_users, test_items, exclude=None, ks=(10, 20), users=None, item_lo=None, item_hi=None):
+def evaluate_ranking(model, test_users, test_items, exclude=None, ks=(10, 20), users=None, item_lo=None, item_hi=None,
+                     bf16=False):
     """Rank each user's held-out items (the ``test_users`` / ``test_items`` columns, e.g. a ``dataio`` frame's) over the whole
     catalogue on the device and report the module's metrics.  ``exclude``: as in ``recommend`` (typically
     ``rated_matrix`` of the training columns).  ``users``: the users to evaluate (default: every user with a held-out item).
     ``model``: an ``SvdModel``, or an ``FmModel`` with ``item_lo`` / ``item_hi`` (ids relative to ``item_lo``, users are
     user features).  Returns a dict: ``users``, ``indptr`` / ``items`` / ``ranks`` (the target CSR and its ranks), the
-    per-user arrays of ``ranking_metrics`` and ``mean`` (each metric's mean over the users with at least one target)."""
+    per-user arrays of ``ranking_metrics`` and ``mean`` (each metric's mean over the users with at least one target).
+    ``bf16=True`` ranks from an ``SvdModel``'s bf16 snapshot (``rank_items_bf16``, after ``snapshot_bf16``): what a service
+    that answers with ``recommend_bf16`` would be measured by.  An FM model has no snapshot: ValueError."""
     fm = item_lo is not None or item_hi is not None
+    if bf16 and (fm or not hasattr(model, "rank_items_bf16")):
+        raise ValueError("bf16=True needs an SvdModel: only it has a bf16 snapshot")
     if fm:
         if item_lo is None or item_hi is None:
             raise ValueError("an FM model needs item_lo and item_hi")
@@ -114,7 +119,7 @@ def evaluate_ranking(model, test_users, test_items, exclude=None, ks=(10, 20), u
     if fm:
         ranks = model.rank_items(users, item_lo, item_hi, (indptr, items), exclude=ex)
     else:
-        ranks = model.rank_items(users, (indptr, items), exclude=ex)
+        ranks = (model.rank_items_bf16 if bf16 else model.rank_items)(users, (indptr, items), exclude=ex)
     n = users.size
     n_elig = np.full(n, n_items, np.int64)
     t_elig = np.diff(indptr).astype(np.int64)

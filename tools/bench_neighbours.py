@@ -6,7 +6,10 @@ calls are served from the cache).  Beside it, in the same process, ``recommend_d
 same number of candidates: a user table of item_num rows, so rows x candidates and the MFMA work are equal.  ``ratio`` =
 neighbours / recommend_dev (medians).  ``rnorm_us``: the cosine form with the cache defeated (a table_devptr hand-out) minus
 the cached form - what one k_row_rnorm pass costs.
-python tools/bench_neighbours.py [--reps N] [--only name,...] [--out profiles/bench_neighbours.jsonl]"""
+``--bf16``: on the same shapes one model and one snapshot; ``similar_items_dev`` and ``similar_items_bf16_dev`` alternate call
+by call in one process (3 warm-up calls, the first of which builds each form's inverse norms, and `--reps` timed calls each;
+median and minimum), and the share of queries whose nearest neighbour is the same in both.
+python tools/bench_neighbours.py [--reps N] [--only name,...] [--bf16] [--out profiles/bench_neighbours.jsonl]"""
 import argparse
 import json
 import os
@@ -37,7 +40,52 @@ def time_dev(fn, reps, warmup=3):
     return float(np.median(ts)), float(np.min(ts))
 
 
-def case(name, I, D, k, reps, seed=0):
+def alternate(arms, reps, warmup=3):
+    """arms: name -> call.  Warm-up and timed calls alternate the arms call by call."""
+    for _ in range(warmup):
+        for fn in arms.values():
+            fn()
+    torch.cuda.synchronize()
+    ts = {name: [] for name in arms}
+    for _ in range(reps):
+        for name, fn in arms.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            ts[name].append(a.elapsed_time(b) * 1e3)
+    return {name: (float(np.median(v)), float(np.min(v))) for name, v in ts.items()}
+
+
+def case_bf16(name, I, D, k, reps, seed=0):
+    rng = np.random.default_rng(seed)
+    U = I
+    m = T.SvdModel(U, I, D)
+    m.set_tables(np.float32(0.1), rng.standard_normal(U, dtype=np.float32) * .5, rng.standard_normal(I, dtype=np.float32) * .5,
+                 rng.standard_normal((U, D), dtype=np.float32) * .3, rng.standard_normal((I, D), dtype=np.float32) * .3)
+    m.snapshot_bf16()
+    m.sync()
+    rows = torch.arange(I, dtype=torch.int32, device="cuda")
+    out = []
+    for metric in ("cosine", "dot"):
+        res = alternate({"f32": lambda: m.similar_items_dev(rows, k, metric),
+                         "bf16": lambda: m.similar_items_bf16_dev(rows, k, metric)}, reps)
+        fi = m.similar_items_dev(rows, k, metric, return_scores=False)
+        bi = m.similar_items_bf16_dev(rows, k, metric, return_scores=False)
+        m.sync()
+        (fm, fb), (bm, bb) = res["f32"], res["bf16"]
+        out.append(dict(shape=name, metric=metric, rows=I, candidates=I, dim=D, k=k, reps=reps,
+                        f32_us_median=round(fm, 1), f32_us_min=round(fb, 1), bf16_us_median=round(bm, 1),
+                        bf16_us_min=round(bb, 1), bf16_over_f32=round(bm / fm, 3),
+                        top1_agreement=round(float((fi[:, 0] == bi[:, 0]).float().mean().item()), 4)))
+    m.close()
+    return out
+
+
+def case(name, I, D, k, reps, seed=0, bf16=False):
+    if bf16:
+        return case_bf16(name, I, D, k, reps, seed)
     rng = np.random.default_rng(seed)
     U = I                                           # recommend_dev over the same rows x candidates
     m = T.SvdModel(U, I, D)
@@ -67,11 +115,12 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--only", default="")
     ap.add_argument("--out", default="")
+    ap.add_argument("--bf16", action="store_true", help="alternate similar_items_dev and similar_items_bf16_dev")
     a = ap.parse_args()
     torch.cuda.init()
     cases = {
-        "ml1m_all_items": lambda: case("ml1m_all_items", 3706, 64, 10, a.reps),
-        "ml10m_all_items": lambda: case("ml10m_all_items", 10677, 64, 10, a.reps),
+        "ml1m_all_items": lambda: case("ml1m_all_items", 3706, 64, 10, a.reps, bf16=a.bf16),
+        "ml10m_all_items": lambda: case("ml10m_all_items", 10677, 64, 10, a.reps, bf16=a.bf16),
     }
     only = [s for s in a.only.split(",") if s]
     lines = []

@@ -6,7 +6,11 @@ baseline - NumPy f32 ``P[users] @ Q.T`` + biases, then the counting of the contr
 dropped), timed on up to `--host-users` users and scaled linearly (labelled with the thread count and the users it ran on).
 ``frac_f32_matrix_peak_call`` divides the pairs' 2·D flops by the whole call's time; the counting kernel's own fraction
 comes from a ``rocprofv3 --kernel-trace --stats`` run of this script.
-python tools/bench_rank.py [--reps N] [--only name,...]"""
+``--bf16``: on the same shapes one model and one snapshot; `rank_items` and `rank_items_bf16` alternate call by call in one
+process, 2 warm-up calls and `--reps` timed calls each, by the host clock around the whole call (staging and copies included;
+median and minimum), and how far the two rankings differ on the held-out set.  No speed-up is promised: the counting does
+the same integer work in both forms, only the tile gets cheaper.
+python tools/bench_rank.py [--reps N] [--only name,...] [--bf16] [--out FILE]"""
 import argparse
 import json
 import os
@@ -76,7 +80,46 @@ def host_baseline(t, users, tg, xp, xi, max_users):
     return dict(host_us=round(dt * 1e6 * users.size / sub, 1), host_threads=os.cpu_count(), host_users_timed=int(sub))
 
 
-def run(name, t, users, tg, ex, reps, host_users, rec_users=None):
+def alternate_host(arms, reps, warmup=2):
+    """arms: name -> call.  Warm-up and timed calls alternate the arms call by call."""
+    for _ in range(warmup):
+        for fn in arms.values():
+            fn()
+    ts = {name: [] for name in arms}
+    for _ in range(reps):
+        for name, fn in arms.items():
+            t0 = time.perf_counter()
+            fn()
+            ts[name].append((time.perf_counter() - t0) * 1e6)
+    return {name: (float(np.median(v)), float(np.min(v))) for name, v in ts.items()}
+
+
+def run_bf16(name, t, users, tg, ex, reps):
+    U, D = t["P"].shape
+    I = t["Q"].shape[0]
+    m = T.SvdModel(U, I, D)
+    m.set_tables(t["mu"], t["bu"], t["bi"], t["P"], t["Q"])
+    m.snapshot_bf16()
+    m.sync()
+    res = alternate_host({"f32": lambda: m.rank_items(users, tg, exclude=ex),
+                          "bf16": lambda: m.rank_items_bf16(users, tg, exclude=ex)}, reps)
+    rf, rb = m.rank_items(users, tg, exclude=ex), m.rank_items_bf16(users, tg, exclude=ex)
+    m.close()
+    (fm, fb), (bm, bb) = res["f32"], res["bf16"]
+    ranked = (rf >= 0) & (rb >= 0)
+    d = np.abs(rf[ranked].astype(np.int64) - rb[ranked])
+    return dict(shape=name, users=int(users.size), items=I, dim=D, targets=int(tg[1].size),
+                exclusions=0 if ex is None else int(ex[1].size), reps=reps,
+                f32_us_median=round(fm, 1), f32_us_min=round(fb, 1), bf16_us_median=round(bm, 1), bf16_us_min=round(bb, 1),
+                bf16_over_f32=round(bm / fm, 3), same_rank_fraction=round(float(np.mean(d == 0)), 4),
+                median_abs_rank_shift=float(np.median(d)), max_abs_rank_shift=int(d.max()),
+                targets_in_top10_f32=round(float(np.mean((rf >= 0) & (rf < 10))), 5),
+                targets_in_top10_bf16=round(float(np.mean((rb >= 0) & (rb < 10))), 5))
+
+
+def run(name, t, users, tg, ex, reps, host_users, bf16=False):
+    if bf16:
+        return run_bf16(name, t, users, tg, ex, reps)
     U, D = t["P"].shape
     I = t["Q"].shape[0]
     m = T.SvdModel(U, I, D)
@@ -100,7 +143,7 @@ def run(name, t, users, tg, ex, reps, host_users, rec_users=None):
     return out
 
 
-def ml1m(reps, host_users):
+def ml1m(reps, host_users, bf16=False):
     rng = np.random.default_rng(0)
     U, I, D, N = 6040, 3706, 64, 1000209
     t = tables(rng, U, I, D)
@@ -112,10 +155,10 @@ def ml1m(reps, host_users):
     tg = (np.ascontiguousarray(tm[users].indptr, np.int64), np.ascontiguousarray(tm[users].indices, np.int32))
     x = train_x[users]
     ex = (np.ascontiguousarray(x.indptr, np.int64), np.ascontiguousarray(x.indices, np.int32))
-    return run("ml1m_80_20", t, users, tg, ex, reps, host_users)
+    return run("ml1m_80_20", t, users, tg, ex, reps, host_users, bf16)
 
 
-def large(reps, host_users):
+def large(reps, host_users, bf16=False):
     rng = np.random.default_rng(1)
     U, I, D = 4096, 1 << 20, 64
     t = tables(rng, U, I, D)
@@ -124,7 +167,7 @@ def large(reps, host_users):
     xrows = [np.sort(rng.choice(I, 200, replace=False)) for _ in range(U)]
     tg = (np.arange(0, 32 * U + 1, 32, dtype=np.int64), np.concatenate(trows).astype(np.int32))
     ex = (np.arange(0, 200 * U + 1, 200, dtype=np.int64), np.concatenate(xrows).astype(np.int32))
-    return run("large_4096x1M", t, users, tg, ex, reps, host_users)
+    return run("large_4096x1M", t, users, tg, ex, reps, host_users, bf16)
 
 
 def main():
@@ -132,14 +175,22 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--host-users", type=int, default=128)
     ap.add_argument("--only", default="")
+    ap.add_argument("--bf16", action="store_true", help="alternate rank_items and rank_items_bf16 on the same shapes")
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
     torch.cuda.init()
-    cases = {"ml1m_80_20": lambda: ml1m(a.reps, a.host_users), "large_4096x1M": lambda: large(a.reps, a.host_users)}
+    cases = {"ml1m_80_20": lambda: ml1m(a.reps, a.host_users, a.bf16),
+             "large_4096x1M": lambda: large(a.reps, a.host_users, a.bf16)}
     only = [s for s in a.only.split(",") if s]
+    lines = []
     for name, fn in cases.items():
         if only and name not in only:
             continue
-        print(json.dumps(fn()), flush=True)
+        lines.append(json.dumps(fn()))
+        print(lines[-1], flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
