@@ -117,7 +117,18 @@ int tfr_eval_resident(tfr_model* m, double* sum_sq_err_out, int64_t* n_equal_out
 int tfr_eval_binary(tfr_model* m, const int32_t* user, const int32_t* item, const float* rate, int64_t batch,
                     int64_t* n_equal_out, double* nll_sum_out, double* auc_out);
 int tfr_eval_binary_resident(tfr_model* m, int64_t* n_equal_out, double* nll_sum_out, double* auc_out, int64_t* n_out);
-/* roc_auc_score(rates, sigmoid(logits)) of the batch the last tfr_train_step ran on (svd_train_val.py:97) */
+/* roc_auc_score(rates, sigmoid(logits)) of the batch the last tfr_train_step or tfr_train_steps_repeat ran on (svd_train_val.py:97):
+ * its rates against the pre-update logits that call returned (tfr_train_steps_repeat: of its last step).  The batch is kept
+ * in the handle's workspace, not copied, so the call is valid only while that batch is still there: after a tfr_train_step /
+ * tfr_train_steps_repeat that was given logits_out, of any batch size, and before
+ *   - any other training call (the resident, staged, drawn, device-pointer, BPR, fine-tuning, data-parallel and row-sharded
+ *     steps, and a tfr_train_step without logits_out),
+ *   - tfr_forward, tfr_forward_resident, tfr_eval, tfr_eval_binary[_resident], tfr_bf16_forward, tfr_bf16_eval,
+ *   - any call whose batch exceeds the workspace and makes it grow.
+ * Each of these forgets the kept batch, and the call then returns TFR_ERR_STATE; it never returns the AUC of other numbers.
+ * Calls that leave the batch workspace alone (top-K, ranking, neighbours, the snapshot, get / set of tables, step, frozen
+ * mask and hyper-parameters, tfr_eval_resident, tfr_auc_dev and tfr_sort_segments within the capacity, the id draws) keep
+ * it; the call itself may be repeated. */
 int tfr_last_batch_auc(tfr_model* m, double* auc_out);
 /* roc_auc_score(label > 0.5, score) for device arrays */
 int tfr_auc_dev(tfr_model* m, const float* d_score, const float* d_label, int64_t n, double* auc_out);

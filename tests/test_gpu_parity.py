@@ -669,10 +669,12 @@ def test_train_step_large_against_compacted_oracle(opt, mode):
 @pytest.mark.parametrize("opt,mode,item_abs", [("adam", "lazy", False), ("sgd", "tf1", True)])
 def test_two_table_item_rows_settle_before_every_other_reader(opt, mode, item_abs):
     """The fused big-table step keeps no copy of the pre-update item rows: an updated row goes to the alternate item table and
-    the row's word flips (svd_kernels.h RedArgs::sel).  Everything else that looks at item_features - forward, eval, get /
-    set_table, the row-sharded and data-parallel entry points - must first see every row back in the main table.  Steps and readers are
-    interleaved here and each result is held against the float64 oracle; the same item rows are touched again and again
-    (they flip back and forth), some by runs cut at a block boundary (finished in place by k_apply_rows)."""
+    the row's word flips (svd_kernels.h RedArgs::sel).  Everything else that looks at item_features must first see every row
+    back in the main table.  Four such readers are interleaved with the steps here - forward, get_table, set_table and a
+    small step - and each result is held against the float64 oracle; the same item rows are touched again and again
+    (they flip back and forth), some by runs cut at a block boundary (finished in place by k_apply_rows).  Every other entry
+    point (eval, top-K, ranking, neighbours, fine-tuning, BPR, the snapshot, the row-sharded and data-parallel calls,
+    init_tables, the steps of the other paths) meets the two-table state in tests/test_gpu_call_sequences.py."""
     U, I, D, B = 40000, 30000, 64, 20000
     rs = np.random.RandomState(31)
     t = rand_tables(rs, U, I, D, scale=0.15)

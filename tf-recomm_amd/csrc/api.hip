@@ -274,8 +274,14 @@ static float* item_copy_rows(const tfr_model* m) { return m->gq + 2 * (size_t)m-
 static float* grad_rows(const tfr_model* m, int side) { return side == TFR_P ? user_grad_rows(m) : m->gq.get(); }
 static float* grad_bias(const tfr_model* m, int side) { return side == TFR_P ? m->gbp.get() : m->gbq.get(); }
 
+// tfr_last_batch_auc reads the kept batch where the step left it: the logits in d_logits, the rates in d_in (staged batches)
+// or d_r.  Whatever overwrites, swaps or reallocates one of them, and every training call, forgets the batch first, so that
+// the call refuses (TFR_ERR_STATE) where it would otherwise rank unrelated numbers or read freed memory.
+static void forget_kept_batch(tfr_model* m) { m->last_r = nullptr; m->last_B = 0; }
+
 static int ensure_capacity(tfr_model* m, int64_t B) {
     if (B <= m->cap) return TFR_OK;
+    forget_kept_batch(m);                                // d_logits and d_r are reallocated
     const int64_t cap = pow2_cap(B);
     if (cap > (int64_t)1 << 30) return fail(TFR_ERR_ARG, "batch %lld too large", (long long)B);
     hipStream_t s = m->stream;
@@ -1330,6 +1336,7 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
     int nblk = 0, rc;
     hipStream_t s = m->stream;
     bool fin_done = false;
+    forget_kept_batch(m);                                // (tfr_train_step / tfr_train_steps_repeat keep theirs after this)
     FinArgs f = mu_fin(m, k, !((m->frozen >> TFR_MU) & 1), out3);
     f.partials = m->partials; f.out_err = out_err ? 1 : 0;
     const bool tiles = tiles_eligible(m, B);
@@ -1388,6 +1395,7 @@ static void rollback_step(tfr_model* m, const StepMark& k) {
 static const int64_t STAGE_MAX = 1 << 20;
 static int ensure_staging(tfr_model* m, int64_t B) {
     const int64_t cap = pow2_cap(B);
+    forget_kept_batch(m);                                // d_in is about to be rewritten, perhaps reallocated
     HIPCHK(m->d_in.reserve(3 * cap, m->stream));
     HIPCHK(m->h_in.reserve(3 * cap, m->stream));
     HIPCHK(m->h_out.reserve(cap + 4, m->stream));
@@ -1402,6 +1410,7 @@ static int check_batch(const void* u, const void* i, int64_t B) {
 
 // a host batch's three columns into d_u / d_i / d_r (the workspace holds B: ensure_capacity)
 static int upload_triples(tfr_model* m, const int32_t* u, const int32_t* i, const float* r, int64_t B) {
+    forget_kept_batch(m);
     HIPCHK(hipMemcpyAsync(m->d_u, u, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(m->d_i, i, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
     HIPCHK(hipMemcpyAsync(m->d_r, r, (size_t)B * 4, hipMemcpyHostToDevice, m->stream));
@@ -1431,6 +1440,7 @@ static int forward_host(tfr_model* m, FwdRows rows, const int32_t* u, const int3
     if (B == 0) return TFR_OK;
     if (!logits_out) return fail(TFR_ERR_ARG, "null logits pointer");
     if ((rc = ensure_capacity(m, B))) return rc;
+    forget_kept_batch(m);                                // the logits land in d_logits
     if (B <= STAGE_MAX) {                                // pinned staging: one copy in, one out (+ the error flag)
         if ((rc = ensure_staging(m, B))) return rc;
         memcpy(m->h_in, u, (size_t)B * 4);
@@ -1491,6 +1501,7 @@ static int eval_device(tfr_model* m, const int32_t* du, const int32_t* di, const
                        FwdRows rows = ROWS_F32) {
     int nblk = 0, rc;
     if (auc_out && (rc = ensure_capacity(m, B))) return rc;
+    if (auc_out) forget_kept_batch(m);                   // the logits land in d_logits
     if ((rc = run_forward(m, MODE_EVAL, du, di, dr, B, auc_out ? m->d_logits : nullptr, nullptr, &nblk, nullptr, rows))) return rc;
     std::vector<float> part((size_t)nblk * 4);
     HIPCHK(hipMemcpyAsync(part.data(), m->partials, part.size() * 4, hipMemcpyDeviceToHost, m->stream));
@@ -1675,7 +1686,7 @@ int tfr_train_step(tfr_model* m, const int32_t* u, const int32_t* i, const float
     if ((rc = ensure_capacity(m, B > 0 ? B : 1))) return rc;
     const StepMark mark = mark_step(m);
     float sc[4] = {0.f, 0.f, 0.f, 0.f};
-    m->last_r = nullptr;
+    forget_kept_batch(m);
     if (B > 0 && B <= STAGE_MAX) {
         // one pinned H2D copy in, the kernels, one D2H copy out: [logits | loss, reg, sum g, error flag]
         if ((rc = ensure_staging(m, B))) return rc;
@@ -1708,6 +1719,7 @@ int tfr_train_step(tfr_model* m, const int32_t* u, const int32_t* i, const float
             rollback_step(m, mark);
             return rc;
         }
+        if (logits_out && B > 0) { m->last_r = m->d_r; m->last_B = B; }
     }
     if (loss_out) *loss_out = sc[0];
     if (reg_out) *reg_out = sc[1];
@@ -1725,7 +1737,6 @@ int tfr_train_steps_repeat(tfr_model* m, const int32_t* u, const int32_t* i, con
     if ((rc = ensure_capacity(m, B))) return rc;
     if (loss_out) HIPCHK(m->step_out.reserve((int64_t)nsteps * 4, m->stream));
     const StepMark mark = mark_step(m);
-    m->last_r = nullptr;
     if ((rc = upload_triples(m, u, i, r, B))) return rc;
     for (int32_t s = 0; s < nsteps; ++s) {
         const bool last = s + 1 == nsteps;
@@ -1751,12 +1762,14 @@ int tfr_train_steps_repeat(tfr_model* m, const int32_t* u, const int32_t* i, con
     return TFR_OK;
 }
 
-/* roc_auc_score(rates, sigmoid(logits)) of the batch the last tfr_train_step ran on (its pre-update logits, the ones
- * the caller was handed): svd_train_val.py:97, without sklearn on the host.  Needs that call to have asked for logits. */
+/* roc_auc_score(rates, sigmoid(logits)) of the batch the last tfr_train_step / tfr_train_steps_repeat ran on (its pre-update
+ * logits, the ones the caller was handed): svd_train_val.py:97, without sklearn on the host.  Needs that call to have asked
+ * for logits, and nothing since to have trained or used the batch workspace (forget_kept_batch): TFR_ERR_STATE otherwise. */
 int tfr_last_batch_auc(tfr_model* m, double* auc_out) {
     MODEL_ENTER(m);
     if (!auc_out) return fail(TFR_ERR_ARG, "null output");
-    if (!m->last_r || m->last_B < 1) return fail(TFR_ERR_STATE, "no kept batch: call tfr_train_step with logits_out first (batches up to 2^20)");
+    if (!m->last_r || m->last_B < 1) return fail(TFR_ERR_STATE, "no kept batch: tfr_last_batch_auc follows a tfr_train_step / tfr_train_steps_repeat that returned logits, "
+                                                                "with no training, forward or evaluation call in between");
     return auc_device(m, m->d_logits, m->last_r, m->last_B, auc_out);
 }
 
@@ -1858,6 +1871,7 @@ static int gather_batch(tfr_model* m, const int64_t* d_ids, int64_t lo, int64_t 
     g.ids = d_ids; g.lo = lo; g.B = B; g.N = m->N;
     g.store = m->store;
     g.u = m->d_u; g.it = m->d_i; g.r = m->d_r; g.err = m->d_err;
+    forget_kept_batch(m);
     {
         Prof p(m, TFR_K_GATHER);
         launch_gather(g, m->stream);
@@ -2502,7 +2516,7 @@ int tfr_forward_resident(tfr_model* m, int64_t lo, int64_t hi, float* logits_out
     if (B == 0) return TFR_OK;
     int rc;
     if ((rc = ensure_capacity(m, B))) return rc;
-    if ((rc = gather_batch(m, nullptr, lo, B))) return rc;
+    if ((rc = gather_batch(m, nullptr, lo, B))) return rc;      // (forgets the kept batch: d_r and d_logits are rewritten)
     if ((rc = run_forward(m, MODE_INFER, m->d_u, m->d_i, nullptr, B, m->d_logits, nullptr, nullptr))) return rc;
     if (logits_out) {
         HIPCHK(hipMemcpyAsync(logits_out, m->d_logits, (size_t)B * 4, hipMemcpyDeviceToHost, m->stream));
@@ -2659,6 +2673,7 @@ static int shard_forward_reduce_part(tfr_model* m, const float* d_item_rows, flo
     const int32_t* du = R.u; const int32_t* dslot = R.slot; const float* dr = R.r;
     const int32_t* dB = R.counts;                         // the local batch size, on the device
     int rc;
+    forget_kept_batch(m);                                // a training call
     if ((rc = ensure_capacity(m, B > nI ? B : nI))) return rc;
     const OptStep k = opt_step(m);
     hipStream_t s = m->stream;
@@ -2905,6 +2920,7 @@ int tfr_dp_local_grads(tfr_model* m, const int32_t* du, const int32_t* di, const
         return fail(TFR_ERR_STATE, "data-parallel steps need dense semantics: Adam tf1 or SGD");
     int rc;
     if ((rc = settle_q(m))) return rc;
+    forget_kept_batch(m);
     const int64_t* next_ids = d_store_ids ? m->dp_next_ids : nullptr;     // one-shot hint (tfr_dp_hint_next)
     m->dp_next_ids = nullptr;
     if ((rc = ensure_capacity(m, B > 0 ? B : 1))) return rc;
@@ -3827,6 +3843,7 @@ int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, cons
                  o_final = take(final_logits_out ? (size_t)n_rows * 4 : 0);
     HIPCHK(m->ft_buf.reserve((int64_t)off, m->stream));
     if ((rc = settle_q(m))) return rc;                   // item rows the fused big-table step left in q_alt come back first
+    forget_kept_batch(m);                                // a training call
     char* b = m->ft_buf;
     hipStream_t s = m->stream;
     auto up = [&](size_t at, const void* src, size_t bytes) -> int {

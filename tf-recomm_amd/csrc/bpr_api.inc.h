@@ -80,6 +80,7 @@ static int bpr_step(tfr_model* m, BprState* h, const int32_t* du, const int32_t*
     const OptStep k = opt_step(m);
     int rc;
     if ((rc = settle_q(m)) || (rc = bpr_ensure_batch(m, h, B))) return rc;
+    forget_kept_batch(m);                                // a training call
     hipStream_t s = m->stream;
     if (B > 0) {
         BprSampleArgs sa;

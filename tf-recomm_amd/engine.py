@@ -276,7 +276,11 @@ class SvdModel:
         return dict(acc=neq.value / max(1, n.value), mean_nll=nll.value / max(1, n.value), auc=auc.value, n=n.value)
 
     def last_batch_auc(self):
-        """AUC of the batch the last ``train_step`` (with logits) ran on - svd_train_val.py:97 on the device."""
+        """AUC of the batch the last ``train_step`` / ``train_steps_repeat`` (with logits) ran on - svd_train_val.py:97 on
+        the device: that batch's rates against the logits the call returned.  The batch stays in the handle's workspace, so
+        ask right after the step: any other training call, ``forward``, ``forward_resident``, ``eval``, ``eval_binary*``,
+        ``forward_bf16`` / ``eval_bf16`` or a call that makes the workspace grow forgets it, and this then raises
+        ``TfrError`` (``ERR_STATE``) rather than rank other numbers (include/tfrecomm.h tfr_last_batch_auc)."""
         auc = C.c_double()
         L.check(self._lib.tfr_last_batch_auc(self._h, C.byref(auc)))
         return auc.value
