@@ -776,6 +776,38 @@ int tfr_bf16_neighbours_dev(tfr_model* m, int32_t which, int32_t metric, const i
                             const int64_t* d_excl_indptr, const int32_t* d_excl, int64_t lo, int64_t hi,
                             int32_t* d_ids_out, float* d_scores_out);
 
+/* ---- the FM from a bf16 snapshot: forward, resident predict / eval and top-K at half the row bytes - DESIGN §28 ----------
+ *      The snapshot is the one described above, taken of an FM handle: V as bf16 rows (format, rounding, stride DP and
+ *      pads as above), W and mu of the same moment in float32.  tfr_fm_train_step*, tfr_fm_train_steps_resident,
+ *      tfr_fm_set and tfr_fm_init do not change it, only another tfr_fm_bf16_snapshot does; tfr_fm_destroy frees it.
+ *      tfr_fm_bf16_snapshot builds or refreshes it on the model's stream and does not synchronise (n_features * DP * 2
+ *      bytes plus the copy of W); tfr_fm_bf16_drop frees it (TFR_OK when there is none).  tfr_fm_bf16_get_rows copies the
+ *      packed V out for debugging: n = n_features * DP.
+ *      Every other entry below returns TFR_ERR_STATE (naming tfr_fm_bf16_snapshot) before a snapshot, also for
+ *      n_rows = 0 or n_users = 0, and reads the snapshot only.  Argument lists, checks, device-pointer conventions and
+ *      the deferred TFR_ERR_OOB of a feature id outside [0, n_features) are those of the entry without bf16 in its name.
+ *      tfr_fm_bf16_forward*: the formula of tfr_fm_forward with V widened by a shift, in float32: per element
+ *      xv = x * v, s += xv, q = fmaf(xv, xv, q) over the row's entries in CSR order, then sum_e (s_e^2 - q_e) over a
+ *      lane's 8 elements ascending, the lanes' sums by a butterfly, y = (mu + x.W) + 0.5 * that.  Where every product
+ *      and sum is exact it equals tfr_fm_forward bit for bit; results are bit-identical from run to run and do not
+ *      depend on the other rows of the call.
+ *      tfr_fm_bf16_predict_resident / tfr_fm_bf16_eval_binary_resident: tfr_fm_predict_resident /
+ *      tfr_fm_eval_binary_resident with that forward; the metrics are computed from its predictions as theirs are.
+ *      tfr_fm_bf16_topk: tfr_fm_topk's users, item range, ids relative to item_lo and exclusions with tfr_bf16_topk's
+ *      score, keys, tie order and padding on the snapshot: ((dot + mu) + W[u]) + W[item_lo + i]. */
+int tfr_fm_bf16_snapshot(tfr_fm* m);
+int tfr_fm_bf16_drop(tfr_fm* m);
+int tfr_fm_bf16_get_rows(tfr_fm* m, uint16_t* host, int64_t n);
+int tfr_fm_bf16_forward(tfr_fm* m, const int64_t* indptr, const int32_t* indices, const float* data,
+                        int64_t n_rows, float* out);                           /* host CSR, synchronous */
+int tfr_fm_bf16_forward_dev(tfr_fm* m, const int64_t* d_indptr, const int32_t* d_indices,
+                            const float* d_data, int64_t n_rows, float* d_out); /* device CSR, async */
+int tfr_fm_bf16_predict_resident(tfr_fm* m, int32_t which, float* out);
+int tfr_fm_bf16_eval_binary_resident(tfr_fm* m, int64_t* n_equal_out, double* nll_sum_out, double* auc_out, int64_t* n_out);
+int tfr_fm_bf16_topk(tfr_fm* m, const int32_t* user_features, int64_t n_users, int64_t item_lo, int64_t item_hi,
+                     int32_t k, const int64_t* excl_indptr, const int32_t* excl_items,
+                     int32_t* items_out, float* scores_out);
+
 /* ---- misc ------------------------------------------------------------------------------ */
 int tfr_sync(tfr_model* m);            /* drains the stream; reports deferred TFR_ERR_OOB   */
 const char* tfr_last_error(void);

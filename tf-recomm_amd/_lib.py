@@ -147,6 +147,14 @@ SIGNATURES = {
     "tfr_fm_gather_rows": (C.c_int, [_p, C.c_int32, _i64p, C.c_int64, _i64p, _i32p, _f32p, _f32p, C.c_int64]),
     "tfr_fm_predict_resident": (C.c_int, [_p, C.c_int32, _f32p]),
     "tfr_fm_eval_binary_resident": (C.c_int, [_p, _i64p, _f64p, _f64p, _i64p]),
+    "tfr_fm_bf16_snapshot": (C.c_int, [_p]),
+    "tfr_fm_bf16_drop": (C.c_int, [_p]),
+    "tfr_fm_bf16_get_rows": (C.c_int, [_p, C.POINTER(C.c_uint16), C.c_int64]),
+    "tfr_fm_bf16_forward": (C.c_int, [_p, _i64p, _i32p, _f32p, C.c_int64, _f32p]),
+    "tfr_fm_bf16_forward_dev": (C.c_int, [_p, _p, _p, _p, C.c_int64, _p]),
+    "tfr_fm_bf16_predict_resident": (C.c_int, [_p, C.c_int32, _f32p]),
+    "tfr_fm_bf16_eval_binary_resident": (C.c_int, [_p, _i64p, _f64p, _f64p, _i64p]),
+    "tfr_fm_bf16_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
     "tfr_als_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_int32, C.c_double, C.c_int32]),
     "tfr_als_destroy": (C.c_int, [_p]),
     "tfr_als_set": (C.c_int, [_p, _f64p, _f64p, _f64p, _f64p]),

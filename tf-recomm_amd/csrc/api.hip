@@ -21,6 +21,7 @@
 #include "rank.h"
 #include "finetune.h"
 #include "bf16_rows.h"
+#include "fm_bf16.h"
 #include "devbuf.h"
 
 using namespace tfr;
@@ -1417,8 +1418,9 @@ static int upload_triples(tfr_model* m, const int32_t* u, const int32_t* i, cons
     return TFR_OK;
 }
 
-static int bf16_need_snapshot(const tfr_model* m) {
-    return m->bf.valid ? TFR_OK : fail(TFR_ERR_STATE, "no bf16 snapshot: call tfr_bf16_snapshot first");
+// `call`: the entry that makes the snapshot of this handle (an FM handle's is tfr_fm_bf16_snapshot)
+static int bf16_need_snapshot(const tfr_model* m, const char* call = "tfr_bf16_snapshot") {
+    return m->bf.valid ? TFR_OK : fail(TFR_ERR_STATE, "no bf16 snapshot: call %s first", call);
 }
 
 // ---- forward ---------------------------------------------------------------------------
@@ -3065,8 +3067,36 @@ static int fm_variant(const tfr_model* m) {
     return ((size_t)m->U * m->D * 4 >= ((size_t)128 << 20)) ? 2 : 0;      // V beyond half the Infinity Cache: stream it
 }
 
+static int fm_bf16_need_snapshot(const tfr_fm* f) { return bf16_need_snapshot(f->m, "tfr_fm_bf16_snapshot"); }
+
+// TFR_FM_BF16_NTV=0|1: A/B override of the non-temporal V rows of k_fm_forward_bf16 (unset: fm_variant's rule on the
+// snapshot's bytes).  Read at every launch, so that one process can alternate the two (tools/bench_bf16_fm.py --ntv-ab).
+static bool fm_bf16_ntv(const tfr_model* m) {
+    if (env_default_off("TFR_FM_BF16_NTV")) return true;
+    if (!env_default_on("TFR_FM_BF16_NTV")) return false;
+    return (size_t)m->U * bf16_row_stride(m->D) * 2 >= ((size_t)128 << 20);
+}
+
+// the same forward on the snapshot's rows (fm_bf16.hip); the caller has tested for the snapshot
+static int fm_bf16_forward_core(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_indices, const float* d_data,
+                                int64_t n_rows, float* d_out) {
+    tfr_model* m = f->m;
+    FmBf16Args a;
+    memset(&a, 0, sizeof(a));
+    a.V = m->bf.p; a.W = m->bf.bu; a.mu = m->bf.mu;
+    a.indptr = d_indptr; a.indices = d_indices; a.data = d_data; a.out = d_out; a.err = m->d_err;
+    a.n_rows = n_rows; a.F = m->U; a.DP = bf16_row_stride(m->D);
+    const int G = bf16_geometry(m->D);
+    (void)hipEventRecord(f->ev0, m->stream);
+    launch_fm_bf16(a, G, fm_bf16_grid(n_rows, G), fm_bf16_ntv(m), m->stream);
+    (void)hipEventRecord(f->ev1, m->stream);
+    HIPCHK(hipGetLastError());
+    return TFR_OK;
+}
+
 static int fm_forward_core(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_indices, const float* d_data,
-                           int64_t n_rows, float* d_out) {
+                           int64_t n_rows, float* d_out, FwdRows rows = ROWS_F32) {
+    if (rows == ROWS_BF16) return fm_bf16_forward_core(f, d_indptr, d_indices, d_data, n_rows, d_out);
     tfr_model* m = f->m;
     FmArgs a;
     memset(&a, 0, sizeof(a));
@@ -3236,28 +3266,74 @@ int tfr_fm_init(tfr_fm* f, uint64_t seed, float stddev) {
     return TFR_OK;
 }
 
-int tfr_fm_forward_dev(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_indices, const float* d_data,
-                       int64_t n_rows, float* d_out) {
+}  // extern "C"
+
+// the bodies of tfr_fm_forward_dev / tfr_fm_forward and of their snapshot twins, which differ in `rows` and in the snapshot
+// test (which comes before n_rows == 0, as in the tfr_bf16_* entries)
+static int fm_forward_dev(tfr_fm* f, FwdRows rows, const int64_t* d_indptr, const int32_t* d_indices, const float* d_data,
+                          int64_t n_rows, float* d_out) {
     if (!f || n_rows < 0 || (n_rows > 0 && (!d_indptr || !d_out))) return fail(TFR_ERR_ARG, "bad arguments");
     HIPCHK(hipSetDevice(f->m->device));
+    int rc;
+    if (rows == ROWS_BF16 && (rc = fm_bf16_need_snapshot(f))) return rc;
     if (n_rows == 0) return TFR_OK;
-    int rc = ensure_capacity(f->m, 1);
-    if (rc) return rc;
-    return fm_forward_core(f, d_indptr, d_indices, d_data, n_rows, d_out);
+    if ((rc = ensure_capacity(f->m, 1))) return rc;
+    return fm_forward_core(f, d_indptr, d_indices, d_data, n_rows, d_out, rows);
+}
+
+static int fm_forward_host(tfr_fm* f, FwdRows rows, const int64_t* indptr, const int32_t* indices, const float* data,
+                           int64_t n_rows, float* out) {
+    if (!f || n_rows < 0 || (n_rows > 0 && (!indptr || !out))) return fail(TFR_ERR_ARG, "bad arguments");
+    tfr_model* m = f->m;
+    HIPCHK(hipSetDevice(m->device));
+    int rc;
+    if (rows == ROWS_BF16 && (rc = fm_bf16_need_snapshot(f))) return rc;
+    if (n_rows == 0) return TFR_OK;
+    int64_t nnz = 0;
+    if ((rc = fm_stage_csr(f, indptr, indices, data, nullptr, n_rows, &nnz))) return rc;
+    if ((rc = fm_forward_core(f, f->d_indptr, f->d_indices, f->d_data, n_rows, f->d_out, rows))) return rc;
+    HIPCHK(hipMemcpyAsync(out, f->d_out, (size_t)n_rows * 4, hipMemcpyDeviceToHost, m->stream));
+    return check_device_error(m);
+}
+
+extern "C" {
+
+int tfr_fm_forward_dev(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_indices, const float* d_data,
+                       int64_t n_rows, float* d_out) {
+    return fm_forward_dev(f, ROWS_F32, d_indptr, d_indices, d_data, n_rows, d_out);
 }
 
 int tfr_fm_forward(tfr_fm* f, const int64_t* indptr, const int32_t* indices, const float* data,
                    int64_t n_rows, float* out) {
-    if (!f || n_rows < 0 || (n_rows > 0 && (!indptr || !out))) return fail(TFR_ERR_ARG, "bad arguments");
-    tfr_model* m = f->m;
-    HIPCHK(hipSetDevice(m->device));
-    if (n_rows == 0) return TFR_OK;
-    int64_t nnz = 0;
-    int rc = fm_stage_csr(f, indptr, indices, data, nullptr, n_rows, &nnz);
-    if (rc) return rc;
-    if ((rc = fm_forward_core(f, f->d_indptr, f->d_indices, f->d_data, n_rows, f->d_out))) return rc;
-    HIPCHK(hipMemcpyAsync(out, f->d_out, (size_t)n_rows * 4, hipMemcpyDeviceToHost, m->stream));
-    return check_device_error(m);
+    return fm_forward_host(f, ROWS_F32, indptr, indices, data, n_rows, out);
+}
+
+// ---- the FM on the bf16 snapshot (fm_bf16.h): V = the wrapped model's P, W = its bu, so the snapshot is the wrapped model's
+int tfr_fm_bf16_snapshot(tfr_fm* f) {
+    if (!f) return fail(TFR_ERR_ARG, "null model");
+    return tfr_bf16_snapshot(f->m);
+}
+
+int tfr_fm_bf16_drop(tfr_fm* f) {
+    if (!f) return fail(TFR_ERR_ARG, "null model");
+    return tfr_bf16_drop(f->m);
+}
+
+int tfr_fm_bf16_get_rows(tfr_fm* f, uint16_t* host, int64_t n) {
+    if (!f) return fail(TFR_ERR_ARG, "null model");
+    HIPCHK(hipSetDevice(f->m->device));
+    if (int rc = fm_bf16_need_snapshot(f)) return rc;
+    return tfr_bf16_get_rows(f->m, TFR_P, host, n);
+}
+
+int tfr_fm_bf16_forward_dev(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_indices, const float* d_data,
+                            int64_t n_rows, float* d_out) {
+    return fm_forward_dev(f, ROWS_BF16, d_indptr, d_indices, d_data, n_rows, d_out);
+}
+
+int tfr_fm_bf16_forward(tfr_fm* f, const int64_t* indptr, const int32_t* indices, const float* data,
+                        int64_t n_rows, float* out) {
+    return fm_forward_host(f, ROWS_BF16, indptr, indices, data, n_rows, out);
 }
 
 int tfr_fm_train_step_dev(tfr_fm* f, const int64_t* d_indptr, const int32_t* d_indices, const float* d_data,
@@ -3295,7 +3371,10 @@ int tfr_fm_sync(tfr_fm* f, float* last_kernel_ms) {
     if (rc) return rc;
     if (last_kernel_ms) {
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, f->ev0, f->ev1) != hipSuccess) ms = 0.f;
+        if (hipEventElapsedTime(&ms, f->ev0, f->ev1) != hipSuccess) {   // no timed launch yet (a snapshot is none)
+            ms = 0.f;
+            (void)hipGetLastError();                     // or the next launch's check would report this one
+        }
         *last_kernel_ms = ms;
     }
     return TFR_OK;
@@ -3566,6 +3645,41 @@ int tfr_fm_topk(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_
     int rc = check_k("top-K", k);
     if (rc || (rc = fm_topk_tables(m, "top-K", item_lo, item_hi, &t))) return rc;
     return topk_host(m, t, user_features, n_users, k, excl_indptr, excl_items, items_out, scores_out);
+}
+
+}  // extern "C"
+
+// fm_topk_tables taken from the wrapped model's snapshot: users are all features, items the features [item_lo, item_hi)
+struct FmBf16TopkQuery : SlicedQuery {
+    tfr_model* m;
+    int64_t item_lo;
+    FmBf16TopkQuery(tfr_model* m_, int64_t lo, int64_t n_items)
+        : SlicedQuery{"bf16 top-K", n_items, n_items, 0, false}, m(m_), item_lo(lo) {}
+    int64_t users() const { return m->U; }
+    void score(const SlicedArgs& c, const TopkPlan& p, hipStream_t s) const {
+        Bf16TopkArgs a = {};
+        static_cast<SlicedArgs&>(a) = c;
+        const int DP = bf16_row_stride(m->D);
+        a.P = m->bf.p; a.bu = m->bf.bu; a.Q = m->bf.p + item_lo * DP; a.bi = m->bf.bu + item_lo; a.mu = m->bf.mu;
+        a.U = m->U; a.n_items = n_cand; a.DP = DP;
+        launch_bf16_topk_score(a, p, s);
+    }
+};
+
+extern "C" {
+
+// the snapshot test comes before every other check, n_users == 0 included, as in tfr_bf16_topk
+int tfr_fm_bf16_topk(tfr_fm* f, const int32_t* user_features, int64_t n_users, int64_t item_lo, int64_t item_hi, int32_t k,
+                     const int64_t* excl_indptr, const int32_t* excl_items, int32_t* items_out, float* scores_out) {
+    if (!f) return fail(TFR_ERR_ARG, "null model");
+    tfr_model* m = f->m;
+    HIPCHK(hipSetDevice(m->device));
+    int rc = fm_bf16_need_snapshot(f);
+    if (rc) return rc;
+    TopkTables t;                                        // for its range check and item count; the float32 pointers are not used
+    if ((rc = check_k("bf16 top-K", k)) || (rc = fm_topk_tables(m, "bf16 top-K", item_lo, item_hi, &t))) return rc;
+    return topk_host(m, FmBf16TopkQuery(m, item_lo, t.n_items), user_features, n_users, k, excl_indptr, excl_items, items_out,
+                     scores_out);
 }
 
 }  // extern "C"

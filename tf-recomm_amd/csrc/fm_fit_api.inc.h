@@ -88,12 +88,12 @@ static int fm_fit_gather(tfr_fm* f, const FmStore& st, const int64_t* d_ids, int
     return TFR_OK;
 }
 
-// the wrapped model's predictions of a store's rows -> f->d_out
-static int fm_fit_forward(tfr_fm* f, const FmStore& st) {
+// the wrapped model's predictions of a store's rows -> f->d_out, from its float32 tables or from its bf16 snapshot
+static int fm_fit_forward(tfr_fm* f, const FmStore& st, FwdRows rows) {
     int rc = ensure_capacity(f->m, 1);
     if (rc) return rc;
     HIPCHK(f->d_out.reserve(st.n, f->m->stream));
-    return fm_forward_core(f, st.indptr, st.indices, st.data, st.n, f->d_out);
+    return fm_forward_core(f, st.indptr, st.indices, st.data, st.n, f->d_out, rows);
 }
 
 extern "C" {
@@ -214,29 +214,34 @@ int tfr_fm_train_steps_resident(tfr_fm* f, const int64_t* ids, int64_t batch, in
     return TFR_OK;
 }
 
-int tfr_fm_predict_resident(tfr_fm* f, int32_t which, float* out) {
+}  // extern "C"
+
+// the bodies of tfr_fm_predict_resident / tfr_fm_eval_binary_resident and of their snapshot twins: only the forward differs
+static int fm_predict_resident(tfr_fm* f, FwdRows rows, int32_t which, float* out) {
     if (!f || !out) return fail(TFR_ERR_ARG, "predict_resident: null argument");
     tfr_model* m = f->m;
     HIPCHK(hipSetDevice(m->device));
+    int rc;
+    if (rows == ROWS_BF16 && (rc = fm_bf16_need_snapshot(f))) return rc;
     FmStore* st;
-    int rc = fm_fit_store(f, which, &st);
-    if (rc) return rc;
-    if ((rc = fm_fit_forward(f, *st))) return rc;
+    if ((rc = fm_fit_store(f, which, &st))) return rc;
+    if ((rc = fm_fit_forward(f, *st, rows))) return rc;
     HIPCHK(hipMemcpyAsync(out, f->d_out, (size_t)st->n * 4, hipMemcpyDeviceToHost, m->stream));
     return check_device_error(m);
 }
 
-/* tfr_eval_binary_resident for the FM: accuracy count, summed sigmoid cross-entropy and AUC over the eval store */
-int tfr_fm_eval_binary_resident(tfr_fm* f, int64_t* neq_out, double* nll_sum_out, double* auc_out, int64_t* n_out) {
+static int fm_eval_binary_resident(tfr_fm* f, FwdRows rows, int64_t* neq_out, double* nll_sum_out, double* auc_out,
+                                   int64_t* n_out) {
     if (!f) return fail(TFR_ERR_ARG, "null model");
     tfr_model* m = f->m;
     HIPCHK(hipSetDevice(m->device));
+    int rc;
+    if (rows == ROWS_BF16 && (rc = fm_bf16_need_snapshot(f))) return rc;
     FmStore* st;
-    int rc = fm_fit_store(f, 1, &st);
-    if (rc) return rc;
+    if ((rc = fm_fit_store(f, 1, &st))) return rc;
     if (m->o.loss != TFR_LOSS_NLL) return fail(TFR_ERR_STATE, "eval_binary needs the binary-outcome model (loss = nll)");
     if (n_out) *n_out = st->n;
-    if ((rc = fm_fit_forward(f, *st))) return rc;
+    if ((rc = fm_fit_forward(f, *st, rows))) return rc;
     const int nblk = fm_metrics_grid(st->n);
     HIPCHK(f->fit->met.reserve((int64_t)nblk * 2, m->stream));
     launch_fm_binary_metrics(f->d_out, st->y, st->n, f->fit->met, m->stream);
@@ -253,6 +258,22 @@ int tfr_fm_eval_binary_resident(tfr_fm* f, int64_t* neq_out, double* nll_sum_out
     if (neq_out) *neq_out = neq;
     if (nll_sum_out) *nll_sum_out = nll;
     return auc_device(m, f->d_out, st->y, st->n, auc_out);
+}
+
+extern "C" {
+
+int tfr_fm_predict_resident(tfr_fm* f, int32_t which, float* out) { return fm_predict_resident(f, ROWS_F32, which, out); }
+
+/* tfr_eval_binary_resident for the FM: accuracy count, summed sigmoid cross-entropy and AUC over the eval store */
+int tfr_fm_eval_binary_resident(tfr_fm* f, int64_t* neq_out, double* nll_sum_out, double* auc_out, int64_t* n_out) {
+    return fm_eval_binary_resident(f, ROWS_F32, neq_out, nll_sum_out, auc_out, n_out);
+}
+
+/* the same two from the bf16 snapshot (fm_bf16.h): TFR_ERR_STATE before tfr_fm_bf16_snapshot, whatever the stores hold */
+int tfr_fm_bf16_predict_resident(tfr_fm* f, int32_t which, float* out) { return fm_predict_resident(f, ROWS_BF16, which, out); }
+
+int tfr_fm_bf16_eval_binary_resident(tfr_fm* f, int64_t* neq_out, double* nll_sum_out, double* auc_out, int64_t* n_out) {
+    return fm_eval_binary_resident(f, ROWS_BF16, neq_out, nll_sum_out, auc_out, n_out);
 }
 
 }  // extern "C"

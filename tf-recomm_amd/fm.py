@@ -144,50 +144,101 @@ class FmModel(object):
         return loss
 
     def predict_resident(self, which="eval"):
+        return self._predict_resident(self._lib.tfr_fm_predict_resident, which)
+
+    def predict_resident_bf16(self, which="eval"):
+        """``predict_resident`` from the bf16 snapshot (``snapshot_bf16``)."""
+        return self._predict_resident(self._lib.tfr_fm_bf16_predict_resident, which)
+
+    def _predict_resident(self, entry, which):
         n = self._row_lengths.get(which)
         out = np.empty(0 if n is None else n.size, np.float32)
-        self._check(self._lib.tfr_fm_predict_resident(self._h, self._WHICH[which], L.ptr_f32(out)))
+        self._check(entry(self._h, self._WHICH[which], L.ptr_f32(out)))
         return out
 
     def eval_binary_resident(self):
         """Accuracy, mean sigmoid cross-entropy and AUC of the eval store (fm.py:162-166), computed on the device."""
+        return self._eval_binary_resident(self._lib.tfr_fm_eval_binary_resident)
+
+    def eval_binary_resident_bf16(self):
+        """``eval_binary_resident`` of the predictions ``predict_resident_bf16`` makes."""
+        return self._eval_binary_resident(self._lib.tfr_fm_bf16_eval_binary_resident)
+
+    def _eval_binary_resident(self, entry):
         neq, n, nll, auc = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
-        self._check(self._lib.tfr_fm_eval_binary_resident(self._h, C.byref(neq), C.byref(nll), C.byref(auc), C.byref(n)))
+        self._check(entry(self._h, C.byref(neq), C.byref(nll), C.byref(auc), C.byref(n)))
         return {"acc": neq.value / n.value, "mean_nll": nll.value / n.value, "auc": auc.value, "n": n.value}
+
+    # ---- the bf16 snapshot: forward, resident predict / eval and top-K at half the row bytes (bf16.py, DESIGN §28)
+    def snapshot_bf16(self):
+        """Build or refresh the bf16 copy of ``V`` (with ``W`` and ``mu`` of the same moment) the ``*_bf16`` calls score
+        from; training, ``set`` and ``init`` do not move it."""
+        self._check(self._lib.tfr_fm_bf16_snapshot(self._h))
+
+    def drop_bf16(self):
+        self._check(self._lib.tfr_fm_bf16_drop(self._h))
+
+    def bf16_rows(self):
+        """The snapshot's ``V`` as the library stores it: uint16 [n_features, DP] (``bf16.pack_rows(V)``)."""
+        from . import bf16
+        out = np.empty((self.n_features, bf16.row_stride(self.dim)), np.uint16)
+        self._check(self._lib.tfr_fm_bf16_get_rows(self._h, out.ctypes.data_as(C.POINTER(C.c_uint16)), out.size))
+        return out
 
     def init(self, seed=0, stddev=0.1):
         self._check(self._lib.tfr_fm_init(self._h, int(seed), stddev))
 
     def forward_csr(self, indptr, indices, data):
+        return self._forward_csr(self._lib.tfr_fm_forward, indptr, indices, data)
+
+    def forward_csr_bf16(self, indptr, indices, data):
+        """``forward_csr`` from the bf16 snapshot (``snapshot_bf16``): the same formula on ``V`` as the snapshot holds it,
+        with the snapshot's ``W`` and ``mu`` (include/tfrecomm.h tfr_fm_bf16_forward)."""
+        return self._forward_csr(self._lib.tfr_fm_bf16_forward, indptr, indices, data)
+
+    def _forward_csr(self, entry, indptr, indices, data):
         indptr = np.ascontiguousarray(indptr, np.int64)
         indices = np.ascontiguousarray(indices, np.int32)
         data = np.ascontiguousarray(data, np.float32)
         n = indptr.size - 1
         out = np.empty(n, np.float32)
-        self._check(self._lib.tfr_fm_forward(self._h, L.ptr_i64(indptr), L.ptr_i32(indices), L.ptr_f32(data), n,
-                                             L.ptr_f32(out)))
+        self._check(entry(self._h, L.ptr_i64(indptr), L.ptr_i32(indices), L.ptr_f32(data), n, L.ptr_f32(out)))
         return out
 
     def fma(self, x):
         """forward.py:21-22 on a scipy.sparse matrix (any format; converted to CSR)."""
+        return self.forward_csr(*self._csr_arrays(x))
+
+    def fma_bf16(self, x):
+        """``fma`` from the bf16 snapshot."""
+        return self.forward_csr_bf16(*self._csr_arrays(x))
+
+    def _csr_arrays(self, x):
         x = x.tocsr()
         if x.shape[1] != self.n_features:
             raise ValueError("X has %d columns, the model %d features" % (x.shape[1], self.n_features))
-        return self.forward_csr(x.indptr, x.indices, x.data)
+        return x.indptr, x.indices, x.data
 
     def topk(self, user_features, item_lo, item_hi, k=50, exclude=None, return_scores=True):
         """The ``k`` best item features ``j`` in ``[item_lo, item_hi)`` for each user feature ``u``: forward.py:21-22 on the
         two-hot row ``e_u + e_j``, computed as ``((V[u].V[j] + mu) + W[u]) + W[j]``.  Item ids (returned and in ``exclude``)
         are relative to ``item_lo``; ``exclude`` as in ``SvdModel.recommend`` (a sparse matrix is indexed by user feature)."""
+        return self._topk(self._lib.tfr_fm_topk, user_features, item_lo, item_hi, k, exclude, return_scores)
+
+    def topk_bf16(self, user_features, item_lo, item_hi, k=50, exclude=None, return_scores=True):
+        """``topk`` from the bf16 snapshot (``snapshot_bf16``): the same arguments and return values, the scores of the
+        snapshot's tables with the dot taken 16 features per bf16 matrix instruction (include/tfrecomm.h tfr_fm_bf16_topk)."""
+        return self._topk(self._lib.tfr_fm_bf16_topk, user_features, item_lo, item_hi, k, exclude, return_scores)
+
+    def _topk(self, entry, user_features, item_lo, item_hi, k, exclude, return_scores):
         from .engine import exclusion_csr
         u = L.as_i32(user_features, "user features").reshape(-1)
         indptr, excl = exclusion_csr(exclude, u)
         items = np.empty((u.size, int(k)), np.int32)
         scores = np.empty((u.size, int(k)), np.float32) if return_scores else None
-        self._check(self._lib.tfr_fm_topk(self._h, L.ptr_i32(u), u.size, int(item_lo), int(item_hi), int(k),
-                                          None if indptr is None else L.ptr_i64(indptr),
-                                          None if excl is None else L.ptr_i32(excl),
-                                          L.ptr_i32(items), None if scores is None else L.ptr_f32(scores)))
+        self._check(entry(self._h, L.ptr_i32(u), u.size, int(item_lo), int(item_hi), int(k),
+                          None if indptr is None else L.ptr_i64(indptr), None if excl is None else L.ptr_i32(excl),
+                          L.ptr_i32(items), None if scores is None else L.ptr_f32(scores)))
         return (items, scores) if return_scores else items
 
     def similar_features(self, features, lo=0, hi=None, k=10, metric="cosine", exclude=None, return_scores=True):
@@ -219,8 +270,16 @@ class FmModel(object):
         items, scores = self.topk([int(encoded_user_id)], int(user_num), int(user_num) + int(item_num), k, exclude)
         return items[0], scores[0]
 
+    def get_ranking_bf16(self, encoded_user_id, user_num, item_num, k=50, exclude=None):
+        """``get_ranking`` from the bf16 snapshot (``topk_bf16``)."""
+        items, scores = self.topk_bf16([int(encoded_user_id)], int(user_num), int(user_num) + int(item_num), k, exclude)
+        return items[0], scores[0]
+
     def forward_dev(self, d_indptr, d_indices, d_data, n_rows, d_out):
         self._check(self._lib.tfr_fm_forward_dev(self._h, d_indptr, d_indices, d_data, n_rows, d_out))
+
+    def forward_bf16_dev(self, d_indptr, d_indices, d_data, n_rows, d_out):
+        self._check(self._lib.tfr_fm_bf16_forward_dev(self._h, d_indptr, d_indices, d_data, n_rows, d_out))
 
     def sync(self):
         ms = C.c_float()
