@@ -440,6 +440,40 @@ const char* tfr_ials_last_error(void);
 int tfr_ials_create_cg(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t d, double lambda_, double alpha,
                        int32_t cg_steps, int32_t device);
 
+/* ---- implicit-feedback ALS: folding new users and items into fitted factors, on a handle of either solver ----------------
+ *      tfr_ials_fold_in solves, for each of n lists (a CSR of partner ids and positive values: items for side 0, users for
+ *      side 1, each list strictly increasing), the row a half-sweep of `side` would give an entity holding that list, from the
+ *      partner table as it stands and the model's lambda, alpha and solver.  It runs the half-sweep's kernels on these lists
+ *      (chunks of `chunk` entries for longer lists on the Cholesky path): for a list the model holds, loaded at the same chunk,
+ *      the row has the bits tfr_ials_half would write.  An empty list gives exactly 0; n = 0 is a no-op.  It needs factors,
+ *      not a load.
+ *      Cholesky handle: the half-sweep's system.  Conjugate-gradient handle: cg_steps steps from start[e] when `start` is
+ *      given, else from row rows[e] of side's table as it stands when `rows` is given, else from 0.
+ *      The rows stay in a device buffer of the handle until the next fold-in (tfr_ials_export_f32, which = 2); they are
+ *      copied to `out` when given and written into rows rows[e] of side's table when `rows` is given.  The resident lists
+ *      and their chunk plans are never changed: a later sweep uses what tfr_ials_load gave it.
+ *      The Gram of the partner table is computed only when the handle's Gram is not already that table's: the handle
+ *      remembers which table its Gram was taken of and forgets it whenever that table may have changed (tfr_ials_set of it,
+ *      a half-sweep of its side, a fold-in with `rows` into it).  The Gram is deterministic, so the rows do not depend on
+ *      which case applied.
+ *      Checked before any device work (tables, resident lists and chunk plans are left as they were): TFR_ERR_ARG for a bad
+ *      side, a null indptr, an indptr that does not start at 0 or decreases, a list that is not strictly increasing, a value
+ *      that is not positive and finite, a chunk that is not a positive multiple of 32 (0 = 512), duplicate or negative
+ *      `rows`, `start` on a Cholesky handle; TFR_ERR_OOB for a partner id or a `rows` entry out of range.
+ *      tfr_ials_export_f32 writes rows [row_lo, row_lo + n_rows) of X (which = 0), Y (1) or the last fold-in (2) as float32,
+ *      rounded to nearest even, into the caller's DEVICE buffer d_dst [n_rows, d]: the device form of the cast a serving
+ *      table needs.  TFR_ERR_ARG for a window outside the table or outside the last fold-in, TFR_ERR_STATE for which = 2
+ *      before any fold-in.  Host pointers except d_dst; both calls synchronise. */
+int tfr_ials_fold_in(tfr_ials* m, int32_t side /* 0: new users from item lists; 1: new items from user lists */,
+                     int64_t n, const int64_t* indptr /* [n+1] */, const int32_t* ids, const double* vals,
+                     int32_t chunk /* 0 = 512 */,
+                     const int32_t* rows  /* NULL, or [n] distinct rows of side's table: results are written there */,
+                     const double* start  /* NULL, or [n, d]: conjugate-gradient handles only */,
+                     double* out          /* NULL, or [n, d] host */,
+                     float* elapsed_ms    /* may be NULL */);
+int tfr_ials_export_f32(tfr_ials* m, int32_t which /* 0 X, 1 Y, 2 the rows of the last fold-in */,
+                        int64_t row_lo, int64_t n_rows, void* d_dst /* device, float [n_rows, d] */);
+
 /* ---- top-K recommendation: forward.py:47-61 get_ranking(), als3.py:110-113 (rank the dense U.V^T + biases) ----------------
  *      score(u, i) = ((dot + mu) + bu[u]) + bi[i] (the forward's order), dot = the f32 fmaf chain over f = 0..dim-1 ascending,
  *      from +0, of P[u,f] * Q'[i,f] (Q' = |Q| with item_abs); the logit under the NLL head.  Per requested user the k best

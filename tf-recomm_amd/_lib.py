@@ -174,6 +174,8 @@ SIGNATURES = {
     "tfr_ials_sweep": (C.c_int, [_p, C.c_int32, _f32p]),
     "tfr_ials_gram": (C.c_int, [_p, C.c_int32, _f64p]),
     "tfr_ials_loss": (C.c_int, [_p, _f64p]),
+    "tfr_ials_fold_in": (C.c_int, [_p, C.c_int32, C.c_int64, _i64p, _i32p, _f64p, C.c_int32, _i32p, _f64p, _f64p, _f32p]),
+    "tfr_ials_export_f32": (C.c_int, [_p, C.c_int32, C.c_int64, C.c_int64, _p]),
     "tfr_ials_last_error": (C.c_char_p, []),
     "tfr_sort_segments": (C.c_int, [_p, C.c_int32, _i32p, C.c_int64, _i32p, _i32p]),
     "tfr_kernel_plan": (C.c_int, [_p, C.c_int64, C.c_char_p, C.c_int64]),

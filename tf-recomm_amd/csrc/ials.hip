@@ -18,6 +18,12 @@
 //   (k_ials_gram_narrow): the same sums in the same order, so the same bits; the width alone chooses.
 //   Loss: L = sum_u [ x_u^T G x_u + sum_{i in N(u)} (c_ui (1 - s_ui)^2 - s_ui^2) ] + lambda (||X||^2 + trace(G)),
 //   s_ui = x_u . y_i, G = Y^T Y - the dense U x I matrix is never formed.
+//   Fold-in (tfr_ials_fold_in): the row a half-sweep would give an entity with a list the model does not hold.  The same
+//   k_ials_partial / k_ials_fit (k_ials_cg_fit on a conjugate-gradient handle) run on an argument block made of the call's
+//   lists, a fold buffer as the own rows, the partner table and G; the call's lists get a chunk plan and partial sums of
+//   their own.  G is computed only when the handle's tag (gram_of) does not already name the partner's table.  Three
+//   per-element kernels move the rows: k_ials_rows_gather (warm start), k_ials_rows_scatter (into named rows) and
+//   k_ials_export_f32 (float32 rows into a caller's device buffer, tfr_ials_export_f32).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdarg.h>
@@ -262,6 +268,28 @@ __global__ __launch_bounds__(256) void k_ials_loss_reduce(const double* per_user
     }
 }
 
+// Fold-in's three copies, one lane per element t = e d + c, coalesced along the row; the stride loop only covers counts
+// past the grid cap.  rows[] holds distinct rows (checked on the host), so no two lanes write one element.
+// fold[e] = tab[rows[e]]: the conjugate-gradient warm start
+__global__ __launch_bounds__(256) void k_ials_rows_gather(const double* tab, const int32_t* rows, int64_t n, int d, double* fold) {
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n * d; t += (int64_t)gridDim.x * 256)
+        fold[t] = tab[(size_t)rows[t / d] * d + t % d];
+}
+
+// tab[rows[e]] = fold[e]
+__global__ __launch_bounds__(256) void k_ials_rows_scatter(const double* fold, const int32_t* rows, int64_t n, int d, double* tab) {
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n * d; t += (int64_t)gridDim.x * 256)
+        tab[(size_t)rows[t / d] * d + t % d] = fold[t];
+}
+
+// dst[t] = float(src[t]), round to nearest even: overflow gives infinity, float32 subnormals are kept
+__global__ __launch_bounds__(256) void k_ials_export_f32(const double* src, int64_t count, float* dst) {
+    for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < count; t += (int64_t)gridDim.x * 256)
+        dst[t] = __double2float_rn(src[t]);
+}
+
+inline dim3 per_element_grid(int64_t count) { return dim3((unsigned)std::min<int64_t>((count + 255) / 256, 1 << 20)); }
+
 thread_local char g_ials_err[512] = "";
 int ials_fail(int code, const char* fmt, ...) {
     va_list ap;
@@ -288,19 +316,25 @@ hipError_t queue_gram(tfr_ials* m, int side) {
                            m->gram_partial.get());
     hipLaunchKernelGGL(k_ials_gram_sum, dim3((unsigned)((d * d + 255) / 256)), dim3(256), 0, m->stream, m->gram_partial.get(), ns, d,
                        m->G.get());
+    m->gram_of = side;
     return hipGetLastError();
 }
 
-// one half-sweep of `side`, queued: the partner table's Gram, the long lists' chunks, every entity
-hipError_t queue_half(tfr_ials* m, int side) {
-    hipError_t e = queue_gram(m, 1 - side);
-    if (e != hipSuccess) return e;
-    if (m->cg_steps) return tfr::ials_cg_queue_fit(m, side);
-    const IalsArgs a = tfr::ials_side_args(m, side);
-    const tfr::ChunkArgs ch = m->chunks[side].args(m->partial);
+// every entity of the argument block solved from a.G, queued: the long lists' chunks first (Cholesky path; the
+// conjugate-gradient path reads no chunk table).  A half-sweep and a fold-in differ in the block they hand over, not here.
+hipError_t queue_fit(tfr_ials* m, const IalsArgs& a, const tfr::ChunkArgs& ch) {
+    if (a.cg_steps) return tfr::ials_cg_queue_fit(a, m->stream);
     if (ch.n) hipLaunchKernelGGL(k_ials_partial, dim3((unsigned)std::min<int64_t>(ch.n, 65535)), dim3(256), 0, m->stream, a, ch);
     hipLaunchKernelGGL(k_ials_fit, dim3((unsigned)std::min<int64_t>(a.n, 65535)), dim3(256), 0, m->stream, a, ch);
     return hipGetLastError();
+}
+
+// one half-sweep of `side`, queued: the partner table's Gram, then every entity.  It rewrites side's table; the tag names
+// the partner's from the Gram on, so a Gram of side's table kept from before is not taken for current afterwards.
+hipError_t queue_half(tfr_ials* m, int side) {
+    hipError_t e = queue_gram(m, 1 - side);
+    if (e != hipSuccess) return e;
+    return queue_fit(m, tfr::ials_side_args(m, side), m->chunks[side].args(m->partial));
 }
 
 int finish_timed(tfr_ials* m, float* elapsed_ms) {
@@ -388,6 +422,7 @@ int tfr_ials_create_cg(tfr_ials** out, int64_t n_users, int64_t n_items, int32_t
 int tfr_ials_set(tfr_ials* m, const double* X, const double* Y) {
     if (!m) return ials_fail(TFR_ERR_ARG, "null model");
     IALSCHK(hipSetDevice(m->device));
+    if ((X && m->gram_of == 0) || (Y && m->gram_of == 1)) m->gram_of = -1;
     if (X) IALSCHK(hipMemcpyAsync(m->tab[0], X, (size_t)m->n[0] * m->d * 8, hipMemcpyHostToDevice, m->stream));
     if (Y) IALSCHK(hipMemcpyAsync(m->tab[1], Y, (size_t)m->n[1] * m->d * 8, hipMemcpyHostToDevice, m->stream));
     IALSCHK(hipStreamSynchronize(m->stream));
@@ -460,6 +495,117 @@ int tfr_ials_load(tfr_ials* m, const int64_t* indptr, const int32_t* items, cons
         IALSCHK(hipMemcpy(m->vals[1], vi.data(), (size_t)nnz * 8, hipMemcpyHostToDevice));
     }
     m->loaded = true;
+    return TFR_OK;
+}
+
+// what a fold-in refuses, all of it on the host: TFR_OK, or the code with the message set
+static int fold_in_check(const tfr_ials* m, int32_t side, int64_t n, const int64_t* indptr, const int32_t* ids, const double* vals,
+                         int32_t chunk, const int32_t* rows, const double* start) {
+    if (side < 0 || side > 1) return ials_fail(TFR_ERR_ARG, "fold_in: side must be 0 or 1");
+    if (n < 0 || n > 0x7fffffffLL || !indptr) return ials_fail(TFR_ERR_ARG, "fold_in: need 0 <= n < 2^31 and an indptr");
+    if (chunk < IALS_TILE || chunk % IALS_TILE) return ials_fail(TFR_ERR_ARG, "fold_in: chunk must be a positive multiple of %d", IALS_TILE);
+    if (start && !m->cg_steps) return ials_fail(TFR_ERR_ARG, "fold_in: a start is for conjugate-gradient handles only");
+    if (indptr[0] != 0) return ials_fail(TFR_ERR_ARG, "fold_in: indptr must start at 0");
+    for (int64_t e = 0; e < n; ++e)
+        if (indptr[e + 1] < indptr[e]) return ials_fail(TFR_ERR_ARG, "fold_in: indptr decreases at list %lld", (long long)e);
+    if (indptr[n] > 0 && (!ids || !vals)) return ials_fail(TFR_ERR_ARG, "fold_in: null ids or values");
+    const int64_t n_other = m->n[1 - side];
+    for (int64_t e = 0; e < n; ++e)
+        for (int64_t k = indptr[e]; k < indptr[e + 1]; ++k) {
+            if (ids[k] < 0 || ids[k] >= n_other) return ials_fail(TFR_ERR_OOB, "fold_in: list %lld: id %d out of range", (long long)e, ids[k]);
+            if (k > indptr[e] && ids[k] <= ids[k - 1])
+                return ials_fail(TFR_ERR_ARG, "fold_in: list %lld is not strictly increasing", (long long)e);
+            if (!(vals[k] > 0.0) || !std::isfinite(vals[k]))
+                return ials_fail(TFR_ERR_ARG, "fold_in: list %lld: values must be positive and finite", (long long)e);
+        }
+    if (rows) {
+        for (int64_t e = 0; e < n; ++e) {
+            if (rows[e] < 0) return ials_fail(TFR_ERR_ARG, "fold_in: rows[%lld] is negative", (long long)e);
+            if (rows[e] >= m->n[side]) return ials_fail(TFR_ERR_OOB, "fold_in: rows[%lld] = %d out of range", (long long)e, rows[e]);
+        }
+        std::vector<int32_t> sorted(rows, rows + n);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return ials_fail(TFR_ERR_ARG, "fold_in: rows repeats a row");
+    }
+    return TFR_OK;
+}
+
+// The rows a half-sweep of `side` would give entities with these lists: the half-sweep's kernels on an argument block whose
+// lists are the caller's, whose own rows are the fold buffer and whose partner table and Gram are the model's.  The lists,
+// their chunk plan and the chunks' partial sums live in the handle's fold_* members: nothing a sweep reads is touched, except
+// side's rows `rows` when they are asked for.
+int tfr_ials_fold_in(tfr_ials* m, int32_t side, int64_t n, const int64_t* indptr, const int32_t* ids, const double* vals, int32_t chunk,
+                     const int32_t* rows, const double* start, double* out, float* elapsed_ms) {
+    if (!m) return ials_fail(TFR_ERR_ARG, "null model");
+    if (chunk == 0) chunk = 512;
+    const int rc = fold_in_check(m, side, n, indptr, ids, vals, chunk, rows, start);
+    if (rc != TFR_OK) return rc;
+    if (elapsed_ms) *elapsed_ms = 0.f;
+    if (n == 0) return TFR_OK;
+    const int d = m->d;
+    const int64_t nnz = indptr[n], cap = std::max<int64_t>(1, nnz);
+    tfr::ChunkPlan plan;                                   // the conjugate-gradient path forms no per-row matrix: no chunks
+    if (!m->cg_steps) plan = tfr::plan_chunks(std::vector<int64_t>(indptr, indptr + n + 1), n, chunk);
+
+    IALSCHK(hipSetDevice(m->device));
+    m->fold_n = -1;
+    IALSCHK(m->fold_ptr.reserve(n + 1, m->stream));
+    IALSCHK(m->fold_ids.reserve(cap, m->stream));
+    IALSCHK(m->fold_vals.reserve(cap, m->stream));
+    IALSCHK(m->fold.reserve(n * d, m->stream));
+    IALSCHK(hipMemcpy(m->fold_ptr, indptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
+    if (nnz) {
+        IALSCHK(hipMemcpy(m->fold_ids, ids, (size_t)nnz * 4, hipMemcpyHostToDevice));
+        IALSCHK(hipMemcpy(m->fold_vals, vals, (size_t)nnz * 8, hipMemcpyHostToDevice));
+    }
+    if (rows) {
+        IALSCHK(m->fold_rows.reserve(n, m->stream));
+        IALSCHK(hipMemcpy(m->fold_rows, rows, (size_t)n * 4, hipMemcpyHostToDevice));
+    }
+    tfr::ChunkArgs ch{};
+    if (!m->cg_steps) {
+        IALSCHK(m->fold_chunks.upload(plan, n, m->stream));
+        IALSCHK(m->fold_partial.reserve(std::max<int64_t>(1, m->fold_chunks.n * (d * d + d)), m->stream));
+        ch = m->fold_chunks.args(m->fold_partial);
+    }
+
+    (void)hipEventRecord(m->ev0, m->stream);
+    if (m->cg_steps) {                                     // the start: the caller's, else the rows as they stand, else 0
+        if (start) IALSCHK(hipMemcpyAsync(m->fold, start, (size_t)n * d * 8, hipMemcpyHostToDevice, m->stream));
+        else if (rows) hipLaunchKernelGGL(k_ials_rows_gather, per_element_grid(n * d), dim3(256), 0, m->stream, m->tab[side].get(),
+                                          m->fold_rows.get(), n, d, m->fold.get());
+        else IALSCHK(hipMemsetAsync(m->fold, 0, (size_t)n * d * 8, m->stream));
+    }
+    if (m->gram_of != 1 - side) IALSCHK(queue_gram(m, 1 - side));
+    const IalsArgs a{n, m->fold_ptr.get(), m->fold_ids.get(), m->fold_vals.get(), m->fold.get(), m->tab[1 - side].get(), m->G.get(),
+                     m->lambda, m->alpha, d, m->cg_steps};
+    IALSCHK(queue_fit(m, a, ch));
+    // the scatter writes side's table; the tag names the partner's here, so no Gram of side's table is kept as current
+    if (rows) hipLaunchKernelGGL(k_ials_rows_scatter, per_element_grid(n * d), dim3(256), 0, m->stream, m->fold.get(), m->fold_rows.get(), n,
+                                 d, m->tab[side].get());
+    IALSCHK(hipGetLastError());
+    if (out) IALSCHK(hipMemcpyAsync(out, m->fold, (size_t)n * d * 8, hipMemcpyDeviceToHost, m->stream));
+    const int done = finish_timed(m, elapsed_ms);
+    if (done == TFR_OK) m->fold_n = n;
+    return done;
+}
+
+// float64 rows as float32, device to device: X (0), Y (1) or the rows of the last fold-in (2)
+int tfr_ials_export_f32(tfr_ials* m, int32_t which, int64_t row_lo, int64_t n_rows, void* d_dst) {
+    if (!m || which < 0 || which > 2) return ials_fail(TFR_ERR_ARG, "export_f32: null model or bad table");
+    if (which == 2 && m->fold_n < 0) return ials_fail(TFR_ERR_STATE, "export_f32: no fold-in yet");
+    const int64_t have = which == 2 ? m->fold_n : m->n[which];
+    if (row_lo < 0 || n_rows < 0 || row_lo > have || n_rows > have - row_lo)
+        return ials_fail(TFR_ERR_ARG, "export_f32: rows [%lld, %lld + %lld) are not inside the %lld there are", (long long)row_lo,
+                         (long long)row_lo, (long long)n_rows, (long long)have);
+    if (n_rows == 0) return TFR_OK;
+    if (!d_dst) return ials_fail(TFR_ERR_ARG, "export_f32: null destination");
+    IALSCHK(hipSetDevice(m->device));
+    const double* src = (which == 2 ? m->fold.get() : m->tab[which].get()) + (size_t)row_lo * m->d;
+    hipLaunchKernelGGL(k_ials_export_f32, per_element_grid(n_rows * m->d), dim3(256), 0, m->stream, src, n_rows * m->d,
+                       static_cast<float*>(d_dst));
+    IALSCHK(hipGetLastError());
+    IALSCHK(hipStreamSynchronize(m->stream));
     return TFR_OK;
 }
 

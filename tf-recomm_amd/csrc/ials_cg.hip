@@ -223,9 +223,8 @@ hipError_t with_nc(const IalsArgs& a, Launch launch) {
 
 namespace tfr {
 
-hipError_t ials_cg_queue_fit(tfr_ials* m, int side) {
-    const IalsArgs a = ials_side_args(m, side);
-    return with_nc(a, [&](auto nc, dim3 grid) { hipLaunchKernelGGL(k_ials_cg_fit<decltype(nc)::value>, grid, dim3(256), 0, m->stream, a); });
+hipError_t ials_cg_queue_fit(const IalsArgs& a, hipStream_t s) {
+    return with_nc(a, [&](auto nc, dim3 grid) { hipLaunchKernelGGL(k_ials_cg_fit<decltype(nc)::value>, grid, dim3(256), 0, s, a); });
 }
 
 hipError_t ials_cg_queue_loss_users(tfr_ials* m) {

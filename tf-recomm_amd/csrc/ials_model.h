@@ -1,7 +1,8 @@
 // ials_model.h - the implicit-ALS handle and the one argument block of its kernels, shared by the Cholesky path (ials.hip)
 // and the conjugate-gradient path (ials_cg.hip).  ials.hip owns the C-ABI entries, the Gram and the loss's last kernel; a
 // handle with cg_steps > 0 was made by tfr_ials_create_cg and its half-sweeps and per-user loss go through the two queue_*
-// functions below.
+// functions below.  Fold-in (tfr_ials_fold_in, ials.hip) gives the same kernels an argument block built from a call's own
+// lists: its buffers and its chunk plan are the handle's fold_* members, apart from everything a sweep reads.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,6 +37,15 @@ struct tfr_ials {
     tfr::DevBuf<double> vals[2];
     tfr::DevChunks chunks[2];
     tfr::DevBuf<double> partial, G, gram_partial, per_user, loss;
+    // Which side's table the Gram in G belongs to, or -1.  Every Gram sets it; whatever may change that side's table
+    // (tfr_ials_set, a half-sweep of the side, a fold-in that writes rows of it) clears it.  Only fold-in reads it.
+    int gram_of = -1;
+    // fold-in: the last call's lists, its chunk plan with the chunks' partial sums, its rows [fold_n, d] and where they went
+    tfr::DevBuf<int64_t> fold_ptr;
+    tfr::DevBuf<int32_t> fold_ids, fold_rows;
+    tfr::DevBuf<double> fold_vals, fold_partial, fold;
+    tfr::DevChunks fold_chunks;
+    int64_t fold_n = -1;                                 // rows of the last fold-in; -1 before any
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
 };
 
@@ -54,6 +64,6 @@ inline IalsArgs ials_side_args(const tfr_ials* m, int side) {
                     m->tab[1 - side].get(), m->G.get(), m->lambda, m->alpha, m->d, m->cg_steps};
 }
 // queued on the model's stream; each returns hipGetLastError() after its launches
-hipError_t ials_cg_queue_fit(tfr_ials* m, int side);           // cg_steps steps for every entity of `side`, from m->G
+hipError_t ials_cg_queue_fit(const IalsArgs& a, hipStream_t s); // a.cg_steps steps for every entity of the block, from a.G
 hipError_t ials_cg_queue_loss_users(tfr_ials* m);              // m->per_user, from m->G = Y^T Y
 }  // namespace tfr

@@ -3,6 +3,7 @@
     python tools/bench_ials.py [--dims 32,64] [--iters 10] [--out profiles/bench_ials.jsonl]
     python tools/bench_ials.py --solver cg --cg-steps 3 --dims 32,64,128,256 --also-cholesky 32,64 --cap 1024,256 \
         --out profiles/bench_ials_cg.jsonl                                      
+    python tools/bench_ials.py --fold-in --out profiles/bench_ials_fold.jsonl   
 
 Data: ML-1M-shaped synthetic pairs (6040 x 3706, 1 M draws, item popularity p(i) ~ 1 / (i + 50), as tools/bench_bpr.py),
 values 1 .. 5.  Legs: ImplicitALS.sweep (device time per iteration from the library's events) and each half on its own
@@ -12,6 +13,10 @@ With --solver cg the rows are the conjugate-gradient path's (dims up to 256; no 
 each half, and the loss after 15 iterations from the library's initialisation.  --also-cholesky adds the Cholesky path's rows
 at those dims in the same process; --cap N[,M] adds a further row per width and length on the same pairs with every item's list cut to its
 first N users (popularity capped), which takes the longest lists (one block each) out of the halves.
+With --fold-in the rows are fold-in's, at d = 64 (Cholesky) and d = 128 (conjugate gradient), one per n in 1, 256, 6040: the
+rows of the first n users' lists by fold_in_users against a second ImplicitALS(n, ...) with set_factors, load and a
+half-sweep, and their top-10 by recommend_lists against a second SvdModel set through the host; medians of --reps repeats,
+the ways alternating in one process.
 """
 import argparse
 import ctypes as C
@@ -151,6 +156,84 @@ def run_dim(d, iters, sample):
     return row
 
 
+def _wall_ms(fn):
+    t0 = time.perf_counter()
+    fn()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def run_fold_in(d, solver, cg_steps, reps, guests=256):
+    """one row per n: the rows of the first n users' stored lists by fold_in_users (first call after the item factors were
+    set, which pays the Gram, and later calls) against a second ImplicitALS(n, ...) with set_factors, load and a half-sweep;
+    and their top-10 by recommend_lists against a second SvdModel set through the host.  Wall-clock medians, the two ways
+    alternating in one process; the device times are the library's events."""
+    import scipy.sparse as sp
+    import tfrecomm_amd as T
+    U, I, npairs = SHAPE
+    u, i, v = pairs(U, I, npairs)
+    x = sp.csr_matrix((v, (u, i)), shape=(U, I))
+    x.sum_duplicates()
+    x.sort_indices()
+    kw = dict(solver="cg", cg_steps=cg_steps) if solver == "cg" else {}
+    rows = []
+    with T.ImplicitALS(U, I, factors=d, regularization=0.01, alpha=40.0, **kw) as m:
+        m.load(x)
+        m.init_factors(0)
+        m.sweep(3)
+        Y = m.item_factors
+        half_ms = float(np.median([m.half_sweep(0) for _ in range(reps)]))
+        m.gram(1)
+        with m.to_svd_model(extra_users=guests) as svd:
+            for n in (1, 256, U):
+                lists = x[:n]
+                row = dict(users=U, items=I, pairs=int(x.nnz), d=d, solver=solver, n=n, reps=reps, guests=guests,
+                           user_half_device_ms=half_ms)
+                if solver == "cg":
+                    row["cg_steps"] = cg_steps
+
+                def first():
+                    m.set_factors(Y=Y)                     # the Gram in the handle is no longer the item table's
+                    t0 = time.perf_counter()
+                    m.fold_in_users(lists)
+                    return (time.perf_counter() - t0) * 1e3, m.fold_ms
+
+                def second_model():
+                    with T.ImplicitALS(n, I, factors=d, regularization=0.01, alpha=40.0, **kw) as m2:
+                        m2.set_factors(Y=Y)
+                        m2.load(lists)
+                        m2.half_sweep(0)
+                        return m2.user_factors
+
+                def second_svd():
+                    got = m.fold_in_users(lists)
+                    with T.SvdModel(n, I, d, device=m.device) as s2:
+                        s2.set_tables(np.float32(0.0), np.zeros(n, np.float32), np.zeros(I, np.float32), got.astype(np.float32),
+                                      Y.astype(np.float32))
+                        return s2.recommend(np.arange(n, dtype=np.int32), 10, exclude=lists)
+
+                assert second_model().tobytes() == m.fold_in_users(lists).tobytes()        # both ways give the same rows
+                a = m.recommend_lists(svd, lists, k=10)
+                b = second_svd()
+                assert a[0].tobytes() == b[0].tobytes() and a[1].tobytes() == b[1].tobytes()
+                t = dict(first=[], first_dev=[], later=[], later_dev=[], kept_dev=[], model=[], lists=[], svd=[])
+                for _ in range(reps):
+                    w, dev = first()
+                    t["first"].append(w); t["first_dev"].append(dev)
+                    t["later"].append(_wall_ms(lambda: m.fold_in_users(lists))); t["later_dev"].append(m.fold_ms)
+                    t["model"].append(_wall_ms(second_model))
+                    t["lists"].append(_wall_ms(lambda: m.recommend_lists(svd, lists, k=10)))
+                    t["kept_dev"].append(m.fold_ms)        # recommend_lists' fold-in copies no rows to the host
+                    t["svd"].append(_wall_ms(second_svd))
+                med = {k: float(np.median(val)) for k, val in t.items()}
+                row.update(fold_in_first_ms=med["first"], fold_in_first_device_ms=med["first_dev"], fold_in_later_ms=med["later"],
+                           fold_in_later_device_ms=med["later_dev"], fold_in_rows_kept_device_ms=med["kept_dev"],
+                           second_model_half_ms=med["model"],
+                           second_model_over_fold_in=med["model"] / med["later"], recommend_lists_ms=med["lists"],
+                           second_svd_model_ms=med["svd"], second_svd_over_recommend_lists=med["svd"] / med["lists"])
+                rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dims", default="32,64")
@@ -160,21 +243,26 @@ def main():
     ap.add_argument("--cg-steps", type=int, default=3)
     ap.add_argument("--also-cholesky", default="", help="with --solver cg: dims at which the Cholesky path runs too")
     ap.add_argument("--cap", default="", help="with --solver: a further row per width and per listed length, every item's list cut to it")
+    ap.add_argument("--fold-in", action="store_true",
+                    help="fold-in and recommend_lists against a second model, n = 1, 256, 6040: d = 64 Cholesky and d = 128 CG (DESIGN §29)")
+    ap.add_argument("--reps", type=int, default=9, help="with --fold-in: alternated repeats behind each median")
     ap.add_argument("--out")
     a = ap.parse_args()
     fh = open(a.out, "a") if a.out else None
-    if a.solver is None:
-        jobs = [lambda d=int(d): run_dim(d, a.iters, a.numpy_rows) for d in a.dims.split(",")]
+    if a.fold_in:
+        jobs = [lambda: run_fold_in(64, "cholesky", 0, a.reps), lambda: run_fold_in(128, "cg", a.cg_steps, a.reps)]
+    elif a.solver is None:
+        jobs = [lambda d=int(d): [run_dim(d, a.iters, a.numpy_rows)] for d in a.dims.split(",")]
     else:
         legs = [(a.solver, int(d)) for d in a.dims.split(",")] + [("cholesky", int(d)) for d in a.also_cholesky.split(",") if d]
-        jobs = [lambda s=s, d=d, cap=cap: run_solver(d, a.iters, s, a.cg_steps, cap) for s, d in legs for cap in [0] + [int(c) for c in a.cap.split(",") if c]]
+        jobs = [lambda s=s, d=d, cap=cap: [run_solver(d, a.iters, s, a.cg_steps, cap)] for s, d in legs for cap in [0] + [int(c) for c in a.cap.split(",") if c]]
     for job in jobs:
-        row = job()
-        line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row.items()})
-        print(line, flush=True)
-        if fh:
-            fh.write(line + "\n")
-            fh.flush()
+        for row in job():
+            line = json.dumps({k: (round(v, 4) if isinstance(v, float) else v) for k, v in row.items()})
+            print(line, flush=True)
+            if fh:
+                fh.write(line + "\n")
+                fh.flush()
     if fh:
         fh.close()
 
