@@ -41,16 +41,28 @@ struct GatherArgs {
 // after the other along its dependent chain; after this they hit the scalar cache.
 // `args` must lie inside the kernel-argument block (an array element: check the index first - reading past the block's end is
 // a page fault when the block ends a page).
+//
+// In two halves for the kernels whose first vector loads take their operands from preloaded SGPRs (leading scalar kernel
+// parameters): warm_args_issue() puts the lines in flight at the kernel's first instruction, warm_args_land()
+// marks where they must have arrived - behind those first loads, so the block's trip runs beside them, not in front.
 template <typename T>
-__device__ __forceinline__ void warm_args(const T& args) {
+struct WarmLines { int32_t w[(sizeof(T) + 63) / 64]; };
+template <typename T>
+__device__ __forceinline__ WarmLines<T> warm_args_issue(const T& args) {
     const char* base = reinterpret_cast<const char*>(&args);
     constexpr int NL = (int)((sizeof(T) + 63) / 64);
-    int32_t w[NL];
+    WarmLines<T> x;
 #pragma unroll
-    for (int k = 0; k < NL; ++k) w[k] = *reinterpret_cast<const int32_t*>(base + (k * 64 < (int)sizeof(T) - 4 ? k * 64 : (int)sizeof(T) - 4));
-#pragma unroll
-    for (int k = 0; k < NL; ++k) asm volatile("" :: "s"(w[k]));
+    for (int k = 0; k < NL; ++k) x.w[k] = *reinterpret_cast<const int32_t*>(base + (k * 64 < (int)sizeof(T) - 4 ? k * 64 : (int)sizeof(T) - 4));
+    return x;
 }
+template <typename T>
+__device__ __forceinline__ void warm_args_land(const WarmLines<T>& x) {
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(x.w) / sizeof(x.w[0])); ++k) asm volatile("" :: "s"(x.w[k]));
+}
+template <typename T>
+__device__ __forceinline__ void warm_args(const T& args) { warm_args_land(warm_args_issue(args)); }
 
 // The binary-outcome formulas every evaluation shares (the SVD forward's evaluation mode, the FM trainer's metrics):
 // ops.py:77-78 infer = round(sigmoid(logit)), half-to-even; ops.py:125-126 sigmoid cross-entropy on the fed logit.
@@ -184,6 +196,9 @@ struct TileDenseArgs {
     float alpha, b1, b2, eps, lr;
 };
 struct TileDenseLaunch { TileDenseArgs a[2]; FinArgs f; int32_t with_fin; int32_t wt; int32_t rounds; };   // rounds: the full-width three-round form (set by the launcher)
+// Both sides share err and ntiles.  launch_dense_tiles passes the head of the kernel's dependent chain (each side's tab, nbins,
+// rows; ntiles, err) and these two switches once more as leading scalar kernel parameters, which are preloaded into SGPRs.
+enum { DENSE_FLAG_ROUNDS = 1, DENSE_FLAG_FIN = 2 };
 void launch_dense_tiles(const TileDenseLaunch& L, bool write, bool with_fin, int G, int VEC, hipStream_t s);
 // the instantiation launch_dense_tiles takes for this geometry and tile count (nullptr: none), its grid's block columns,
 // and whether a launch of `rows` rows of width D takes the three-round form

@@ -267,7 +267,7 @@ struct TileLds {
 __device__ __forceinline__ void tile_sort(int32_t* cnt_, int32_t* rec_u_, int32_t* rec_i_, float* rec_r_, int32_t* srt_key_,
                                           int32_t* srt_pos_, int32_t* wtot_, const int64_t* ids, const int4* store, const int4* recs,
                                           const int32_t* bu_, const int32_t* bi_, const float* br_, int64_t tile0, int nvalid, int side,
-                                          int nb, int64_t N, int64_t U, int64_t I, int32_t* err) {
+                                          int nb, int64_t N, int64_t U, int64_t I, int32_t* err, bool have_rec, int4 rec_in) {
     TileLds L;
     L.cnt = cnt_; L.rec_u = rec_u_; L.rec_i = rec_i_; L.rec_r = rec_r_; L.srt_key = srt_key_; L.srt_pos = srt_pos_; L.wtot = wtot_;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -278,7 +278,9 @@ __device__ __forceinline__ void tile_sort(int32_t* cnt_, int32_t* rec_u_, int32_
     if (valid) {
         const int64_t k = tile0 + tid;
         bool oob = false;
-        if (recs) {                                      // the batch's store records, left beside the ids by the stream that drew
+        if (have_rec) {                                  // recs[k], requested by the caller already (k_tile_step's look-ahead blocks)
+            u = rec_in.x; it = rec_in.y; r = __int_as_float(rec_in.z);
+        } else if (recs) {                               // the batch's store records, left beside the ids by the stream that drew
             const int4 rec = recs[k];                    // them (api.hip RecBuf): one round trip instead of ids -> store
             u = rec.x; it = rec.y; r = __int_as_float(rec.z);
         } else if (ids) {
@@ -321,17 +323,24 @@ __device__ __forceinline__ void tile_sort(int32_t* cnt_, int32_t* rec_u_, int32_
     __syncthreads();
 }
 
+// partials[from, to) = 0 by the whole block (k_tile_step: the item side's last block; from = INT32_MAX elsewhere)
+__device__ __forceinline__ void zero_tail(float* partials, int from, int to) {
+    if (from < to) for (int k = from + (int)threadIdx.x; k < to; k += 1024) partials[k] = 0.f;
+}
+
 struct TileStamp {                                       // diagnostic (TFR_TILE_DEBUG): when did this block start, pass its phases, end?
-    unsigned long long* p; unsigned long long t0;
-    __device__ void mark(int k) const { if (p && threadIdx.x == 0) p[k] = __builtin_amdgcn_s_memrealtime(); }
-    __device__ ~TileStamp() { if (p && threadIdx.x == 0) { p[0] = t0; p[1] = __builtin_amdgcn_s_memrealtime(); } }
+    unsigned long long* p; unsigned long long t0;        // p: none until arm() - a.dbg is a word of the struct, in hand only behind warm_args_land
+    __device__ __forceinline__ void arm(unsigned long long* dbg) { p = dbg ? dbg + 8 * (size_t)blockIdx.x : nullptr; }
+    __device__ __forceinline__ void mark(int k) const { if (p && threadIdx.x == 0) p[k] = __builtin_amdgcn_s_memrealtime(); }
+    __device__ __forceinline__ ~TileStamp() { if (p && threadIdx.x == 0) { p[0] = t0; p[1] = __builtin_amdgcn_s_memrealtime(); } }
 };
 
-template <int G, int VEC, int EPG>
+template <int G, int VEC, int EPG, bool PRE>
 __device__ __forceinline__ void tile_pieces(const TileStepArgs& a, int32_t* dyn, const int32_t* rec_u, const int32_t* rec_i,
                                             const float* rec_r, const int32_t* srt_key, const int32_t* srt_pos, float* lds_gb,
-                                            int32_t* lds_key, float* lds_stage, const TileStamp& stamp, int side, int bx, int slice,
-                                            int64_t tile0, int nvalid, bool presorted);
+                                            int32_t* lds_key, float* lds_stage, TileStamp& stamp, int side, int bx, int slice,
+                                            int64_t tile0, int nvalid, const int4* srt, const WarmLines<TileStepArgs>& warm,
+                                            int zero_from, int zero_to);
 
 // grid = nsort + nblk_u + nblk_i, one dimension: the look-ahead sort blocks, then the user side's blocks, then the
 // item side's, each side cut to the blocks that hold entries (ceil(B / entries per block)).
@@ -348,9 +357,17 @@ __device__ __forceinline__ void tile_pieces(const TileStepArgs& a, int32_t* dyn,
 //    logits and the per-piece {loss, reg, sum g}.  The user side takes EPG pieces per block, the item
 //    side a.epg_item = EPG, or EPG / 2 where the grid has room for it (TFR_ITEM_SPLIT=1, tile_step_item_epg);
 //    the grid stays within one block per CU.
+//
+// The leading scalar parameters are what a block needs to issue its first vector loads - the published records of a step
+// block on the presorted path (srt_u / srt_i = a.srt[], B = a.B, epg_item, ntiles), the next batch's store records of a
+// look-ahead block (next_recs, next_ntiles, next_B = a.next_*), and whether TFR_TILE_DEBUG wants the block's start stamped
+// (stamps = a.dbg != NULL): 14 dwords, all the command processor preloads into user SGPRs, so those loads wait
+// for no scalar load.  The struct's lines are requested at once and awaited behind those loads (warm_args_land).  B fits 32
+// bits: the tile path takes at most 16 tiles of 1024.
 template <int G, int VEC, int EPG>
-__global__ __launch_bounds__(1024) void k_tile_step(TileStepArgs a, int nsort, int nblk_u) {
-    warm_args(a);
+__global__ __launch_bounds__(1024) void k_tile_step(const int4* srt_u, const int4* srt_i, const int4* next_recs, int B, int nsort, int nblk_u,
+                                                    int epg_item, int ntiles, int next_ntiles, int next_B, int stamps, TileStepArgs a) {
+    const WarmLines<TileStepArgs> warm = warm_args_issue(a);
     constexpr int EPB = 1024 / G;                        // entries per piece = lane groups per block
     extern __shared__ __attribute__((aligned(16))) int32_t dyn[];   // sort: cnt[nbins]; then the wave-level sums
     __shared__ int32_t rec_u[1024], rec_i[1024], srt_key[1024], srt_pos[1024];
@@ -362,33 +379,57 @@ __global__ __launch_bounds__(1024) void k_tile_step(TileStepArgs a, int nsort, i
     static_assert(sizeof(rec_u) + sizeof(rec_i) + sizeof(srt_key) + sizeof(srt_pos) + sizeof(rec_r) + sizeof(lds_gb) + sizeof(lds_key) +
                   sizeof(lds_stage) + sizeof(wtot) == tile_step_static_lds(G, EPG), "tile_step_static_lds() is out of date");
     static_assert(tile_step_static_lds(G, EPG) + 64 * 1024 <= LDS_PER_CU, "static LDS leaves no room for 16384 sort bins");
-    TileStamp stamp = {a.dbg ? a.dbg + 8 * (size_t)blockIdx.x : nullptr, a.dbg ? __builtin_amdgcn_s_memrealtime() : 0ull};
+    TileStamp stamp = {nullptr, stamps ? __builtin_amdgcn_s_memrealtime() : 0ull};
     const int tid = threadIdx.x;
     const bool ahead = (int)blockIdx.x < nsort;          // look-ahead block: sort (side, tile) of the next batch
     const int b0 = (int)blockIdx.x - nsort;
-    const int side = ahead ? (int)blockIdx.x / a.next_ntiles : (b0 < nblk_u ? 0 : 1);   // 0: user rows, 1: item rows
+    const int side = ahead ? (int)blockIdx.x / next_ntiles : (b0 < nblk_u ? 0 : 1);   // 0: user rows, 1: item rows
     const int bx = ahead ? 0 : (side ? b0 - nblk_u : b0);
-    const int epg = side ? a.epg_item : EPG;
+    const int epg = side ? epg_item : EPG;
     const int EPS = EPB * epg;                           // entries per block
     const int NSL = 1024 / EPS;                          // blocks per tile
-    const int tile = ahead ? (int)blockIdx.x % a.next_ntiles : bx / NSL;
+    const int tile = ahead ? (int)blockIdx.x % next_ntiles : bx / NSL;
     const int slice = bx % NSL;
     const int64_t tile0 = (int64_t)tile * 1024;
-    const int64_t Bt = ahead ? a.next_B : a.B;
-    const int nvalid = (Bt - tile0 < 1024) ? (int)(Bt - tile0) : 1024;
-    if (!ahead && side == 1 && (int64_t)(bx + 1) * EPS >= a.B) {   // the item side's last block: the pieces past the
-        const int np = a.ntiles * G;                     // batch's end have no block - their {loss, reg, sum g} are zero
-        for (int k = (bx + 1) * epg * 4 + tid; k < np * 4; k += 1024) a.partials[k] = 0.f;
-    }
+    const int Bt = ahead ? next_B : B;
+    const int nvalid = (Bt - (int)tile0 < 1024) ? Bt - (int)tile0 : 1024;
+    // the item side's last block: the pieces past the batch's end have no block - their {loss, reg, sum g} are zero.  Which
+    // words, decided here from the preloaded scalars; written where a.partials is in hand (zero_tail)
+    const int zero_from = (!ahead && side == 1 && (int64_t)(bx + 1) * EPS >= B) ? (bx + 1) * epg * 4 : INT32_MAX;
+    const int zero_to = ntiles * G * 4;
     if (!ahead && slice * EPS >= nvalid) {               // a short last tile: nothing in this slice
+        stamp.arm(a.dbg);
+        zero_tail(a.partials, zero_from, zero_to);
         if (side == 1 && tid < 4 * epg) a.partials[(size_t)bx * epg * 4 + tid] = 0.f;
         return;
     }
-    const bool presorted = a.srt[0] != nullptr;
-    const int nb = a.nbins[side];
-    if (ahead || !presorted) {
-        tile_sort(dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, wtot, ahead ? a.next_ids : a.ids, a.store, ahead ? a.next_recs : a.recs,
-                  a.u, a.it, a.r, tile0, nvalid, side, nb, a.N, a.U, a.I, a.err);
+    // A step block on the presorted path: a branch of its own, so that nothing the sorting blocks leave pending (their LDS
+    // traffic shares a counter with the scalar loads) is waited for in front of the record loads.
+    if (!ahead && srt_u != nullptr) {
+        const int4* srt = side ? srt_i : srt_u;
+        if constexpr (EPG > 1) {
+            if (epg != EPG) {
+                tile_pieces<G, VEC, EPG / 2, true>(a, dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, lds_gb, lds_key, lds_stage, stamp, side, bx,
+                                                   slice, tile0, nvalid, srt, warm, zero_from, zero_to);
+                return;
+            }
+        }
+        tile_pieces<G, VEC, EPG, true>(a, dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, lds_gb, lds_key, lds_stage, stamp, side, bx, slice,
+                                       tile0, nvalid, srt, warm, zero_from, zero_to);
+        return;
+    }
+    {
+        // a look-ahead block's own record, requested from the preloaded scalars before the struct's lines are awaited
+        const bool early = ahead && next_recs != nullptr;
+        int4 early_rec = make_int4(0, 0, 0, 0);
+        if (early) early_rec = next_recs[tile0 + (tid < nvalid ? tid : 0)];     // (unconditional: slot 0 of a tile always exists)
+        __builtin_amdgcn_sched_barrier(0);
+        warm_args_land(warm);
+        stamp.arm(a.dbg);
+        zero_tail(a.partials, zero_from, zero_to);
+        const int nb = a.nbins[side];
+        tile_sort(dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, wtot, ahead ? a.next_ids : a.ids, a.store, ahead ? next_recs : a.recs,
+                  a.u, a.it, a.r, tile0, nvalid, side, nb, a.N, a.U, a.I, a.err, early, early_rec);
         const bool wt = a.wt & TFR_WT_PUBLISH;
         if (ahead) {                                     // publish the packed table and the sorted records
             int32_t* nt = a.next_tab[side];
@@ -413,28 +454,28 @@ __global__ __launch_bounds__(1024) void k_tile_step(TileStepArgs a, int nsort, i
     }
     if constexpr (EPG > 1) {
         if (epg != EPG) {
-            tile_pieces<G, VEC, EPG / 2>(a, dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, lds_gb, lds_key, lds_stage, stamp, side, bx, slice,
-                                         tile0, nvalid, presorted);
+            tile_pieces<G, VEC, EPG / 2, false>(a, dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, lds_gb, lds_key, lds_stage, stamp, side, bx, slice,
+                                                tile0, nvalid, nullptr, warm, zero_from, zero_to);
             return;
         }
     }
-    tile_pieces<G, VEC, EPG>(a, dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, lds_gb, lds_key, lds_stage, stamp, side, bx, slice, tile0,
-                             nvalid, presorted);
+    tile_pieces<G, VEC, EPG, false>(a, dyn, rec_u, rec_i, rec_r, srt_key, srt_pos, lds_gb, lds_key, lds_stage, stamp, side, bx, slice, tile0,
+                                    nvalid, nullptr, warm, zero_from, zero_to);
 }
 
 // the step part of k_tile_step for one block of EPG pieces (see above)
-template <int G, int VEC, int EPG>
+template <int G, int VEC, int EPG, bool PRE>
 __device__ __forceinline__ void tile_pieces(const TileStepArgs& a, int32_t* dyn, const int32_t* rec_u, const int32_t* rec_i,
                                             const float* rec_r, const int32_t* srt_key, const int32_t* srt_pos, float* lds_gb,
-                                            int32_t* lds_key, float* lds_stage, const TileStamp& stamp, int side, int bx, int slice,
-                                            int64_t tile0, int nvalid, bool presorted) {
+                                            int32_t* lds_key, float* lds_stage, TileStamp& stamp, int side, int bx, int slice,
+                                            int64_t tile0, int nvalid, const int4* srt, const WarmLines<TileStepArgs>& warm,
+                                            int zero_from, int zero_to) {
+    constexpr bool presorted = PRE;                      // PRE: the entries come from srt, this side's published records (a preloaded scalar)
     constexpr int EPB = 1024 / G;                        // entries per piece = lane groups per block
     constexpr int EPS = EPB * EPG;                       // entries per block
     const int tid = threadIdx.x;
     // ---- this block's entries (EPG per lane group, one from each piece): forward + contribution
     const int grp = tid / G, gl = tid % G, d0 = gl * VEC;
-    const int D = a.D;
-    const float mu = *a.mu;
     int jl[EPG], bpos[EPG];
     int32_t row[EPG], uu[EPG], ii[EPG];
     float rr[EPG];
@@ -451,12 +492,17 @@ __device__ __forceinline__ void tile_pieces(const TileStepArgs& a, int32_t* dyn,
 #pragma unroll                                           // row gathers below for why they are not written `if (ev) rec = *sr`)
         for (int h = 0; h < EPG; ++h) {
             const int js = ev[h] ? jl[h] : 0;            // slot 0 of the tile always exists
-            const int4* sr = a.srt[side] + tile0 + js;
+            const int4* sr = srt + tile0 + js;
             rec_[h] = *sr;
             prev_[h] = reinterpret_cast<const int32_t*>(sr - (js > 0 ? 1 : 0))[side];
         }
         __builtin_amdgcn_sched_barrier(0);
+        warm_args_land(warm);                            // nothing of the struct was needed up to here
+        stamp.arm(a.dbg);
     }
+    const int D = a.D;
+    const float mu = *a.mu;
+    if (presorted) zero_tail(a.partials, zero_from, zero_to);   // (the self-sorting blocks did both in front of their sort)
 #pragma unroll
     for (int h = 0; h < EPG; ++h) {
         row[h] = -1; uu[h] = 0; ii[h] = 0; rr[h] = 0.f; bpos[h] = 0;
@@ -1419,8 +1465,14 @@ __global__ __launch_bounds__(256) void k_adam_dense(DensePair pr) {
 //      goes through the round-major loop from k = 1 as in the general form.  Absent pieces are loads past the
 //      resource's end (zeros, no memory access) and are added as +0.0f: the sums start at +0.0f and never become
 //      -0.0f, so that changes no bit.
+//
+//      What the chain's head needs - this side's table, its bins and rows, the tile count and the error word's address -
+//      comes in DenseHead from preloaded SGPRs (k_dense_tiles' leading scalar parameters), so round 1's entries and
+//      error word are requested before any line of the struct has arrived; the struct is awaited behind them
+//      (warm_args_land), in front of w, m, v, whose addresses it holds.
+struct DenseHead { const int32_t* tab; const int32_t* err; int nbins, rows, ntiles; };
 template <int G, int VEC, bool WRITE, int NT>
-__device__ __forceinline__ void dense_tiles_rounds(const TileDenseLaunch& L) {
+__device__ __forceinline__ void dense_tiles_rounds(const TileDenseLaunch& L, const DenseHead& h, const WarmLines<TileDenseArgs>& warm) {
     const TileDenseArgs& a = L.a[blockIdx.y];
     constexpr int GPB = 256 / G;
     constexpr int EPB = 1024 / G;
@@ -1429,15 +1481,16 @@ __device__ __forceinline__ void dense_tiles_rounds(const TileDenseLaunch& L) {
     const int gl = threadIdx.x % G;
     const int d0 = gl * VEC;
     const int row = (int)blockIdx.x * GPB + threadIdx.x / G;
-    if (row >= a.rows) return;
+    if (row >= h.rows) return;
     // ---- round 1
     const __amdgpu_buffer_rsrc_t rtab =                  // ends with the last tile's table: entries of tiles past it read as 0
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(a.tab), 0, a.ntiles * a.nbins * 4, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(h.tab), 0, h.ntiles * h.nbins * 4, 0x00020000);
     int32_t ent[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) ent[t] = (int32_t)buf_load_word(rtab, (t * a.nbins + row) * 4);
-    int32_t err = (int32_t)buf_load_word(wt_rsrc(a.err), 0);
+    for (int t = 0; t < NT; ++t) ent[t] = (int32_t)buf_load_word(rtab, (t * h.nbins + row) * 4);
+    int32_t err = (int32_t)buf_load_word(wt_rsrc(h.err), 0);
     __builtin_amdgcn_sched_barrier(0);
+    warm_args_land(warm);                                // the struct's lines: first needed here
     const int roff = (row * D + d0) * 4;
     Frag<VEC> w, mrow, vrow;
     float bw = 0.f, mb = 0.f, vb = 0.f;
@@ -1574,28 +1627,36 @@ __device__ __forceinline__ void dense_tiles_rounds(const TileDenseLaunch& L) {
 }
 
 template <int G, int VEC, bool WRITE, int NT>
-__global__ __launch_bounds__(256, (NT > 12 && VEC == 4 && !WRITE) ? 2 : 3) void k_dense_tiles(TileDenseLaunch L) {   // (the register budget)
-    warm_args(L.a[blockIdx.y]);
-    if (blockIdx.x == gridDim.x - 1) {                   // the extra block column: K4 (optional), nothing else
-        if (blockIdx.y == 0 && L.with_fin) finalize_body(L.f);
+__global__ __launch_bounds__(256, (NT > 12 && VEC == 4 && !WRITE) ? 2 : 3)                // (the register budget)
+void k_dense_tiles(const int32_t* tab0, const int32_t* tab1, const int32_t* errp, int nbins0, int nbins1, int rows0, int rows1, int ntiles,
+                   int ncols, int flags, TileDenseLaunch L) {
+    // The 13 leading dwords are preloaded into user SGPRs: L.a[y].tab / nbins / rows for y = 0, 1, the tile count
+    // and error word both sides share, the block columns that hold rows (gridDim.x - 1, which would be a scalar load too) and
+    // DENSE_FLAG_* = L.rounds / L.with_fin.  blockIdx.y picks between the two sets by scalar selects.
+    const WarmLines<TileDenseArgs> warm = warm_args_issue(L.a[blockIdx.y]);
+    if ((int)blockIdx.x == ncols) {                      // the extra block column: K4 (optional), nothing else
+        if (blockIdx.y == 0 && (flags & DENSE_FLAG_FIN)) finalize_body(L.f);
         return;
     }
+    const bool users = blockIdx.y != 0;
+    const DenseHead h = {users ? tab1 : tab0, errp, users ? nbins1 : nbins0, users ? rows1 : rows0, ntiles};
     if constexpr (VEC == 4) {                            // (VEC == 1 rows are never full width: D % 4 != 0 there)
-        if (L.rounds) {                                  // block-uniform: full-width rows, one lane group per row (launch_dense_tiles)
-            dense_tiles_rounds<G, VEC, WRITE, NT>(L);
+        if (flags & DENSE_FLAG_ROUNDS) {                 // block-uniform: full-width rows, one lane group per row (launch_dense_tiles)
+            dense_tiles_rounds<G, VEC, WRITE, NT>(L, h, warm);
             return;
         }
     }
     const TileDenseArgs& a = L.a[blockIdx.y];
-    const int32_t err = *a.err;                          // looked at behind the first round of loads (they need no lookup table):
-    constexpr int GPB = 256 / G;                         // its round trip is then not a round of its own
+    const int32_t err = *h.err;                          // looked at behind the first round of loads (they need no lookup table):
+    warm_args_land(warm);                                // its round trip is then not a round of its own - and runs beside the struct's
+    constexpr int GPB = 256 / G;
     constexpr int EPB = 1024 / G;
     const int gl = threadIdx.x % G;
     const int d0 = gl * VEC;
     const int D = a.D;
     const AdamC c = {a.alpha, a.b1, a.b2, a.eps, 1.f - a.b1, 1.f - a.b2};
-    for (int64_t row = (int64_t)blockIdx.x * GPB + threadIdx.x / G; row < a.rows;
-         row += (int64_t)(gridDim.x - 1) * GPB) {
+    for (int64_t row = (int64_t)blockIdx.x * GPB + threadIdx.x / G; row < h.rows;
+         row += (int64_t)ncols * GPB) {
         const size_t roff = (size_t)row * D;
         Frag<VEC> w, mrow, vrow;
 #pragma unroll
@@ -1624,7 +1685,7 @@ __global__ __launch_bounds__(256, (NT > 12 && VEC == 4 && !WRITE) ? 2 : 3) void 
         constexpr int NB = (NT > 12) ? 8 : NT;
         int32_t ent[NT];
 #pragma unroll
-        for (int t = 0; t < NT; ++t) ent[t] = (t < a.ntiles) ? a.tab[(size_t)t * a.nbins + row] : 0;
+        for (int t = 0; t < NT; ++t) ent[t] = (t < h.ntiles) ? h.tab[(size_t)t * h.nbins + row] : 0;
         if (err) return;                                 // a voided step: the tables' contents are not to be trusted as addresses
 #pragma unroll
         for (int t0 = 0; t0 < NT; t0 += NB) {
@@ -1891,7 +1952,9 @@ void launch_tile_step(const TileStepArgs& a0, int G, int VEC, hipStream_t s) {
                     return;                              // no launch: leaves the error for the caller's hipGetLastError()
                 attr = dyn;
             }
-            hipLaunchKernelGGL((k_tile_step<g.value, v.value, e.value>), grid, dim3(1024), dyn, s, a, nsort, nblk_u);
+            // the first round's operands lead as scalars (preloaded SGPRs); the struct keeps its copies for everything later
+            hipLaunchKernelGGL((k_tile_step<g.value, v.value, e.value>), grid, dim3(1024), dyn, s, a.srt[0], a.srt[1], a.next_recs, (int)a.B, nsort,
+                               nblk_u, a.epg_item, a.ntiles, a.next_ntiles, (int)a.next_B, a.dbg ? 1 : 0, a);
         });
     });
 }
@@ -1974,7 +2037,14 @@ void launch_dense_tiles(const TileDenseLaunch& L, bool write, bool with_fin, int
     LL.with_fin = with_fin ? 1 : 0;
     LL.wt = tile_step_wt() & (TFR_WT_ROWS | TFR_WT_MOMENTS | TFR_WT_BIAS);
     LL.rounds = (L.a[0].D == L.a[1].D && dense_tiles_rounds_taken(rows, L.a[0].D, G, VEC)) ? 1 : 0;
-    with_dense_tiles(write, G, VEC, L.a[0].ntiles, [&](auto* kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, LL); });
+    // the chain's head as leading scalars (preloaded SGPRs); both sides share the tile count and the error word (api.hip tile_dense)
+    const TileDenseArgs &i = LL.a[0], &u = LL.a[1];
+    if (i.err != u.err || i.ntiles != u.ntiles || rows > INT32_MAX) return;   // cannot happen for a launch tile_dense builds: no launch
+    const int flags = (LL.rounds ? DENSE_FLAG_ROUNDS : 0) | (LL.with_fin ? DENSE_FLAG_FIN : 0);
+    with_dense_tiles(write, G, VEC, i.ntiles, [&](auto* kernel) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, i.tab, u.tab, i.err, i.nbins, u.nbins, (int)i.rows, (int)u.rows, i.ntiles, (int)grid.x - 1,
+                           flags, LL);
+    });
 }
 
 void launch_adam_dense(DensePair& p, int n, int G, int VEC, hipStream_t s, const FinArgs* fin) {

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Manifest of the gfx950 device code the library is built from: for every source the Makefile
-compiles, each function symbol with its code size, and each kernel's registers, LDS, scratch and
-kernel-argument bytes.  A change that touches host code only must leave this manifest as it is:
+compiles, each function symbol with its code size, and each kernel's registers, LDS, scratch,
+kernel-argument bytes and - where it has any - the dwords of its argument block the kernel descriptor
+asks the command processor to preload into user SGPRs.  A source is compiled with the flags the Makefile
+gives it (its `<stem>.o: CXXFLAGS += ...` line included).  A change that touches host code only must leave this manifest as it is:
 same kernels, same sizes, same resources (profiles/kernel_manifest.txt holds the committed one).
 
 Needs no GPU.  Reads the symbol table and the metadata notes only.
@@ -33,6 +35,31 @@ def makefile_sources(csrc):
     return [s for s in m.group(1).split() if os.path.exists(os.path.join(csrc, s))]
 
 
+def makefile_extra_flags(csrc, stem):
+    """the flags of a target-specific `<stem>.o: CXXFLAGS += ...` line"""
+    m = re.search(r"^%s\.o:\s*CXXFLAGS\s*\+=\s*(.*)$" % re.escape(stem), open(os.path.join(csrc, "Makefile")).read(), re.M)
+    return m.group(1).split() if m else []
+
+
+def preload_lengths(elf, names):
+    """{kernel: KERNARG_PRELOAD_SPEC_LENGTH}: bits 0-6 of the 16-bit word at byte 58 of the kernel descriptor <kernel>.kd"""
+    sections = run([os.path.join(LLVM, "llvm-readelf"), "-S", "-W", elf])
+    where = {}
+    for line in sections.splitlines():
+        m = re.match(r"^\s*\[\s*\d+\]\s+(\S+)\s+\S+\s+([0-9a-f]+)\s+([0-9a-f]+)\s+([0-9a-f]+)", line)
+        if m:
+            where[m.group(1)] = (int(m.group(2), 16), int(m.group(3), 16), int(m.group(4), 16))
+    blob = open(elf, "rb").read()
+    out = {}
+    for line in run([os.path.join(LLVM, "llvm-objdump"), "-t", elf]).splitlines():
+        m = re.match(r"^([0-9a-f]+)\s+\S+\s+O\s+(\S+)\s+[0-9a-f]+\s+(?:\.\w+\s+)?(\S+)\.kd$", line)
+        if m and m.group(3) in names and m.group(2) in where:
+            addr, off, size = where[m.group(2)]
+            at = int(m.group(1), 16) - addr + off + 58
+            out[m.group(3)] = int.from_bytes(blob[at:at + 2], "little") & 0x7f
+    return out
+
+
 def run(cmd, cwd=None):
     return subprocess.run(cmd, cwd=cwd, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True).stdout
 
@@ -41,8 +68,8 @@ def manifest_of(src, csrc, tmp):
     stem = os.path.splitext(src)[0]
     bundle, elf = os.path.join(tmp, stem + ".bundle.o"), os.path.join(tmp, stem + ".elf")
     run([os.path.join(ROCM, "bin", "hipcc"), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC",
-         "-I" + os.path.join(ROOT, "include"), "-I.", "-Wall", "-Wno-unused-result",
-         "--cuda-device-only", "-c", src, "-o", bundle], cwd=csrc)
+         "-I" + os.path.join(ROOT, "include"), "-I.", "-Wall", "-Wno-unused-result"] + makefile_extra_flags(csrc, stem) +
+        ["--cuda-device-only", "-c", src, "-o", bundle], cwd=csrc)
     run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o",
          "--targets=hip-amdgcn-amd-amdhsa--" + ARCH, "--input=" + bundle, "--output=" + elf])
     funcs = []
@@ -64,14 +91,16 @@ def manifest_of(src, csrc, tmp):
         if len(cur) == len(META_KEYS) + 1:
             kernels[cur[".name"]] = cur
             cur = {}
+    preload = preload_lengths(elf, kernels)
     out = ["== %s: %d functions, %d kernels" % (src, len(funcs), len(kernels))]
     for name, size in sorted(funcs):
         out.append("func %s size=%d" % (name, size))
     for name in sorted(kernels):
         k = kernels[name]
-        out.append("kernel %s vgpr=%s sgpr=%s lds=%s scratch=%s kernarg=%s" % (
+        out.append("kernel %s vgpr=%s sgpr=%s lds=%s scratch=%s kernarg=%s%s" % (
             name, k[".vgpr_count"], k[".sgpr_count"], k[".group_segment_fixed_size"],
-            k[".private_segment_fixed_size"], k[".kernarg_segment_size"]))
+            k[".private_segment_fixed_size"], k[".kernarg_segment_size"],
+            " preload=%d" % preload[name] if preload.get(name) else ""))
     return "\n".join(out) + "\n"
 
 
