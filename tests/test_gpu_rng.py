@@ -28,19 +28,21 @@ def model():
         yield m
 
 
+# ranges around powers of two (no rejection / ~50 % rejection), tiny, ML-1M's 900188, 90M; counts that
+# end inside, exactly at and just past a 624-word block
+DRAW_CASES = [(900188, 10000), (7, 5), (1 << 20, 3000), ((1 << 20) + 1, 3000), (90_000_000, 5000), (2, 1), (2, 623), (2, 1),
+              (2, 624), (2, 625), (1, 17), (3, 0), ((1 << 32) - 1, 2000), (1 << 32, 1500), (1000209, 262144),
+              # the wide form (k_mt_blocks / k_mt_count / k_mt_emit, from 32768 ids): at its threshold, without rejection, at ~50 %
+              # rejection, the C3 draw, tiny ranges, and more ids than one wide pass holds (2^22)
+              (900188, 32767), (900188, 32768), (1 << 20, 65536), ((1 << 20) + 1, 100000), (90_000_000, 262144), (2, 40000),
+              (3, 50001), (70_000_000, 5_000_000), (1 << 32, 33000), ((1 << 31) + 1, 70000)]
+
+
 def test_draw_matches_numpy_and_leaves_numpy_state(model):
     m = model
     np.random.seed(13575)                                        # svd_train_val.py:15
     m.rng_seed(13575)
-    # ranges around powers of two (no rejection / ~50 % rejection), tiny, ML-1M's 900188, 90M; counts that
-    # end inside, exactly at and just past a 624-word block
-    cases = [(900188, 10000), (7, 5), (1 << 20, 3000), ((1 << 20) + 1, 3000), (90_000_000, 5000), (2, 1), (2, 623), (2, 1),
-             (2, 624), (2, 625), (1, 17), (3, 0), ((1 << 32) - 1, 2000), (1 << 32, 1500), (1000209, 262144),
-             # the wide form (k_mt_blocks / k_mt_count / k_mt_emit, from 32768 ids): at its threshold, without rejection, at ~50 %
-             # rejection, the C3 draw, tiny ranges, and more ids than one wide pass holds (2^22)
-             (900188, 32767), (900188, 32768), (1 << 20, 65536), ((1 << 20) + 1, 100000), (90_000_000, 262144), (2, 40000),
-             (3, 50001), (70_000_000, 5_000_000), (1 << 32, 33000), ((1 << 31) + 1, 70000)]
-    for high, count in cases:
+    for high, count in DRAW_CASES:
         want = np.random.randint(0, high, (count,))
         got = m.draw_ids(high, count)
         assert got.dtype == want.dtype == np.int64

@@ -912,6 +912,10 @@ static int run_forward(tfr_model* m, int mode, const int32_t* du, const int32_t*
     return TFR_OK;
 }
 
+// which pass a radix sort of B keys takes: the 4096-key tiles from TFR_RSORT_WIDE_MIN keys up unless TFR_RSORT_WIDE=0
+// (radix_sort_columns launches by it, tfr_kernel_plan reports it)
+static bool rsort_wide_taken(int64_t B) { return switch_rsort_wide() && rsortw_eligible(B); }
+
 // hand-written LSD radix sort of one or two key columns: column c = (keys[c], bits[c]) ->
 // sorted keys in ks_out[c], original positions in ps_out[c].  ceil(maxbits/8) passes, 3 launches each.
 static int radix_sort_columns(tfr_model* m, int ncols, const int32_t* const* keys, const int* bits,
@@ -950,8 +954,7 @@ static int radix_sort_columns(tfr_model* m, int ncols, const int32_t* const* key
         }
         r.err = (p == 0 && limits) ? m->d_err : nullptr;         // ids outside the tables void the step
         if (limits) for (int c = 0; c < ncols; ++c) r.limit[c] = (int32_t)limits[c];
-        static const bool wide = env_default_on("TFR_RSORT_WIDE");   // TFR_RSORT_WIDE=0: A/B switch
-        if (wide && rsortw_eligible(B)) launch_rsortw_pass(r, ncols, m->stream);   // from 65536 keys: 4096-key tiles, LDS-staged scatter
+        if (rsort_wide_taken(B)) launch_rsortw_pass(r, ncols, m->stream);   // from 65536 keys: 4096-key tiles, LDS-staged scatter
         else launch_rsort_pass(r, ncols, m->stream);
     }
     HIPCHK(hipGetLastError());
@@ -1357,8 +1360,7 @@ static int run_train_step(tfr_model* m, const int32_t* du, const int32_t* di, co
             }
         }
         if (!dual && (rc = settle_q(m))) return rc;
-        static const bool split_tiles = env_default_off("TFR_TILE_SPLIT");   // TFR_TILE_SPLIT=1: the three-launch form (k_front + k_seg_reduce), kept for A/B
-        one_launch = tiles && !split_tiles;
+        one_launch = tiles && !switch_tile_split();
         if (!one_launch && !(presorted_big && fwd_fused))     // presorted_big: gathered + sorted ahead, on the second stream
             if ((rc = front_and_sort(m, du, di, dr, B, d_logits, d_store_ids, f, nblk, fin_done, tiles, fwd_fused))) return rc;
     }
@@ -2380,7 +2382,10 @@ int tfr_kernel_plan(tfr_model* m, int64_t B, char* buf, int64_t buflen) {
     const int G = m->G, V = m->VEC;
     const int64_t ntiles = (B + CSORT_TILE - 1) / CSORT_TILE;
     char tmp[1024];
-    if (tiles_eligible(m, B)) {
+    if (tiles_eligible(m, B) && switch_tile_split()) {       // the three launches of run_train_step's !one_launch: k_front sorts tile-locally
+        snprintf(tmp, sizeof(tmp), "forward=k_front<%d, %d>;reduce_item=k_seg_reduce<%d, %d, %d, false, true, false>;apply=k_dense_tiles<%d, %d, false, %d>",
+                 G, V, G, V, (int)RMODE_SCRATCH, G, V, dense_tiles_nt(ntiles));
+    } else if (tiles_eligible(m, B)) {
         snprintf(tmp, sizeof(tmp), "reduce_item=k_tile_step<%d, %d, %d>;apply=k_dense_tiles<%d, %d, false, %d>", G, V,
                  tile_step_epg((int)ntiles, G, V), G, V, dense_tiles_nt(ntiles));
     } else if (fwd_in_reduce(m, B)) {
@@ -2388,10 +2393,12 @@ int tfr_kernel_plan(tfr_model* m, int64_t B, char* buf, int64_t buflen) {
         // the sixth argument: the three-round load form (launch_seg_reduce picks it for the two-table step on full-width rows)
         // (a coarser rule than seg_reduce_pick's, kept: bench.py looks kernels up by this string)
         const bool fast = switch_dualq() && switch_fast() && switch_lean() && m->D == G * V;
-        snprintf(tmp, sizeof(tmp), "sort=%s x%d passes (the first gathers the batch);reduce_item=k_seg_reduce<%d, %d, %d, true, true, %s>;"
+        // the fifth: LEAN, false on the item side of the Adam step under TFR_LEAN=0 only (seg_reduce_pick)
+        const bool lean = fast || !(rm == RMODE_ADAM && !switch_lean());
+        snprintf(tmp, sizeof(tmp), "sort=%s x%d passes (the first gathers the batch);reduce_item=k_seg_reduce<%d, %d, %d, true, %s, %s>;"
                  "reduce_user=k_seg_reduce<%d, %d, %d, false, true, %s>;apply=k_apply_rows<%d, %d, %d>",   // K4 rides in the apply launch
-                 rsortw_eligible(B) ? "k_rsortw_hist/k_rsort_scan/k_rsortw_scatter" : "k_rsort_rank/scan/scatter",
-                 ((m->bits_u > m->bits_i ? m->bits_u : m->bits_i) + 7) / 8, G, V, rm, fast ? "true" : "false", G, V, rm, fast ? "true" : "false", G, V, apply_mode(k));
+                 rsort_wide_taken(B) ? "k_rsortw_hist/k_rsort_scan/k_rsortw_scatter" : "k_rsort_rank/scan/scatter",
+                 ((m->bits_u > m->bits_i ? m->bits_u : m->bits_i) + 7) / 8, G, V, rm, lean ? "true" : "false", fast ? "true" : "false", G, V, rm, fast ? "true" : "false", G, V, apply_mode(k));
     } else if (csort_path(m, B)) {
         snprintf(tmp, sizeof(tmp), "forward=k_front<%d, %d>;sort=k_csort_scan/scatter;reduce_item=k_seg_reduce<%d, %d, %d, false, true, false>;apply=%s",
                  G, V, G, V, reduce_mode(k), k.tf1 ? "k_adam_dense" : "k_apply_rows");

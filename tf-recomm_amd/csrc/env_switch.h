@@ -20,5 +20,8 @@ inline long long env_int(const char* name, long long dflt) { const char* e = get
 inline bool switch_dualq() { static const bool on = env_default_on("TFR_DUALQ"); return on; }   // TFR_DUALQ=0: the big-table step copies the pre-update item rows (one table)
 inline bool switch_fast() { static const bool on = env_default_on("TFR_FAST"); return on; }     // TFR_FAST=0: k_seg_reduce's general form everywhere
 inline bool switch_lean() { static const bool on = env_default_on("TFR_LEAN"); return on; }     // TFR_LEAN=0: own row kept in registers
+// read by the step (api.hip radix_sort_columns, run_train_step) and by tfr_kernel_plan
+inline bool switch_rsort_wide() { static const bool on = env_default_on("TFR_RSORT_WIDE"); return on; }     // TFR_RSORT_WIDE=0: the 1024-key radix pass at every size
+inline bool switch_tile_split() { static const bool on = env_default_off("TFR_TILE_SPLIT"); return on; }   // TFR_TILE_SPLIT=1: the three-launch small-table step (k_front + k_seg_reduce), kept for A/B
 
 }  // namespace tfr
