@@ -653,6 +653,67 @@ int tfr_bpr_train_step_dev(tfr_model* m, const int32_t* d_user, const int32_t* d
  * synchronise): data term per step. */
 int tfr_bpr_train_steps_drawn(tfr_model* m, int64_t batch, int32_t nsteps, float* loss_out);
 
+/* ---- WARP (Weston, Bengio, Usunier, "WSABIE: Scaling Up To Large Vocabulary Image Annotation", IJCAI 2011) - DESIGN §30 --
+ *      A WARP step trains the SVD model's own tables as a BPR step does, through a trainer handle created from the model and
+ *      bound to it.  The positives and the sampler's seed and attempts are the model's (tfr_bpr_set_positives,
+ *      tfr_bpr_set_sampler); the trainer holds the margin.  A trainer must not outlive its model: tfr_destroy on a model
+ *      with a live trainer returns TFR_ERR_STATE and leaves both intact.
+ *
+ *      Scores and candidates.  For a triple (u, i), s(u, k), Q' and the dot's operation order are BPR's.  With
+ *          key = mix(mix(seed ^ 0x9E3779B97F4A7C15) ^ step)        step = the model's step counter before this step
+ *          c_t = ((mix(key ^ ((b << 6) | t)) >> 32) * item_num) >> 32      for t = 0 .. attempts - 1
+ *      the candidates are the draws tfr_bpr_negatives makes at the same seed, step and position b.
+ *
+ *      Violator search.  The candidates are walked in order, n from 0.  A candidate in row u of the positives is passed
+ *      over and not counted.  Otherwise n += 1 and
+ *          x_t = (d_i + bi[i]) - (d_c + bi[c])     f32, d_k = dot(P[u], Q'[k]) as in a BPR step, this order of operations
+ *      and if x_t < margin the negative is j = c_t, the trial count N = n, and the search stops.  If no candidate violates,
+ *      the triple is skipped: neg = -1, N = 0; it contributes nothing and touches nothing, exactly as a skipped BPR triple.
+ *      Every score uses the tables as they were before the step.  The x the step then uses for (u, i, j) is formed by the
+ *      same function on the same operands: it has the bits the search compared, so margin - x > 0 for every live triple
+ *      of a search.
+ *
+ *      Weight.  w = logf((float)max(1, (item_num - 1) / N)), the division in integers.  item_num >= 2 is required: every
+ *      searching or training call on a model with one item returns TFR_ERR_ARG.
+ *
+ *      Step.
+ *          data = sum_b w_b max(0, margin - x_b)
+ *          reg and cost = data + lam reg as in a BPR step
+ *      Per live triple g_b = -w_b if x_b < margin, else 0; dP, dQ[i], dQ[j], dbi[i], dbi[j] are BPR's formulas with that g.  A
+ *      live triple with g = 0 (a caller's negative that does not violate) still gets its lam terms and its lazy-Adam touch.
+ *      As in a BPR step: SGD or lazy Adam on the touched rows, tf1 Adam refused with TFR_ERR_STATE, the frozen bits TFR_BI,
+ *      TFR_P, TFR_Q, one advance of the step counter and the beta powers per step, an id out of range voids the step (every
+ *      table), mu and bu are never read or written, every sum runs in a fixed order.
+ *
+ *      Negatives given by the caller are used as given (checked as ids, never rejected, j == i legal) with N = 1 for every
+ *      triple, so w = logf(item_num - 1).
+ *
+ *      Consequences: with margin = +INFINITY the negatives equal tfr_bpr_negatives' and every N is 1; with margin =
+ *      -INFINITY every triple is skipped.  A NaN margin is TFR_ERR_ARG.
+ *
+ *      Calls before tfr_bpr_set_positives return TFR_ERR_STATE.  Errors and the rollback of a void step follow
+ *      tfr_bpr_train_step. */
+typedef struct tfr_warp tfr_warp;
+/* the trainer of model m with this margin; any number may be bound to one model */
+int tfr_warp_create(tfr_warp** out, tfr_model* m, float margin);
+int tfr_warp_destroy(tfr_warp* w);           /* NULL is a no-op; drains the model's stream */
+int tfr_warp_set_margin(tfr_warp* w, float margin);
+/* the search alone on the current tables, at counter `step`, for host users and positives (checked on the host:
+ * TFR_ERR_OOB); neg_out [batch] (-1 = no violator), trials_out [batch] (may be NULL) the trial counts N; synchronises */
+int tfr_warp_negatives(tfr_warp* w, const int32_t* user, const int32_t* pos, int64_t batch, int64_t step, int32_t* neg_out,
+                       int32_t* trials_out);
+/* one WARP step on host columns; neg NULL = search.  neg_out [batch] receives the negatives used (-1 = skipped), trials_out
+ * [batch] the trial counts, n_skipped_out the number of skipped triples.  Any output may be NULL; synchronises. */
+int tfr_warp_train_step(tfr_warp* w, const int32_t* user, const int32_t* pos, const int32_t* neg /* NULL = search */,
+                        int64_t batch, int32_t* neg_out, int32_t* trials_out, float* loss_out, float* reg_out,
+                        int64_t* n_skipped_out);
+/* the same on device columns, asynchronous (id errors surface at the next synchronising call of the model) */
+int tfr_warp_train_step_dev(tfr_warp* w, const int32_t* d_user, const int32_t* d_pos, const int32_t* d_neg /* NULL = search */,
+                            int64_t batch, int32_t* d_neg_out /* may be NULL */, int32_t* d_trials_out /* may be NULL */);
+/* tfr_bpr_train_steps_drawn with WARP steps: it consumes the model's MT19937 stream exactly as that call does (from one
+ * generator state both draw the same pairs).  loss_out[nsteps] (may be NULL; then the call does not synchronise). */
+int tfr_warp_train_steps_drawn(tfr_warp* w, int64_t batch, int32_t nsteps, float* loss_out);
+
 /* ---- nearest neighbours in factor space: "what is like item i", "who is like user u" - DESIGN §17 -----------------------
  *      One table T [R, dim] gives the query rows and the candidate rows: TFR_NB_ITEMS = item_features (|Q| with item_abs),
  *      TFR_NB_USERS = user_features; for SVD++ users the effective rows P[u] + z_u that tfr_svdpp_topk scores with; for the

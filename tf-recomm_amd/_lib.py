@@ -231,6 +231,13 @@ SIGNATURES = {
     "tfr_bpr_train_step": (C.c_int, [_p, _i32p, _i32p, _i32p, C.c_int64, _i32p, _f32p, _f32p, _i64p]),
     "tfr_bpr_train_step_dev": (C.c_int, [_p, _p, _p, _p, C.c_int64, _p]),
     "tfr_bpr_train_steps_drawn": (C.c_int, [_p, C.c_int64, C.c_int32, _f32p]),
+    "tfr_warp_create": (C.c_int, [C.POINTER(_p), _p, C.c_float]),
+    "tfr_warp_destroy": (C.c_int, [_p]),
+    "tfr_warp_set_margin": (C.c_int, [_p, C.c_float]),
+    "tfr_warp_negatives": (C.c_int, [_p, _i32p, _i32p, C.c_int64, C.c_int64, _i32p, _i32p]),
+    "tfr_warp_train_step": (C.c_int, [_p, _i32p, _i32p, _i32p, C.c_int64, _i32p, _i32p, _f32p, _f32p, _i64p]),
+    "tfr_warp_train_step_dev": (C.c_int, [_p, _p, _p, _p, C.c_int64, _p, _p]),
+    "tfr_warp_train_steps_drawn": (C.c_int, [_p, C.c_int64, C.c_int32, _f32p]),
     "tfr_sync": (C.c_int, [_p]),
     "tfr_last_error": (C.c_char_p, []),
     "tfr_version": (C.c_int, []),

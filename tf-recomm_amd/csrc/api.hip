@@ -193,6 +193,8 @@ struct tfr_model {
     } bf;
     // BPR steps (tfr_bpr_*): the positives, the sampler's settings and the step's buffers; created by the first BPR call
     BprState* bpr = nullptr;
+    // WARP trainers (tfr_warp_*) bound to this model: tfr_destroy refuses while one is alive
+    int32_t warp_live = 0;
     // profiling
     bool prof = false;
     std::vector<ProfEvent> events;
@@ -438,6 +440,8 @@ static void bpr_release(tfr_model* m);
 
 int tfr_destroy(tfr_model* m) {
     if (!m) return TFR_OK;
+    if (m->warp_live > 0)
+        return fail(TFR_ERR_STATE, "tfr_destroy: %d WARP trainer(s) are bound to this model (tfr_warp_destroy them first)", m->warp_live);
     (void)hipSetDevice(m->device);                       // the buffers are freed with the model's device current
     if (m->stream) (void)hipStreamSynchronize(m->stream);
     if (m->stream2) (void)hipStreamSynchronize(m->stream2);
@@ -4011,6 +4015,8 @@ int tfr_finetune_users(tfr_model* m, int64_t n_users, const int32_t* users, cons
 #include "svdpp_api.inc.h"
 // ---- BPR steps (tfr_bpr_*, bpr.hip) on the model's own tables
 #include "bpr_api.inc.h"
+// ---- WARP trainer (tfr_warp_*, warp.hip): BPR's step with the violator search and the weighted hinge
+#include "warp_api.inc.h"
 // ---- FM trainer (tfr_fm_*_resident, fm_fit.hip): resident row stores, gathered minibatches, metrics
 #include "fm_fit_api.inc.h"
 

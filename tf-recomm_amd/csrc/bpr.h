@@ -39,7 +39,7 @@ struct BprArgs {
     const int32_t* ks_u; const int32_t* ps_u;          // the 2B user keys sorted, their positions
     const int32_t* ks_i; const int32_t* ps_i;          // the 2B item keys sorted, their positions
     const int32_t* pos; const int32_t* neg;            // [B]
-    float* g;                                          // [B] g_b = -sigmoid(-x_b)
+    float* g;                                          // [B] g_b = -sigmoid(-x_b); the hinge form: -w_b where x_b < margin, else 0
     int32_t* head;                                     // [B] the pold row of triple b's user
     float* pold;                                       // [B, D] pre-step P rows of the user runs (row = run head / 2)
     float* scal;                                       // [B, 4] {data, reg, -, -} per user run (zero elsewhere)
@@ -48,6 +48,8 @@ struct BprArgs {
     int32_t D, item_abs, reg_bias, opt;                // opt: 0 lazy Adam, 1 SGD
     uint32_t frozen;                                   // bits TFR_MU..TFR_Q
     float lam, alpha, b1, b2, eps, omb1, omb2, lr;
+    // the hinge form (WARP, warp.h): the per-triple weights and the margin; wgt NULL = the logistic form
+    const float* wgt; float margin;
 };
 
 // the sampler's counter key of a step: the restatement in include/tfrecomm.h
@@ -59,9 +61,14 @@ __host__ __device__ inline uint64_t bpr_mix(uint64_t z) {
 }
 inline uint64_t bpr_key(uint64_t seed, int64_t step) { return bpr_mix(bpr_mix(seed ^ 0x9E3779B97F4A7C15ull) ^ (uint64_t)step); }
 
+// x of a triple from its two dots and its two biases: the one place it is formed, so that the WARP search (warp.hip) and
+// the user runs compare and use the same bits
+__device__ __forceinline__ float bpr_x(float di, float bii, float dj, float bij) { return (di + bii) - (dj + bij); }
+
 // one thread per triple: (u, i) from the columns or the drawn entries, j from the sampler or the caller
 void launch_bpr_sample(const BprSampleArgs& a, hipStream_t s);
-// one wave per user run (B waves, wave w at sorted position 2w): scores, g, the run's scalars, pold, the P update
+// one wave per user run (B waves, wave w at sorted position 2w): scores, g, the run's scalars, pold, the P update;
+// a.wgt set = the hinge form: g = x < margin ? -w : 0 and the data term w max(0, margin - x)
 void launch_bpr_users(const BprArgs& a, hipStream_t s);
 // one wave per item run (2B waves): the Q / item_bias gradient over the run's occurrences from pold and g, and the update
 void launch_bpr_items(const BprArgs& a, hipStream_t s);

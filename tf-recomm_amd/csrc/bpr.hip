@@ -66,7 +66,8 @@ __global__ void __launch_bounds__(256) k_bpr_sample(BprSampleArgs a) {
     }
 }
 
-template <int NJ>
+// HINGE: the weighted hinge of a WARP step (warp.h) in place of the logistic g and the softplus term
+template <int NJ, bool HINGE>
 __global__ void __launch_bounds__(64 * BPR_WAVES) k_bpr_users(BprArgs a) {
     const int64_t w = wave_slot();
     const int lane = threadIdx.x & 63, D = a.D;
@@ -114,9 +115,12 @@ __global__ void __launch_bounds__(64 * BPR_WAVES) k_bpr_users(BprArgs a) {
         qisq = wave_sum_all(qisq);
         qjsq = wave_sum_all(qjsq);
         const float bii = a.bi[ip], bij = a.bi[jn];
-        const float x = (di + bii) - (dj + bij);
-        const float g = -1.f / (1.f + expf(x));                   // -sigmoid(-x)
-        loss += fmaxf(-x, 0.f) + log1pf(expf(-fabsf(x)));         // softplus(-x)
+        const float x = bpr_x(di, bii, dj, bij);
+        const float wb = HINGE ? a.wgt[b] : 0.f;                   // (HINGE is a template argument: one side is compiled)
+        const float g = HINGE ? (x < a.margin ? -wb : 0.f)
+                              : -1.f / (1.f + expf(x));           // -sigmoid(-x)
+        loss += HINGE ? wb * fmaxf(a.margin - x, 0.f)
+                      : fmaxf(-x, 0.f) + log1pf(expf(-fabsf(x))); // softplus(-x)
         float rk = (0.5f * psq + 0.5f * qisq) + 0.5f * qjsq;
         if (a.reg_bias) rk += 0.5f * (bii * bii) + 0.5f * (bij * bij);
         reg += rk;
@@ -180,7 +184,11 @@ void launch_bpr_sample(const BprSampleArgs& a, hipStream_t s) {
 
 void launch_bpr_users(const BprArgs& a, hipStream_t s) {
     if (a.B <= 0) return;
-    with_nj(a.D, [&](auto nj) { hipLaunchKernelGGL(k_bpr_users<decltype(nj)::value>, wave_grid(a.B), wave_block(), 0, s, a); });
+    with_nj(a.D, [&](auto nj) {
+        constexpr int NJ = decltype(nj)::value;
+        if (a.wgt) hipLaunchKernelGGL((k_bpr_users<NJ, true>), wave_grid(a.B), wave_block(), 0, s, a);
+        else hipLaunchKernelGGL((k_bpr_users<NJ, false>), wave_grid(a.B), wave_block(), 0, s, a);
+    });
 }
 
 void launch_bpr_items(const BprArgs& a, hipStream_t s) {

@@ -9,6 +9,7 @@
 //   k_bpr_items    per item run: the Q / item_bias gradient from pold and g, and its update
 //   k_finalize     {data, reg} over the per-run scalars in position order (bias_global is not touched)
 #include "bpr.h"
+#include "warp.h"
 
 struct BprState {
     // the positives CSR and the row of each entry
@@ -46,6 +47,22 @@ static int bpr_state(tfr_model* m, BprState** out) {
     return TFR_OK;
 }
 
+// the search's argument block from the sampler's: the same batch, positives, key and outputs, plus the tables it scores on
+static WarpSampleArgs warp_sample_args(const tfr_model* m, const BprSampleArgs& sa, const WarpStep& wp) {
+    WarpSampleArgs wa;
+    memset(&wa, 0, sizeof(wa));
+    wa.pos = sa.pos;
+    wa.ids = sa.ids; wa.u_in = sa.u_in; wa.i_in = sa.i_in; wa.neg_in = sa.neg_in;
+    wa.P = m->w[TFR_P]; wa.Q = m->w[TFR_Q]; wa.bi = m->w[TFR_BI];
+    wa.ou = sa.ou; wa.oi = sa.oi; wa.pos_out = sa.pos_out; wa.neg = sa.neg; wa.neg_copy = sa.neg_copy;
+    wa.trials = wp.trials; wa.wgt = wp.wgt; wa.trials_copy = wp.trials_copy;
+    wa.key = sa.key;
+    wa.B = sa.B; wa.U = sa.U; wa.I = sa.I;
+    wa.D = m->D; wa.item_abs = m->o.item_abs; wa.attempts = sa.attempts;
+    wa.margin = wp.margin;
+    return wa;
+}
+
 static int bpr_need_pos(const tfr_model* m) {
     return m->bpr && m->bpr->have_pos ? TFR_OK : fail(TFR_ERR_STATE, "BPR: the positives are not set (tfr_bpr_set_positives)");
 }
@@ -74,9 +91,10 @@ static int bpr_ensure_batch(tfr_model* m, BprState* h, int64_t B) {
 }
 
 // one step: users du + positives dpos, or drawn entries d_ids of the positives; negatives dneg (NULL = sample).
-// d_neg_copy (may be NULL) receives the negatives; out4 (device, may be NULL) {data, reg, 0, error flag}
+// d_neg_copy (may be NULL) receives the negatives; out4 (device, may be NULL) {data, reg, 0, error flag}.
+// wp (warp_api.inc.h) makes it a WARP step: the violator search in place of the sampler, the hinge form of the user runs
 static int bpr_step(tfr_model* m, BprState* h, const int32_t* du, const int32_t* dpos, const int32_t* dneg,
-                    const int64_t* d_ids, int64_t B, int32_t* d_neg_copy, float* out4) {
+                    const int64_t* d_ids, int64_t B, int32_t* d_neg_copy, float* out4, const WarpStep* wp = nullptr) {
     const OptStep k = opt_step(m);
     int rc;
     if ((rc = settle_q(m)) || (rc = bpr_ensure_batch(m, h, B))) return rc;
@@ -92,7 +110,8 @@ static int bpr_step(tfr_model* m, BprState* h, const int32_t* du, const int32_t*
         sa.B = B; sa.U = m->U; sa.I = m->I; sa.attempts = h->attempts;
         {
             Prof p(m, TFR_K_GATHER);
-            launch_bpr_sample(sa, s);
+            if (wp) launch_warp_sample(warp_sample_args(m, sa, *wp), s);
+            else launch_bpr_sample(sa, s);
         }
         HIPCHK(hipGetLastError());
         {
@@ -108,6 +127,7 @@ static int bpr_step(tfr_model* m, BprState* h, const int32_t* du, const int32_t*
         a.err = m->d_err;
         a.B = B; a.D = m->D; a.item_abs = m->o.item_abs; a.reg_bias = m->o.reg_bias; a.opt = k.adam ? 0 : 1;
         a.frozen = m->frozen; a.lam = m->o.reg;
+        if (wp) { a.wgt = wp->wgt; a.margin = wp->margin; }
         set_hyper(a, k);
         a.omb1 = 1.f - k.b1; a.omb2 = 1.f - k.b2;
         {
@@ -248,8 +268,10 @@ int tfr_bpr_train_step_dev(tfr_model* m, const int32_t* d_user, const int32_t* d
     return bpr_step(m, m->bpr, d_user, d_pos, d_neg, nullptr, B, d_neg_out, nullptr);
 }
 
-int tfr_bpr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* loss_out) {
-    MODEL_ENTER(m);
+}  // extern "C"
+
+// the drawn form of tfr_bpr_train_steps_drawn and tfr_warp_train_steps_drawn (wp set)
+static int bpr_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* loss_out, const WarpStep* wp) {
     int rc;
     if ((rc = bpr_need_opt(m)) || (rc = bpr_need_pos(m))) return rc;
     if (!m->rng_set) return fail(TFR_ERR_STATE, "no generator state: call tfr_rng_seed / tfr_rng_set_state first");
@@ -284,7 +306,7 @@ int tfr_bpr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* lo
     const StepMark mark = mark_step(m);
     for (int32_t st = 0; st < nsteps; ++st)
         if ((rc = bpr_step(m, h, nullptr, nullptr, nullptr, h->ids + (int64_t)st * B, B, nullptr,
-                           loss_out ? h->losses + 4 * (int64_t)st : nullptr)))
+                           loss_out ? h->losses + 4 * (int64_t)st : nullptr, wp)))
             return rc;
     if (!loss_out) return TFR_OK;
     std::vector<float> back((size_t)nsteps * 4);
@@ -299,6 +321,13 @@ int tfr_bpr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* lo
         loss_out[st] = back[(size_t)st * 4];
     }
     return TFR_OK;
+}
+
+extern "C" {
+
+int tfr_bpr_train_steps_drawn(tfr_model* m, int64_t B, int32_t nsteps, float* loss_out) {
+    MODEL_ENTER(m);
+    return bpr_steps_drawn(m, B, nsteps, loss_out, nullptr);
 }
 
 }  // extern "C"

@@ -130,6 +130,9 @@ class SvdModel:
     # -- lifetime -----------------------------------------------------------------
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
+            if getattr(self, "_warp", None):             # the WARP trainer goes before the model it is bound to
+                self._lib.tfr_warp_destroy(self._warp)
+                self._warp = None
             self._lib.tfr_destroy(self._h)
             self._h = None
 
@@ -655,6 +658,78 @@ class SvdModel:
         loss = np.empty(nsteps, np.float32) if want_loss else None
         L.check(self._lib.tfr_bpr_train_steps_drawn(self._h, int(batch), int(nsteps),
                                                     L.ptr_f32(loss) if want_loss else None))
+        return loss
+
+    # -- WARP on implicit feedback (include/tfrecomm.h tfr_warp_*) ----------------------------------------
+    def set_warp(self, margin=1.0):
+        """The margin of the WARP steps.  The trainer handle is created by the first call and closed before the model; the
+        positives and the sampler's seed and attempts are the BPR ones (``set_positives``, ``set_bpr_sampler``)."""
+        if getattr(self, "_warp", None):
+            L.check(self._lib.tfr_warp_set_margin(self._warp, float(margin)))
+            return
+        h = L._p()
+        L.check(self._lib.tfr_warp_create(C.byref(h), self._h, float(margin)))
+        self._warp = h
+
+    def _warp_handle(self):
+        if not getattr(self, "_warp", None):
+            self.set_warp()
+        return self._warp
+
+    def warp_negatives(self, users, pos_items, step=None):
+        """The violator search alone on the current tables, at counter ``step`` (default: the model's step counter, i.e.
+        what the next step would find).  Returns (int32 negatives, -1 where no candidate violates the margin; int32 trial
+        counts N, 0 there)."""
+        u, i = L.as_i32(users, "user ids").reshape(-1), L.as_i32(pos_items, "item ids").reshape(-1)
+        if u.shape != i.shape:
+            raise ValueError("batches must be 1-D and of equal length")
+        neg, trials = np.empty(u.size, np.int32), np.empty(u.size, np.int32)
+        L.check(self._lib.tfr_warp_negatives(self._warp_handle(), L.ptr_i32(u), L.ptr_i32(i), u.size,
+                                             self.step if step is None else int(step), L.ptr_i32(neg), L.ptr_i32(trials)))
+        return neg, trials
+
+    def train_warp_step(self, users, pos_items, neg_items=None):
+        """One WARP step on host columns; ``neg_items`` None = search on the device.  Returns (negatives used, trial counts,
+        data loss, regulariser, number of skipped triples)."""
+        u, i = L.as_i32(users, "user ids").reshape(-1), L.as_i32(pos_items, "item ids").reshape(-1)
+        j = None if neg_items is None else L.as_i32(neg_items, "item ids").reshape(-1)
+        if u.shape != i.shape or (j is not None and j.shape != u.shape):
+            raise ValueError("batches must be 1-D and of equal length")
+        neg, trials = np.empty(u.size, np.int32), np.empty(u.size, np.int32)
+        loss, reg, skipped = C.c_float(), C.c_float(), C.c_int64()
+        L.check(self._lib.tfr_warp_train_step(self._warp_handle(), L.ptr_i32(u), L.ptr_i32(i),
+                                              None if j is None else L.ptr_i32(j), u.size, L.ptr_i32(neg), L.ptr_i32(trials),
+                                              C.byref(loss), C.byref(reg), C.byref(skipped)))
+        return neg, trials, loss.value, reg.value, skipped.value
+
+    def train_warp_step_dev(self, users, pos_items, neg_items=None, want_negatives=False):
+        """One WARP step on torch int32 device tensors, asynchronous: ordered after torch's current stream, and that stream
+        after it; an id error surfaces at the next ``sync()``.  Returns (negatives, trial counts) as device tensors when
+        asked."""
+        import torch
+        cols = [users.contiguous(), pos_items.contiguous()] + ([] if neg_items is None else [neg_items.contiguous()])
+        if any(c.dtype != torch.int32 or c.dim() != 1 or c.shape != cols[0].shape for c in cols):
+            raise TypeError("users / items must be 1-D int32 tensors of equal length")
+        n = cols[0].numel()
+        neg = torch.empty(n, dtype=torch.int32, device=cols[0].device) if want_negatives else None
+        trials = torch.empty(n, dtype=torch.int32, device=cols[0].device) if want_negatives else None
+        w = self._warp_handle()
+        mine = torch.cuda.ExternalStream(self.get_stream(), device=cols[0].device)
+        cur = torch.cuda.current_stream(cols[0].device)
+        mine.wait_stream(cur)
+        L.check(self._lib.tfr_warp_train_step_dev(w, cols[0].data_ptr(), cols[1].data_ptr(),
+                                                  None if neg_items is None else cols[2].data_ptr(), n,
+                                                  None if neg is None else neg.data_ptr(),
+                                                  None if trials is None else trials.data_ptr()))
+        cur.wait_stream(mine)
+        return (neg, trials) if want_negatives else None
+
+    def train_warp_steps_drawn(self, batch, nsteps, want_loss=False):
+        """nsteps x { e = np.random.randint(0, nnz, batch) (the device generator, as ``train_bpr_steps_drawn``); (u, i) =
+        entry e of the positives; one WARP step with the search }, all on the device.  Per-step data loss if asked."""
+        loss = np.empty(nsteps, np.float32) if want_loss else None
+        L.check(self._lib.tfr_warp_train_steps_drawn(self._warp_handle(), int(batch), int(nsteps),
+                                                     L.ptr_f32(loss) if want_loss else None))
         return loss
 
     # -- device-pointer plumbing --------------------------------------------------

@@ -187,11 +187,11 @@ def svdpp(train, test, *, user_num=None, item_num=None, dim=None, batch_size=Non
 
 
 def bpr(train, test, *, user_num=None, item_num=None, dim=None, batch_size=None, epoch_max=None, learning_rate=0.01,
-        reg=0.005, device=None, log=print):
+        reg=0.005, device=None, log=print, margin=None):
     """BPR on implicit feedback: the positives are the training frame's (user, item) pairs; each epoch runs
     nnz / batch drawn steps (pairs drawn with the ShuffleIterator's randint, negatives sampled on the device), then ranks
     the validation pairs over the whole catalogue with the training positives excluded.  Lazy Adam.  Returns the list of
-    (epoch, mean BPR loss per triple, recall@10, ndcg@10, auc, seconds) rows."""
+    (epoch, mean BPR loss per triple, recall@10, ndcg@10, auc, seconds) rows.  ``margin`` set: WARP steps (``warp``)."""
     from . import _lib as L
     from .engine import SvdModel, rated_matrix
     from .ranking import evaluate_ranking
@@ -207,11 +207,15 @@ def bpr(train, test, *, user_num=None, item_num=None, dim=None, batch_size=None,
         m.init_tables(seed=C.SEED, feature_stddev=0.1)
         m.set_table(L.BI, np.zeros(item_num, np.float32))
         m.set_positives(pos)
+        if margin is not None:
+            m.set_warp(margin)
+        step = m.train_bpr_steps_drawn if margin is None else m.train_warp_steps_drawn
         m.rng_from_numpy()                                              # the ShuffleIterator's generator
-        log("{} {} {} {} {} {}".format("epoch", "bpr_loss", "recall@10", "ndcg@10", "auc", "elapsed_time"))
+        log("{} {} {} {} {} {}".format("epoch", "bpr_loss" if margin is None else "warp_loss", "recall@10", "ndcg@10", "auc",
+                                       "elapsed_time"))
         start = time.time()
         for epoch in range(epoch_max):
-            loss = m.train_bpr_steps_drawn(batch_size, steps, want_loss=True)
+            loss = step(batch_size, steps, want_loss=True)
             ev = evaluate_ranking(m, test["user"], test["item"], exclude=pos, ks=(10,))["mean"]
             end = time.time()
             row = (epoch, float(np.mean(loss)) / batch_size, float(ev["recall@10"]), float(ev["ndcg@10"]),
@@ -221,6 +225,13 @@ def bpr(train, test, *, user_num=None, item_num=None, dim=None, batch_size=None,
             start = end
         m.rng_to_numpy()
     return rows
+
+
+def warp(train, test, *, margin=1.0, **kw):
+    """WARP on implicit feedback: the ``bpr`` driver with the step swapped - each drawn triple searches its
+    candidates for the first margin violator and is weighted by how few it took - and the same epoch line, the loss column
+    being the mean weighted hinge per triple."""
+    return bpr(train, test, margin=margin, **kw)
 
 
 def synthetic_frames(user_num, item_num, n, seed=C.SEED):
@@ -243,8 +254,9 @@ def main(argv=None):
     ap.add_argument("--epochs", type=int, default=10)
     ap.add_argument("--batch", type=int, default=C.BATCH_SIZE)
     ap.add_argument("--dim", type=int, default=C.DIM)
-    ap.add_argument("--model", choices=("svd", "svdpp", "bpr"), default="svd",
-                    help="svdpp: Koren's SVD++ with N(u) = training items; bpr: BPR on the training pairs as implicit feedback")
+    ap.add_argument("--model", choices=("svd", "svdpp", "bpr", "warp"), default="svd",
+                    help="svdpp: Koren's SVD++ with N(u) = training items; bpr: BPR on the training pairs as implicit feedback; "
+                         "warp: WARP on the same pairs (margin 1)")
     a = ap.parse_args(argv)
     np.random.seed(C.SEED)                                              # svd_train_val.py:15
     if a.data:
@@ -260,8 +272,9 @@ def main(argv=None):
     else:
         un, inum = C.USER_NUM, C.ITEM_NUM
         df_train, df_val = synthetic_frames(un, inum, 1000209)
-    if a.model == "bpr":
-        bpr(df_train, df_val, user_num=un, item_num=inum, dim=a.dim, batch_size=a.batch, epoch_max=a.epochs)
+    if a.model in ("bpr", "warp"):
+        (bpr if a.model == "bpr" else warp)(df_train, df_val, user_num=un, item_num=inum, dim=a.dim, batch_size=a.batch,
+                                            epoch_max=a.epochs)
     elif a.model == "svdpp":
         svdpp(df_train, df_val, user_num=un, item_num=inum, dim=a.dim, batch_size=a.batch, epoch_max=a.epochs)
     else:
