@@ -528,6 +528,64 @@ int tfr_fm_rank_items(tfr_fm* m, const int32_t* user_features, int64_t n_users, 
 int tfr_rank_plan(int32_t dim, int64_t n_users, int64_t n_targets, int64_t item_num, int64_t* lds_bytes,
                   int32_t* pieces_per_block, int32_t* item_slices, int32_t* targets_per_piece, int64_t* piece_chunk);
 
+/* ---- item-based nearest neighbours (ItemKNN) from the interaction matrix itself - DESIGN §31 ---------------------------------
+ *      X: the binary user x item matrix, a CSR pattern [n_users, n_items] with strictly increasing rows (no values).
+ *      n_i = the users of item i, c_ij = the users who have both i and j.  Similarity, in float64 with IEEE operations from
+ *      the three integers and rounded once to float32:
+ *          metric 0 cosine   c / (sqrt((double)n_i * (double)n_j) + shrink)
+ *          metric 1 jaccard  c / ((double)(n_i + n_j - c) + shrink)
+ *          metric 2 count    (double)c                                      (shrink must be 0)
+ *      The neighbours of i: the K items j != i with c_ij > 0 that have the largest tfr_topk key (the order-preserving uint32
+ *      of the similarity, then ~j: similarity descending, then id ascending); rows with fewer are padded with item -1 /
+ *      score -INFINITY as tfr_topk pads.  1 <= K <= 256.  Counts are integers: the lists are bit-identical run to run.
+ *          score(u, j) = sum over i in N(u), i ascending, of s(i -> j)     s(i -> j) = the float32 similarity when j is
+ *      among i's K kept neighbours.  A float32 add chain from +0.  Every item of the catalogue is a candidate; one without
+ *      evidence scores exactly 0 and is ordered by id like any tie.  tfr_knn_topk / tfr_knn_topk_lists / tfr_knn_rank_items
+ *      are tfr_topk / tfr_rank_items on these scores, word for word: 1 <= k <= 256, exclusion CSR aligned with the queries
+ *      with non-decreasing rows, the key, the padding, -1 for an excluded target, target rows strictly increasing, duplicate
+ *      users allowed, and 0 <= rank < k exactly when tfr_knn_topk(k) returns the target, at that position.
+ *      tfr_knn_load takes the user CSR and builds its transpose; a second load replaces the first and forgets the fitted
+ *      lists.  tfr_knn_fit computes the [n_items, K] lists, which stay on the device.  tfr_knn_get_neighbours copies rows
+ *      [row_lo, row_lo + n_rows) out; tfr_knn_set_neighbours writes them from host arrays of the same shape (a fitted model
+ *      reloaded without a fit; rows never written are empty): ids in [-1, n_items), -1 is padding, no row lists itself or
+ *      repeats an item, the scores of real ids are finite.  tfr_knn_topk queries resident users (their loaded rows are the
+ *      lists); tfr_knn_topk_lists queries n given lists (a CSR from 0 with strictly increasing rows): users the model does
+ *      not hold.  It needs lists, not a load.
+ *      Host pointers; every call synchronises.  Checked on the host before any device work (the model is left as it was):
+ *      TFR_ERR_ARG for K or k outside [1, 256], an unknown metric, a shrink that is negative or not finite, a shrink with
+ *      metric 2, a catalogue of more than 16384 * min(256, 8192 / K) items (fit) or 8192 * min(256, 8192 / k) items (top-K:
+ *      the slices the merge takes, tfr_knn_plan), an indptr that
+ *      does not start at 0 (user and list CSR) or decreases, a row out of order, a set_neighbours row that lists itself,
+ *      repeats an item or carries a score that is not finite; TFR_ERR_OOB for an id out of range; TFR_ERR_STATE for fit
+ *      before a load, and for get_neighbours, top-K and ranking before a fit or set_neighbours (top-K of users and ranking
+ *      also before a load).  n = 0 and rows without targets are no-ops.  scores_out may be NULL. */
+typedef struct tfr_knn tfr_knn;
+int tfr_knn_create(tfr_knn** out, int64_t n_users, int64_t n_items, int32_t K, int32_t metric /* 0 cosine, 1 jaccard, 2 count */,
+                   double shrink, int32_t device);
+int tfr_knn_destroy(tfr_knn* m);
+int tfr_knn_load(tfr_knn* m, const int64_t* indptr /* [n_users+1] */, const int32_t* items);
+int tfr_knn_fit(tfr_knn* m, float* elapsed_ms /* may be NULL */);
+int tfr_knn_get_neighbours(tfr_knn* m, int64_t row_lo, int64_t n_rows, int32_t* items_out /* [n_rows,K], may be NULL */,
+                           float* scores_out /* [n_rows,K], may be NULL */);
+int tfr_knn_set_neighbours(tfr_knn* m, int64_t row_lo, int64_t n_rows, const int32_t* items, const float* scores);
+int tfr_knn_topk(tfr_knn* m, const int32_t* users, int64_t n, int32_t k,
+                 const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                 int32_t* items_out /* [n,k] */, float* scores_out /* [n,k], may be NULL */);
+int tfr_knn_topk_lists(tfr_knn* m, const int64_t* list_indptr /* [n+1] */, const int32_t* list_items, int64_t n, int32_t k,
+                       const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                       int32_t* items_out, float* scores_out);
+int tfr_knn_rank_items(tfr_knn* m, const int32_t* users, int64_t n,
+                       const int64_t* tgt_indptr /* [n+1] */, const int32_t* tgt_items,
+                       const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                       int32_t* ranks_out /* [tgt_indptr[n] - tgt_indptr[0]] */);
+/* host-only, no device: what the launcher of the fit (which = 0: k is K, n_rows the items) or of the scoring (which = 1: k is
+ * the query's k, n_rows the queries) will do - columns per catalogue slice, slices, rows per chunk, LDS bytes per workgroup
+ * (the larger of that kernel and the merge), and how many list entries a wave loads ahead (fit: users of the item whose
+ * row bounds are fetched at once; scoring: items of the query whose neighbour rows are).  Outputs may be NULL. */
+int tfr_knn_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t which, int32_t* slice_width, int32_t* slices,
+                 int64_t* row_chunk, int64_t* lds_bytes, int32_t* look_ahead);
+const char* tfr_knn_last_error(void);
+
 /* ---- batched per-user fine-tuning: every user of adaptive_test.py:87-116 / non_adaptive_test.py:56-87 in one launch -----------
  *      A schedule: for user u = users[x] (each at most once), training rows items / rates [row_ptr[x], row_ptr[x+1]) and rounds
  *      [round_ptr[x], round_ptr[x+1]).  Round k first predicts ask_items[k] with the parameters of the moment (its logit, the

@@ -14,8 +14,9 @@ from .svdpp import SvdppModel
 from . import svdpp
 from .als import MangakiALS3
 from .ials import ImplicitALS
+from .itemknn import ItemKNN
 from . import ranking, neighbours, bf16
 from .ranking import ranking_metrics, evaluate_ranking
 
 __all__ = ["SvdModel", "device_copy_rate", "rated_matrix", "TfrError", "OutOfRangeError", "_lib", "dataio", "graph", "ops", "config", "cats", "adaptive_test", "finetune",
-           "FmModel", "SvdppModel", "svdpp", "MangakiALS3", "ImplicitALS", "ranking", "ranking_metrics", "evaluate_ranking", "neighbours", "bf16"]
+           "FmModel", "SvdppModel", "svdpp", "MangakiALS3", "ImplicitALS", "ItemKNN", "ranking", "ranking_metrics", "evaluate_ranking", "neighbours", "bf16"]

@@ -177,6 +177,17 @@ SIGNATURES = {
     "tfr_ials_fold_in": (C.c_int, [_p, C.c_int32, C.c_int64, _i64p, _i32p, _f64p, C.c_int32, _i32p, _f64p, _f64p, _f32p]),
     "tfr_ials_export_f32": (C.c_int, [_p, C.c_int32, C.c_int64, C.c_int64, _p]),
     "tfr_ials_last_error": (C.c_char_p, []),
+    "tfr_knn_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32]),
+    "tfr_knn_destroy": (C.c_int, [_p]),
+    "tfr_knn_load": (C.c_int, [_p, _i64p, _i32p]),
+    "tfr_knn_fit": (C.c_int, [_p, _f32p]),
+    "tfr_knn_get_neighbours": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _f32p]),
+    "tfr_knn_set_neighbours": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _f32p]),
+    "tfr_knn_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
+    "tfr_knn_topk_lists": (C.c_int, [_p, _i64p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
+    "tfr_knn_rank_items": (C.c_int, [_p, _i32p, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
+    "tfr_knn_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i64p, _i32p]),
+    "tfr_knn_last_error": (C.c_char_p, []),
     "tfr_sort_segments": (C.c_int, [_p, C.c_int32, _i32p, C.c_int64, _i32p, _i32p]),
     "tfr_kernel_plan": (C.c_int, [_p, C.c_int64, C.c_char_p, C.c_int64]),
     "tfr_forward_plan": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_char_p, C.c_int64]),
