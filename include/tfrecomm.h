@@ -586,6 +586,73 @@ int tfr_knn_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t which, int3
                  int64_t* row_chunk, int64_t* lds_bytes, int32_t* look_ahead);
 const char* tfr_knn_last_error(void);
 
+/* ---- EASE (Steck 2019, "Embarrassingly Shallow Autoencoders"): a dense item x item model in closed form - DESIGN §32 ----------
+ *      X: the binary user x item matrix, a CSR pattern [n_users, n_items] under the rules of tfr_knn_load (rows strictly
+ *      increasing, no values).  n_i = the users of item i, c_ij = the users who have both i and j.
+ *          G = X^T X + lambda I   float64: off the diagonal the exact integers c_ij, on it (double)n_i + lambda; lambda > 0, finite
+ *          P = G^-1               float64, by a blocked Cholesky factorisation on the device; symmetric by construction: both
+ *                                 triangles are stored with the same bits, and two solves of one G give the same bits
+ *          B[i, j] = (float)(-P[i, j] / P[j, j]) for i != j: one correctly rounded float64 division, one rounding to float32;
+ *          B[j, j] = +0.  B is a dense float32 [n_items, n_items], row-major.
+ *          score(u, j) = the float32 add chain from +0, over i in N(u) ascending, of B[i, j]
+ *      Every item is a candidate; a user with an empty list scores +0 everywhere and is served by id.  tfr_ease_topk /
+ *      tfr_ease_topk_lists / tfr_ease_rank_items are tfr_topk / tfr_rank_items on these scores, word for word as their
+ *      tfr_knn_* namesakes: 1 <= k <= 256, the key (the order-preserving uint32 of the score, then ~j), padding with item -1 /
+ *      score -INFINITY, the exclusion CSR aligned with the queries with non-decreasing rows, target rows strictly increasing,
+ *      duplicate users allowed, -1 for an excluded target, 0 <= rank < k exactly when top-K of k returns the target, at that
+ *      position; a NaN score is never returned and never ranked.
+ *      The dense matrices cost 12 bytes per entry: n_items > 32768 is refused with TFR_ERR_ARG before any device work.
+ *      tfr_ease_load takes the user CSR and builds its transpose; a second load replaces the first and forgets the Gram matrix
+ *      and the weights.  tfr_ease_gram builds G from the loaded pattern into the float64 buffer.  tfr_ease_set_gram takes a
+ *      caller's full [n_items, n_items] matrix instead (weighted or time-decayed co-counts): it must be finite, bit-symmetric
+ *      and have a positive diagonal (TFR_ERR_ARG otherwise); lambda is not added to it.  tfr_ease_solve inverts the float64
+ *      buffer in place, forms B and frees the float64 buffer unless keep_inverse; elapsed_ms, if given, receives three device
+ *      times: of the tfr_ease_gram that built the matrix (0 for a caller's), of the inverse and of the weights.  A pivot that
+ *      is not positive and finite (the matrix is not positive definite) returns TFR_ERR_ARG, the message names the column;
+ *      the model is then unfitted, holds no float64 matrix, and the handle stays usable.  tfr_ease_get_f64 copies rows
+ *      [row_lo, row_lo + n_rows) of the float64 buffer out: G after gram / set_gram, P after a solve that kept it,
+ *      TFR_ERR_STATE otherwise.  tfr_ease_get_weights / tfr_ease_set_weights read and write rows of B, so a fitted model moves
+ *      without a refit: set_weights refuses values that are not finite (TFR_ERR_ARG); a handle without weights takes all
+ *      rows in one call (TFR_ERR_STATE for fewer), which makes it fitted.  tfr_ease_topk queries resident users (their loaded
+ *      rows are the lists); tfr_ease_topk_lists queries n given lists (a CSR from 0 with strictly increasing rows): it needs
+ *      weights, not a load.
+ *      Host pointers; every call synchronises.  Checked on the host before any device work (the model is left as it was):
+ *      TFR_ERR_ARG for a lambda that is not positive and finite, k outside [1, 256], an indptr that does not start at 0 (user
+ *      and list CSR) or decreases, a row out of order, rows outside the matrix; TFR_ERR_OOB for an id out of range;
+ *      TFR_ERR_STATE for gram before a load, solve without a Gram matrix, get_weights, top-K and ranking without weights
+ *      (top-K of users and ranking also before a load).  n = 0 and rows without targets are no-ops.  scores_out may be NULL. */
+typedef struct tfr_ease tfr_ease;
+int tfr_ease_create(tfr_ease** out, int64_t n_users, int64_t n_items, double lambda, int32_t device);
+int tfr_ease_destroy(tfr_ease* m);
+int tfr_ease_load(tfr_ease* m, const int64_t* indptr /* [n_users+1] */, const int32_t* items);
+int tfr_ease_gram(tfr_ease* m);
+int tfr_ease_set_gram(tfr_ease* m, const double* G /* [n_items,n_items] */);
+int tfr_ease_solve(tfr_ease* m, int32_t keep_inverse, float* elapsed_ms /* [3]: Gram, inverse, weights; may be NULL */);
+int tfr_ease_get_f64(tfr_ease* m, int64_t row_lo, int64_t n_rows, double* out /* [n_rows,n_items] */);
+int tfr_ease_get_weights(tfr_ease* m, int64_t row_lo, int64_t n_rows, float* out /* [n_rows,n_items] */);
+int tfr_ease_set_weights(tfr_ease* m, int64_t row_lo, int64_t n_rows, const float* in /* [n_rows,n_items] */);
+int tfr_ease_topk(tfr_ease* m, const int32_t* users, int64_t n, int32_t k,
+                  const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                  int32_t* items_out /* [n,k] */, float* scores_out /* [n,k], may be NULL */);
+int tfr_ease_topk_lists(tfr_ease* m, const int64_t* list_indptr /* [n+1] */, const int32_t* list_items, int64_t n, int32_t k,
+                        const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                        int32_t* items_out, float* scores_out);
+int tfr_ease_rank_items(tfr_ease* m, const int32_t* users, int64_t n,
+                        const int64_t* tgt_indptr /* [n+1] */, const int32_t* tgt_items,
+                        const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                        int32_t* ranks_out /* [tgt_indptr[n] - tgt_indptr[0]] */);
+/* host-only, no handle and no device: what the launches to come will do.  For the fit - the factorisation block size, the
+ * MFMA tile of the update kernel (tile x tile results per workgroup), and the float64 / float32 device bytes a fit allocates
+ * (G / P with the work panel and the inverted diagonal blocks; B).  For which = 0 (the fit: k must be valid, n_rows is not
+ * used) the slicing is the Gram kernel's and lds_bytes the largest of the fit's kernels; for which = 1 (scoring n_rows
+ * queries for k) - columns per catalogue slice, slices, queries per chunk, LDS bytes per workgroup (the larger of the
+ * scoring kernel and the merge) and how many list items a wave loads ahead.  TFR_ERR_ARG for what a launch would refuse:
+ * n_items outside [1, 32768], k outside [1, 256], n_rows < 0.  Outputs may be NULL. */
+int tfr_ease_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t which, int32_t* block, int32_t* tile, int64_t* lds_bytes,
+                  int64_t* f64_bytes, int64_t* f32_bytes, int32_t* slice_width, int32_t* slices, int64_t* row_chunk,
+                  int32_t* look_ahead);
+const char* tfr_ease_last_error(void);
+
 /* ---- batched per-user fine-tuning: every user of adaptive_test.py:87-116 / non_adaptive_test.py:56-87 in one launch -----------
  *      A schedule: for user u = users[x] (each at most once), training rows items / rates [row_ptr[x], row_ptr[x+1]) and rounds
  *      [round_ptr[x], round_ptr[x+1]).  Round k first predicts ask_items[k] with the parameters of the moment (its logit, the

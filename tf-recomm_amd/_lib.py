@@ -188,6 +188,21 @@ SIGNATURES = {
     "tfr_knn_rank_items": (C.c_int, [_p, _i32p, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
     "tfr_knn_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i64p, _i32p]),
     "tfr_knn_last_error": (C.c_char_p, []),
+    "tfr_ease_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_double, C.c_int32]),
+    "tfr_ease_destroy": (C.c_int, [_p]),
+    "tfr_ease_load": (C.c_int, [_p, _i64p, _i32p]),
+    "tfr_ease_gram": (C.c_int, [_p]),
+    "tfr_ease_set_gram": (C.c_int, [_p, _f64p]),
+    "tfr_ease_solve": (C.c_int, [_p, C.c_int32, _f32p]),
+    "tfr_ease_get_f64": (C.c_int, [_p, C.c_int64, C.c_int64, _f64p]),
+    "tfr_ease_get_weights": (C.c_int, [_p, C.c_int64, C.c_int64, _f32p]),
+    "tfr_ease_set_weights": (C.c_int, [_p, C.c_int64, C.c_int64, _f32p]),
+    "tfr_ease_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
+    "tfr_ease_topk_lists": (C.c_int, [_p, _i64p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
+    "tfr_ease_rank_items": (C.c_int, [_p, _i32p, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
+    "tfr_ease_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i64p, _i64p, _i32p, _i32p,
+                                _i64p, _i32p]),
+    "tfr_ease_last_error": (C.c_char_p, []),
     "tfr_sort_segments": (C.c_int, [_p, C.c_int32, _i32p, C.c_int64, _i32p, _i32p]),
     "tfr_kernel_plan": (C.c_int, [_p, C.c_int64, C.c_char_p, C.c_int64]),
     "tfr_forward_plan": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_char_p, C.c_int64]),

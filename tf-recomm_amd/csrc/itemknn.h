@@ -11,6 +11,7 @@
 #include "tfrecomm.h"
 #include "devbuf.h"
 #include "topk.h"
+#include "score_tile.h"
 
 constexpr int KNN_KMAX = tfr::TOPK_KMAX;
 constexpr int KNN_WAVES = 4;                             // waves per block of both kernels
@@ -91,3 +92,26 @@ struct tfr_knn {
     tfr::DevBuf<int64_t> q_ptr, x_ptr, t_ptr;
     tfr::DevBuf<float> out_scores;
 };
+
+// The per-wave key queue of both scoring tails (k_knn_cooc, k_knn_score, ease.hip k_ease_score): q is the wave's own LDS.
+// sort the wave's queue, keep its k best, raise its threshold; cnt and thr are wave-uniform registers
+template <int CAP>
+__device__ __forceinline__ void knn_compact(uint64_t* q, int& cnt, uint64_t& thr, int k, int lane) {
+    for (int t = cnt + lane; t < CAP; t += 64) q[t] = 0;
+    tfr::wave_lds_sync();
+    tfr::wave_sort_desc<CAP>(q, lane);
+    cnt = cnt < k ? cnt : k;
+    thr = cnt == k ? q[k - 1] : 0;
+}
+
+// each lane offers one key; needs cnt <= CAP - 64 on entry and leaves it so
+template <int CAP>
+__device__ __forceinline__ void knn_offer(uint64_t* q, int& cnt, uint64_t& thr, int k, int lane, bool ok, uint64_t key) {
+    ok = ok && key > thr;
+    const uint64_t mask = __ballot(ok);
+    if (mask) {
+        if (ok) q[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = key;
+        cnt += __popcll(mask);
+        if (cnt > CAP - 64) knn_compact<CAP>(q, cnt, thr, k, lane);
+    }
+}

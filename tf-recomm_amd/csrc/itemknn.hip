@@ -38,7 +38,6 @@ namespace {
 
 using tfr::topk_key;
 using tfr::wave_lds_sync;
-using tfr::wave_sort_desc;
 
 enum { KNN_COSINE = 0, KNN_JACCARD = 1, KNN_COUNT = 2 };
 
@@ -49,28 +48,6 @@ __device__ __forceinline__ float knn_sim(int metric, uint32_t c, int64_t ni, int
     else if (metric == KNN_JACCARD) s = (double)c / ((double)(ni + nj - (int64_t)c) + shrink);
     else s = (double)c;
     return __double2float_rn(s);
-}
-
-// sort the wave's queue, keep its k best, raise its threshold; cnt and thr are wave-uniform registers
-template <int CAP>
-__device__ __forceinline__ void knn_compact(uint64_t* q, int& cnt, uint64_t& thr, int k, int lane) {
-    for (int t = cnt + lane; t < CAP; t += 64) q[t] = 0;
-    wave_lds_sync();
-    wave_sort_desc<CAP>(q, lane);
-    cnt = cnt < k ? cnt : k;
-    thr = cnt == k ? q[k - 1] : 0;
-}
-
-// each lane offers one key; needs cnt <= CAP - 64 on entry and leaves it so
-template <int CAP>
-__device__ __forceinline__ void knn_offer(uint64_t* q, int& cnt, uint64_t& thr, int k, int lane, bool ok, uint64_t key) {
-    ok = ok && key > thr;
-    const uint64_t mask = __ballot(ok);
-    if (mask) {
-        if (ok) q[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = key;
-        cnt += __popcll(mask);
-        if (cnt > CAP - 64) knn_compact<CAP>(q, cnt, thr, k, lane);
-    }
 }
 
 // first position in the increasing x[lo, hi) whose value is not below v
