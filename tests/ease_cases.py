@@ -138,3 +138,20 @@ def ladder(n_items, seed=35):
     a = ahead()
     lens = [0, 1, a - 1, a, a + 1, 2 * a + 1, 40] * 3
     return IC.csr_of_rows([rs.choice(n_items, min(n, n_items), replace=False) for n in lens], n_items)
+
+
+def twin_case(n_items=1025, K=4, seed=36):
+    """one model spelt both ways, for the two scoring tails to be held against each other: ItemKNN neighbour lists (nb, sc)
+    of every fill whose scores are multiples of 1/8 in [-2, 2] - the sums of a few are exact in any order - and the dense
+    weights they spell out, B[i, nb[i, c]] = sc[i, c] and +0 elsewhere.  1025 items: one ItemKNN scoring slice, two of EASE."""
+    rs = np.random.RandomState(seed)
+    nb = np.full((n_items, K), -1, np.int32)
+    sc = np.full((n_items, K), -np.inf, np.float32)
+    B = np.zeros((n_items, n_items), np.float32)
+    for i in range(n_items):
+        cand = rs.choice(n_items - 1, rs.randint(0, K + 1), replace=False)
+        cand = cand + (cand >= i)                          # skip i itself
+        nb[i, :cand.size] = cand
+        sc[i, :cand.size] = (rs.randint(-16, 17, cand.size) / 8.0).astype(np.float32)
+        B[i, cand] = sc[i, :cand.size]
+    return nb, sc, B

@@ -188,3 +188,18 @@ def test_the_error_constant_of_the_inverse():
         len(cases), max(EC.inverse_case(*c)[2] for c in cases), min(ratios.values()), r_max, worst, K))
     assert r_max == ratios[worst] and K == 8 * r_max
     assert 0 < r_max < 64                                                      # a backward-stable order: a small multiple of eps cond
+
+
+def test_twin_case_gives_one_set_of_keys_in_both_restatements():
+    """tests/test_gpu_ease.py holds the two devices' scoring tails against each other on this case: here the two restatements
+    agree on it first, key for key, so a difference there is the device's"""
+    from tests import itemknn_cases as IC, itemknn_ref as KR
+    nb, sc, B = EC.twin_case()
+    ni = B.shape[0]
+    assert E.plan(ni, 10, 1, 1)["slices"] == 2 and not B.diagonal().any()
+    indptr, items, nu, _ = EC.ladder(ni, seed=43)
+    assert 0 in np.diff(indptr)                                                # a query with an empty list
+    for lst in IC.rows_of(indptr, items, range(nu)):
+        a, b = KR.user_scores(lst, nb, sc, ni), R.user_scores(lst, B)
+        assert np.array_equal(KR.keys(a), R.keys(b))
+        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))

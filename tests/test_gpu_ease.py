@@ -393,3 +393,56 @@ def test_argument_and_state_errors():
         assert lib.tfr_ease_set_weights(h, 0, 2, L.ptr_f32(before)) == L.ERR_STATE          # without weights: all rows at once
         assert lib.tfr_ease_set_weights(h, 0, n, L.ptr_f32(before)) == L.OK
         assert lib.tfr_ease_topk(h, L.ptr_i32(u), 2, 2, None, None, L.ptr_i32(out), None) == L.OK
+
+
+# ---- 9. what EASE shares with ItemKNN (csrc/item_lists.h) ------------------------------------------------------------------------
+def test_a_refused_load_leaves_a_fitted_model_serving():
+    (indptr, items, nu, ni), _, _ = EC.planted_case()
+    users = np.arange(0, nu, 5, dtype=np.int32)
+    x = csr_of(IC.rows_of(indptr, items, users))
+    with T.EASE(nu, ni, regularization=5.0) as m:
+        m.fit((indptr, items), keep_inverse=True)
+        before, B, P = m.recommend(users, 10, exclude=x), m.weights(), m.inverse()
+        bad = items.copy()
+        bad[-1] = ni                                                           # the last id of the last row: out of range
+        assert L.load().tfr_ease_load(m._h, L.ptr_i64(indptr), L.ptr_i32(bad)) == L.ERR_OOB
+        assert_same(m.recommend(users, 10, exclude=x), before, "after the refused load")
+        assert np.array_equal(bits(m.weights()), bits(B)) and np.array_equal(bits64(m.inverse()), bits64(P))
+
+
+def test_the_two_scoring_tails_agree():
+    """ItemKNN's neighbour table and the dense weights that spell it out (tests/ease_cases.py twin_case: every sum exact in
+    either order, tests/test_ease_host.py holds the two restatements to one set of keys): the two kernels accumulate in
+    their own ways and then run the one shared tail, so items, scores and ranks are the same bits - over one slice there,
+    over two here"""
+    from tests import itemknn_ref as KR
+    nb, sc, B = EC.twin_case()
+    ni, K = B.shape[0], nb.shape[1]
+    assert E.plan(ni, 10, 1, 1)["slices"] == 2
+    indptr, items, nu, _ = EC.ladder(ni, seed=43)
+    users = np.arange(nu, dtype=np.int32)
+    lists = IC.rows_of(indptr, items, users)
+    assert len(lists[0]) == 0                                                  # a query with an empty list
+    rs = np.random.RandomState(7)
+    targets = [np.sort(rs.choice(ni, 6, replace=False)).astype(np.int32) for _ in users]
+    others = all_but(ni, lists[5])                                             # query 5: one target of its own list, three not
+    targets[5] = np.sort(np.concatenate([lists[5][:1], others[[0, others.size // 2, -1]]])).astype(np.int32)
+    with T.ItemKNN(nu, ni, K=K) as knn, T.EASE(nu, ni) as ease:
+        knn.load((indptr, items))
+        knn.set_neighbours(nb, sc)
+        ease.load((indptr, items))
+        ease.set_weights(B)
+        for name, excl in exclusion_modes(lists, ni):
+            x = None if excl is None else csr_of(excl)
+            for k in (1, 10):
+                got = knn.recommend(users, k, exclude=x)
+                assert_same(ease.recommend(users, k, exclude=x), got, "recommend k=%d excl=%s" % (k, name))
+                assert_same(got, want_topk(lists, B, k, excl), "both against the restatement k=%d excl=%s" % (k, name))
+                assert_same(ease.recommend_lists((indptr, items), k, exclude=False if x is None else x), got, "lists k=%d" % k)
+            ranks = knn.rank_items(users, csr_of(targets), exclude=x)
+            assert np.array_equal(ease.rank_items(users, csr_of(targets), exclude=x), ranks), name
+            want = np.concatenate([KR.ranks(KR.user_scores(lst, nb, sc, ni), t, () if excl is None else excl[q])
+                                   for q, (lst, t) in enumerate(zip(lists, targets))])
+            assert np.array_equal(ranks, want), name
+            if name == "own":
+                assert (ranks[30:34] == -1).sum() == 1                         # the excluded target

@@ -377,3 +377,101 @@ def test_argument_and_state_errors():
         assert lib.tfr_knn_set_neighbours(h, 4, 3, L.ptr_i32(nb), L.ptr_f32(ok_sc)) == L.ERR_ARG              # window past the items
         m._nb = None                                                           # read the device's lists again
         assert m.neighbours()[0].tolist() == [[1, -1], [0, 2], [1, -1], [-1, -1], [-1, -1], [-1, -1]]         # untouched
+
+
+# ---- what ItemKNN shares with EASE (csrc/item_lists.h): one set of checks behind both handles ------------------------------------
+def malformed_csrs():
+    """(name, indptr of two rows, ids, code as a from-0 strict CSR, code as an exclusion CSR): every rule of check_csr.  The
+    user CSR of a load, a list CSR and a target CSR are strict; list and user CSRs start at 0; an exclusion CSR may start
+    anywhere and repeat an id.  None as a code: not malformed for that kind."""
+    A, O = L.ERR_ARG, L.ERR_OOB
+    return [("null indptr", None, [0, 1], A, None),                        # no exclusion CSR at all is legal
+            ("indptr starts at 1", [1, 2, 3], [0, 1, 2], A, L.OK),
+            ("indptr starts below 0", [-1, 1, 2], [0, 1, 2], A, A),
+            ("indptr decreases", [0, 2, 1], [0, 1], A, A),
+            ("ids missing", [0, 1, 2], None, A, A),
+            ("id -1", [0, 2, 2], [-1, 2], O, O),
+            ("id n_items", [0, 2, 2], [2, 5], O, O),
+            ("row repeats an id", [0, 2, 2], [3, 3], A, L.OK),
+            ("row decreases", [0, 2, 2], [4, 1], A, A)]
+
+
+def test_shared_checks_refuse_alike_through_both_handles():
+    lib = L.load()
+    i64 = lambda v: None if v is None else L.ptr_i64(np.array(v, np.int64))
+    i32 = lambda v: None if v is None else L.ptr_i32(np.array(v, np.int32))
+    indptr, items = np.array([0, 2, 4, 4], np.int64), np.array([0, 1, 1, 2], np.int32)
+    out = np.full(8, 77, np.int32)
+    o = L.ptr_i32(out)
+    u, good = [0, 1], ([0, 1, 2], [1, 2])
+    with T.ItemKNN(3, 5, K=2) as knn, T.EASE(3, 5, regularization=1.0) as ease:
+        knn.fit((indptr, items))
+        ease.fit((indptr, items))
+        served = knn.recommend(u, 5), ease.recommend(u, 5)
+        fam = {"knn": knn._h, "ease": ease._h}
+        fn = lambda f, name: getattr(lib, "tfr_%s_%s" % (f, name))
+        text = lambda f: fn(f, "last_error")().decode()
+
+        def mark():
+            """each family's last error set to a text of its own"""
+            for f in fam:
+                assert fn(f, "plan")(5, 1, 1, 7, *[None] * (5 if f == "knn" else 9)) == L.ERR_ARG
+                assert text(f).startswith(f + " plan: which")
+            return {f: text(f) for f in fam}
+
+        def both(what, want, call, *words):
+            got = {}
+            for f, other in (("knn", "ease"), ("ease", "knn")):
+                marks = mark()
+                assert call(f, fam[f]) == want, (what, f)
+                assert text(other) == marks[other], (what, f, "wrote to the other family's text")
+                if want == L.OK:
+                    assert text(f) == marks[f], (what, f)
+                else:
+                    assert all(w in text(f) for w in words), (what, f, text(f))
+                got[f] = text(f)
+            assert want == L.OK or got["knn"] == got["ease"], (what, got)
+
+        for name, p, ids, strict0, excl in malformed_csrs():
+            # the target CSR is strict but need not start at 0
+            tgt = (L.OK if name == "indptr starts at 1" else strict0)
+            p3 = None if p is None else p + p[-1:]                             # three rows for the load
+            both("load: " + name, strict0, lambda f, h: fn(f, "load")(h, i64(p3), i32(ids)), "load: ", "user ")
+            both("lists: " + name, strict0, lambda f, h: fn(f, "topk_lists")(h, i64(p), i32(ids), 2, 2, None, None, o, None),
+                 "top-K of lists: ", "list ")
+            both("targets: " + name, tgt, lambda f, h: fn(f, "rank_items")(h, i32(u), 2, i64(p), i32(ids), None, None, o),
+                 "rank: ", "target ")
+            if excl is None:
+                continue
+            both("top-K exclusions: " + name, excl, lambda f, h: fn(f, "topk")(h, i32(u), 2, 2, i64(p), i32(ids), o, None),
+                 "top-K: ", "exclusion ")
+            both("lists' exclusions: " + name, excl,
+                 lambda f, h: fn(f, "topk_lists")(h, i64(good[0]), i32(good[1]), 2, 2, i64(p), i32(ids), o, None),
+                 "top-K of lists: ", "exclusion ")
+            both("rank exclusions: " + name, excl,
+                 lambda f, h: fn(f, "rank_items")(h, i32(u), 2, i64(good[0]), i32(good[1]), i64(p), i32(ids), o), "rank: ", "exclusion ")
+        for bad in (-1, 3):                                                    # a user id of -1 and one of n_users
+            both("top-K user %d" % bad, L.ERR_OOB, lambda f, h: fn(f, "topk")(h, i32([0, bad]), 2, 2, None, None, o, None),
+                 "top-K: user id %d " % bad)
+            both("rank user %d" % bad, L.ERR_OOB,
+                 lambda f, h: fn(f, "rank_items")(h, i32([0, bad]), 2, i64(good[0]), i32(good[1]), None, None, o), "rank: user id %d " % bad)
+        for k in (0, 257):                                                     # k of 0 and KMAX + 1
+            both("top-K k %d" % k, L.ERR_ARG, lambda f, h: fn(f, "topk")(h, i32(u), 2, k, None, None, o, None), "top-K: k must be", "%d" % k)
+            both("lists k %d" % k, L.ERR_ARG, lambda f, h: fn(f, "topk_lists")(h, i64(good[0]), i32(good[1]), 2, k, None, None, o, None),
+                 "top-K of lists: k must be", "%d" % k)
+        # no refused load reached either model: both still serve what they were fitted to
+        assert_same(knn.recommend(u, 5), served[0], "ItemKNN after the refusals")
+        assert_same(ease.recommend(u, 5), served[1], "EASE after the refusals")
+
+
+def test_a_refused_load_leaves_a_fitted_model_serving():
+    indptr, items, nu, ni = IC.case("lengths")
+    users = np.arange(0, nu, 5, dtype=np.int32)
+    x = csr_of(IC.rows_of(indptr, items, users))
+    with fitted_model("lengths", 10) as m:
+        before = m.recommend(users, 10, exclude=x)
+        bad = items.copy()
+        bad[-1] = ni                                                           # the last id of the last row: out of range
+        assert L.load().tfr_knn_load(m._h, L.ptr_i64(indptr), L.ptr_i32(bad)) == L.ERR_OOB
+        assert_same(m.recommend(users, 10, exclude=x), before, "after the refused load")
+        assert_same(m.neighbours(), IC.fitted("lengths", 10, "cosine", 0.0), "the lists after the refused load")

@@ -178,28 +178,18 @@ SIGNATURES = {
     "tfr_ials_export_f32": (C.c_int, [_p, C.c_int32, C.c_int64, C.c_int64, _p]),
     "tfr_ials_last_error": (C.c_char_p, []),
     "tfr_knn_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32]),
-    "tfr_knn_destroy": (C.c_int, [_p]),
-    "tfr_knn_load": (C.c_int, [_p, _i64p, _i32p]),
     "tfr_knn_fit": (C.c_int, [_p, _f32p]),
     "tfr_knn_get_neighbours": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _f32p]),
     "tfr_knn_set_neighbours": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _f32p]),
-    "tfr_knn_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
-    "tfr_knn_topk_lists": (C.c_int, [_p, _i64p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
-    "tfr_knn_rank_items": (C.c_int, [_p, _i32p, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
     "tfr_knn_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i64p, _i32p]),
     "tfr_knn_last_error": (C.c_char_p, []),
     "tfr_ease_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_double, C.c_int32]),
-    "tfr_ease_destroy": (C.c_int, [_p]),
-    "tfr_ease_load": (C.c_int, [_p, _i64p, _i32p]),
     "tfr_ease_gram": (C.c_int, [_p]),
     "tfr_ease_set_gram": (C.c_int, [_p, _f64p]),
     "tfr_ease_solve": (C.c_int, [_p, C.c_int32, _f32p]),
     "tfr_ease_get_f64": (C.c_int, [_p, C.c_int64, C.c_int64, _f64p]),
     "tfr_ease_get_weights": (C.c_int, [_p, C.c_int64, C.c_int64, _f32p]),
     "tfr_ease_set_weights": (C.c_int, [_p, C.c_int64, C.c_int64, _f32p]),
-    "tfr_ease_topk": (C.c_int, [_p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
-    "tfr_ease_topk_lists": (C.c_int, [_p, _i64p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
-    "tfr_ease_rank_items": (C.c_int, [_p, _i32p, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
     "tfr_ease_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i64p, _i64p, _i32p, _i32p,
                                 _i64p, _i32p]),
     "tfr_ease_last_error": (C.c_char_p, []),
@@ -270,6 +260,16 @@ SIGNATURES = {
     "tfr_device_count": (C.c_int, []),
     "tfr_device_copy_rate": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _f64p, _f64p]),
 }
+
+# what the item x item families share (item_lists.py): the same five signatures under each prefix
+for _family in ("knn", "ease"):
+    SIGNATURES.update({
+        "tfr_%s_destroy" % _family: (C.c_int, [_p]),
+        "tfr_%s_load" % _family: (C.c_int, [_p, _i64p, _i32p]),
+        "tfr_%s_topk" % _family: (C.c_int, [_p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
+        "tfr_%s_topk_lists" % _family: (C.c_int, [_p, _i64p, _i32p, C.c_int64, C.c_int32, _i64p, _i32p, _i32p, _f32p]),
+        "tfr_%s_rank_items" % _family: (C.c_int, [_p, _i32p, C.c_int64, _i64p, _i32p, _i64p, _i32p, _i32p]),
+    })
 
 _lib = None
 

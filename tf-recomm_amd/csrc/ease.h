@@ -1,8 +1,8 @@
 // ease.h - EASE (tfr_ease_*): the launch plan, the argument blocks of the kernels and the handle.  ease.hip owns
-// the kernels and the C-ABI entries; the per-slice key lists are merged by topk.hip's launch_topk_merge (topk.h), the
-// per-wave key queue is itemknn.h's.
+// the kernels and the C-ABI entries; the CSR, the serving drivers, the count loop, the per-wave key queue and the scoring tail
+// are item_lists.h's; the per-slice key lists are merged by topk.hip's launch_topk_merge (topk.h).
 //
-// Fit: G = X^T X + lambda I in float64 (k_ease_gram, the accumulation of k_knn_cooc), P = G^-1 by a blocked Cholesky in
+// Fit: G = X^T X + lambda I in float64 (k_ease_gram, on item_lists.h count_row), P = G^-1 by a blocked Cholesky in
 // place on the lower triangle (k_ease_diag factors and inverts one EASE_NB block in LDS, k_ease_gemm is every O(n^3)
 // stage), B = -P / diag(P) in float32 (k_ease_weights).  Scoring: one wave per (query, slice of EASE_W columns) adds the
 // query's rows of B in registers, four waves per block.
@@ -12,6 +12,7 @@
 #include "tfrecomm.h"
 #include "devbuf.h"
 #include "topk.h"
+#include "item_lists.h"
 
 constexpr int64_t EASE_MAX_ITEMS = 32768;                // the dense cap: 8 + 4 bytes per entry = 12 GiB there
 constexpr int EASE_KMAX = tfr::TOPK_KMAX;
@@ -109,24 +110,13 @@ struct EaseScoreArgs {
     int32_t k, slices;
 };
 
-struct tfr_ease {
-    int64_t n_users = 0, n_items = 0;
+struct tfr_ease : tfr::ItemListModel {
     double lambda = 0.0;
-    int device = 0;
-    bool loaded = false, fitted = false;
     int f64_is = 0;                                      // what the f64 buffer holds: 0 nothing, 1 G, 2 P
-    hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     float gram_ms = 0.f;                                 // device time of the tfr_ease_gram that built the matrix in G (0: a caller's)
-    tfr::DevBuf<int64_t> pu, pi;                         // [n_users + 1], [n_items + 1]
-    tfr::DevBuf<int32_t> items, iu;                      // the CSR as loaded and its transpose
     tfr::DevBuf<double> G;                               // [n_items, n_items]: G, then P in place
     tfr::DevBuf<double> work, dinv;                      // [EASE_NB, n_items] row panel; [blocks, EASE_NB, EASE_NB] inverted blocks
     tfr::DevBuf<float> B;                                // [n_items, n_items]
     tfr::DevBuf<int32_t> err;
-    tfr::DevBuf<uint64_t> part, tkeys;
-    // one call's staged inputs and outputs
-    tfr::DevBuf<int32_t> q_users, q_ids, x_ids, t_ids, out_items, ranks;
-    tfr::DevBuf<int64_t> q_ptr, x_ptr, t_ptr;
-    tfr::DevBuf<float> out_scores;
 };

@@ -3,8 +3,8 @@
 //   B[i, j] = (float)(-P[i, j] / P[j, j]) with a zero diagonal, score(u, j) = the float32 add chain from +0 over
 //   i in N(u) ascending of B[i, j].
 //
-// k_ease_gram: k_knn_cooc's accumulation (one block per item and slice of EASE_W_GRAM columns, uint32 LDS counters, 64
-//   users' row bounds searched at once), then the counters go out as float64 into row i of G, n_i + lambda on the diagonal.
+// k_ease_gram: one block per item and slice of EASE_W_GRAM columns counts the item's co-occurrences in uint32 LDS counters
+//   (item_lists.h count_row), then the counters go out as float64 into row i of G, n_i + lambda on the diagonal.
 // The inverse works in place on the lower triangle, EASE_NB columns at a time, in three sweeps over the diagonal blocks:
 //   1. Cholesky G = L L^T: k_ease_diag factors the block in LDS and leaves its inverse W in `dinv`; the panel below is
 //      multiplied by W^T; the trailing lower triangle loses panel * panel^T.
@@ -19,39 +19,24 @@
 // k_ease_weights: one pass over P and its diagonal.
 // k_ease_score<MODE>: one wave per (query, slice of EASE_W columns); the lanes hold EASE_COLS accumulators each, load the
 //   rows of EASE_AHEAD list items at once (coalesced, the addresses depend on the list alone) and add them in list order.
-//   The sums then go to the wave's LDS row and everything after is k_knn_score's tail: exclusions as NaN, keys and queue
-//   (itemknn.h knn_offer / knn_compact), part[query, slice, k] for launch_topk_merge, the two ranking modes.
+//   The sums then go to the wave's LDS row and everything after is item_lists.h score_tail: exclusions as NaN, keys and
+//   queue, part[query, slice, k] for launch_topk_merge, the two ranking modes.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdio.h>
 #include <string.h>
-#include <new>
-#include <vector>
 #include <algorithm>
 #include "tfrecomm.h"
-#include "devbuf.h"
 #include "svd_kernels.h"
-#include "score_tile.h"
-#include "topk.h"
-#include "itemknn.h"
 #include "ease.h"
 
 namespace {
 
-using tfr::topk_key;
 using tfr::wave_lds_sync;
+using tfr::fail;
+using tfr::check_k;
+using tfr::window;
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-// first position in the increasing x[lo, hi) whose value is not below v
-__device__ __forceinline__ int64_t ease_lower_bound(const int32_t* x, int64_t lo, int64_t hi, int64_t v) {
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if ((int64_t)x[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(256) void k_ease_gram(EaseGramArgs a) {
     __shared__ uint32_t counts[EASE_W_GRAM];
@@ -65,21 +50,7 @@ __global__ __launch_bounds__(256) void k_ease_gram(EaseGramArgs a) {
         for (int t = tid; t < width; t += 256) counts[t] = 0;
         __syncthreads();
 
-        for (int64_t b = p0 + wave * 64; b < p1; b += 64 * EASE_WAVES) {
-            unsigned long long st = 0, en = 0;
-            if (b + lane < p1) {
-                const int32_t u = a.iu[b + lane];
-                const int64_t ulo = a.pu[u], uhi = a.pu[u + 1];
-                const int64_t s0 = ease_lower_bound(a.items, ulo, uhi, lo);
-                st = (unsigned long long)s0;
-                en = (unsigned long long)ease_lower_bound(a.items, s0, uhi, lo + width);
-            }
-            const int nb = (int)(p1 - b < 64 ? p1 - b : 64);
-            for (int z = 0; z < nb; ++z) {
-                const int64_t zs = (int64_t)__shfl(st, z), ze = (int64_t)__shfl(en, z);
-                for (int64_t t = zs + lane; t < ze; t += 64) atomicAdd(&counts[(int64_t)a.items[t] - lo], 1u);
-            }
-        }
+        tfr::count_row<EASE_WAVES>(a, counts, p0, p1, lo, width, lane, wave);
         __syncthreads();
 
         double* row = a.G + i * a.n_items + lo;
@@ -289,114 +260,10 @@ __global__ __launch_bounds__(256) void k_ease_score(EaseScoreArgs a) {
     for (int c = 0; c < EASE_COLS; ++c)
         if (lane + 64 * c < width) A[lane + 64 * c] = s[c];
     wave_lds_sync();
-    if (a.xptr) {
-        const int64_t x0 = a.xptr[qi], x1 = a.xptr[qi + 1];
-        for (int64_t t = x0 + lane; t < x1; t += 64) {
-            const int64_t col = (int64_t)a.xids[t] - lo;
-            if (col >= 0 && col < width) A[col] = __builtin_nanf("");
-        }
-        wave_lds_sync();
-    }
-
-    if (MODE == 0) {
-        uint64_t* q = queue[wave];
-        int qn = 0;
-        uint64_t thr = 0;
-        for (int base = 0; base < width; base += 64) {
-            const int j = base + lane;
-            const float v = j < width ? A[j] : __builtin_nanf("");
-            const bool ok = !__builtin_isnan(v);
-            knn_offer<EASE_SCORE_CAP>(q, qn, thr, a.k, lane, ok, ok ? topk_key(v, lo + j) : 0);
-        }
-        if (qn > 0) knn_compact<EASE_SCORE_CAP>(q, qn, thr, a.k, lane);
-        uint64_t* dst = a.part + (size_t)w * a.k;        // w = (query of the chunk) * slices + slice
-        for (int t = lane; t < a.k; t += 64) dst[t] = t < qn ? q[t] : 0;
-    } else if (MODE == 1) {
-        const int64_t t0 = a.tptr[qi], t1 = a.tptr[qi + 1];
-        for (int64_t t = t0 + lane; t < t1; t += 64) {
-            const int64_t col = (int64_t)a.tids[t] - lo;
-            if (col >= 0 && col < width) {
-                const float v = A[col];
-                const bool ranked = !__builtin_isnan(v);
-                a.tkeys[t] = ranked ? topk_key(v, lo + col) : 0;
-                a.ranks[t] = ranked ? 0 : -1;
-            }
-        }
-    } else {
-        const int64_t t0 = a.tptr[qi], t1 = a.tptr[qi + 1];
-        for (int64_t tb = t0; tb < t1; tb += 64) {
-            const uint64_t tk = tb + lane < t1 ? a.tkeys[tb + lane] : 0;
-            if (__ballot(tk != 0) == 0) continue;
-            int32_t above = 0;
-            for (int j = 0; j < width; ++j) {
-                const float v = A[j];                    // one address for the wave: a broadcast read
-                if (!__builtin_isnan(v)) above += topk_key(v, lo + j) > tk ? 1 : 0;
-            }
-            if (tk != 0 && above > 0) atomicAdd(&a.ranks[tb + lane], above);
-        }
-    }
+    tfr::score_tail<MODE, EASE_SCORE_CAP>(a, A, queue[wave], qi, w, lo, width, lane);
 }
 
-thread_local char g_ease_err[512] = "";
-int ease_fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_ease_err, sizeof(g_ease_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-#define EASECHK(expr)                                                                                  \
-    do {                                                                                               \
-        hipError_t e_ = (expr);                                                                        \
-        if (e_ != hipSuccess) return ease_fail(e_ == hipErrorOutOfMemory ? TFR_ERR_NOMEM : TFR_ERR_HIP, \
-                                               "%s: %s", #expr, hipGetErrorString(e_));                \
-    } while (0)
-
-// a CSR of n rows over ids in [0, bound): the rules and codes of itemknn.hip's knn_check_csr
-int ease_check_csr(const char* who, const char* what, bool from0, bool strict, const int64_t* indptr, const int32_t* ids, int64_t n,
-                   int64_t bound) {
-    if (!indptr) return ease_fail(TFR_ERR_ARG, "%s: null %s indptr", who, what);
-    if (from0 ? indptr[0] != 0 : indptr[0] < 0) return ease_fail(TFR_ERR_ARG, "%s: %s indptr must start at 0", who, what);
-    for (int64_t r = 0; r < n; ++r)
-        if (indptr[r + 1] < indptr[r]) return ease_fail(TFR_ERR_ARG, "%s: %s indptr decreases at row %lld", who, what, (long long)r);
-    if (indptr[n] > indptr[0] && !ids) return ease_fail(TFR_ERR_ARG, "%s: %s indptr without ids", who, what);
-    for (int64_t r = 0; r < n; ++r)
-        for (int64_t e = indptr[r]; e < indptr[r + 1]; ++e) {
-            if (ids[e] < 0 || ids[e] >= bound)
-                return ease_fail(TFR_ERR_OOB, "%s: %s row %lld: id %d out of range", who, what, (long long)r, ids[e]);
-            if (e > indptr[r] && (strict ? ids[e] <= ids[e - 1] : ids[e] < ids[e - 1]))
-                return ease_fail(TFR_ERR_ARG, "%s: %s row %lld is not %s", who, what, (long long)r,
-                                 strict ? "strictly increasing" : "non-decreasing");
-        }
-    return TFR_OK;
-}
-
-int ease_check_users(const char* who, const tfr_ease* m, const int32_t* users, int64_t n) {
-    if (!users) return ease_fail(TFR_ERR_ARG, "%s: null users", who);
-    for (int64_t q = 0; q < n; ++q)
-        if (users[q] < 0 || users[q] >= m->n_users) return ease_fail(TFR_ERR_OOB, "%s: user id %d out of range", who, users[q]);
-    return TFR_OK;
-}
-
-int ease_check_k(const char* who, int32_t k) {
-    return k < 1 || k > EASE_KMAX ? ease_fail(TFR_ERR_ARG, "%s: k must be in [1, %d] (got %d)", who, EASE_KMAX, k) : TFR_OK;
-}
-
-// a host CSR onto the device: indptr as it stands, the ids [0, indptr[n])
-int ease_stage_csr(tfr_ease* m, tfr::DevBuf<int64_t>& dp, tfr::DevBuf<int32_t>& di, const int64_t* indptr, const int32_t* ids, int64_t n) {
-    EASECHK(dp.reserve(n + 1, m->stream));
-    EASECHK(di.reserve(std::max<int64_t>(1, indptr[n]), m->stream));
-    EASECHK(hipMemcpyAsync(dp, indptr, (size_t)(n + 1) * 8, hipMemcpyHostToDevice, m->stream));
-    if (indptr[n] > 0) EASECHK(hipMemcpyAsync(di, ids, (size_t)indptr[n] * 4, hipMemcpyHostToDevice, m->stream));
-    return TFR_OK;
-}
-
-int ease_window(const tfr_ease* m, const char* who, int64_t row_lo, int64_t n_rows) {
-    if (row_lo < 0 || n_rows < 0 || row_lo > m->n_items || n_rows > m->n_items - row_lo)
-        return ease_fail(TFR_ERR_ARG, "%s: rows [%lld, %lld + %lld) are not inside the %lld items", who, (long long)row_lo,
-                         (long long)row_lo, (long long)n_rows, (long long)m->n_items);
-    return TFR_OK;
-}
+thread_local tfr::ErrText g_ease_err;
 
 void launch_gemm(hipStream_t s, const double* A, int64_t lda, int ta, const double* B, int64_t ldb, int tb, double* C, int64_t ldc,
                  int M, int N, int K, int sign, int beta, int lower, int kskip) {
@@ -456,62 +323,35 @@ void ease_invert_factor(tfr_ease* m) {
     hipLaunchKernelGGL(k_ease_mirror, dim3(t, t), dim3(256), 0, s, G, (int64_t)n);
 }
 
-template <int MODE>
-void launch_ease_score(const EaseScoreArgs& a, hipStream_t s) {
-    const dim3 g((unsigned)((a.n * a.slices + EASE_WAVES - 1) / EASE_WAVES));
-    hipLaunchKernelGGL(k_ease_score<MODE>, g, dim3(256), 0, s, a);
-}
+// what the serving drivers of item_lists.h ask of a family
+struct EaseServe {
+    using Model = tfr_ease;
+    using Args = EaseScoreArgs;
+    using Plan = EasePlan;
+    static constexpr auto plan = ease_plan;
+    static constexpr const char* load_fn = "tfr_ease_load";
+    static constexpr const char* not_fitted = "no weights: call tfr_ease_solve or tfr_ease_set_weights first";
 
-// the query side of an argument block: the resident rows named by staged users, or staged lists
-struct EaseQuery { const int32_t* users; const int64_t* ptr; const int32_t* ids; };
-
-EaseScoreArgs ease_score_args(const tfr_ease* m, const EaseQuery& q) {
-    EaseScoreArgs a = {};
-    a.users = q.users; a.ptr = q.ptr; a.ids = q.ids;
-    a.B = m->B;
-    a.n_items = m->n_items;
-    return a;
-}
-
-// top-K of n queries whose lists are on the device; the exclusion CSR is the host's, already checked
-int ease_topk_run(tfr_ease* m, const char* who, const EaseQuery& q, int64_t n, int32_t k, const int64_t* xip, const int32_t* xit,
-                  int32_t* items_out, float* scores_out) {
-    EasePlan p;
-    if (!ease_plan(1, m->n_items, k, n, &p)) return ease_fail(TFR_ERR_ARG, "%s: no plan for k %d over %lld items", who, k, (long long)m->n_items);
-    hipStream_t s = m->stream;
-    if (xip) if (int rc = ease_stage_csr(m, m->x_ptr, m->x_ids, xip, xit, n)) return rc;
-    EASECHK(m->out_items.reserve(n * k, s));
-    if (scores_out) EASECHK(m->out_scores.reserve(n * k, s));
-    EASECHK(m->part.reserve(p.chunk * p.slices * k, s));
-    EaseScoreArgs a = ease_score_args(m, q);
-    if (xip) { a.xptr = m->x_ptr; a.xids = m->x_ids; }
-    a.part = m->part; a.k = k; a.slices = p.slices;
-    for (int64_t c0 = 0; c0 < n; c0 += p.chunk) {
-        a.q_lo = c0;
-        a.n = n - c0 < p.chunk ? n - c0 : p.chunk;
-        launch_ease_score<0>(a, s);
-        EASECHK(hipGetLastError());
-        tfr::TopkMergeArgs g;
-        memset(&g, 0, sizeof(g));
-        g.part = m->part; g.items_out = m->out_items.get() + c0 * k;
-        g.scores_out = scores_out ? m->out_scores.get() + c0 * k : nullptr;
-        g.n_rows = a.n; g.k = k; g.slices = p.slices;
-        tfr::launch_topk_merge(g, s);
-        EASECHK(hipGetLastError());
+    static Args args(const Model* m) {
+        Args a = {};
+        a.B = m->B;
+        return a;
     }
-    EASECHK(hipMemcpyAsync(items_out, m->out_items, (size_t)n * k * 4, hipMemcpyDeviceToHost, s));
-    if (scores_out) EASECHK(hipMemcpyAsync(scores_out, m->out_scores, (size_t)n * k * 4, hipMemcpyDeviceToHost, s));
-    EASECHK(hipStreamSynchronize(s));
-    return TFR_OK;
-}
+
+    template <int MODE>
+    static void launch(const Args& a, hipStream_t s) {
+        const dim3 g((unsigned)((a.n * a.slices + EASE_WAVES - 1) / EASE_WAVES));
+        hipLaunchKernelGGL(k_ease_score<MODE>, g, dim3(256), 0, s, a);
+    }
+};
 
 // the f64 buffer and what the factorisation needs beside it
 int ease_reserve_f64(tfr_ease* m) {
     EasePlan p;
-    if (!ease_plan(0, m->n_items, 1, 0, &p)) return ease_fail(TFR_ERR_ARG, "no plan for %lld items", (long long)m->n_items);
-    EASECHK(m->G.reserve(m->n_items * m->n_items, m->stream));
-    EASECHK(m->work.reserve((int64_t)EASE_NB * m->n_items, m->stream));
-    EASECHK(m->dinv.reserve((int64_t)p.blocks * EASE_NB * EASE_NB, m->stream));
+    if (!ease_plan(0, m->n_items, 1, 0, &p)) return fail(g_ease_err, TFR_ERR_ARG, "no plan for %lld items", (long long)m->n_items);
+    LISTCHK(g_ease_err, m->G.reserve(m->n_items * m->n_items, m->stream));
+    LISTCHK(g_ease_err, m->work.reserve((int64_t)EASE_NB * m->n_items, m->stream));
+    LISTCHK(g_ease_err, m->dinv.reserve((int64_t)p.blocks * EASE_NB * EASE_NB, m->stream));
     return TFR_OK;
 }
 
@@ -519,17 +359,17 @@ int ease_reserve_f64(tfr_ease* m) {
 
 extern "C" {
 
-const char* tfr_ease_last_error(void) { return g_ease_err; }
+const char* tfr_ease_last_error(void) { return g_ease_err.text; }
 
 int tfr_ease_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t which, int32_t* block, int32_t* tile, int64_t* lds_bytes,
                   int64_t* f64_bytes, int64_t* f32_bytes, int32_t* slice_width, int32_t* slices, int64_t* row_chunk,
                   int32_t* look_ahead) {
-    if (which < 0 || which > 1) return ease_fail(TFR_ERR_ARG, "ease plan: which must be 0 (fit) or 1 (scoring)");
+    if (which < 0 || which > 1) return fail(g_ease_err, TFR_ERR_ARG, "ease plan: which must be 0 (fit) or 1 (scoring)");
     if (n_items < 1 || n_items > EASE_MAX_ITEMS || n_rows < 0)
-        return ease_fail(TFR_ERR_ARG, "ease plan: n_rows >= 0 and 1 <= n_items <= %lld", (long long)EASE_MAX_ITEMS);
-    if (int rc = ease_check_k("ease plan", k)) return rc;
+        return fail(g_ease_err, TFR_ERR_ARG, "ease plan: n_rows >= 0 and 1 <= n_items <= %lld", (long long)EASE_MAX_ITEMS);
+    if (int rc = check_k(g_ease_err, "ease plan", k)) return rc;
     EasePlan p;
-    if (!ease_plan(which, n_items, k, n_rows, &p)) return ease_fail(TFR_ERR_ARG, "ease plan: no plan for k %d over %lld items", k, (long long)n_items);
+    if (!ease_plan(which, n_items, k, n_rows, &p)) return fail(g_ease_err, TFR_ERR_ARG, "ease plan: no plan for k %d over %lld items", k, (long long)n_items);
     if (block) *block = p.nb;
     if (tile) *tile = p.tile;
     if (lds_bytes) *lds_bytes = (int64_t)(which ? std::max(p.lds, tfr::topk_merge_lds(p.slices, k)) : std::max(p.lds, ease_gemm_lds()));
@@ -542,90 +382,44 @@ int tfr_ease_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t which, int
     return TFR_OK;
 }
 
-int tfr_ease_destroy(tfr_ease* m) {
-    if (!m) return TFR_OK;
-    (void)hipSetDevice(m->device);                       // the buffers are freed with the model's device current
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    if (m->ev0) (void)hipEventDestroy(m->ev0);
-    if (m->ev1) (void)hipEventDestroy(m->ev1);
-    if (m->ev2) (void)hipEventDestroy(m->ev2);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
-    delete m;
-    return TFR_OK;
-}
+int tfr_ease_destroy(tfr_ease* m) { return m ? tfr::destroy_handle(m, {m->ev0, m->ev1, m->ev2}) : TFR_OK; }
 
 int tfr_ease_create(tfr_ease** out, int64_t n_users, int64_t n_items, double lambda, int32_t device) {
-    if (!out) return ease_fail(TFR_ERR_ARG, "out is null");
+    if (!out) return fail(g_ease_err, TFR_ERR_ARG, "out is null");
     *out = nullptr;
-    if (n_users < 1 || n_items < 1 || n_users > 0x7fffffffLL) return ease_fail(TFR_ERR_ARG, "need positive int32 user and item counts");
+    // an item count past the dense cap is refused with the cap's own message
+    if (int rc = tfr::check_counts(g_ease_err, n_users, std::min(n_items, EASE_MAX_ITEMS))) return rc;
     if (n_items > EASE_MAX_ITEMS)
-        return ease_fail(TFR_ERR_ARG, "%lld items are past the dense cap of %lld (12 bytes per entry of the item x item matrices)",
-                         (long long)n_items, (long long)EASE_MAX_ITEMS);
-    if (!(lambda > 0.0) || !std::isfinite(lambda)) return ease_fail(TFR_ERR_ARG, "lambda must be positive and finite");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-        return ease_fail(TFR_ERR_HIP, "no HIP device available - this library has no CPU path");
-    if (device < 0 || device >= ndev) return ease_fail(TFR_ERR_ARG, "device %d not in [0,%d)", device, ndev);
-    EASECHK(hipSetDevice(device));
-    tfr_ease* m = new (std::nothrow) tfr_ease();
-    if (!m) return ease_fail(TFR_ERR_NOMEM, "host allocation failed");
-    m->n_users = n_users; m->n_items = n_items; m->lambda = lambda; m->device = device;
-    hipError_t e = hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = m->err.reserve(1, m->stream);
+        return fail(g_ease_err, TFR_ERR_ARG, "%lld items are past the dense cap of %lld (12 bytes per entry of the item x item matrices)",
+                    (long long)n_items, (long long)EASE_MAX_ITEMS);
+    if (!(lambda > 0.0) || !std::isfinite(lambda)) return fail(g_ease_err, TFR_ERR_ARG, "lambda must be positive and finite");
+    tfr_ease* m = nullptr;
+    if (int rc = tfr::create_handle(g_ease_err, "ease_create", &m, n_users, n_items, device)) return rc;
+    m->lambda = lambda;
+    hipError_t e = m->err.reserve(1, m->stream);
     if (e == hipSuccess) e = hipEventCreate(&m->ev0);
     if (e == hipSuccess) e = hipEventCreate(&m->ev1);
     if (e == hipSuccess) e = hipEventCreate(&m->ev2);
     if (e != hipSuccess) {
         const int code = e == hipErrorOutOfMemory ? TFR_ERR_NOMEM : TFR_ERR_HIP;
         tfr_ease_destroy(m);
-        return ease_fail(code, "ease_create: %s", hipGetErrorString(e));
+        return fail(g_ease_err, code, "ease_create: %s", hipGetErrorString(e));
     }
     *out = m;
     return TFR_OK;
 }
 
-// The user CSR.  Everything is checked and the transpose built on the host before any device work, so a refused load
-// leaves the model as it was.  A load forgets the Gram matrix and the weights.
+// A load forgets the Gram matrix and the weights (item_lists.h load_lists: `fitted`, and what the f64 buffer holds).
 int tfr_ease_load(tfr_ease* m, const int64_t* indptr, const int32_t* items) {
-    if (!m) return ease_fail(TFR_ERR_ARG, "null model");
-    const int64_t nu = m->n_users, ni = m->n_items;
-    if (int rc = ease_check_csr("load", "user", true, true, indptr, items, nu, ni)) return rc;
-    const int64_t nnz = indptr[nu];
-    std::vector<int64_t> pi((size_t)ni + 1, 0);
-    for (int64_t e = 0; e < nnz; ++e) pi[(size_t)items[e] + 1]++;
-    for (int64_t i = 0; i < ni; ++i) pi[(size_t)i + 1] += pi[(size_t)i];
-    std::vector<int64_t> cur(pi.begin(), pi.end() - 1);
-    std::vector<int32_t> iu((size_t)nnz);
-    for (int64_t u = 0; u < nu; ++u)
-        for (int64_t e = indptr[u]; e < indptr[u + 1]; ++e) iu[(size_t)cur[(size_t)items[e]]++] = (int32_t)u;
-
-    EASECHK(hipSetDevice(m->device));
-    EASECHK(hipStreamSynchronize(m->stream));
-    m->loaded = false;
-    m->fitted = false;
-    m->f64_is = 0;
-    m->gram_ms = 0.f;
-    const int64_t cap = std::max<int64_t>(1, nnz);
-    EASECHK(m->pu.reserve(nu + 1, m->stream));
-    EASECHK(m->pi.reserve(ni + 1, m->stream));
-    EASECHK(m->items.reserve(cap, m->stream));
-    EASECHK(m->iu.reserve(cap, m->stream));
-    EASECHK(hipMemcpy(m->pu, indptr, (size_t)(nu + 1) * 8, hipMemcpyHostToDevice));
-    EASECHK(hipMemcpy(m->pi, pi.data(), pi.size() * 8, hipMemcpyHostToDevice));
-    if (nnz) {
-        EASECHK(hipMemcpy(m->items, items, (size_t)nnz * 4, hipMemcpyHostToDevice));
-        EASECHK(hipMemcpy(m->iu, iu.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
-    }
-    m->loaded = true;
-    return TFR_OK;
+    return tfr::load_lists(g_ease_err, m, indptr, items, [m] { m->f64_is = 0; m->gram_ms = 0.f; });
 }
 
 int tfr_ease_gram(tfr_ease* m) {
-    if (!m) return ease_fail(TFR_ERR_ARG, "null model");
-    if (!m->loaded) return ease_fail(TFR_ERR_STATE, "no data: call tfr_ease_load first");
+    if (!m) return fail(g_ease_err, TFR_ERR_ARG, "null model");
+    if (!m->loaded) return fail(g_ease_err, TFR_ERR_STATE, "no data: call tfr_ease_load first");
     EasePlan p;
-    if (!ease_plan(0, m->n_items, 1, 0, &p)) return ease_fail(TFR_ERR_ARG, "gram: no plan");
-    EASECHK(hipSetDevice(m->device));
+    if (!ease_plan(0, m->n_items, 1, 0, &p)) return fail(g_ease_err, TFR_ERR_ARG, "gram: no plan");
+    LISTCHK(g_ease_err, hipSetDevice(m->device));
     m->f64_is = 0;
     if (int rc = ease_reserve_f64(m)) return rc;
     hipStream_t s = m->stream;
@@ -634,63 +428,63 @@ int tfr_ease_gram(tfr_ease* m) {
     a.pu = m->pu; a.items = m->items; a.pi = m->pi; a.iu = m->iu; a.G = m->G; a.n_items = m->n_items; a.lambda = m->lambda;
     const dim3 g((unsigned)std::min<int64_t>(m->n_items, EASE_GRID_ROWS), (unsigned)p.slices);
     hipLaunchKernelGGL(k_ease_gram, g, dim3(256), 0, s, a);
-    EASECHK(hipGetLastError());
+    LISTCHK(g_ease_err, hipGetLastError());
     (void)hipEventRecord(m->ev1, s);
-    EASECHK(hipStreamSynchronize(s));
+    LISTCHK(g_ease_err, hipStreamSynchronize(s));
     if (hipEventElapsedTime(&m->gram_ms, m->ev0, m->ev1) != hipSuccess) m->gram_ms = 0.f;
     m->f64_is = 1;
     return TFR_OK;
 }
 
 int tfr_ease_set_gram(tfr_ease* m, const double* G) {
-    if (!m) return ease_fail(TFR_ERR_ARG, "null model");
-    if (!G) return ease_fail(TFR_ERR_ARG, "set_gram: null matrix");
+    if (!m) return fail(g_ease_err, TFR_ERR_ARG, "null model");
+    if (!G) return fail(g_ease_err, TFR_ERR_ARG, "set_gram: null matrix");
     const int64_t n = m->n_items;
     for (int64_t i = 0; i < n; ++i) {
         for (int64_t j = 0; j < n; ++j)
-            if (!std::isfinite(G[i * n + j])) return ease_fail(TFR_ERR_ARG, "set_gram: entry (%lld, %lld) is not finite", (long long)i, (long long)j);
-        if (!(G[i * n + i] > 0.0)) return ease_fail(TFR_ERR_ARG, "set_gram: diagonal entry %lld is not positive", (long long)i);
+            if (!std::isfinite(G[i * n + j])) return fail(g_ease_err, TFR_ERR_ARG, "set_gram: entry (%lld, %lld) is not finite", (long long)i, (long long)j);
+        if (!(G[i * n + i] > 0.0)) return fail(g_ease_err, TFR_ERR_ARG, "set_gram: diagonal entry %lld is not positive", (long long)i);
         for (int64_t j = 0; j < i; ++j)
             if (memcmp(&G[i * n + j], &G[j * n + i], 8) != 0)
-                return ease_fail(TFR_ERR_ARG, "set_gram: entries (%lld, %lld) and (%lld, %lld) differ", (long long)i, (long long)j,
+                return fail(g_ease_err, TFR_ERR_ARG, "set_gram: entries (%lld, %lld) and (%lld, %lld) differ", (long long)i, (long long)j,
                                  (long long)j, (long long)i);
     }
-    EASECHK(hipSetDevice(m->device));
+    LISTCHK(g_ease_err, hipSetDevice(m->device));
     m->f64_is = 0;
     if (int rc = ease_reserve_f64(m)) return rc;
-    EASECHK(hipMemcpyAsync(m->G, G, (size_t)n * n * 8, hipMemcpyHostToDevice, m->stream));
-    EASECHK(hipStreamSynchronize(m->stream));
+    LISTCHK(g_ease_err, hipMemcpyAsync(m->G, G, (size_t)n * n * 8, hipMemcpyHostToDevice, m->stream));
+    LISTCHK(g_ease_err, hipStreamSynchronize(m->stream));
     m->gram_ms = 0.f;
     m->f64_is = 1;
     return TFR_OK;
 }
 
 int tfr_ease_solve(tfr_ease* m, int32_t keep_inverse, float* elapsed_ms) {
-    if (!m) return ease_fail(TFR_ERR_ARG, "null model");
-    if (m->f64_is != 1) return ease_fail(TFR_ERR_STATE, "no Gram matrix: call tfr_ease_gram or tfr_ease_set_gram first");
+    if (!m) return fail(g_ease_err, TFR_ERR_ARG, "null model");
+    if (m->f64_is != 1) return fail(g_ease_err, TFR_ERR_STATE, "no Gram matrix: call tfr_ease_gram or tfr_ease_set_gram first");
     const int64_t n = m->n_items;
-    EASECHK(hipSetDevice(m->device));
+    LISTCHK(g_ease_err, hipSetDevice(m->device));
     hipStream_t s = m->stream;
     m->fitted = false;
     m->f64_is = 0;                                       // the factorisation overwrites G
-    EASECHK(m->B.reserve(n * n, s));
-    EASECHK(hipMemsetAsync(m->err, 0, 4, s));
+    LISTCHK(g_ease_err, m->B.reserve(n * n, s));
+    LISTCHK(g_ease_err, hipMemsetAsync(m->err, 0, 4, s));
     (void)hipEventRecord(m->ev0, s);
     ease_factor(m);
-    EASECHK(hipGetLastError());
+    LISTCHK(g_ease_err, hipGetLastError());
     int32_t bad = 0;
-    EASECHK(hipMemcpyAsync(&bad, m->err, 4, hipMemcpyDeviceToHost, s));
-    EASECHK(hipStreamSynchronize(s));
+    LISTCHK(g_ease_err, hipMemcpyAsync(&bad, m->err, 4, hipMemcpyDeviceToHost, s));
+    LISTCHK(g_ease_err, hipStreamSynchronize(s));
     if (bad != 0)
-        return ease_fail(TFR_ERR_ARG, "solve: the matrix is not positive definite: the pivot of column %d is not positive and finite", bad - 1);
+        return fail(g_ease_err, TFR_ERR_ARG, "solve: the matrix is not positive definite: the pivot of column %d is not positive and finite", bad - 1);
     ease_invert_factor(m);
-    EASECHK(hipGetLastError());
+    LISTCHK(g_ease_err, hipGetLastError());
     (void)hipEventRecord(m->ev1, s);
     const int64_t blocks = (n * n + 255) / 256;
     hipLaunchKernelGGL(k_ease_weights, dim3((unsigned)std::min<int64_t>(blocks, 16384)), dim3(256), 0, s, m->G.get(), m->B.get(), n);
-    EASECHK(hipGetLastError());
+    LISTCHK(g_ease_err, hipGetLastError());
     (void)hipEventRecord(m->ev2, s);
-    EASECHK(hipStreamSynchronize(s));
+    LISTCHK(g_ease_err, hipStreamSynchronize(s));
     if (elapsed_ms) {
         elapsed_ms[0] = m->gram_ms;
         if (hipEventElapsedTime(&elapsed_ms[1], m->ev0, m->ev1) != hipSuccess) elapsed_ms[1] = 0.f;
@@ -708,116 +502,62 @@ int tfr_ease_solve(tfr_ease* m, int32_t keep_inverse, float* elapsed_ms) {
 }
 
 int tfr_ease_get_f64(tfr_ease* m, int64_t row_lo, int64_t n_rows, double* out) {
-    if (!m) return ease_fail(TFR_ERR_ARG, "null model");
-    if (m->f64_is == 0) return ease_fail(TFR_ERR_STATE, "no float64 matrix: it holds G after gram / set_gram and P after a solve that kept it");
-    if (int rc = ease_window(m, "get_f64", row_lo, n_rows)) return rc;
+    if (!m) return fail(g_ease_err, TFR_ERR_ARG, "null model");
+    if (m->f64_is == 0) return fail(g_ease_err, TFR_ERR_STATE, "no float64 matrix: it holds G after gram / set_gram and P after a solve that kept it");
+    if (int rc = window(g_ease_err, m, "get_f64", row_lo, n_rows)) return rc;
     if (n_rows == 0) return TFR_OK;
-    if (!out) return ease_fail(TFR_ERR_ARG, "get_f64: null out");
-    EASECHK(hipSetDevice(m->device));
-    EASECHK(hipMemcpyAsync(out, m->G.get() + row_lo * m->n_items, (size_t)n_rows * m->n_items * 8, hipMemcpyDeviceToHost, m->stream));
-    EASECHK(hipStreamSynchronize(m->stream));
+    if (!out) return fail(g_ease_err, TFR_ERR_ARG, "get_f64: null out");
+    LISTCHK(g_ease_err, hipSetDevice(m->device));
+    LISTCHK(g_ease_err, hipMemcpyAsync(out, m->G.get() + row_lo * m->n_items, (size_t)n_rows * m->n_items * 8, hipMemcpyDeviceToHost, m->stream));
+    LISTCHK(g_ease_err, hipStreamSynchronize(m->stream));
     return TFR_OK;
 }
 
 int tfr_ease_get_weights(tfr_ease* m, int64_t row_lo, int64_t n_rows, float* out) {
-    if (!m) return ease_fail(TFR_ERR_ARG, "null model");
-    if (!m->fitted) return ease_fail(TFR_ERR_STATE, "no weights: call tfr_ease_solve or tfr_ease_set_weights first");
-    if (int rc = ease_window(m, "get_weights", row_lo, n_rows)) return rc;
+    if (!m) return fail(g_ease_err, TFR_ERR_ARG, "null model");
+    if (!m->fitted) return fail(g_ease_err, TFR_ERR_STATE, "no weights: call tfr_ease_solve or tfr_ease_set_weights first");
+    if (int rc = window(g_ease_err, m, "get_weights", row_lo, n_rows)) return rc;
     if (n_rows == 0) return TFR_OK;
-    if (!out) return ease_fail(TFR_ERR_ARG, "get_weights: null out");
-    EASECHK(hipSetDevice(m->device));
-    EASECHK(hipMemcpyAsync(out, m->B.get() + row_lo * m->n_items, (size_t)n_rows * m->n_items * 4, hipMemcpyDeviceToHost, m->stream));
-    EASECHK(hipStreamSynchronize(m->stream));
+    if (!out) return fail(g_ease_err, TFR_ERR_ARG, "get_weights: null out");
+    LISTCHK(g_ease_err, hipSetDevice(m->device));
+    LISTCHK(g_ease_err, hipMemcpyAsync(out, m->B.get() + row_lo * m->n_items, (size_t)n_rows * m->n_items * 4, hipMemcpyDeviceToHost, m->stream));
+    LISTCHK(g_ease_err, hipStreamSynchronize(m->stream));
     return TFR_OK;
 }
 
 // Rows [row_lo, row_lo + n_rows) of B from a host array.  Checked before any device work.  A handle without weights takes
 // all rows at once, which makes it fitted; a fitted one takes any window.
 int tfr_ease_set_weights(tfr_ease* m, int64_t row_lo, int64_t n_rows, const float* in) {
-    if (!m) return ease_fail(TFR_ERR_ARG, "null model");
-    if (int rc = ease_window(m, "set_weights", row_lo, n_rows)) return rc;
-    if (n_rows > 0 && !in) return ease_fail(TFR_ERR_ARG, "set_weights: null weights");
+    if (!m) return fail(g_ease_err, TFR_ERR_ARG, "null model");
+    if (int rc = window(g_ease_err, m, "set_weights", row_lo, n_rows)) return rc;
+    if (n_rows > 0 && !in) return fail(g_ease_err, TFR_ERR_ARG, "set_weights: null weights");
     const int64_t n = m->n_items;
     for (int64_t e = 0; e < n_rows * n; ++e)
         if (!std::isfinite(in[e]))
-            return ease_fail(TFR_ERR_ARG, "set_weights: the weight (%lld, %lld) is not finite", (long long)(row_lo + e / n), (long long)(e % n));
-    if (!m->fitted && n_rows != n) return ease_fail(TFR_ERR_STATE, "set_weights: a model without weights takes all %lld rows at once", (long long)n);
+            return fail(g_ease_err, TFR_ERR_ARG, "set_weights: the weight (%lld, %lld) is not finite", (long long)(row_lo + e / n), (long long)(e % n));
+    if (!m->fitted && n_rows != n) return fail(g_ease_err, TFR_ERR_STATE, "set_weights: a model without weights takes all %lld rows at once", (long long)n);
     if (n_rows == 0) return TFR_OK;
-    EASECHK(hipSetDevice(m->device));
-    EASECHK(m->B.reserve(n * n, m->stream));
-    EASECHK(hipMemcpyAsync(m->B.get() + row_lo * n, in, (size_t)n_rows * n * 4, hipMemcpyHostToDevice, m->stream));
-    EASECHK(hipStreamSynchronize(m->stream));
+    LISTCHK(g_ease_err, hipSetDevice(m->device));
+    LISTCHK(g_ease_err, m->B.reserve(n * n, m->stream));
+    LISTCHK(g_ease_err, hipMemcpyAsync(m->B.get() + row_lo * n, in, (size_t)n_rows * n * 4, hipMemcpyHostToDevice, m->stream));
+    LISTCHK(g_ease_err, hipStreamSynchronize(m->stream));
     m->fitted = true;
     return TFR_OK;
 }
 
 int tfr_ease_topk(tfr_ease* m, const int32_t* users, int64_t n, int32_t k, const int64_t* excl_indptr, const int32_t* excl_items,
                   int32_t* items_out, float* scores_out) {
-    if (!m) return ease_fail(TFR_ERR_ARG, "null model");
-    if (n < 0) return ease_fail(TFR_ERR_ARG, "top-K: negative n");
-    if (int rc = ease_check_k("top-K", k)) return rc;
-    if (!m->loaded) return ease_fail(TFR_ERR_STATE, "top-K: no data: call tfr_ease_load first");
-    if (!m->fitted) return ease_fail(TFR_ERR_STATE, "top-K: no weights: call tfr_ease_solve or tfr_ease_set_weights first");
-    if (n == 0) return TFR_OK;
-    if (!items_out) return ease_fail(TFR_ERR_ARG, "top-K: null items_out");
-    if (int rc = ease_check_users("top-K", m, users, n)) return rc;
-    if (excl_indptr) if (int rc = ease_check_csr("top-K", "exclusion", false, false, excl_indptr, excl_items, n, m->n_items)) return rc;
-    EASECHK(hipSetDevice(m->device));
-    EASECHK(m->q_users.reserve(n, m->stream));
-    EASECHK(hipMemcpyAsync(m->q_users, users, (size_t)n * 4, hipMemcpyHostToDevice, m->stream));
-    return ease_topk_run(m, "top-K", EaseQuery{m->q_users, m->pu, m->items}, n, k, excl_indptr, excl_items, items_out, scores_out);
+    return tfr::topk_users<EaseServe>(g_ease_err, m, users, n, k, excl_indptr, excl_items, items_out, scores_out);
 }
 
 int tfr_ease_topk_lists(tfr_ease* m, const int64_t* list_indptr, const int32_t* list_items, int64_t n, int32_t k,
                         const int64_t* excl_indptr, const int32_t* excl_items, int32_t* items_out, float* scores_out) {
-    if (!m) return ease_fail(TFR_ERR_ARG, "null model");
-    if (n < 0) return ease_fail(TFR_ERR_ARG, "top-K of lists: negative n");
-    if (int rc = ease_check_k("top-K of lists", k)) return rc;
-    if (!m->fitted) return ease_fail(TFR_ERR_STATE, "top-K of lists: no weights: call tfr_ease_solve or tfr_ease_set_weights first");
-    if (n == 0) return TFR_OK;
-    if (!items_out) return ease_fail(TFR_ERR_ARG, "top-K of lists: null items_out");
-    if (int rc = ease_check_csr("top-K of lists", "list", true, true, list_indptr, list_items, n, m->n_items)) return rc;
-    if (excl_indptr)
-        if (int rc = ease_check_csr("top-K of lists", "exclusion", false, false, excl_indptr, excl_items, n, m->n_items)) return rc;
-    EASECHK(hipSetDevice(m->device));
-    if (int rc = ease_stage_csr(m, m->q_ptr, m->q_ids, list_indptr, list_items, n)) return rc;
-    return ease_topk_run(m, "top-K of lists", EaseQuery{nullptr, m->q_ptr, m->q_ids}, n, k, excl_indptr, excl_items, items_out, scores_out);
+    return tfr::topk_lists<EaseServe>(g_ease_err, m, list_indptr, list_items, n, k, excl_indptr, excl_items, items_out, scores_out);
 }
 
 int tfr_ease_rank_items(tfr_ease* m, const int32_t* users, int64_t n, const int64_t* tgt_indptr, const int32_t* tgt_items,
                         const int64_t* excl_indptr, const int32_t* excl_items, int32_t* ranks_out) {
-    if (!m) return ease_fail(TFR_ERR_ARG, "null model");
-    if (n < 0) return ease_fail(TFR_ERR_ARG, "rank: negative n");
-    if (!m->loaded) return ease_fail(TFR_ERR_STATE, "rank: no data: call tfr_ease_load first");
-    if (!m->fitted) return ease_fail(TFR_ERR_STATE, "rank: no weights: call tfr_ease_solve or tfr_ease_set_weights first");
-    if (n == 0) return TFR_OK;
-    if (int rc = ease_check_users("rank", m, users, n)) return rc;
-    if (int rc = ease_check_csr("rank", "target", false, true, tgt_indptr, tgt_items, n, m->n_items)) return rc;
-    if (excl_indptr) if (int rc = ease_check_csr("rank", "exclusion", false, false, excl_indptr, excl_items, n, m->n_items)) return rc;
-    const int64_t t0 = tgt_indptr[0], n_tgt = tgt_indptr[n] - t0;
-    if (n_tgt == 0) return TFR_OK;
-    if (!ranks_out) return ease_fail(TFR_ERR_ARG, "rank: null ranks_out");
-    EasePlan p;                                          // the ranking merges nothing: only the slicing of the plan is used
-    if (!ease_plan(1, m->n_items, 1, n, &p)) return ease_fail(TFR_ERR_ARG, "rank: no plan");
-    EASECHK(hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    EASECHK(m->q_users.reserve(n, s));
-    EASECHK(hipMemcpyAsync(m->q_users, users, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    if (int rc = ease_stage_csr(m, m->t_ptr, m->t_ids, tgt_indptr, tgt_items, n)) return rc;
-    if (excl_indptr) if (int rc = ease_stage_csr(m, m->x_ptr, m->x_ids, excl_indptr, excl_items, n)) return rc;
-    EASECHK(m->tkeys.reserve(tgt_indptr[n], s));
-    EASECHK(m->ranks.reserve(tgt_indptr[n], s));
-    EaseScoreArgs a = ease_score_args(m, EaseQuery{m->q_users, m->pu, m->items});
-    if (excl_indptr) { a.xptr = m->x_ptr; a.xids = m->x_ids; }
-    a.tptr = m->t_ptr; a.tids = m->t_ids; a.tkeys = m->tkeys; a.ranks = m->ranks;
-    a.q_lo = 0; a.n = n; a.k = 1; a.slices = p.slices;
-    launch_ease_score<1>(a, s);
-    EASECHK(hipGetLastError());
-    launch_ease_score<2>(a, s);
-    EASECHK(hipGetLastError());
-    EASECHK(hipMemcpyAsync(ranks_out, m->ranks.get() + t0, (size_t)n_tgt * 4, hipMemcpyDeviceToHost, s));
-    EASECHK(hipStreamSynchronize(s));
-    return TFR_OK;
+    return tfr::rank_users<EaseServe>(g_ease_err, m, users, n, tgt_indptr, tgt_items, excl_indptr, excl_items, ranks_out);
 }
 
 }  // extern "C"

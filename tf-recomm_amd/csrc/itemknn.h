@@ -1,6 +1,6 @@
 // itemknn.h - item-based nearest neighbours (tfr_knn_*): the launch plans, the argument blocks of the two kernels
-// and the handle.  itemknn.hip owns the kernels and the C-ABI entries; the per-slice key lists are merged by topk.hip's
-// launch_topk_merge (topk.h).
+// and the handle.  itemknn.hip owns the kernels and the C-ABI entries; the CSR, the serving drivers and the device pieces it
+// shares with EASE are item_lists.h's; the per-slice key lists are merged by topk.hip's launch_topk_merge (topk.h).
 //
 // Fit (which = 0): one block per (item, catalogue slice of KNN_W_FIT columns) counts co-occurrences in uint32 LDS counters
 // and keeps the slice's K best keys.  Scoring (which = 1): one wave per (query, slice of KNN_W_SCORE columns) sums the
@@ -12,6 +12,7 @@
 #include "devbuf.h"
 #include "topk.h"
 #include "score_tile.h"
+#include "item_lists.h"
 
 constexpr int KNN_KMAX = tfr::TOPK_KMAX;
 constexpr int KNN_WAVES = 4;                             // waves per block of both kernels
@@ -74,44 +75,10 @@ struct KnnScoreArgs {
     int32_t K, k, slices;
 };
 
-struct tfr_knn {
-    int64_t n_users = 0, n_items = 0;
+struct tfr_knn : tfr::ItemListModel {
     int32_t K = 0, metric = 0;
     double shrink = 0.0;
-    int device = 0;
-    bool loaded = false, fitted = false;
-    hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    tfr::DevBuf<int64_t> pu, pi;                         // [n_users + 1], [n_items + 1]
-    tfr::DevBuf<int32_t> items, iu;                      // the CSR as loaded and its transpose
     tfr::DevBuf<int32_t> nb_items;                       // [n_items, K]
     tfr::DevBuf<float> nb_scores;
-    tfr::DevBuf<uint64_t> part, tkeys;
-    // one call's staged inputs and outputs
-    tfr::DevBuf<int32_t> q_users, q_ids, x_ids, t_ids, out_items, ranks;
-    tfr::DevBuf<int64_t> q_ptr, x_ptr, t_ptr;
-    tfr::DevBuf<float> out_scores;
 };
-
-// The per-wave key queue of both scoring tails (k_knn_cooc, k_knn_score, ease.hip k_ease_score): q is the wave's own LDS.
-// sort the wave's queue, keep its k best, raise its threshold; cnt and thr are wave-uniform registers
-template <int CAP>
-__device__ __forceinline__ void knn_compact(uint64_t* q, int& cnt, uint64_t& thr, int k, int lane) {
-    for (int t = cnt + lane; t < CAP; t += 64) q[t] = 0;
-    tfr::wave_lds_sync();
-    tfr::wave_sort_desc<CAP>(q, lane);
-    cnt = cnt < k ? cnt : k;
-    thr = cnt == k ? q[k - 1] : 0;
-}
-
-// each lane offers one key; needs cnt <= CAP - 64 on entry and leaves it so
-template <int CAP>
-__device__ __forceinline__ void knn_offer(uint64_t* q, int& cnt, uint64_t& thr, int k, int lane, bool ok, uint64_t key) {
-    ok = ok && key > thr;
-    const uint64_t mask = __ballot(ok);
-    if (mask) {
-        if (ok) q[cnt + __popcll(mask & ((1ull << lane) - 1ull))] = key;
-        cnt += __popcll(mask);
-        if (cnt > CAP - 64) knn_compact<CAP>(q, cnt, thr, k, lane);
-    }
-}

@@ -20,8 +20,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .engine import exclusion_csr, rank_call
-from .itemknn import _pattern
+from .item_lists import ItemListModel
 
 
 def plan(item_num, k=1, n_rows=0, which=0):
@@ -40,7 +39,9 @@ def plan(item_num, k=1, n_rows=0, which=0):
                 slices=s.value, chunk=ch.value, ahead=a.value)
 
 
-class EASE(object):
+class EASE(ItemListModel):
+    _family = "ease"
+
     def __init__(self, user_num, item_num, regularization=500.0, device=0):
         self.user_num, self.item_num = int(user_num), int(item_num)
         self.regularization, self.device = float(regularization), int(device)
@@ -51,37 +52,12 @@ class EASE(object):
         self._h = L._p()
         self._check(self._lib.tfr_ease_create(C.byref(self._h), self.user_num, self.item_num, self.regularization, self.device))
 
-    def _check(self, rc):
-        if rc != L.OK:
-            text = self._lib.tfr_ease_last_error().decode("utf-8", "replace")
-            raise (L.OutOfRangeError if rc == L.ERR_OOB else L.TfrError)(rc, text)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.tfr_ease_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     # -- data and fit -------------------------------------------------------------------
     def load(self, user_items):
         """``user_items``: scipy sparse [user_num, item_num] (its pattern: values are ignored, explicit zeros dropped) or an
         (indptr, items) pair with strictly increasing rows.  A second load replaces the first and forgets Gram and weights."""
-        indptr, items = _pattern(user_items, self.item_num, "user_items")
-        if indptr.size != self.user_num + 1:
-            raise ValueError("user_items must hold %d rows" % self.user_num)
         self._f64_is = None
-        self._check(self._lib.tfr_ease_load(self._h, L.ptr_i64(indptr), L.ptr_i32(items)))
+        self._load(user_items)
 
     def _solve(self, keep_inverse):
         ms = (C.c_float * 3)()
@@ -152,46 +128,3 @@ class EASE(object):
         if B.shape != (self.item_num, self.item_num):
             raise ValueError("B must be [%d, %d]" % (self.item_num, self.item_num))
         self._check(self._lib.tfr_ease_set_weights(self._h, 0, self.item_num, L.ptr_f32(B)))
-
-    # -- serving ------------------------------------------------------------------------
-    def recommend(self, users, k=10, exclude=None, return_scores=True):
-        """The ``k`` best items of each of ``users`` (resident: their loaded rows are the lists), best first, equal scores by
-        item id.  ``exclude`` as in ``SvdModel.recommend``.  Returns ``items`` int32 [n, k] (-1 past the eligible items) and,
-        if asked, ``scores`` float32 [n, k] (-inf there)."""
-        u = L.as_i32(users, "user ids").reshape(-1)
-        xp, xi = exclusion_csr(exclude, u)
-        items = np.empty((u.size, int(k)), np.int32)
-        scores = np.empty((u.size, int(k)), np.float32) if return_scores else None
-        self._check(self._lib.tfr_ease_topk(self._h, L.ptr_i32(u), u.size, int(k), None if xp is None else L.ptr_i64(xp),
-                                            None if xi is None else L.ptr_i32(xi), L.ptr_i32(items),
-                                            None if scores is None else L.ptr_f32(scores)))
-        return (items, scores) if return_scores else items
-
-    def recommend_lists(self, user_items, k=10, exclude=True, return_scores=True):
-        """``recommend`` for users the model does not hold, known by their lists: ``user_items`` is a scipy sparse
-        [n, item_num] or an (indptr, items) pair.  ``exclude``: True leaves out each list's own items, None / False nothing,
-        anything else as in ``recommend`` (aligned with the lists)."""
-        indptr, ids = _pattern(user_items, self.item_num, "user_items")
-        n = indptr.size - 1
-        if exclude is True:
-            xp, xi = indptr, ids
-        elif exclude is None or exclude is False:
-            xp, xi = None, None
-        else:
-            xp, xi = exclusion_csr(exclude, np.arange(n))
-        items = np.empty((n, int(k)), np.int32)
-        scores = np.empty((n, int(k)), np.float32) if return_scores else None
-        self._check(self._lib.tfr_ease_topk_lists(self._h, L.ptr_i64(indptr), L.ptr_i32(ids), n, int(k),
-                                                  None if xp is None else L.ptr_i64(xp), None if xi is None else L.ptr_i32(xi),
-                                                  L.ptr_i32(items), None if scores is None else L.ptr_f32(scores)))
-        return (items, scores) if return_scores else items
-
-    def rank_items(self, users, targets, exclude=None):
-        """0-based rank of each target item of each of ``users`` among all items not in ``exclude``, by the keys of
-        ``recommend``: ``rank < k`` exactly when ``recommend(users, k, exclude)`` holds the target, at that position; -1 for
-        an excluded target.  Arguments and return value as ``SvdModel.rank_items``."""
-        u = L.as_i32(users, "user ids").reshape(-1)
-
-        def call(ip, it, xp, xi, out):
-            self._check(self._lib.tfr_ease_rank_items(self._h, L.ptr_i32(u), u.size, ip, it, xp, xi, out))
-        return rank_call(call, u, targets, exclude)
