@@ -653,6 +653,75 @@ int tfr_ease_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t which, int
                   int32_t* look_ahead);
 const char* tfr_ease_last_error(void);
 
+/* ---- SLIM (Ning & Karypis 2011, "Sparse Linear Methods for Top-N Recommender Systems"): elastic-net item weights - DESIGN §34 --
+ *      X as for EASE.  A = X^T X + beta I in float64: exactly tfr_ease_gram's matrix with lambda = beta (beta >= 0, finite).
+ *      For each item j the column w of W minimises
+ *          1/2 w^T A w - a_j^T w + l1 * sum|w|,   w[j] = 0,   w >= 0 when positive
+ *      where a_j is column j of A (its entry j is never read).  In sklearn's ElasticNet(alpha, l1_ratio) terms over the U
+ *      users: l1 = U * alpha * l1_ratio, beta = U * alpha * (1 - l1_ratio).  The solver is cyclic coordinate descent on the
+ *      residual q[i] = a_j[i] - sum over k != i of A[i, k] w[k]; the device produces the bits of
+ *          q = a_j;  w = 0;  d[i] = A[i, i]
+ *          for sweep in 1..max_iter:
+ *              dmax = 0
+ *              for i in 0..n-1 ascending, i != j, d[i] > 0:           (d[i] <= 0: w[i] stays 0)
+ *                  positive:      t = q[i] - l1;   wn = t > 0 ? t / d[i] : 0
+ *                  not positive:  t = |q[i]| - l1; wn = t > 0 ? copysign(t / d[i], q[i]) : 0
+ *                  dl = wn - w[i]
+ *                  if dl != 0:
+ *                      for k != i:  q[k] = q[k] - (dl * A[i, k])      (the product rounded, then the difference: no fma)
+ *                      w[i] = wn;  updates += 1;  dmax = max(dmax, |dl|)
+ *              if dmax <= tol * max|w|:  converged; stop              (both 0 stop too)
+ *          W[i, j] = (float)w[i] where w[i] != 0, +0 elsewhere
+ *      in float64 throughout, whatever the launch geometry: two solves give the same bits.  W is a dense float32
+ *      [n_items, n_items], row-major, and scores, top-K and ranks are EASE's on it, word for word (tfr_ease_topk and its
+ *      neighbours above): score(u, j) = the float32 add chain from +0, over i in N(u) ascending, of W[i, j].
+ *      A column's residual lives in the LDS of one workgroup: n_items > 16384 is refused with TFR_ERR_ARG before any device work.
+ *      tfr_slim_load takes the user CSR; a second load replaces the first and forgets the Gram matrix, the weights and the
+ *      statistics.  tfr_slim_gram builds A from the loaded pattern.  tfr_slim_set_gram takes a caller's full matrix instead: it
+ *      must be finite and bit-symmetric (TFR_ERR_ARG otherwise); beta is not added to it.  tfr_slim_get_gram copies rows of A
+ *      out.  tfr_slim_solve runs the solver for every column and keeps A, so another solve (another l1) needs no new Gram
+ *      matrix; elapsed_ms, if given, receives two device times: of the tfr_slim_gram that built A (0 for a caller's) and of
+ *      the solve.  A column whose weights leave the finite range (a caller's matrix with a tiny diagonal) returns TFR_ERR_ARG
+ *      naming it, and the model is unfitted.  tfr_slim_get_stats copies out, per column of the last solve, the sweeps run, the
+ *      coordinate updates applied and whether the stopping rule was met (each may be NULL); TFR_ERR_STATE when the weights
+ *      are not a solve's.  tfr_slim_get_weights / tfr_slim_set_weights follow tfr_ease_get_weights / tfr_ease_set_weights.
+ *      Host pointers; every call synchronises.  Checked on the host before any device work (the model is left as it was):
+ *      TFR_ERR_ARG for a beta, l1 or tol that is negative or not finite, max_iter < 1, k outside [1, 256] and the CSR errors of
+ *      tfr_ease_*; TFR_ERR_OOB for an id out of range; TFR_ERR_STATE for gram before a load, solve and get_gram without a Gram
+ *      matrix, get_weights, top-K and ranking without weights (top-K of users and ranking also before a load). */
+typedef struct tfr_slim tfr_slim;
+int tfr_slim_create(tfr_slim** out, int64_t n_users, int64_t n_items, double beta, int32_t device);
+int tfr_slim_destroy(tfr_slim* m);
+int tfr_slim_load(tfr_slim* m, const int64_t* indptr /* [n_users+1] */, const int32_t* items);
+int tfr_slim_gram(tfr_slim* m);
+int tfr_slim_set_gram(tfr_slim* m, const double* A /* [n_items,n_items] */);
+int tfr_slim_get_gram(tfr_slim* m, int64_t row_lo, int64_t n_rows, double* out /* [n_rows,n_items] */);
+int tfr_slim_solve(tfr_slim* m, double l1, int32_t positive, int32_t max_iter, double tol,
+                   float* elapsed_ms /* [2]: Gram, solve; may be NULL */);
+int tfr_slim_get_stats(tfr_slim* m, int32_t* sweeps /* [n_items] */, int32_t* updates /* [n_items] */, int32_t* converged /* [n_items] */);
+int tfr_slim_get_weights(tfr_slim* m, int64_t row_lo, int64_t n_rows, float* out /* [n_rows,n_items] */);
+int tfr_slim_set_weights(tfr_slim* m, int64_t row_lo, int64_t n_rows, const float* in /* [n_rows,n_items] */);
+int tfr_slim_topk(tfr_slim* m, const int32_t* users, int64_t n, int32_t k,
+                  const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                  int32_t* items_out /* [n,k] */, float* scores_out /* [n,k], may be NULL */);
+int tfr_slim_topk_lists(tfr_slim* m, const int64_t* list_indptr /* [n+1] */, const int32_t* list_items, int64_t n, int32_t k,
+                        const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                        int32_t* items_out, float* scores_out);
+int tfr_slim_rank_items(tfr_slim* m, const int32_t* users, int64_t n,
+                        const int64_t* tgt_indptr /* [n+1] */, const int32_t* tgt_items,
+                        const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                        int32_t* ranks_out /* [tgt_indptr[n] - tgt_indptr[0]] */);
+/* host-only, no handle and no device.  For which = 0 (the fit: k must be valid, n_rows is not used): the window (coordinates
+ * the solver examines at once = threads per workgroup), the solver's grid, the LDS bytes of one solver workgroup (the Gram
+ * kernel's are tfr_ease_plan's), whether the column's weights live in LDS beside q (0: in a global scratch row per workgroup),
+ * and the float64 / float32 device bytes of a fit (A, its diagonal and the scratch rows; W).  For which = 1 (scoring n_rows
+ * queries for k): tfr_ease_plan's scoring slicing.  TFR_ERR_ARG for n_items outside [1, 16384], k outside [1, 256],
+ * n_rows < 0.  Outputs may be NULL. */
+int tfr_slim_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t which, int32_t* window, int32_t* grid, int64_t* lds_bytes,
+                  int32_t* w_in_lds, int64_t* f64_bytes, int64_t* f32_bytes, int32_t* slice_width, int32_t* slices,
+                  int64_t* row_chunk, int32_t* look_ahead);
+const char* tfr_slim_last_error(void);
+
 /* ---- batched per-user fine-tuning: every user of adaptive_test.py:87-116 / non_adaptive_test.py:56-87 in one launch -----------
  *      A schedule: for user u = users[x] (each at most once), training rows items / rates [row_ptr[x], row_ptr[x+1]) and rounds
  *      [round_ptr[x], round_ptr[x+1]).  Round k first predicts ask_items[k] with the parameters of the moment (its logit, the

@@ -193,6 +193,17 @@ SIGNATURES = {
     "tfr_ease_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i64p, _i64p, _i32p, _i32p,
                                 _i64p, _i32p]),
     "tfr_ease_last_error": (C.c_char_p, []),
+    "tfr_slim_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_double, C.c_int32]),
+    "tfr_slim_gram": (C.c_int, [_p]),
+    "tfr_slim_set_gram": (C.c_int, [_p, _f64p]),
+    "tfr_slim_get_gram": (C.c_int, [_p, C.c_int64, C.c_int64, _f64p]),
+    "tfr_slim_solve": (C.c_int, [_p, C.c_double, C.c_int32, C.c_int32, C.c_double, _f32p]),
+    "tfr_slim_get_stats": (C.c_int, [_p, _i32p, _i32p, _i32p]),
+    "tfr_slim_get_weights": (C.c_int, [_p, C.c_int64, C.c_int64, _f32p]),
+    "tfr_slim_set_weights": (C.c_int, [_p, C.c_int64, C.c_int64, _f32p]),
+    "tfr_slim_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i32p, _i64p, _i64p, _i32p, _i32p,
+                                _i64p, _i32p]),
+    "tfr_slim_last_error": (C.c_char_p, []),
     "tfr_sort_segments": (C.c_int, [_p, C.c_int32, _i32p, C.c_int64, _i32p, _i32p]),
     "tfr_kernel_plan": (C.c_int, [_p, C.c_int64, C.c_char_p, C.c_int64]),
     "tfr_forward_plan": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_char_p, C.c_int64]),
@@ -262,7 +273,7 @@ SIGNATURES = {
 }
 
 # what the item x item families share (item_lists.py): the same five signatures under each prefix
-for _family in ("knn", "ease"):
+for _family in ("knn", "ease", "slim"):
     SIGNATURES.update({
         "tfr_%s_destroy" % _family: (C.c_int, [_p]),
         "tfr_%s_load" % _family: (C.c_int, [_p, _i64p, _i32p]),

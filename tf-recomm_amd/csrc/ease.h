@@ -110,6 +110,11 @@ struct EaseScoreArgs {
     int32_t k, slices;
 };
 
+// The launches another dense item x item family shares with EASE (SLIM: slim.hip); the kernels stay ease.hip's.
+// k_ease_gram over `slices` column slices of EASE_W_GRAM (ease_plan(0).slices); k_ease_score<mode> for a.n * a.slices waves.
+void ease_launch_gram(const EaseGramArgs& a, int32_t slices, hipStream_t s);
+void ease_launch_score(int mode, const EaseScoreArgs& a, hipStream_t s);
+
 struct tfr_ease : tfr::ItemListModel {
     double lambda = 0.0;
     int f64_is = 0;                                      // what the f64 buffer holds: 0 nothing, 1 G, 2 P

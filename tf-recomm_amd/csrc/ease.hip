@@ -339,10 +339,7 @@ struct EaseServe {
     }
 
     template <int MODE>
-    static void launch(const Args& a, hipStream_t s) {
-        const dim3 g((unsigned)((a.n * a.slices + EASE_WAVES - 1) / EASE_WAVES));
-        hipLaunchKernelGGL(k_ease_score<MODE>, g, dim3(256), 0, s, a);
-    }
+    static void launch(const Args& a, hipStream_t s) { ease_launch_score(MODE, a, s); }
 };
 
 // the f64 buffer and what the factorisation needs beside it
@@ -356,6 +353,18 @@ int ease_reserve_f64(tfr_ease* m) {
 }
 
 }  // namespace
+
+void ease_launch_gram(const EaseGramArgs& a, int32_t slices, hipStream_t s) {
+    const dim3 g((unsigned)std::min<int64_t>(a.n_items, EASE_GRID_ROWS), (unsigned)slices);
+    hipLaunchKernelGGL(k_ease_gram, g, dim3(256), 0, s, a);
+}
+
+void ease_launch_score(int mode, const EaseScoreArgs& a, hipStream_t s) {
+    const dim3 g((unsigned)((a.n * a.slices + EASE_WAVES - 1) / EASE_WAVES));
+    if (mode == 0) hipLaunchKernelGGL(k_ease_score<0>, g, dim3(256), 0, s, a);
+    else if (mode == 1) hipLaunchKernelGGL(k_ease_score<1>, g, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_ease_score<2>, g, dim3(256), 0, s, a);
+}
 
 extern "C" {
 
@@ -426,8 +435,7 @@ int tfr_ease_gram(tfr_ease* m) {
     (void)hipEventRecord(m->ev0, s);
     EaseGramArgs a = {};
     a.pu = m->pu; a.items = m->items; a.pi = m->pi; a.iu = m->iu; a.G = m->G; a.n_items = m->n_items; a.lambda = m->lambda;
-    const dim3 g((unsigned)std::min<int64_t>(m->n_items, EASE_GRID_ROWS), (unsigned)p.slices);
-    hipLaunchKernelGGL(k_ease_gram, g, dim3(256), 0, s, a);
+    ease_launch_gram(a, p.slices, s);
     LISTCHK(g_ease_err, hipGetLastError());
     (void)hipEventRecord(m->ev1, s);
     LISTCHK(g_ease_err, hipStreamSynchronize(s));

@@ -1,6 +1,7 @@
-// item_lists.h - what the item x item models share (ItemKNN: itemknn.{h,hip}; EASE: ease.{h,hip}, §32; the layer
-// itself: §33).  Both start from one binary user x item CSR and its transpose, and both serve the same way: a wave holds one
-// (query, catalogue slice) row of float32 scores in LDS, and the same tail turns that row into top-K keys or ranks.
+// item_lists.h - what the item x item models share (ItemKNN: itemknn.{h,hip}; EASE: ease.{h,hip}, §32; SLIM:
+// slim.{h,hip}, §34, which serves through EASE's scoring launches; the layer itself: §33).  They start from one binary user x
+// item CSR and its transpose, and serve the same way: a wave holds one (query, catalogue slice) row of float32 scores in LDS,
+// and the same tail turns that row into top-K keys or ranks.
 //
 // Device side: the binary search and the co-occurrence count loop of the two fit kernels, the per-wave key queue, and the
 // scoring tail.  They are templated on the calling kernel's own argument block and read the fields both blocks name alike.

@@ -1,5 +1,5 @@
-"""What ``ItemKNN`` and ``EASE`` share: both hold a binary user x item CSR on the device and serve from it through C entries
-that differ only in their family prefix (csrc/item_lists.h is the native side of this module)."""
+"""What ``ItemKNN``, ``EASE`` and ``SLIM`` share: each holds a binary user x item CSR on the device and serves from it through C
+entries that differ only in their family prefix (csrc/item_lists.h is the native side of this module)."""
 from __future__ import annotations
 
 import numpy as np
