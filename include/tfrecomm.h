@@ -584,6 +584,30 @@ int tfr_knn_rank_items(tfr_knn* m, const int32_t* users, int64_t n,
  * row bounds are fetched at once; scoring: items of the query whose neighbour rows are).  Outputs may be NULL. */
 int tfr_knn_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t which, int32_t* slice_width, int32_t* slices,
                  int64_t* row_chunk, int64_t* lds_bytes, int32_t* look_ahead);
+/* ---- weighted co-occurrence fit on the same handle (RP3beta, P3alpha, TF-IDF / BM25 neighbours on binary data) - DESIGN §35 --
+ *      X as loaded; N(i) = the users of item i.  The caller gives q[u], a uint64 weight per user; row_scale[i] and
+ *      col_scale[j], a float64 per item, finite and >= 0; and shift, an integer in [0, 62].
+ *          S_ij = sum of q[u] over u in N(i) and N(j)                        an exact integer below 2^63
+ *          sim(i -> j) = (float)(((double)S_ij * 2^-shift) * row_scale[i] * col_scale[j])
+ *      (double)S_ij is correctly rounded, the scaling by a power of two is exact, the two float64 products go left to right,
+ *      and there is one rounding to float32; there is no add, so nothing contracts into an fma.  The neighbours of i are
+ *      the K items j != i with S_ij > 0 - whatever float32 the similarity rounds to, +0 included - that have the largest
+ *      tfr_topk key; padding is item -1 / score -INFINITY as tfr_knn_fit writes it.  The diagonal is left out by
+ *      definition.  A user with q[u] = 0 contributes nothing.  Integer sums: the lists are bit-identical run to run.
+ *      RP3beta (Paudel et al. 2017) with user weights rounded to multiples of 2^-shift:
+ *          q[u] = rint(deg(u)^-alpha * 2^shift), row_scale[i] = n_i^-alpha, col_scale[j] = n_j^-beta, 0 for empty users
+ *      and items; beta = 0 is P3alpha (Cooper et al. 2014).  The Python classes RP3beta / WeightedItemKNN build these in
+ *      NumPy float64.  The metric and shrink given at create play no part.  The lists replace those of tfr_knn_fit and
+ *      are served, read and written by the same entries.
+ *      Checked on the host before any device work (the model is left as it was): TFR_ERR_ARG for a NULL handle or array,
+ *      a shift outside [0, 62], a scale that is negative or not finite, max q[u] * (the longest loaded item list) not
+ *      below 2^63, that product * 2^-shift * max row_scale * max col_scale past FLT_MAX (so every kept similarity is
+ *      finite), a catalogue of more than 8192 * min(256, 8192 / K) items (tfr_knn_weighted_plan); TFR_ERR_STATE before a
+ *      load.  tfr_knn_weighted_plan is tfr_knn_plan's which = 0 for this fit: host-only, outputs may be NULL. */
+int tfr_knn_fit_weighted(tfr_knn* m, const uint64_t* user_w /* [n_users] */, const double* row_scale /* [n_items] */,
+                         const double* col_scale /* [n_items] */, int32_t shift, float* elapsed_ms /* may be NULL */);
+int tfr_knn_weighted_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t* slice_width, int32_t* slices,
+                          int64_t* row_chunk, int64_t* lds_bytes, int32_t* look_ahead);
 const char* tfr_knn_last_error(void);
 
 /* ---- EASE (Steck 2019, "Embarrassingly Shallow Autoencoders"): a dense item x item model in closed form - DESIGN §32 ----------

@@ -182,6 +182,8 @@ SIGNATURES = {
     "tfr_knn_get_neighbours": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _f32p]),
     "tfr_knn_set_neighbours": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _f32p]),
     "tfr_knn_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i64p, _i32p]),
+    "tfr_knn_fit_weighted": (C.c_int, [_p, C.POINTER(C.c_uint64), _f64p, _f64p, C.c_int32, _f32p]),
+    "tfr_knn_weighted_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, _i32p, _i32p, _i64p, _i64p, _i32p]),
     "tfr_knn_last_error": (C.c_char_p, []),
     "tfr_ease_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_double, C.c_int32]),
     "tfr_ease_gram": (C.c_int, [_p]),

@@ -3,8 +3,8 @@
 // item CSR and its transpose, and serve the same way: a wave holds one (query, catalogue slice) row of float32 scores in LDS,
 // and the same tail turns that row into top-K keys or ranks.
 //
-// Device side: the binary search and the co-occurrence count loop of the two fit kernels, the per-wave key queue, and the
-// scoring tail.  They are templated on the calling kernel's own argument block and read the fields both blocks name alike.
+// Device side: the binary search and the co-occurrence count loop of the fit kernels (uint32 counts, and uint64 sums of user
+// weights for ItemKNN's weighted fit, §35), the per-wave key queue, and the scoring tail.  They are templated on the calling kernel's own argument block and read the fields both blocks name alike.
 // Host side: the handle's base (ItemListModel), the error text, the CSR / user / k / window checks, the staging of a host CSR,
 // the load, the shared ends of create and destroy, and the three serving bodies behind tfr_{knn,ease}_{topk,topk_lists,
 // rank_items}.  A family describes itself to the serving bodies with a struct F:
@@ -60,6 +60,32 @@ __device__ __forceinline__ void count_row(const Args& a, uint32_t* counts, int64
         for (int z = 0; z < nb; ++z) {
             const int64_t zs = (int64_t)__shfl(st, z), ze = (int64_t)__shfl(en, z);
             for (int64_t t = zs + lane; t < ze; t += 64) atomicAdd(&counts[(int64_t)a.items[t] - lo], 1u);
+        }
+    }
+}
+
+// The weighted sibling: sums[j - lo] += a.uw[u] over the users u that the item list shares with column j.  The lane that
+// loads user l's row bounds loads its uint64 weight too, and the three travel together by __shfl; a user of weight 0 is
+// not walked.  64-bit integer LDS atomics: the sums are exact in any order as long as none reaches 2^64.
+template <int WAVES, class Args>
+__device__ __forceinline__ void count_row(const Args& a, unsigned long long* sums, int64_t p0, int64_t p1, int64_t lo, int width,
+                                          int lane, int wave) {
+    for (int64_t b = p0 + wave * 64; b < p1; b += 64 * WAVES) {
+        unsigned long long st = 0, en = 0, wt = 0;
+        if (b + lane < p1) {
+            const int32_t u = a.iu[b + lane];
+            wt = a.uw[u];
+            const int64_t ulo = a.pu[u], uhi = a.pu[u + 1];
+            const int64_t s0 = list_lower_bound(a.items, ulo, uhi, lo);
+            st = (unsigned long long)s0;
+            en = (unsigned long long)list_lower_bound(a.items, s0, uhi, lo + width);
+        }
+        const int nb = (int)(p1 - b < 64 ? p1 - b : 64);
+        for (int z = 0; z < nb; ++z) {
+            const unsigned long long zw = __shfl(wt, z);
+            if (zw == 0) continue;
+            const int64_t zs = (int64_t)__shfl(st, z), ze = (int64_t)__shfl(en, z);
+            for (int64_t t = zs + lane; t < ze; t += 64) atomicAdd(&sums[(int64_t)a.items[t] - lo], zw);
         }
     }
 }

@@ -12,6 +12,9 @@
 //   its own by ballot and prefix count; a queue that cannot take 64 more is sorted (score_tile.h wave_sort_desc) and cut
 //   to K.  Wave 0 then takes in the other three queues and writes part[row, slice]; launch_topk_merge joins the slices.
 //   Keys within a row are distinct, so neither the fill order nor the split over waves reaches the result.
+// k_knn_cooc_w: the same block for tfr_knn_fit_weighted, over slices of KNN_W_WFIT columns:
+//   uint64 LDS sums S_ij of fixed-point user weights in place of the counts, by 64-bit integer LDS atomics, exact in any
+//   order; sim = (float)((double)S_ij * 2^-shift * row_scale[i] * col_scale[j]); a candidate by S_ij > 0.
 // k_knn_score<R, MODE>: one wave per (query, slice of KNN_W_SCORE columns) with a float32 accumulator of its own in LDS,
 //   four waves per block, no block barrier.  For the query's items i ascending, KNN_SCORE_AHEAD at a time: the lanes load
 //   the items' neighbour rows (coalesced, R rounds of 64 slots), then add them item by item with plain LDS read-add-write.
@@ -20,6 +23,7 @@
 //   part[query, slice].  MODE 1 (ranking): the targets inside the slice get their key.  MODE 2: lane t counts the slots of
 //   the slice whose key beats target t's; the slices' counts meet in an integer atomic.
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <string.h>
 #include <vector>
@@ -45,6 +49,12 @@ __device__ __forceinline__ float knn_sim(int metric, uint32_t c, int64_t ni, int
     else if (metric == KNN_JACCARD) s = (double)c / ((double)(ni + nj - (int64_t)c) + shrink);
     else s = (double)c;
     return __double2float_rn(s);
+}
+
+// the weighted fit's similarity: the exact integer sum scaled by a power of two, then two float64 products left to right
+// (no add: nothing contracts into an fma), rounded once to float32
+__device__ __forceinline__ float knn_wsim(unsigned long long s, double unit, double row_scale, double col_scale) {
+    return __double2float_rn((double)s * unit * row_scale * col_scale);
 }
 
 template <int CAP>
@@ -77,6 +87,61 @@ __global__ __launch_bounds__(256) void k_knn_cooc(KnnFitArgs a) {
             const bool ok = c > 0 && lo + j != i;
             uint64_t key = 0;
             if (ok) key = topk_key(knn_sim(a.metric, c, p1 - p0, a.pi[lo + j + 1] - a.pi[lo + j], a.shrink), lo + j);
+            tfr::queue_offer<CAP>(q, qn, thr, K, lane, ok, key);
+        }
+        if (qn > 0) tfr::queue_compact<CAP>(q, qn, thr, K, lane);
+        if (lane == 0) wcnt[wave] = qn;
+        __syncthreads();
+
+        if (wave == 0) {
+            for (int w = 1; w < KNN_WAVES; ++w) {
+                const int n = wcnt[w];
+                for (int off = 0; off < n; off += 64) {
+                    const bool ok = off + lane < n;
+                    tfr::queue_offer<CAP>(q, qn, thr, K, lane, ok, ok ? queue[w][off + lane] : 0);
+                }
+            }
+            if (qn > 0) tfr::queue_compact<CAP>(q, qn, thr, K, lane);
+            uint64_t* dst = a.part + ((size_t)r * a.slices + slice) * K;
+            for (int t = lane; t < K; t += 64) dst[t] = t < qn ? q[t] : 0;
+        }
+        // the next row's appends to the other waves' queues come after two more barriers, which wave 0 joins when it is done
+    }
+}
+
+// k_knn_cooc with uint64 sums of user weights for the counts and knn_wsim for the similarity; everything from the scan on is
+// the same text.  (One body behind both kernels was tried: it changed k_knn_cooc<256>'s code)
+template <int CAP>
+__global__ __launch_bounds__(256) void k_knn_cooc_w(KnnWFitArgs a) {
+    __shared__ unsigned long long sums[KNN_W_WFIT];
+    __shared__ uint64_t queue[KNN_WAVES][CAP];
+    __shared__ int32_t wcnt[KNN_WAVES];
+    static_assert(sizeof(sums) + sizeof(queue) + sizeof(wcnt) == knn_wfit_lds(CAP), "knn_plan reports another LDS size");
+    static_assert(CAP >= KNN_KMAX + 64 || CAP == 256, "a queue must hold K plus one append");
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int slice = blockIdx.y, K = a.K;
+    const int64_t lo = (int64_t)slice * KNN_W_WFIT;
+    const int width = (int)(a.n_items - lo < KNN_W_WFIT ? a.n_items - lo : KNN_W_WFIT);
+    uint64_t* q = queue[wave];
+
+    for (int64_t r = blockIdx.x; r < a.n_rows; r += gridDim.x) {
+        const int64_t i = a.row_lo + r;
+        const int64_t p0 = a.pi[i], p1 = a.pi[i + 1];
+        const double rs = a.row_scale[i];
+        for (int t = tid; t < width; t += 256) sums[t] = 0;
+        __syncthreads();
+
+        tfr::count_row<KNN_WAVES>(a, sums, p0, p1, lo, width, lane, wave);
+        __syncthreads();
+
+        int qn = 0;
+        uint64_t thr = 0;
+        for (int base = wave * 64; base < width; base += 64 * KNN_WAVES) {
+            const int j = base + lane;
+            const unsigned long long c = j < width ? sums[j] : 0ull;
+            const bool ok = c > 0 && lo + j != i;
+            uint64_t key = 0;
+            if (ok) key = topk_key(knn_wsim(c, a.unit, rs, a.col_scale[lo + j]), lo + j);
             tfr::queue_offer<CAP>(q, qn, thr, K, lane, ok, key);
         }
         if (qn > 0) tfr::queue_compact<CAP>(q, qn, thr, K, lane);
@@ -176,6 +241,40 @@ struct KnnServe {
     }
 };
 
+// The launches of a fit, timed by the handle's events: per row chunk the kernel over (rows, slices), then the merge into
+// the handle's lists.  a: the family's own fields set; the CSR, part, n_items, K and slices are set here.  The model's
+// device is current and `fitted` is false on entry.
+template <class Args>
+int run_fit(tfr_knn* m, const KnnPlan& p, Args a, void (*kernel)(Args), float* elapsed_ms) {
+    hipStream_t s = m->stream;
+    LISTCHK(g_knn_err, m->part.reserve(p.chunk * p.slices * m->K, s));
+    (void)hipEventRecord(m->ev0, s);
+    a.pu = m->pu; a.items = m->items; a.pi = m->pi; a.iu = m->iu; a.part = m->part;
+    a.n_items = m->n_items; a.K = m->K; a.slices = p.slices;
+    for (int64_t r0 = 0; r0 < m->n_items; r0 += p.chunk) {
+        a.row_lo = r0;
+        a.n_rows = m->n_items - r0 < p.chunk ? m->n_items - r0 : p.chunk;
+        const dim3 g((unsigned)std::min<int64_t>(a.n_rows, KNN_GRID_ROWS), (unsigned)p.slices);
+        hipLaunchKernelGGL(kernel, g, dim3(256), 0, s, a);
+        LISTCHK(g_knn_err, hipGetLastError());
+        tfr::TopkMergeArgs mg;
+        memset(&mg, 0, sizeof(mg));
+        mg.part = m->part; mg.items_out = m->nb_items.get() + r0 * m->K; mg.scores_out = m->nb_scores.get() + r0 * m->K;
+        mg.n_rows = a.n_rows; mg.k = m->K; mg.slices = p.slices;
+        tfr::launch_topk_merge(mg, s);
+        LISTCHK(g_knn_err, hipGetLastError());
+    }
+    (void)hipEventRecord(m->ev1, s);
+    LISTCHK(g_knn_err, hipStreamSynchronize(s));
+    if (elapsed_ms) {
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, m->ev0, m->ev1) != hipSuccess) ms = 0.f;
+        *elapsed_ms = ms;
+    }
+    m->fitted = true;
+    return TFR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -229,7 +328,11 @@ int tfr_knn_create(tfr_knn** out, int64_t n_users, int64_t n_items, int32_t K, i
 
 // A load forgets the fitted neighbours (item_lists.h load_lists: `fitted`).
 int tfr_knn_load(tfr_knn* m, const int64_t* indptr, const int32_t* items) {
-    return tfr::load_lists(g_knn_err, m, indptr, items, [] {});
+    if (int rc = tfr::load_lists(g_knn_err, m, indptr, items, [] {})) return rc;
+    std::vector<int64_t> len((size_t)m->n_items, 0);     // the CSR passed load_lists' checks: every id is inside
+    for (int64_t e = 0; e < indptr[m->n_users]; ++e) len[(size_t)items[e]]++;
+    m->max_item_users = *std::max_element(len.begin(), len.end());
+    return TFR_OK;
 }
 
 int tfr_knn_fit(tfr_knn* m, float* elapsed_ms) {
@@ -238,36 +341,70 @@ int tfr_knn_fit(tfr_knn* m, float* elapsed_ms) {
     KnnPlan p;
     if (!knn_plan(0, m->n_items, m->K, m->n_items, &p)) return fail(g_knn_err, TFR_ERR_ARG, "fit: no plan");
     LISTCHK(g_knn_err, hipSetDevice(m->device));
+    m->fitted = false;
+    KnnFitArgs a = {};
+    a.shrink = m->shrink; a.metric = m->metric;
+    return run_fit(m, p, a, p.cap == 256 ? k_knn_cooc<256> : k_knn_cooc<512>, elapsed_ms);
+}
+
+int tfr_knn_weighted_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t* slice_width, int32_t* slices, int64_t* row_chunk,
+                          int64_t* lds_bytes, int32_t* look_ahead) {
+    if (n_items < 1 || n_items > 0x7fffffffLL || n_rows < 0)
+        return fail(g_knn_err, TFR_ERR_ARG, "knn weighted plan: n_rows >= 0 and 1 <= n_items < 2^31");
+    if (int rc = check_k(g_knn_err, "knn weighted plan", k)) return rc;
+    KnnPlan p;
+    if (!knn_plan(2, n_items, k, n_rows, &p))
+        return fail(g_knn_err, TFR_ERR_ARG, "knn weighted plan: %lld items need more than %lld / k slices", (long long)n_items,
+                    (long long)tfr::TOPK_MERGE_KEYS);
+    if (slice_width) *slice_width = p.width;
+    if (slices) *slices = p.slices;
+    if (row_chunk) *row_chunk = p.chunk;
+    if (lds_bytes) *lds_bytes = (int64_t)std::max(p.lds, tfr::topk_merge_lds(p.slices, k));
+    if (look_ahead) *look_ahead = p.ahead;
+    return TFR_OK;
+}
+
+// Everything is checked on the host before any device work: a refused call leaves the lists as they were.
+int tfr_knn_fit_weighted(tfr_knn* m, const uint64_t* user_w, const double* row_scale, const double* col_scale, int32_t shift,
+                         float* elapsed_ms) {
+    if (!m) return fail(g_knn_err, TFR_ERR_ARG, "null model");
+    if (!user_w || !row_scale || !col_scale) return fail(g_knn_err, TFR_ERR_ARG, "fit_weighted: null user_w, row_scale or col_scale");
+    if (shift < 0 || shift > 62) return fail(g_knn_err, TFR_ERR_ARG, "fit_weighted: shift must be in [0, 62] (got %d)", shift);
+    double rmax = 0.0, cmax = 0.0;
+    for (int64_t i = 0; i < m->n_items; ++i) {
+        if (!(row_scale[i] >= 0.0) || !std::isfinite(row_scale[i]) || !(col_scale[i] >= 0.0) || !std::isfinite(col_scale[i]))
+            return fail(g_knn_err, TFR_ERR_ARG, "fit_weighted: the scales of item %lld are not both finite and >= 0", (long long)i);
+        rmax = std::max(rmax, row_scale[i]);
+        cmax = std::max(cmax, col_scale[i]);
+    }
+    KnnPlan p;
+    if (!knn_plan(2, m->n_items, m->K, m->n_items, &p))
+        return fail(g_knn_err, TFR_ERR_ARG, "fit_weighted: %lld items at K %d need more than %lld / K slices of %d columns",
+                    (long long)m->n_items, m->K, (long long)tfr::TOPK_MERGE_KEYS, KNN_W_WFIT);
+    if (!m->loaded) return fail(g_knn_err, TFR_ERR_STATE, "no data: call tfr_knn_load first");
+    uint64_t wmax = 0;
+    for (int64_t u = 0; u < m->n_users; ++u) wmax = std::max(wmax, user_w[u]);
+    // every sum stays below 2^63: max weight * longest item list <= 2^63 - 1, by a division
+    if (m->max_item_users > 0 && wmax > 0x7fffffffffffffffULL / (uint64_t)m->max_item_users)
+        return fail(g_knn_err, TFR_ERR_ARG, "fit_weighted: weight %llu times %lld users of one item reaches 2^63", (unsigned long long)wmax,
+                    (long long)m->max_item_users);
+    // and every similarity is a finite float32: the products grow with each factor, so the largest of each bounds them
+    const double unit = ldexp(1.0, -shift);
+    const double top = (double)(wmax * (uint64_t)m->max_item_users) * unit * rmax * cmax;
+    if (!(top <= (double)FLT_MAX))
+        return fail(g_knn_err, TFR_ERR_ARG, "fit_weighted: a similarity could reach %g, past float32", top);
+    LISTCHK(g_knn_err, hipSetDevice(m->device));
     hipStream_t s = m->stream;
     m->fitted = false;
-    LISTCHK(g_knn_err, m->part.reserve(p.chunk * p.slices * m->K, s));
-    (void)hipEventRecord(m->ev0, s);
-    KnnFitArgs a = {};
-    a.pu = m->pu; a.items = m->items; a.pi = m->pi; a.iu = m->iu; a.part = m->part;
-    a.n_items = m->n_items; a.shrink = m->shrink; a.K = m->K; a.slices = p.slices; a.metric = m->metric;
-    for (int64_t r0 = 0; r0 < m->n_items; r0 += p.chunk) {
-        a.row_lo = r0;
-        a.n_rows = m->n_items - r0 < p.chunk ? m->n_items - r0 : p.chunk;
-        const dim3 g((unsigned)std::min<int64_t>(a.n_rows, KNN_GRID_ROWS), (unsigned)p.slices);
-        void (*kernel)(KnnFitArgs) = p.cap == 256 ? k_knn_cooc<256> : k_knn_cooc<512>;
-        hipLaunchKernelGGL(kernel, g, dim3(256), 0, s, a);
-        LISTCHK(g_knn_err, hipGetLastError());
-        tfr::TopkMergeArgs mg;
-        memset(&mg, 0, sizeof(mg));
-        mg.part = m->part; mg.items_out = m->nb_items.get() + r0 * m->K; mg.scores_out = m->nb_scores.get() + r0 * m->K;
-        mg.n_rows = a.n_rows; mg.k = m->K; mg.slices = p.slices;
-        tfr::launch_topk_merge(mg, s);
-        LISTCHK(g_knn_err, hipGetLastError());
-    }
-    (void)hipEventRecord(m->ev1, s);
-    LISTCHK(g_knn_err, hipStreamSynchronize(s));
-    if (elapsed_ms) {
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, m->ev0, m->ev1) != hipSuccess) ms = 0.f;
-        *elapsed_ms = ms;
-    }
-    m->fitted = true;
-    return TFR_OK;
+    LISTCHK(g_knn_err, m->uw.reserve(m->n_users, s));
+    LISTCHK(g_knn_err, m->row_scale.reserve(m->n_items, s));
+    LISTCHK(g_knn_err, m->col_scale.reserve(m->n_items, s));
+    LISTCHK(g_knn_err, hipMemcpyAsync(m->uw, user_w, (size_t)m->n_users * 8, hipMemcpyHostToDevice, s));
+    LISTCHK(g_knn_err, hipMemcpyAsync(m->row_scale, row_scale, (size_t)m->n_items * 8, hipMemcpyHostToDevice, s));
+    LISTCHK(g_knn_err, hipMemcpyAsync(m->col_scale, col_scale, (size_t)m->n_items * 8, hipMemcpyHostToDevice, s));
+    KnnWFitArgs a = {};
+    a.uw = m->uw; a.row_scale = m->row_scale; a.col_scale = m->col_scale; a.unit = unit;
+    return run_fit(m, p, a, p.cap == 256 ? k_knn_cooc_w<256> : k_knn_cooc_w<512>, elapsed_ms);
 }
 
 int tfr_knn_get_neighbours(tfr_knn* m, int64_t row_lo, int64_t n_rows, int32_t* items_out, float* scores_out) {
