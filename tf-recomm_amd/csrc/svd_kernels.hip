@@ -12,6 +12,7 @@
 // (bf16_rows.hip) shares; k_forward and k_front instantiate it on float32 rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <utility>
 #include "svd_kernels.h"
 #include "forward_body.h"
 #include "finalize.inc.h"
@@ -114,6 +115,22 @@ __device__ __forceinline__ Frag<VEC> buf_load_frag(__amdgpu_buffer_rsrc_t r, int
     }
     return f;
 }
+
+// x of lane L (a constant) of the caller's lane group - of its own 16-lane row where a group spans several - in every lane:
+// one DPP move where a group is one row or more (row_newbcast) or a quad (quad_perm), a bpermute otherwise.  No lane is
+// read that the caller's group does not own, so groups that have left the kernel as a whole are never looked at.
+template <int G, int L>
+__device__ __forceinline__ uint32_t group_bcast(uint32_t x) {
+    static_assert(L < G && L < 16, "group_bcast: L is a lane of the group's 16-lane row");
+    if constexpr (G >= 16) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x150 + L, 0xf, 0xf, false);
+    else if constexpr (G == 4) return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, L * 0x55, 0xf, 0xf, false);
+    else return (uint32_t)__shfl((int)x, L, G);
+}
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in that order
+template <int... K, typename F>
+__device__ __forceinline__ void unrolled(std::integer_sequence<int, K...>, F&& f) { (f(std::integral_constant<int, K>{}), ...); }
+template <int N, typename F>
+__device__ __forceinline__ void unrolled(F&& f) { unrolled(std::make_integer_sequence<int, N>{}, f); }
 
 // per-piece {loss, reg, sum g} for k_tile_step without a cross-lane reduction in every wave: lane
 // group leaders park the entry's loss and g, every lane its share of the regulariser, in LDS;
@@ -1464,7 +1481,8 @@ __global__ __launch_bounds__(256) void k_adam_dense(DensePair pr) {
 //      Round 3: the stores.  A row with more than two k = 1 continuations or a deeper one (a run over three pieces)
 //      goes through the round-major loop from k = 1 as in the general form.  Absent pieces are loads past the
 //      resource's end (zeros, no memory access) and are added as +0.0f: the sums start at +0.0f and never become
-//      -0.0f, so that changes no bit.
+//      -0.0f, so that changes no bit.  A row's 4-byte words - entries, bias sums, its three bias words - come in one
+//      request per round: one lane per tile (or per word) fetches, and the group hands them round by cross-lane moves.
 //
 //      What the chain's head needs - this side's table, its bins and rows, the tile count and the error word's address -
 //      comes in DenseHead from preloaded SGPRs (k_dense_tiles' leading scalar parameters), so round 1's entries and
@@ -1481,35 +1499,53 @@ __device__ __forceinline__ void dense_tiles_rounds(const TileDenseLaunch& L, con
     const int gl = threadIdx.x % G;
     const int d0 = gl * VEC;
     const int row = (int)blockIdx.x * GPB + threadIdx.x / G;
-    if (row >= h.rows) return;
+    if (row >= h.rows) return;                           // a group leaves together: no cross-lane move below reads a lane that is gone
+    // The row's 4-byte words travel one request per round: lane tl of each 16-lane row of the group (of the group itself below
+    // 16 lanes) fetches what belongs to tile tl, GE + tl, ..., and group_bcast hands each word round.  Slots NT and NT + 1 of
+    // that numbering are the two continuation pieces' bias sums.
+    constexpr int GE = G < 16 ? G : 16;
+    constexpr int NE = (NT + GE - 1) / GE;               // requests for the NT entries
+    constexpr int NS = (NT + 2 + GE - 1) / GE;           // requests for the NT + 2 bias sums of round 2
+    const int tl = gl % GE;
+    const bool first_row = G <= 16 || gl < 16;           // lane 0 adds the bias sums: its row alone fetches them
     // ---- round 1
     const __amdgpu_buffer_rsrc_t rtab =                  // ends with the last tile's table: entries of tiles past it read as 0
         __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(h.tab), 0, h.ntiles * h.nbins * 4, 0x00020000);
-    int32_t ent[NT];
+    int32_t own[NS];                                     // lane tl's entries: of tiles tl, GE + tl, ... - one request per GE tiles
 #pragma unroll
-    for (int t = 0; t < NT; ++t) ent[t] = (int32_t)buf_load_word(rtab, (t * h.nbins + row) * 4);
+    for (int i = 0; i < NS; ++i) own[i] = i < NE ? (int32_t)buf_load_word(rtab, ((i * GE + tl) * h.nbins + row) * 4) : 0;
     int32_t err = (int32_t)buf_load_word(wt_rsrc(h.err), 0);
     __builtin_amdgcn_sched_barrier(0);
     warm_args_land(warm);                                // the struct's lines: first needed here
     const int roff = (row * D + d0) * 4;
     Frag<VEC> w, mrow, vrow;
-    float bw = 0.f, mb = 0.f, vb = 0.f;
+    uint32_t b3 = 0;
     if constexpr (!WRITE) {
         const int ow = a.frozen_rows ? BUF_NONE : roff;
         const int om = (a.frozen_rows || a.opt != 0) ? BUF_NONE : roff;
         w = buf_load_frag<VEC>(wt_rsrc(a.w), ow);
         mrow = buf_load_frag<VEC>(wt_rsrc(a.m), om);
         vrow = buf_load_frag<VEC>(wt_rsrc(a.v), om);
-        const int ob = (gl == 0 && !a.frozen_bias) ? row * 4 : BUF_NONE;
-        const int obm = (gl == 0 && !a.frozen_bias && a.opt == 0) ? row * 4 : BUF_NONE;
-        bw = __uint_as_float(buf_load_word(wt_rsrc(a.bias_w), ob));
-        mb = __uint_as_float(buf_load_word(wt_rsrc(a.bias_m), obm));
-        vb = __uint_as_float(buf_load_word(wt_rsrc(a.bias_v), obm));
+        // the three bias words in one request: lanes 0, 1, 2 of the group read bias_w, bias_m, bias_v (every other lane, and
+        // every lane where there are no moments, bias_w again: always a valid address, no branch); lane 0 gets them below
+        const bool mom = (a.opt == 0) & !a.frozen_bias;  // the moments are read where they are used, as before
+        uint64_t pw = (uint64_t)a.bias_w, pm = (uint64_t)a.bias_m, pv = (uint64_t)a.bias_v;
+        asm volatile("" : "+s"(pw), "+s"(pm), "+s"(pv));  // the three pointers as values in SGPRs: a select between them is then
+        uint64_t bp = pw;                                //   a select, not a load of the struct at a per-lane address
+        bp = (mom & (gl % 3 == 1)) ? pm : bp;
+        bp = (mom & (gl % 3 == 2)) ? pv : bp;
+        typedef const float __attribute__((address_space(1))) gfloat;   // a global load: counted in order with the buffer loads
+        b3 = __float_as_uint(reinterpret_cast<gfloat*>(bp)[row]);
     }
     __builtin_amdgcn_sched_barrier(0);                   // everything above is issued before the error word is looked at
     asm volatile("" : "+v"(err) : : "memory");
     if (err) return;                                     // a voided step: the tables' contents are not to be trusted as addresses
     // ---- round 2: addresses from the entries alone
+    int32_t ent[NT];
+    unrolled<NT>([&](auto tc) {
+        constexpr int t = decltype(tc)::value;
+        ent[t] = (int32_t)group_bcast<G, t % GE>((uint32_t)own[t / GE]);
+    });
     int s0 = -1, s1 = -1, nk1 = 0;                       // the first two k = 1 continuation pieces (entry index), how many there are
     bool deep = false, touched = false;
 #pragma unroll
@@ -1529,46 +1565,63 @@ __device__ __forceinline__ void dense_tiles_rounds(const TileDenseLaunch& L, con
     Frag<VEC> tot, c0, c1;
 #pragma unroll
     for (int q = 0; q < VEC; ++q) tot.v[q] = 0.f;
-    float gb = 0.f, cb0 = 0.f, cb1 = 0.f;
+    float gb = 0.f;
+    uint32_t sb[NS];                                     // slot i * GE + tl's bias sum, in the first row's lanes
 #pragma unroll
     for (int t0 = 0; t0 < NT; t0 += NB) {
         Frag<VEC> x[NB];
-        float xb[NB];
+        if (t0 == 0) {                                   // the 4-byte request(s) first: the piece adds below then wait load by load
+#pragma unroll
+            for (int i = 0; i < NS; ++i) {               // own[i] is 0 from tile ntiles on, and there is no own entry past NT
+                const int slot = i * GE + tl;
+                const int32_t e = own[i];
+                int at = (e >> 16) ? slot * 1024 + (e & 0xffff) : -1;
+                at = slot == NT ? s0 : slot == NT + 1 ? s1 : at;
+                sb[i] = buf_load_word(rgb, (at >= 0 && first_row) ? at * 4 : BUF_NONE);
+            }
+        }
 #pragma unroll
         for (int t = 0; t < NB; ++t) {
             const int32_t e = ent[t0 + t];
             const int j = (t0 + t) * 1024 + (e & 0xffff);
             x[t] = buf_load_frag<VEC>(rg, (e >> 16) ? (j * D + d0) * 4 : BUF_NONE);
-            xb[t] = __uint_as_float(buf_load_word(rgb, ((e >> 16) && gl == 0) ? j * 4 : BUF_NONE));
         }
         if (t0 == 0) {
             c0 = buf_load_frag<VEC>(rg, s0 >= 0 ? (s0 * D + d0) * 4 : BUF_NONE);
-            cb0 = __uint_as_float(buf_load_word(rgb, (s0 >= 0 && gl == 0) ? s0 * 4 : BUF_NONE));
             c1 = buf_load_frag<VEC>(rg, s1 >= 0 ? (s1 * D + d0) * 4 : BUF_NONE);
-            cb1 = __uint_as_float(buf_load_word(rgb, (s1 >= 0 && gl == 0) ? s1 * 4 : BUF_NONE));
         }
         __builtin_amdgcn_sched_barrier(0);               // the batch is in flight before its first piece is added
+        unrolled<NT>([&](auto tc) {                      // the heads' bias sums in tile order (lane 0's sum is the one used)
+            constexpr int t = decltype(tc)::value;
+            if (t >= t0 && t < t0 + NB) gb += __uint_as_float(group_bcast<G, t % GE>(sb[t / GE]));
+        });
 #pragma unroll
         for (int t = 0; t < NB; ++t) {                   // head pieces, added in tile order
 #pragma unroll
             for (int q = 0; q < VEC; ++q) tot.v[q] += x[t].v[q];
-            gb += xb[t];
         }
     }
     if (nk1 <= 2 && !deep) {                             // round k = 1 by tile, and there is no round k = 2
 #pragma unroll
         for (int q = 0; q < VEC; ++q) tot.v[q] += c0.v[q];
-        gb += cb0;
+        gb += __uint_as_float(group_bcast<G, NT % GE>(sb[NT / GE]));
 #pragma unroll
         for (int q = 0; q < VEC; ++q) tot.v[q] += c1.v[q];
-        gb += cb1;
+        gb += __uint_as_float(group_bcast<G, (NT + 1) % GE>(sb[(NT + 1) / GE]));
     } else {                                             // hot rows: round-major, tile-minor from k = 1 (see the general form)
         for (int k = 1;; ++k) {
             bool more = false;
+            uint32_t yb[NE];                             // tile i * GE + tl's k-th continuation bias sum
+#pragma unroll
+            for (int i = 0; i < NE; ++i) {
+                const int32_t e = own[i];
+                const int j = (i * GE + tl) * 1024 + (e & 0xffff);
+                const int pp = (j / EPB + k) * EPB;
+                yb[i] = buf_load_word(rgb, (pp < j + (e >> 16) && first_row) ? pp * 4 : BUF_NONE);
+            }
 #pragma unroll
             for (int t0 = 0; t0 < NT; t0 += NB) {
                 Frag<VEC> y[NB];
-                float yb[NB];
 #pragma unroll
                 for (int t = 0; t < NB; ++t) {
                     const int32_t e = ent[t0 + t];
@@ -1576,15 +1629,17 @@ __device__ __forceinline__ void dense_tiles_rounds(const TileDenseLaunch& L, con
                     const int pp = (j / EPB + k) * EPB;
                     const bool has = pp < j + (e >> 16);
                     y[t] = buf_load_frag<VEC>(rg, has ? (pp * D + d0) * 4 : BUF_NONE);
-                    yb[t] = __uint_as_float(buf_load_word(rgb, (has && gl == 0) ? pp * 4 : BUF_NONE));
                     more = more || has;
                 }
 #pragma unroll
                 for (int t = 0; t < NB; ++t) {
 #pragma unroll
                     for (int q = 0; q < VEC; ++q) tot.v[q] += y[t].v[q];
-                    gb += yb[t];
                 }
+                unrolled<NT>([&](auto tc) {
+                    constexpr int t = decltype(tc)::value;
+                    if (t >= t0 && t < t0 + NB) gb += __uint_as_float(group_bcast<G, t % GE>(yb[t / GE]));
+                });
             }
             if (!more) break;
         }
@@ -1612,6 +1667,8 @@ __device__ __forceinline__ void dense_tiles_rounds(const TileDenseLaunch& L, con
             }
             store_frag_p<VEC>(a.w, rfl, d0, D, w, wt & TFR_WT_ROWS);
         }
+        float bw = __uint_as_float(b3);                  // lane 0's own word; its neighbours' come while the group is whole
+        float mb = __uint_as_float(group_bcast<G, 1>(b3)), vb = __uint_as_float(group_bcast<G, 2>(b3));
         if (gl == 0 && !a.frozen_bias) {
             const bool wb = wt & TFR_WT_BIAS;
             if (a.opt == 0) {
