@@ -610,6 +610,67 @@ int tfr_knn_weighted_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t* s
                           int64_t* row_chunk, int64_t* lds_bytes, int32_t* look_ahead);
 const char* tfr_knn_last_error(void);
 
+/* ---- user-based nearest neighbours (UserKNN) from the same interaction matrix - DESIGN §36 -----------------------------------
+ *      X: the binary user x item matrix, a CSR pattern [n_users, n_items] under the rules of tfr_knn_load (rows strictly
+ *      increasing, no values).  d_u = the items of user u, c_uv = the items both u and v have.  sim(u -> v) comes from the
+ *      three integers (c_uv, d_u, d_v) exactly as tfr_knn's similarity comes from (c_ij, n_i, n_j): metric 0 cosine, 1 jaccard,
+ *      2 count, in float64 with IEEE operations, rounded once to float32; the rules for shrink are the same.
+ *      The neighbours of u: the K users v != u with c_uv > 0 that have the largest tfr_topk key (similarity descending, then
+ *      id ascending); rows with fewer are padded with user -1 / score -INFINITY.  1 <= K <= 256.  Counts are integers: the
+ *      lists are bit-identical run to run.
+ *          score(u, j) = sum over u's kept neighbours v in list order, slot 0 first, of s(u -> v) for the v with j in N(v)
+ *      A float32 add chain from +0.  Every item of the catalogue is a candidate; one without evidence scores exactly +0 and
+ *      is ordered by id like any tie.  The sum is NOT divided by the sum of the similarities: a constant per user moves no
+ *      ranking, and without it the chain is a pure sum of stored float32 values.
+ *      tfr_uknn_topk / tfr_uknn_topk_lists / tfr_uknn_rank_items are tfr_topk / tfr_rank_items on these scores, word for word
+ *      as their tfr_knn_* namesakes: 1 <= k <= 256, exclusion CSR aligned with the queries with non-decreasing rows, the key,
+ *      the padding, -1 for an excluded target, target rows strictly increasing, duplicate users allowed, a NaN score never
+ *      returned and never ranked, and 0 <= rank < k exactly when tfr_uknn_topk(k) returns the target, at that position.
+ *      tfr_uknn_load takes the user CSR and builds its transpose; a second load replaces the first and forgets the lists.
+ *      tfr_uknn_fit computes the [n_users, K] lists, which stay on the device.  tfr_uknn_get_neighbours copies rows
+ *      [row_lo, row_lo + n_rows) out; tfr_uknn_set_neighbours writes them from host arrays of the same shape (rows never
+ *      written are empty): ids in [-1, n_users), -1 is padding, no row lists itself or repeats a user, the scores of real ids
+ *      are finite.  tfr_uknn_topk and tfr_uknn_rank_items query resident users through their lists.
+ *      tfr_uknn_topk_lists queries n users known only by a list L (a CSR from 0 with strictly increasing rows): the neighbours
+ *      of L are the K resident users v with |L n N(v)| > 0 and the largest key of sim computed from (|L n N(v)|, |L|, d_v).
+ *      Nothing is left out as "self": a resident user whose row equals L is simply its best neighbour.  The score is the
+ *      same chain over these neighbours.  This entry needs a load, not a fit, and ignores fitted or set lists.
+ *      Host pointers; every call synchronises.  Checked on the host before any device work (the model is left as it was):
+ *      TFR_ERR_ARG for K or k outside [1, 256], an unknown metric, a shrink that is negative or not finite, a shrink with
+ *      metric 2, more than 16384 * min(256, 8192 / K) users (create: the fit and the list search), a catalogue of more than
+ *      8192 * min(256, 8192 / k) items (top-K; tfr_uknn_plan), an indptr that does not start at 0 (user and list CSR) or
+ *      decreases, a row out of order, a window outside the n_users rows, a set_neighbours row that lists itself, repeats a
+ *      user or carries a score that is not finite; TFR_ERR_OOB for an id out of range; TFR_ERR_STATE for fit and top-K of
+ *      lists before a load, and for get_neighbours, top-K and ranking before a fit or set_neighbours (those two also before a
+ *      load).  n = 0 and rows without targets are no-ops.  scores_out may be NULL. */
+typedef struct tfr_uknn tfr_uknn;
+int tfr_uknn_create(tfr_uknn** out, int64_t n_users, int64_t n_items, int32_t K, int32_t metric /* 0 cosine, 1 jaccard, 2 count */,
+                    double shrink, int32_t device);
+int tfr_uknn_destroy(tfr_uknn* m);
+int tfr_uknn_load(tfr_uknn* m, const int64_t* indptr /* [n_users+1] */, const int32_t* items);
+int tfr_uknn_fit(tfr_uknn* m, float* elapsed_ms /* may be NULL */);
+int tfr_uknn_get_neighbours(tfr_uknn* m, int64_t row_lo, int64_t n_rows, int32_t* users_out /* [n_rows,K], may be NULL */,
+                            float* scores_out /* [n_rows,K], may be NULL */);
+int tfr_uknn_set_neighbours(tfr_uknn* m, int64_t row_lo, int64_t n_rows, const int32_t* users, const float* scores);
+int tfr_uknn_topk(tfr_uknn* m, const int32_t* users, int64_t n, int32_t k,
+                  const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                  int32_t* items_out /* [n,k] */, float* scores_out /* [n,k], may be NULL */);
+int tfr_uknn_topk_lists(tfr_uknn* m, const int64_t* list_indptr /* [n+1] */, const int32_t* list_items, int64_t n, int32_t k,
+                        const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                        int32_t* items_out, float* scores_out);
+int tfr_uknn_rank_items(tfr_uknn* m, const int32_t* users, int64_t n,
+                        const int64_t* tgt_indptr /* [n+1] */, const int32_t* tgt_items,
+                        const int64_t* excl_indptr /* [n+1] or NULL */, const int32_t* excl_items,
+                        int32_t* ranks_out /* [tgt_indptr[n] - tgt_indptr[0]] */);
+/* host-only, no device: what the launcher of the fit (which = 0: n_cols the users, k is K, n_rows the users), of the scoring
+ * (which = 1: n_cols the items, k the query's k, n_rows the queries) or of the neighbour search of query lists (which = 2:
+ * n_cols the users, k is K, n_rows the lists) will do - columns per slice, slices, rows per chunk, LDS bytes per workgroup
+ * (the larger of that kernel and the merge), and how many list entries a wave takes at once (fit and search: entries of the
+ * row whose bounds are fetched together; scoring: neighbour slots searched side by side).  Outputs may be NULL. */
+int tfr_uknn_plan(int64_t n_cols, int32_t k, int64_t n_rows, int32_t which, int32_t* slice_width, int32_t* slices,
+                  int64_t* row_chunk, int64_t* lds_bytes, int32_t* look_ahead);
+const char* tfr_uknn_last_error(void);
+
 /* ---- EASE (Steck 2019, "Embarrassingly Shallow Autoencoders"): a dense item x item model in closed form - DESIGN §32 ----------
  *      X: the binary user x item matrix, a CSR pattern [n_users, n_items] under the rules of tfr_knn_load (rows strictly
  *      increasing, no values).  n_i = the users of item i, c_ij = the users who have both i and j.

@@ -15,6 +15,7 @@ from . import svdpp
 from .als import MangakiALS3
 from .ials import ImplicitALS
 from .itemknn import ItemKNN
+from .userknn import UserKNN
 from .rp3beta import WeightedItemKNN, RP3beta
 from .ease import EASE
 from .slim import SLIM
@@ -22,4 +23,4 @@ from . import ranking, neighbours, bf16
 from .ranking import ranking_metrics, evaluate_ranking
 
 __all__ = ["SvdModel", "device_copy_rate", "rated_matrix", "TfrError", "OutOfRangeError", "_lib", "dataio", "graph", "ops", "config", "cats", "adaptive_test", "finetune",
-           "FmModel", "SvdppModel", "svdpp", "MangakiALS3", "ImplicitALS", "ItemKNN", "WeightedItemKNN", "RP3beta", "EASE", "SLIM", "ranking", "ranking_metrics", "evaluate_ranking", "neighbours", "bf16"]
+           "FmModel", "SvdppModel", "svdpp", "MangakiALS3", "ImplicitALS", "ItemKNN", "UserKNN", "WeightedItemKNN", "RP3beta", "EASE", "SLIM", "ranking", "ranking_metrics", "evaluate_ranking", "neighbours", "bf16"]

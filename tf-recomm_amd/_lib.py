@@ -185,6 +185,12 @@ SIGNATURES = {
     "tfr_knn_fit_weighted": (C.c_int, [_p, C.POINTER(C.c_uint64), _f64p, _f64p, C.c_int32, _f32p]),
     "tfr_knn_weighted_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, _i32p, _i32p, _i64p, _i64p, _i32p]),
     "tfr_knn_last_error": (C.c_char_p, []),
+    "tfr_uknn_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32]),
+    "tfr_uknn_fit": (C.c_int, [_p, _f32p]),
+    "tfr_uknn_get_neighbours": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _f32p]),
+    "tfr_uknn_set_neighbours": (C.c_int, [_p, C.c_int64, C.c_int64, _i32p, _f32p]),
+    "tfr_uknn_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i64p, _i32p]),
+    "tfr_uknn_last_error": (C.c_char_p, []),
     "tfr_ease_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_double, C.c_int32]),
     "tfr_ease_gram": (C.c_int, [_p]),
     "tfr_ease_set_gram": (C.c_int, [_p, _f64p]),
@@ -275,7 +281,7 @@ SIGNATURES = {
 }
 
 # what the item x item families share (item_lists.py): the same five signatures under each prefix
-for _family in ("knn", "ease", "slim"):
+for _family in ("knn", "ease", "slim", "uknn"):
     SIGNATURES.update({
         "tfr_%s_destroy" % _family: (C.c_int, [_p]),
         "tfr_%s_load" % _family: (C.c_int, [_p, _i64p, _i32p]),

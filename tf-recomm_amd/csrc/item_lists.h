@@ -13,6 +13,10 @@
 //     load_fn, not_fitted      what the state messages name
 //     args(const Model*)       an argument block with the model's own fields set
 //     launch<MODE>(Args, s)    the scoring launch of a mode (0 top-K, 1 target keys, 2 rank counts)
+// and, only where the lists of unknown users need work of the family's own before they are scored (UserKNN, userknn.{h,hip},
+// §36: their neighbours are searched among the resident users), the pair ListsHook finds:
+//     lists_refuse(const Model*)          NULL, or why top-K of lists cannot run in this state (default: not fitted)
+//     lists_prepare(err, Model*, n)       after the n lists are staged in q_ptr / q_ids, before the scoring (default: nothing)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -22,6 +26,7 @@
 #include <algorithm>
 #include <initializer_list>
 #include <new>
+#include <type_traits>
 #include <vector>
 #include "tfrecomm.h"
 #include "devbuf.h"
@@ -401,6 +406,19 @@ int topk_users(ErrText& err, typename F::Model* m, const int32_t* users, int64_t
     return topk_run<F>(err, m, "top-K", ListQuery{m->q_users, m->pu, m->items}, n, k, excl_indptr, excl_items, items_out, scores_out);
 }
 
+// what top-K of lists asks of the state, and what runs between the staging of the lists and their scoring: a fitted model
+// and nothing, unless the family names lists_refuse and lists_prepare
+template <class F, class = void>
+struct ListsHook {
+    static const char* refuse(const typename F::Model* m) { return m->fitted ? nullptr : F::not_fitted; }
+    static int prepare(ErrText&, typename F::Model*, int64_t) { return TFR_OK; }
+};
+template <class F>
+struct ListsHook<F, std::void_t<decltype(&F::lists_prepare)>> {
+    static const char* refuse(const typename F::Model* m) { return F::lists_refuse(m); }
+    static int prepare(ErrText& err, typename F::Model* m, int64_t n) { return F::lists_prepare(err, m, n); }
+};
+
 // the body of tfr_*_topk_lists: users known by their lists alone; needs no load
 template <class F>
 int topk_lists(ErrText& err, typename F::Model* m, const int64_t* list_indptr, const int32_t* list_items, int64_t n, int32_t k,
@@ -408,7 +426,7 @@ int topk_lists(ErrText& err, typename F::Model* m, const int64_t* list_indptr, c
     if (!m) return fail(err, TFR_ERR_ARG, "null model");
     if (n < 0) return fail(err, TFR_ERR_ARG, "top-K of lists: negative n");
     if (int rc = check_k(err, "top-K of lists", k)) return rc;
-    if (!m->fitted) return fail(err, TFR_ERR_STATE, "top-K of lists: %s", F::not_fitted);
+    if (const char* why = ListsHook<F>::refuse(m)) return fail(err, TFR_ERR_STATE, "top-K of lists: %s", why);
     if (n == 0) return TFR_OK;
     if (!items_out) return fail(err, TFR_ERR_ARG, "top-K of lists: null items_out");
     if (int rc = check_csr(err, "top-K of lists", "list", true, true, list_indptr, list_items, n, m->n_items)) return rc;
@@ -416,6 +434,7 @@ int topk_lists(ErrText& err, typename F::Model* m, const int64_t* list_indptr, c
         if (int rc = check_csr(err, "top-K of lists", "exclusion", false, false, excl_indptr, excl_items, n, m->n_items)) return rc;
     LISTCHK(err, hipSetDevice(m->device));
     if (int rc = stage_csr(err, m, m->q_ptr, m->q_ids, list_indptr, list_items, n)) return rc;
+    if (int rc = ListsHook<F>::prepare(err, m, n)) return rc;
     return topk_run<F>(err, m, "top-K of lists", ListQuery{nullptr, m->q_ptr, m->q_ids}, n, k, excl_indptr, excl_items, items_out, scores_out);
 }
 

@@ -63,6 +63,17 @@ inline bool knn_plan(int which, int64_t n_items, int k, int64_t n_rows, KnnPlan*
     return true;
 }
 
+enum { KNN_COSINE = 0, KNN_JACCARD = 1, KNN_COUNT = 2 };
+
+// float64 with IEEE operations from the three integers, rounded once to float32 (userknn.hip forms its similarities with it too)
+__device__ __forceinline__ float knn_sim(int metric, uint32_t c, int64_t ni, int64_t nj, double shrink) {
+    double s;
+    if (metric == KNN_COSINE) s = (double)c / (sqrt((double)ni * (double)nj) + shrink);
+    else if (metric == KNN_JACCARD) s = (double)c / ((double)(ni + nj - (int64_t)c) + shrink);
+    else s = (double)c;
+    return __double2float_rn(s);
+}
+
 struct KnnFitArgs {
     const int64_t* pu; const int32_t* items;             // the user rows, each strictly increasing
     const int64_t* pi; const int32_t* iu;                // the item lists (users ascending)
@@ -71,6 +82,11 @@ struct KnnFitArgs {
     double shrink;
     int32_t K, slices, metric;
 };
+
+// k_knn_cooc<cap> over a grid of (rows, slices), for a caller outside itemknn.hip.  Nothing in the kernel ties "item" to the
+// catalogue: with pi / iu the user rows, pu / items the item lists and n_items the user count it counts the items two users
+// share - UserKNN's fit (userknn.hip).  cap is knn_fit_cap(K).
+void knn_launch_cooc(const KnnFitArgs& a, int cap, dim3 grid, hipStream_t s);
 
 struct KnnWFitArgs {
     const int64_t* pu; const int32_t* items;             // the user rows, each strictly increasing

@@ -40,17 +40,6 @@ using tfr::fail;
 using tfr::check_k;
 using tfr::window;
 
-enum { KNN_COSINE = 0, KNN_JACCARD = 1, KNN_COUNT = 2 };
-
-// float64 with IEEE operations from the three integers, rounded once to float32
-__device__ __forceinline__ float knn_sim(int metric, uint32_t c, int64_t ni, int64_t nj, double shrink) {
-    double s;
-    if (metric == KNN_COSINE) s = (double)c / (sqrt((double)ni * (double)nj) + shrink);
-    else if (metric == KNN_JACCARD) s = (double)c / ((double)(ni + nj - (int64_t)c) + shrink);
-    else s = (double)c;
-    return __double2float_rn(s);
-}
-
 // the weighted fit's similarity: the exact integer sum scaled by a power of two, then two float64 products left to right
 // (no add: nothing contracts into an fma), rounded once to float32
 __device__ __forceinline__ float knn_wsim(unsigned long long s, double unit, double row_scale, double col_scale) {
@@ -276,6 +265,10 @@ int run_fit(tfr_knn* m, const KnnPlan& p, Args a, void (*kernel)(Args), float* e
 }
 
 }  // namespace
+
+void knn_launch_cooc(const KnnFitArgs& a, int cap, dim3 grid, hipStream_t s) {
+    hipLaunchKernelGGL(cap == 256 ? k_knn_cooc<256> : k_knn_cooc<512>, grid, dim3(256), 0, s, a);
+}
 
 extern "C" {
 
