@@ -738,6 +738,64 @@ int tfr_ease_plan(int64_t n_items, int32_t k, int64_t n_rows, int32_t which, int
                   int32_t* look_ahead);
 const char* tfr_ease_last_error(void);
 
+/* ---- PureSVD (Cremonesi, Koren, Turrin 2010): the rank-d truncated SVD of the interaction matrix (tfr_psvd_*) ----
+ *      X is the binary user x item pattern (a CSR, rows strictly increasing), U x I.  With r = factors + oversample,
+ *      1 <= factors, 0 <= oversample, r <= 128 (anything else: TFR_ERR_ARG at create, the message names r), in float64
+ *      throughout:
+ *          V <- orth(V0)                                  V0 [I, r] is the caller's start block (no device RNG)
+ *          `iterations` times: W = X V, Z = X^T W, V <- orth(Z)
+ *          W = X V, T = W^T W, (lambda, Qe) = eig(T)      eigenvalues descending, equal ones by column index; each
+ *                                                         eigenvector's entry of largest magnitude (lowest index on a tie) > 0
+ *          sigma_j = sqrt(max(lambda_j, 0)), item factors Q = V Qe[:, :factors], user factors P = X Q
+ *      score(u, i) = p_u . q_i = (x_u V_d V_d^T)_i.  Every product with X is one kernel, out[row] = the sum of in[id] over
+ *      the row's list in list order (lists past 256 entries: 256 at a time, the chunks' sums then added in chunk
+ *      order), so P is bit for bit what tfr_psvd_fold_in gives for the list of a resident user.  orth is CholeskyQR
+ *      twice: S = Z^T Z (the Gram of tfr_ials_gram, same slice order), R = chol(S) upper, V = Z R^-1.  A pivot that is not
+ *      finite or not above 2^-44 times its column's entry of S (the block has fewer independent columns than r: r > rank X)
+ *      ends the call with TFR_ERR_ARG; the message names the orthonormalisation (0 = the start block's), the pass (1, 2) and
+ *      the column, nothing further runs, and the handle is loaded, not fitted: an earlier fit is forgotten.  eig is a cyclic Jacobi iteration in
+ *      one workgroup, round-robin pairs in a fixed order, rotating where |t_pq| > 2^-52 max|T|, until a sweep makes no
+ *      rotation; a rotation in sweep 30 is TFR_ERR_ARG.  tfr_psvd_sweeps: sweeps of the last eigen step, the clean one included.
+ *      All results are the same bits from run to run.
+ *
+ *      tfr_psvd_load: the user CSR (checked on the host first: a refused load leaves the model as it was); a load forgets
+ *      the factors.  tfr_psvd_fit: ms [3] (may be NULL) = device time of the products, of the orthonormalisations, of the
+ *      eigen step with the last products.  tfr_psvd_get: what = 0 sigma [factors], 1 Q [I, factors], 2 P [U, factors],
+ *      3 all r Ritz values lambda (TFR_ERR_STATE after set_factors).  tfr_psvd_set_factors: Q and sigma from a fitted model;
+ *      needs a load; P = X Q is recomputed.  tfr_psvd_residuals: out[j] = ||X^T (X q_j) - sigma_j^2 q_j||_2 / sigma_0^2 from
+ *      the factors as they stand (two products).  The stages alone: tfr_psvd_multiply (side 0: out [U, cols] = X in,
+ *      side 1: out [I, cols] = X^T in; 1 <= cols <= 128), tfr_psvd_orthonormalise (block [n, cols] in place; S_out, R_out
+ *      [2, cols, cols] of the two passes, may be NULL; needs no load), tfr_psvd_eig (T symmetric bit for bit; lambda_out [r],
+ *      Q_out [r, r] eigenvectors in columns; needs no load).  tfr_psvd_fold_in: p = x Q for n lists the model does not
+ *      hold (a CSR from 0, rows strictly increasing; an empty list gives zeros); out [n, factors] may be NULL: the rows stay
+ *      on the device for tfr_psvd_export_f32, which writes rows of Q (which = 0), P (1) or the last fold-in (2) as float32
+ *      into a device pointer of the caller.  TFR_ERR_STATE: fit, multiply, set_factors, residuals before a load; get,
+ *      residuals, fold_in, export_f32 before factors.  TFR_ERR_OOB: an id out of range. */
+typedef struct tfr_psvd tfr_psvd;
+int tfr_psvd_create(tfr_psvd** out, int64_t n_users, int64_t n_items, int32_t factors, int32_t oversample, int32_t device);
+int tfr_psvd_destroy(tfr_psvd* m);
+int tfr_psvd_load(tfr_psvd* m, const int64_t* indptr /* [n_users+1] */, const int32_t* items);
+int tfr_psvd_fit(tfr_psvd* m, const double* V0 /* [n_items,r] */, int32_t iterations, float* ms /* [3]; may be NULL */);
+int tfr_psvd_get(tfr_psvd* m, int32_t what, double* out);
+int tfr_psvd_sweeps(tfr_psvd* m, int32_t* out);
+int tfr_psvd_set_factors(tfr_psvd* m, const double* Q /* [n_items,factors] */, const double* sigma /* [factors] */);
+int tfr_psvd_residuals(tfr_psvd* m, double* out /* [factors] */);
+int tfr_psvd_multiply(tfr_psvd* m, int32_t side, const double* in, int32_t cols, double* out);
+/* the product kernel alone on a zeroed device block, `reps` times: ms_out [reps] device times (events); needs a load */
+int tfr_psvd_product_ms(tfr_psvd* m, int32_t side, int32_t cols, int32_t reps, float* ms_out);
+int tfr_psvd_orthonormalise(tfr_psvd* m, int64_t n, double* block /* [n,cols] */, int32_t cols, double* S_out, double* R_out);
+int tfr_psvd_eig(tfr_psvd* m, const double* T /* [r,r] */, int32_t r, double* lambda_out, double* Q_out);
+int tfr_psvd_fold_in(tfr_psvd* m, int64_t n, const int64_t* indptr /* [n+1] */, const int32_t* ids, double* out /* [n,factors] or NULL */);
+int tfr_psvd_export_f32(tfr_psvd* m, int32_t which, int64_t row_lo, int64_t n_rows, void* dst_devptr);
+/* The launch shapes, computed on the host (no device): r, the lanes of a wave that own columns (64 at every width: a wave
+ * per row, two columns per lane, the lanes past r / 2 masked), the chunk of a long list, the entries a wave loads ahead, the
+ * sweep cap, the largest LDS of the fit's launches, the float64 device bytes of a fit, and the slices of r * r doubles its
+ * Gram partial buffer holds: the larger of ceil(n / rows(n)) over the two sides, rows(n) the ALS Gram's slice rule, which is
+ * not monotonic in n.  Each out may be NULL.  TFR_ERR_ARG for what create refuses. */
+int tfr_psvd_plan(int64_t n_users, int64_t n_items, int32_t factors, int32_t oversample, int32_t* r, int32_t* lanes, int32_t* chunk,
+                  int32_t* ahead, int32_t* sweep_cap, int64_t* lds_bytes, int64_t* device_bytes, int64_t* gram_slices);
+const char* tfr_psvd_last_error(void);
+
 /* ---- SLIM (Ning & Karypis 2011, "Sparse Linear Methods for Top-N Recommender Systems"): elastic-net item weights - DESIGN §34 --
  *      X as for EASE.  A = X^T X + beta I in float64: exactly tfr_ease_gram's matrix with lambda = beta (beta >= 0, finite).
  *      For each item j the column w of W minimises

@@ -19,8 +19,9 @@ from .userknn import UserKNN
 from .rp3beta import WeightedItemKNN, RP3beta
 from .ease import EASE
 from .slim import SLIM
+from .puresvd import PureSVD
 from . import ranking, neighbours, bf16
 from .ranking import ranking_metrics, evaluate_ranking
 
 __all__ = ["SvdModel", "device_copy_rate", "rated_matrix", "TfrError", "OutOfRangeError", "_lib", "dataio", "graph", "ops", "config", "cats", "adaptive_test", "finetune",
-           "FmModel", "SvdppModel", "svdpp", "MangakiALS3", "ImplicitALS", "ItemKNN", "UserKNN", "WeightedItemKNN", "RP3beta", "EASE", "SLIM", "ranking", "ranking_metrics", "evaluate_ranking", "neighbours", "bf16"]
+           "FmModel", "SvdppModel", "svdpp", "MangakiALS3", "ImplicitALS", "ItemKNN", "UserKNN", "WeightedItemKNN", "RP3beta", "EASE", "SLIM", "PureSVD", "ranking", "ranking_metrics", "evaluate_ranking", "neighbours", "bf16"]

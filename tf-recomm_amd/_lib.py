@@ -201,6 +201,22 @@ SIGNATURES = {
     "tfr_ease_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, _i32p, _i32p, _i64p, _i64p, _i64p, _i32p, _i32p,
                                 _i64p, _i32p]),
     "tfr_ease_last_error": (C.c_char_p, []),
+    "tfr_psvd_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "tfr_psvd_destroy": (C.c_int, [_p]),
+    "tfr_psvd_load": (C.c_int, [_p, _i64p, _i32p]),
+    "tfr_psvd_fit": (C.c_int, [_p, _f64p, C.c_int32, _f32p]),
+    "tfr_psvd_get": (C.c_int, [_p, C.c_int32, _f64p]),
+    "tfr_psvd_sweeps": (C.c_int, [_p, _i32p]),
+    "tfr_psvd_set_factors": (C.c_int, [_p, _f64p, _f64p]),
+    "tfr_psvd_residuals": (C.c_int, [_p, _f64p]),
+    "tfr_psvd_multiply": (C.c_int, [_p, C.c_int32, _f64p, C.c_int32, _f64p]),
+    "tfr_psvd_product_ms": (C.c_int, [_p, C.c_int32, C.c_int32, C.c_int32, _f32p]),
+    "tfr_psvd_orthonormalise": (C.c_int, [_p, C.c_int64, _f64p, C.c_int32, _f64p, _f64p]),
+    "tfr_psvd_eig": (C.c_int, [_p, _f64p, C.c_int32, _f64p, _f64p]),
+    "tfr_psvd_fold_in": (C.c_int, [_p, C.c_int64, _i64p, _i32p, _f64p]),
+    "tfr_psvd_export_f32": (C.c_int, [_p, C.c_int32, C.c_int64, C.c_int64, _p]),
+    "tfr_psvd_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, _i32p, _i32p, _i32p, _i32p, _i32p, _i64p, _i64p, _i64p]),
+    "tfr_psvd_last_error": (C.c_char_p, []),
     "tfr_slim_create": (C.c_int, [C.POINTER(_p), C.c_int64, C.c_int64, C.c_double, C.c_int32]),
     "tfr_slim_gram": (C.c_int, [_p]),
     "tfr_slim_set_gram": (C.c_int, [_p, _f64p]),

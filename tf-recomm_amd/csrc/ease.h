@@ -113,6 +113,8 @@ struct EaseScoreArgs {
 // The launches another dense item x item family shares with EASE (SLIM: slim.hip); the kernels stay ease.hip's.
 // k_ease_gram over `slices` column slices of EASE_W_GRAM (ease_plan(0).slices); k_ease_score<mode> for a.n * a.slices waves.
 void ease_launch_gram(const EaseGramArgs& a, int32_t slices, hipStream_t s);
+// k_ease_gemm over the tiles of C, for a dense float64 product of another family (PureSVD: puresvd.hip)
+void ease_launch_gemm(const EaseGemmArgs& g, hipStream_t s);
 void ease_launch_score(int mode, const EaseScoreArgs& a, hipStream_t s);
 
 struct tfr_ease : tfr::ItemListModel {

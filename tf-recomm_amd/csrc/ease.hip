@@ -270,8 +270,7 @@ void launch_gemm(hipStream_t s, const double* A, int64_t lda, int ta, const doub
     EaseGemmArgs g;
     g.A = A; g.B = B; g.C = C; g.lda = lda; g.ldb = ldb; g.ldc = ldc;
     g.M = M; g.N = N; g.K = K; g.ta = ta; g.tb = tb; g.sign = sign; g.beta = beta; g.lower = lower; g.kskip = kskip;
-    const dim3 grid((unsigned)((N + EASE_TILE - 1) / EASE_TILE), (unsigned)((M + EASE_TILE - 1) / EASE_TILE));
-    hipLaunchKernelGGL(k_ease_gemm, grid, dim3(256), 0, s, g);
+    ease_launch_gemm(g, s);
 }
 
 void launch_copy(hipStream_t s, double* dst, int64_t ldd, const double* src, int64_t lds, int rows, int cols) {
@@ -357,6 +356,11 @@ int ease_reserve_f64(tfr_ease* m) {
 void ease_launch_gram(const EaseGramArgs& a, int32_t slices, hipStream_t s) {
     const dim3 g((unsigned)std::min<int64_t>(a.n_items, EASE_GRID_ROWS), (unsigned)slices);
     hipLaunchKernelGGL(k_ease_gram, g, dim3(256), 0, s, a);
+}
+
+void ease_launch_gemm(const EaseGemmArgs& g, hipStream_t s) {
+    const dim3 grid((unsigned)((g.N + EASE_TILE - 1) / EASE_TILE), (unsigned)((g.M + EASE_TILE - 1) / EASE_TILE));
+    hipLaunchKernelGGL(k_ease_gemm, grid, dim3(256), 0, s, g);
 }
 
 void ease_launch_score(int mode, const EaseScoreArgs& a, hipStream_t s) {

@@ -307,15 +307,7 @@ int ials_fail(int code, const char* fmt, ...) {
 
 // G = tab[side]^T tab[side] for any d <= 256, queued on the model's stream
 hipError_t queue_gram(tfr_ials* m, int side) {
-    const int64_t n = m->n[side], rows = gram_slice_rows(n), ns = (n + rows - 1) / rows;
-    const int d = m->d, nt = (d + GRAM_T - 1) / GRAM_T;
-    if (d <= GRAM_NARROW_D)
-        hipLaunchKernelGGL(k_ials_gram_narrow, dim3((unsigned)ns), dim3(256), 0, m->stream, m->tab[side].get(), n, d, rows, m->gram_partial.get());
-    else
-        hipLaunchKernelGGL(k_ials_gram_tiled, dim3((unsigned)(ns * nt * nt)), dim3(256), 0, m->stream, m->tab[side].get(), n, d, rows, nt,
-                           m->gram_partial.get());
-    hipLaunchKernelGGL(k_ials_gram_sum, dim3((unsigned)((d * d + 255) / 256)), dim3(256), 0, m->stream, m->gram_partial.get(), ns, d,
-                       m->G.get());
+    tfr::ials_launch_gram(m->tab[side].get(), m->n[side], m->d, m->gram_partial.get(), m->G.get(), m->stream);
     m->gram_of = side;
     return hipGetLastError();
 }
@@ -349,6 +341,17 @@ int finish_timed(tfr_ials* m, float* elapsed_ms) {
 }
 
 }  // namespace
+
+// The Gram launches for any caller (ials_model.h): G = T^T T of T [n, d], d <= 256, through `partial`
+void tfr::ials_launch_gram(const double* T, int64_t n, int d, double* partial, double* G, hipStream_t s) {
+    const int64_t rows = gram_slice_rows(n), ns = (n + rows - 1) / rows;
+    const int nt = (d + GRAM_T - 1) / GRAM_T;
+    if (d <= GRAM_NARROW_D)
+        hipLaunchKernelGGL(k_ials_gram_narrow, dim3((unsigned)ns), dim3(256), 0, s, T, n, d, rows, partial);
+    else
+        hipLaunchKernelGGL(k_ials_gram_tiled, dim3((unsigned)(ns * nt * nt)), dim3(256), 0, s, T, n, d, rows, nt, partial);
+    hipLaunchKernelGGL(k_ials_gram_sum, dim3((unsigned)((d * d + 255) / 256)), dim3(256), 0, s, partial, ns, d, G);
+}
 
 extern "C" {
 

@@ -66,4 +66,7 @@ inline IalsArgs ials_side_args(const tfr_ials* m, int side) {
 // queued on the model's stream; each returns hipGetLastError() after its launches
 hipError_t ials_cg_queue_fit(const IalsArgs& a, hipStream_t s); // a.cg_steps steps for every entity of the block, from a.G
 hipError_t ials_cg_queue_loss_users(tfr_ials* m);              // m->per_user, from m->G = Y^T Y
+// The Gram launches of ials.hip for another family (PureSVD: puresvd.hip): G [d, d] = T^T T of T [n, d], d <= 256,
+// in the slice order of gram_slice_rows(n); partial holds ceil(n / gram_slice_rows(n)) * d * d doubles.
+void ials_launch_gram(const double* T, int64_t n, int d, double* partial, double* G, hipStream_t s);
 }  // namespace tfr

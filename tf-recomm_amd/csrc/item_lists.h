@@ -304,8 +304,10 @@ int destroy_handle(M* m, std::initializer_list<hipEvent_t> events) {
 // The user CSR.  Everything is checked and the transpose built on the host before any device work, so a refused load
 // leaves the model as it was.  Past that the model forgets what it was fitted to - `loaded`, `fitted`, and what the
 // family's `forget` clears - before the first copy.
+// `item_ptr`, where given, receives the item lists' indptr [n_items + 1] on TFR_OK (a family that plans from it).
 template <class Forget>
-int load_lists(ErrText& err, ItemListModel* m, const int64_t* indptr, const int32_t* items, Forget forget) {
+int load_lists(ErrText& err, ItemListModel* m, const int64_t* indptr, const int32_t* items, Forget forget,
+               std::vector<int64_t>* item_ptr = nullptr) {
     if (!m) return fail(err, TFR_ERR_ARG, "null model");
     const int64_t nu = m->n_users, ni = m->n_items;
     if (int rc = check_csr(err, "load", "user", true, true, indptr, items, nu, ni)) return rc;
@@ -335,6 +337,7 @@ int load_lists(ErrText& err, ItemListModel* m, const int64_t* indptr, const int3
         LISTCHK(err, hipMemcpy(m->items, items, (size_t)nnz * 4, hipMemcpyHostToDevice));
         LISTCHK(err, hipMemcpy(m->iu, iu.data(), (size_t)nnz * 4, hipMemcpyHostToDevice));
     }
+    if (item_ptr) item_ptr->swap(pi);
     m->loaded = true;
     return TFR_OK;
 }
