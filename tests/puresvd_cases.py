@@ -5,6 +5,7 @@ import functools
 
 import numpy as np
 
+from tests import list_paths as LP
 from tests import puresvd_ref as R
 
 
@@ -95,7 +96,7 @@ def repeated_column_block():
 
 
 # ----------------------------------------------------------------------------- eigen step
-EIG_SIZES = (1, 2, 3, 37, 128)
+EIG_SIZES = LP.PSVD_EIG_SIZES                             # tests/list_paths.py says what each size is there for
 
 
 @functools.lru_cache(None)
@@ -152,6 +153,24 @@ def random_case():
     return dict(nu=nu, ni=ni, indptr=indptr, items=pairs[:, 1].astype(np.int32))
 
 
+WIDE_FIT = dict(factors=LP.PSVD_WIDE_FIT[0], oversample=LP.PSVD_WIDE_FIT[1], iterations=4)
+
+
+@functools.lru_cache(None)
+def wide_case():
+    """300 x 280 at density 0.15: user 1 and item 1 are empty; user 0 has every other item (279) and item 0 is held by every
+    other user (299), so both lists are longer than the chunk and are cut inside a fit; both sides take several Gram slices"""
+    nu, ni = 300, 280
+    X = np.random.RandomState(6).random_sample((nu, ni)) < 0.15
+    X[0, :] = True
+    X[:, 0] = True
+    X[1, :] = False
+    X[:, 1] = False
+    rows, cols = np.nonzero(X)
+    indptr = np.searchsorted(rows, np.arange(nu + 1)).astype(np.int64)
+    return dict(nu=nu, ni=ni, indptr=indptr, items=cols.astype(np.int32))
+
+
 def dense(case):
     X = np.zeros((case["nu"], case["ni"]))
     X[np.repeat(np.arange(case["nu"]), np.diff(case["indptr"])), case["items"]] = 1
@@ -164,7 +183,7 @@ def start_block(case, fit, seed=0):
 
 @functools.lru_cache(None)
 def fit_ref(which, dtype=np.float64):
-    case, fit = (block_case(), BLOCK_FIT) if which == "block" else (random_case(), RANDOM_FIT)
+    case, fit = {"block": (block_case(), BLOCK_FIT), "random": (random_case(), RANDOM_FIT), "wide": (wide_case(), WIDE_FIT)}[which]
     return R.fit(case["indptr"], case["items"], case["nu"], case["ni"], fit["factors"], fit["oversample"], fit["iterations"],
                  start_block(case, fit), plan()["chunk"], dtype)
 

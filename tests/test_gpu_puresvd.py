@@ -4,8 +4,10 @@ orthonormalisation, the eigen step, a planted fit with an exact answer, a random
 handle keeps between calls.  The constants are tests/puresvd_ref.py's, measured on the CPU by tests/test_puresvd_host.py.
 
 MEASURED on an MI355X (the RATIO lines, run with -s; DESIGN §37 has the table): orth 1.317 of K 11, orthogonality 1.458 of
-K_ORTH 12, eigen step 1.536 of K_EIG 11, block fit 1.788 / 0.965 / 0.966 of K_BLOCK 39 / 9 / 16, random fit sigma 1.070 of
-K_SIGMA 42."""
+K_ORTH 12, eigen step 1.536 of K_EIG 11 (T of the random fit; the planted inputs over tests/list_paths.py PSVD_EIG_SIZES give
+0.600 at r = 4, 1.313 at 37, 1.023 at 99, 1.071 at 100, 1.056 at 101, 1.161 at 127, 1.125 at 128, in at most 11 sweeps), block
+fit 1.788 / 0.965 / 0.966 of K_BLOCK 39 / 9 / 16, random fit sigma 1.070 of K_SIGMA 42, wide fit (r = 101, 9 sweeps) sigma
+3.190 of K_SIGMA_WIDE 256 and orthogonality 1.000 of K_ORTH 12."""
 import numpy as np
 import pytest
 
@@ -28,7 +30,8 @@ def _open(case, fit, load=True):
 
 
 def _fitted(which):
-    case, fit = (PC.block_case(), PC.BLOCK_FIT) if which == "block" else (PC.random_case(), PC.RANDOM_FIT)
+    case, fit = {"block": (PC.block_case(), PC.BLOCK_FIT), "random": (PC.random_case(), PC.RANDOM_FIT),
+                 "wide": (PC.wide_case(), PC.WIDE_FIT)}[which]
     m = _open(case, fit)
     m.fit(start=PC.start_block(case, fit))
     return m, case, fit
@@ -169,6 +172,73 @@ def test_the_random_fit():
     assert np.array_equal(bits(P), bits(R.spmm(case["indptr"], case["items"], Q, ch)))
     want = R.residuals(case["indptr"], case["items"], case["nu"], case["ni"], Q, sigma, ch)
     assert (np.abs(res - want) <= R.residual_bound(case["ni"], want, sigma)).all(), (res, want)
+
+
+# ----------------------------------------------------------------------------- 5b. a wide fit, and fold-ins of long lists
+def _lists_of(rs, n_items, lengths):
+    rows = [np.sort(rs.choice(n_items, n, replace=False)).astype(np.int32) for n in lengths]
+    return np.concatenate(([0], np.cumsum(lengths))).astype(np.int64), np.concatenate(rows).astype(np.int32)
+
+
+def test_the_wide_fit_and_long_fold_ins():
+    """300 x 280, r = 101 (tests/puresvd_cases.py wide_case): inside a fit the product runs at an odd width with both
+    orientations' longest list cut into chunks, every Gram takes three slices, the eigen step keeps its rotations in global
+    scratch with index r sitting out.  Then fold-ins whose lists need a chunk plan of their own, which must leave the model's
+    chunk tables as they were."""
+    m, case, fit = _fitted("wide")
+    ref = PC.fit_ref("wide")
+    indptr, items, nu, ni, f = case["indptr"], case["items"], case["nu"], case["ni"], fit["factors"]
+    ch, cap = PC.plan()["chunk"], PC.plan()["sweep_cap"]
+    assert np.diff(indptr)[0] > ch
+    with m:
+        sigma, Q, P, sweeps = m.singular_values, m.item_factors, m.user_factors, m.sweeps()
+        assert np.array_equal(bits(P), bits(R.spmm(indptr, items, Q, ch)))
+        assert 1 <= sweeps < cap, sweeps
+        rho = float(np.abs(sigma - ref["sigma"]).max() / ref["sigma"][0]) / R.EPS
+        orthogonal = float(np.abs(Q.T @ Q - np.eye(f)).max()) / (R.EPS * (f + fit["oversample"]))
+        print("RATIO wide fit device sweeps %d sigma %.3f (K_SIGMA_WIDE %d) orthogonal %.3f (K_ORTH %d)" % (
+            sweeps, rho, R.K_SIGMA_WIDE, orthogonal, R.K_ORTH))
+        assert rho <= R.K_SIGMA_WIDE and orthogonal <= R.K_ORTH, (rho, orthogonal)
+        m.fit(start=PC.start_block(case, fit))
+        again = (m.singular_values, m.item_factors, m.user_factors)
+        assert all(np.array_equal(bits(a), bits(b)) for a, b in zip((sigma, Q, P), again))   # two fits: the same bits
+
+        rs = np.random.RandomState(12)
+        B = [PC.product_block(ni, 7), PC.product_block(nu, 7)]
+        before = [m.multiply(B[0]), m.multiply(B[1], transpose=True)]
+        tptr, tids = R.transpose_lists(indptr, items, nu, ni)
+        assert np.array_equal(bits(before[0]), bits(R.spmm(indptr, items, B[0], ch)))
+        assert np.array_equal(bits(before[1]), bits(R.spmm(tptr, tids, B[1], ch)))
+        # a list is strictly increasing, so 280 items hold none of 2 chunk + 1 entries: here the longest is every item (a
+        # second chunk of several entries), and the three-chunk list is folded in on a wider catalogue below
+        lengths = [ch - 1, ch, ch + 1, ni, 0]
+        lists = _lists_of(rs, ni, lengths)
+        got = m.fold_in_users(lists)
+        assert np.array_equal(bits(got), bits(R.spmm(lists[0], lists[1], Q, ch))), "fold-in of long lists"
+        assert (got[4] == 0).all() and not np.signbit(got[4]).any()
+        assert np.array_equal(bits(m.fold_in_users((indptr, items))), bits(P)), "fold-in of the resident lists"
+        m.fold_in_users(lists)                                                     # the last plan standing is not the model's
+        after = [m.multiply(B[0]), m.multiply(B[1], transpose=True)]
+        assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(before, after)), "multiply after the fold-ins"
+        assert np.array_equal(bits(m.user_factors), bits(P))
+    # 2 chunk + 1 entries need a catalogue that long: factors set on 2 chunk + 40 items, resident rows of their own, one of
+    # them long; an even and an odd width
+    ni2 = 2 * ch + 40
+    lengths = [ch - 1, ch, ch + 1, 2 * ch + 1, 0]
+    lists = _lists_of(rs, ni2, lengths)
+    own = _lists_of(rs, ni2, [3, ch + 5, 0, 9])
+    for f2 in (8, 7):
+        Q2 = PC.product_block(ni2, f2)
+        with T.PureSVD(4, ni2, factors=f2, oversample=0) as m2:
+            m2.load(own)
+            m2.set_factors(Q2, np.ones(f2))
+            P2 = m2.user_factors
+            assert np.array_equal(bits(P2), bits(R.spmm(own[0], own[1], Q2, ch)))
+            got = m2.fold_in_users(lists)
+            assert np.array_equal(bits(got), bits(R.spmm(lists[0], lists[1], Q2, ch))), "fold-in of a three-chunk list, width %d" % f2
+            assert np.array_equal(bits(m2.fold_in_users(own)), bits(P2))
+            m2.fold_in_users(lists)
+            assert np.array_equal(bits(m2.multiply(Q2)), bits(P2)), "multiply after the fold-ins, width %d" % f2
 
 
 # ----------------------------------------------------------------------------- 6. fold-in and serving

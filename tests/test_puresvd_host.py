@@ -129,6 +129,29 @@ def test_the_block_fit_is_exact_and_the_random_fit_agrees_with_the_svd():
     assert (R.residual_bound(case["ni"], res, f["sigma"]) < 1e-14).all()
 
 
+def test_the_wide_fit_reaches_the_paths_it_is_there_for_and_its_ratio_is_the_recorded_one():
+    from tests import ials_ref
+    case, fit = PC.wide_case(), PC.WIDE_FIT
+    p = puresvd.plan(case["nu"], case["ni"], fit["factors"], fit["oversample"])
+    r = p["r"]
+    assert r == 101 and r % 2 == 1 and fit["factors"] % 2 == 0                 # k_psvd_spmm at an odd and at an even width
+    assert p["lds_bytes"] == r * (r + 1) * 8 + 4096                            # one matrix in LDS: the rotations are in global scratch
+    rows = np.diff(case["indptr"])
+    cols = np.bincount(case["items"], minlength=case["ni"])
+    assert rows[0] > p["chunk"] and cols[0] > p["chunk"] and rows[1] == 0 and cols[1] == 0
+    assert rows[2:].max() <= p["chunk"] and cols[2:].max() <= p["chunk"]       # the crowd is added by the row's own wave
+    assert all(-(-n // ials_ref.gram_slice_rows(n)) >= 3 for n in (case["nu"], case["ni"])) and p["gram_slices"] >= 3
+    f, twin = PC.fit_ref("wide"), PC.fit_ref("wide", R.LD)
+    assert 1 <= f["sweeps"] < p["sweep_cap"] and f["sweeps"] == twin["sweeps"]
+    sv = np.linalg.svd(PC.dense(case), compute_uv=False)[:fit["factors"]]
+    assert np.abs(f["sigma"] / sv - 1).max() < 1e-3        # four iterations on close singular values: the leading digits
+    rho = float(np.abs(f["sigma"] - twin["sigma"]).max() / twin["sigma"][0]) / R.EPS
+    print("RATIO wide fit sigma %.3f" % rho)
+    assert rho == pytest.approx(R.MEASURED_RHO_SIGMA_WIDE, rel=2e-3) and rho <= R.K_SIGMA_WIDE / 8
+    orthogonal = float(np.abs(f["Q"].T @ f["Q"] - np.eye(fit["factors"])).max()) / (R.EPS * r)
+    assert orthogonal <= R.K_ORTH / 8, orthogonal
+
+
 def test_arguments_are_checked_before_any_device_work():
     lib = L.load()
     h = L._p()
